@@ -8,13 +8,18 @@ values landed in the NLP value array and the cost reduced
 Inputs are resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scenarios S] [--batch B] [--config c3|c5]
+                  [--full] [--dump-outputs DIR]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
        (or plain `python bench.py --gpus N`: it then starts the N ranks itself, as child processes, before touching the GPU)
 The batch is the 1024-scenario obstacle-field Monte-Carlo of config 4: it is STRONG-scaled, rank r evaluates
 scenarios [r*S/N, (r+1)*S/N) (S/N = 128 per GPU at N = 8) with no data-path collective; `value` = S*M*K / time.
-The same run then repeats the measurement weak-scaled (1024 scenarios per GPU) and reports it as a second field.
 The only collective of the path, the gather of the trajectories, runs once after the timed region.
 --config c5: the fp32 path of config 5 (12-state fixed wing, N=4096, MFMA D.X), 256 instances per GPU.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not
+need: the check of the timed passes' outputs against the CPU oracle (the number is withheld if they disagree), the
+weak-scaled repeat of a multi-GPU run (1024 scenarios per GPU), the config-5 (fp32) measurement and the CPU baseline.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs()).
 """
 import argparse
 import json
@@ -158,6 +163,24 @@ def roofline_of(m, def_name, key, n_obs, B, M, ns, ms_per_step):
 
 
 PRE_WARM_S = 0.25      # untimed clock warm-up ahead of the W warm-up steps (see measure())
+DUMP_BYTES = 60_000_000    # --dump-outputs: bytes of arrays written at most
+
+
+def dump_outputs(d, outs, first, np, torch):
+    """--dump-outputs DIR: what the timed path computed in its last step, the arrays a caller of eval_dev receives, in the
+    path's precision: res.npy [b][nres][M], vals.npy [b][nvals][M], cost.npy [B].  When RES and VALS of all B instances
+    would exceed DUMP_BYTES, they are written for a fixed, seeded sample of b instances; instances.npy holds the scenario
+    numbers of the b instances written (as float64)."""
+    res, vals, cost = outs
+    B = cost.shape[0]
+    per = (res[0].numel() + vals[0].numel()) * res.element_size()
+    k = min(B, max(1, (DUMP_BYTES - 2 * 8 * B) // per))
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    sel = torch.from_numpy(idx).to(res.device)
+    os.makedirs(d, exist_ok=True)
+    for name, t in (("res", res.index_select(0, sel)), ("vals", vals.index_select(0, sel)), ("cost", cost)):
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy())
+    np.save(os.path.join(d, "instances.npy"), (first + idx).astype(np.float64))
 
 
 def launch_ranks(n):
@@ -238,8 +261,11 @@ def main():
     ap.add_argument("--obstacles", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-weak", action="store_true", help="skip the second, weak-scaled measurement of a multi-GPU run")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-5 (fp32) measurement appended to the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the config-5 (fp32) measurement that --full appends")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true", help="also check the outputs against the CPU oracle and run the weak-scaled "
+                    "repeat, the config-5 measurement and the CPU baseline (the --no-* options above apply to this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -349,6 +375,9 @@ def main():
     ms_per_step = 1e3 * el / a.steps
     value = S * M * a.steps / el
     def_name = ev.last_defect_kernel
+    if a.dump_outputs and rank == 0:
+        # untimed: the outputs of the last timed step (each pass overwrites them), rank 0's shard [lo, hi)
+        dump_outputs(a.dump_outputs, outs, lo, np, torch)
 
     # the path's one collective: gather the trajectories to rank 0 (once per batch, untimed)
     gather_ms = None
@@ -362,7 +391,7 @@ def main():
         if rank == 0:
             assert got[0].shape[0] == S and torch.equal(got[0][:B].to(dX.device), dX)
     checked = None
-    if rank == 0 and world == 1 and not c5 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not c5 and not a.no_cpu_baseline:
         # untimed: what the timed passes left in HBM, against the CPU oracle on sampled instances (first / last of the batch,
         # both sides of a 16-instance tile edge, the middle)
         checked = check_against_oracle(ev, host[0], host[1], host[2] if n_obs else None, outs, M, [0, 15, 16, B // 2, B - 1])
@@ -371,7 +400,7 @@ def main():
     torch.cuda.empty_cache()
 
     weak = None
-    if world > 1 and scaling == "strong" and not a.no_weak:
+    if a.full and world > 1 and scaling == "strong" and not a.no_weak:
         Bw = a.scenarios
         evw, wX, wU, wouts, _ = build(Bw, rank * Bw)
         mw = measure(evw, wX, wU, wouts, a.steps, a.warmup, barrier, torch)
@@ -407,7 +436,7 @@ def main():
             line["weak_scaling"] = weak
         if checked is not None:
             line["checked"] = checked
-        if world == 1 and not c5 and not a.batch and not a.nodes and not a.no_secondary:
+        if a.full and world == 1 and not c5 and not a.batch and not a.nodes and not a.no_secondary:
             # config 5 (BASELINE.json configs[4]) on the same record: 12-state fixed wing, N = 4096, fp32 path with the MFMA
             # D.X defect, 256 instances, fewer steps (a pass is ~1 ms); its own roofline against the f32 MFMA peak and
             # 944 algorithmic bytes per node-eval
@@ -427,7 +456,7 @@ def main():
             ev5.close()
             del X5, U5, outs5
             torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline and not c5:
+        if a.full and world == 1 and not a.no_cpu_baseline and not c5:
             line["cpu_baseline"] = cpu_baseline(M, n_obs, a.cpu_budget)
         bad = checked is not None and not checked["ok"]
         if bad:

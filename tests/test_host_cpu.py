@@ -72,8 +72,11 @@ def test_save_load_roundtrip(H, tmp_path, xmls):
     assert a == b
 
 
-def test_csv_writer_format_and_no_overwrite(H, tmp_path):
-    p = str(tmp_path / "traj.csv")
+def test_csv_writer_format_and_no_overwrite(H, tmp_path, monkeypatch):
+    # save() takes the extension from the FIRST '.' of the path, as the reference's writer does: a relative
+    # name in a directory of the test's own keeps a '.' elsewhere in the temporary path out of the name it numbers
+    monkeypatch.chdir(tmp_path)
+    p = "traj.csv"
     n1 = H.harness_save_csv(p.encode()).decode()
     n2 = H.harness_save_csv(p.encode()).decode()
     n3 = H.harness_save_csv(p.encode()).decode()
