@@ -1353,7 +1353,8 @@ int emi_kkt_factor_batch(int n, const emi_ctx_t* ctxs, const double* const* Qblk
     std::string err;
     st = emi::kkt_factor_batch(n, pws.data(), c0->stream, dD.data(), c0->M, c0->ns, c0->ns + c0->nc, Qblk, Jblk, fixed, dc, info, &err);
     if (st) { c0->err = err; return st; }
-    // scenarios the batch could not take (a node block not positive definite, the ladder exhausted): the single path with its LU
+    // scenarios the batch could not take (a node block not positive definite, the ladder exhausted, more than 16 variables per node):
+    // the single path with its LU
     for (int b = 0; b < n; ++b)
         if (info[b] < 0) {
             const int s1 = emi_kkt_factor(ctxs[b], Qblk[b], Jblk[b], fixed[b], dc[b], &info[b]);

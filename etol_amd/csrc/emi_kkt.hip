@@ -141,12 +141,12 @@ struct KktWorkspace {
     size_t cap_chol_copy = 0;
     // low-rank correction (kkt_lowrank)
     bool lr_active = false;
-    int lr_r = 0, lr_cap = 0, lr_n = 0;
+    int lr_r = 0, lr_cap = 0, lr_n = 0, lr_nv = 0;   // columns in use, columns allocated, rows of lrY, entries per column of lr_vec
     double* lrY = nullptr;      // [N][r]  K~^-1 U
     double* lrC = nullptr;      // [r][r]  Cholesky factor of Delta^-1 - U^T Y
     double* lrT = nullptr;      // [r][<=64] work
     int* lr_node = nullptr;
-    double* lr_vec = nullptr;   // [r][nv]
+    double* lr_vec = nullptr;   // [r][nv] (sorted by node, as lr_node and lr_delta)
     double* lr_delta = nullptr;
     // refined solves (kkt_solve_refined_batch): right-hand side, solution, previous solution on the device
     double *ref_b = nullptr, *ref_x = nullptr, *ref_p = nullptr;
@@ -1580,24 +1580,44 @@ int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* n
         for (void** b : bufs)
             if (*b) { KKT_HIP(hipFree(*b)); *b = nullptr; }
         w->lr_cap = 0;
+        w->lr_nv = 0;
         const int cap = r + r / 4 + 16;
         KKT_HIP(hipMalloc(&w->lrY, (size_t)N * cap * sizeof(double)));
         KKT_HIP(hipMalloc(&w->lrC, (size_t)cap * cap * sizeof(double)));
         KKT_HIP(hipMalloc(&w->lr_node, (size_t)cap * sizeof(int)));
-        KKT_HIP(hipMalloc(&w->lr_vec, (size_t)cap * KKT_NV_MAX * sizeof(double)));
+        KKT_HIP(hipMalloc(&w->lr_vec, (size_t)cap * nv * sizeof(double)));
         KKT_HIP(hipMalloc(&w->lr_delta, (size_t)cap * sizeof(double)));
         KKT_HIP(hipMalloc(&w->lrT, (size_t)cap * 64 * sizeof(double)));
         w->lr_cap = cap;
         w->lr_n = N;
+        w->lr_nv = nv;
     } else if (w->lr_n < N) {
         if (w->lrY) KKT_HIP(hipFree(w->lrY));
         w->lrY = nullptr;
         KKT_HIP(hipMalloc(&w->lrY, (size_t)N * w->lr_cap * sizeof(double)));
         w->lr_n = N;
     }
-    KKT_HIP(hipMemcpyAsync(w->lr_node, node, (size_t)r * sizeof(int), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->lr_vec, vec, (size_t)r * nv * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->lr_delta, delta, (size_t)r * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (w->lr_nv < nv) {            // (the LU path takes node blocks of any size: traced models up to 64 variables per node)
+        if (w->lr_vec) KKT_HIP(hipFree(w->lr_vec));
+        w->lr_vec = nullptr;
+        w->lr_nv = 0;
+        KKT_HIP(hipMalloc(&w->lr_vec, (size_t)w->lr_cap * nv * sizeof(double)));
+        w->lr_nv = nv;
+    }
+    // the columns sorted by node (stable: an order that already is, as solve_nlp's, stays as it is) -- the residual of the refined
+    // solves gives each node's columns to one thread (emi_kkt_residual_lr_b_kernel)
+    std::vector<int> perm(r), s_node(r);
+    std::vector<double> s_vec((size_t)r * nv), s_delta(r);
+    for (int a = 0; a < r; ++a) perm[a] = a;
+    std::stable_sort(perm.begin(), perm.end(), [node](int a, int b) { return node[a] < node[b]; });
+    for (int a = 0; a < r; ++a) {
+        s_node[a] = node[perm[a]];
+        s_delta[a] = delta[perm[a]];
+        std::memcpy(&s_vec[(size_t)a * nv], vec + (size_t)perm[a] * nv, (size_t)nv * sizeof(double));
+    }
+    KKT_HIP(hipMemcpyAsync(w->lr_node, s_node.data(), (size_t)r * sizeof(int), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->lr_vec, s_vec.data(), (size_t)r * nv * sizeof(double), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->lr_delta, s_delta.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, stream));
     KKT_HIP(hipMemsetAsync(w->lrY, 0, (size_t)N * r * sizeof(double), stream));
     hipLaunchKernelGGL(emi_kkt_lr_scatter_kernel, dim3((r + 63) / 64), dim3(64), 0, stream, w->lrY, w->lr_node, w->lr_vec, r, N, M,
                        nv);
@@ -1660,8 +1680,9 @@ int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs
 // correction); the batch is a table of their device pointers (KktDev) plus pointer arrays for rocBLAS' *_batched calls, built on the
 // host in pinned memory and uploaded once per attempt.
 //
-// Restrictions (the caller falls back to the single entry points otherwise): Schur method, one common (M, ns, nv), every scenario's
-// context holding the same differentiation matrix (all of them come from emi_lgl for the same node count).
+// Restrictions (the caller falls back to the single entry points otherwise): Schur method, one common (M, ns, nv), at most KKT_NV_MAX
+// variables per node.  Every scenario keeps its own differentiation matrix (its workspace's Doff): equal node counts need not mean
+// equal meshes.
 // ==================================================================================================================================
 namespace {
 
@@ -1796,11 +1817,16 @@ int chol_batched(KktWorkspace* L, hipStream_t stream, const KktDev* d_tab, int n
 
 // n scenarios, one mesh.  pws[b]: the scenario's workspace slot (created here if empty); dD[b]: its context's differentiation matrix
 // on the device; Qblk / Jblk / fixed / dc as kkt_factor, per scenario (host pointers).  info[b]: 0 factorised (Schur path), > 0 singular,
-// -1: this scenario needs the single entry point (a node block not positive definite, or the regularisation ladder exhausted: the LU).
+// -1: this scenario needs the single entry point (a node block not positive definite, the regularisation ladder exhausted, or more
+// than KKT_NV_MAX variables per node: the LU).
 int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const double* const* dD, int M, int ns, int nv,
                      const double* const* Qblk, const double* const* Jblk, const unsigned char* const* fixed, const double* dc, int* info,
                      std::string* err) {
-    if (n < 1 || nv > KKT_NV_MAX) { *err = "emi_kkt_factor_batch: bad batch"; return EMI_ERR_ARG; }
+    if (n < 1) { *err = "emi_kkt_factor_batch: bad batch"; return EMI_ERR_ARG; }
+    if (nv > KKT_NV_MAX) {              // node blocks beyond the node kernels' arrays: every scenario to the single path (its LU)
+        for (int b = 0; b < n; ++b) info[b] = -1;
+        return EMI_OK;
+    }
     const int nh = nv * (nv + 1) / 2, nz = nv * M, md = ns * M, npairs = ns * (ns + 1) / 2;
     std::vector<KktWorkspace*> W(n);
     for (int b = 0; b < n; ++b) {
@@ -1861,7 +1887,7 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
             const double dc_base = dc[act[a]] > 1e-9 ? dc[act[a]] : 1e-9;
             KktDev t{};
             t.Q = w->Q; t.J = w->J; t.Pinv = w->Pinv; t.G = w->G; t.Rk = w->Rk; t.S = w->S; t.W = w->W; t.chol_blk = w->chol_blk;
-            t.Doff = L->Doff;                       // one copy of the operand for the whole batch (same mesh: same matrix)
+            t.Doff = w->Doff;
             t.fixed = w->fixed;
             t.info = L->b_stat + a;
             t.flag = L->b_stat + na + a;
@@ -1872,7 +1898,7 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
         }
         // pointer arrays of the S build
         size_t q = 0;
-        const size_t at_A = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = L->Doff;
+        const size_t at_A = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Doff;
         const size_t at_B = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->W;
         const size_t at_C = q;
         for (int i = 0; i < ns; ++i)
@@ -1897,7 +1923,7 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
                                                  L->b_ptrs + at_C + (size_t)p * na, (rocblas_int)md, na));
                 else
                     for (int a = 0; a < na; ++a)
-                        KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, L->Doff, M, W[act[a]]->W, M, &zero,
+                        KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, W[act[a]]->Doff, M, W[act[a]]->W, M, &zero,
                                              h_ptr[at_C + (size_t)p * na + a], (rocblas_int)md));
                 hipLaunchKernelGGL(emi_kkt_sblock_terms_b_kernel, dim3(nb2, na), dim3(256), 0, stream, (const KktDev*)d_tab, M, ns, i, ip);
             }
@@ -2017,18 +2043,18 @@ __global__ void emi_kkt_residual_node_b_kernel(const KktDev* __restrict__ tab, i
     }
 }
 // + U Delta (U^T x) of the scenarios whose low-rank correction is active: one thread per FIRST column of a node walks the node's columns
-// (the columns come node by node: fixed order of the additions)
+// (kkt_lowrank stores them sorted by node: one writer per node, fixed order of the additions); grid-stride over any number of columns
 __global__ void emi_kkt_residual_lr_b_kernel(const KktDev* __restrict__ tab, int M, int nv) {
     const KktDev t = tab[blockIdx.y];
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= t.lr_r) return;
-    const int node = t.lr_node[c];
-    if (c > 0 && t.lr_node[c - 1] == node) return;
-    for (int a = c; a < t.lr_r && t.lr_node[a] == node; ++a) {
-        double dot = 0.0;
-        for (int v = 0; v < nv; ++v) dot += t.lr_vec[(size_t)a * nv + v] * t.T[(size_t)v * M + node];
-        dot *= t.lr_delta[a];
-        for (int v = 0; v < nv; ++v) t.rhs[(size_t)v * M + node] += t.lr_vec[(size_t)a * nv + v] * dot;
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < t.lr_r; c += gridDim.x * blockDim.x) {
+        const int node = t.lr_node[c];
+        if (c > 0 && t.lr_node[c - 1] == node) continue;
+        for (int a = c; a < t.lr_r && t.lr_node[a] == node; ++a) {
+            double dot = 0.0;
+            for (int v = 0; v < nv; ++v) dot += t.lr_vec[(size_t)a * nv + v] * t.T[(size_t)v * M + node];
+            dot *= t.lr_delta[a];
+            for (int v = 0; v < nv; ++v) t.rhs[(size_t)v * M + node] += t.lr_vec[(size_t)a * nv + v] * dot;
+        }
     }
 }
 // stat[item] = max |v| over the N entries of the chosen vector (which: 0 rhs, 1 bb); NaN propagates as +inf
@@ -2063,11 +2089,11 @@ __global__ void emi_kkt_vecop_b_kernel(const KktDev* __restrict__ tab, int N, in
 
 struct SolveShape { int M, ns, nv, N, nz, md, nblk; bool blk; };
 
-void fill_solve_entry(KktDev& t, KktWorkspace* w, const KktWorkspace* L) {
+void fill_solve_entry(KktDev& t, KktWorkspace* w) {
     t.Q = w->Q; t.J = w->J; t.Pinv = w->Pinv; t.S = w->S; t.Linv = w->Linv; t.LinvT = w->LinvT; t.T = w->T; t.Cb = w->Cb; t.rhs = w->rhs;
     t.y = w->trsv_y; t.bb = w->ref_b; t.xx = w->ref_x; t.xp = w->ref_p;
     t.fixed = w->fixed;
-    t.Doff = L->Doff;
+    t.Doff = w->Doff;
     t.lr_r = w->lr_active ? w->lr_r : 0;
     t.lr_node = w->lr_node; t.lr_vec = w->lr_vec; t.lr_delta = w->lr_delta;
 }
@@ -2089,12 +2115,12 @@ int solve_arrays(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int 
     A->P = L->b_ptrs;
     for (int b = 0; b < n; ++b) {
         KktDev t{};
-        fill_solve_entry(t, ws[b], L);
+        fill_solve_entry(t, ws[b]);
         h_tab[b] = t;
     }
     size_t q = 0;
     auto arr = [&](auto f) { const size_t at = q; for (int b = 0; b < n; ++b) h_ptr[q++] = f(ws[b]); return at; };
-    A->at_D = arr([&](KktWorkspace*) { return L->Doff; });
+    A->at_D = arr([](KktWorkspace* w) { return w->Doff; });
     A->at_T = arr([](KktWorkspace* w) { return w->T; });
     A->at_Cb = arr([](KktWorkspace* w) { return w->Cb; });
     A->at_X = arr([](KktWorkspace* w) { return w->rhs; });

@@ -243,20 +243,24 @@ int emi_kkt_factor(emi_ctx_t ctx, const double* Qblk, const double* Jblk,
  * to make the Q blocks positive definite).  K~^-1 U and the Cholesky factor of
  * C = Delta^-1 - U^T K~^-1 U stay on the device.  *exact = 1 iff C is positive
  * definite, i.e. iff K has the inertia of K~; emi_kkt_solve then returns
- * solutions of K (Woodbury), else of K~.  r = 0 clears the correction.       */
+ * solutions of K (Woodbury), else of K~.  r = 0 clears the correction.  The
+ * columns may come in any order (they are kept sorted by node) and for any
+ * number of variables per node the factorisation took.                      */
 int emi_kkt_lowrank(emi_ctx_t ctx, int r, const int* node, const double* vec,
                     const double* delta, int* exact);
 /* The Newton steps of n scenarios at once: ctxs[b] are n DIFFERENT contexts on one
- * device with the same mesh size and model dimensions (one scenario of a
+ * device with the same mesh size and model dimensions, each with its own mesh
+ * (emi_set_mesh: tau and D may differ between them) (one scenario of a
  * Monte-Carlo batch each, BASELINE configs[3]); arguments per scenario as the
  * single entry points take them (host pointers).  Every launch of the
  * factorisation then carries the whole batch -- the 96-step dependency chain of a
  * 1024-node Cholesky is paid once per batch instead of once per scenario -- on
  * ctxs[0]'s stream; each context keeps its own factors, so emi_kkt_lowrank /
  * emi_kkt_solve / emi_kkt_solve_batch may follow in any grouping.  A scenario
- * the batch cannot take (a node block that is not positive definite, or one
- * whose regularisation ladder is exhausted) is factorised through
- * emi_kkt_factor inside the call.  info[b] as emi_kkt_factor's.  What IPOPT does
+ * the batch cannot take (a node block that is not positive definite, one
+ * whose regularisation ladder is exhausted, or any scenario of a model with more
+ * than 16 variables per node) is factorised through emi_kkt_factor inside the
+ * call.  info[b] as emi_kkt_factor's.  What IPOPT does
  * once per scenario behind ePSOPT (reference src/ePSOPT/ePSOPT.cpp:62-66, 84).     */
 int emi_kkt_factor_batch(int n, const emi_ctx_t* ctxs, const double* const* Qblk,
                          const double* const* Jblk, const unsigned char* const* fixed,
