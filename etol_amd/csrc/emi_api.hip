@@ -108,6 +108,15 @@ struct emi_ctx_s {
     int sym_combine = 1;        // "sym_combine" option: 1 slices combined in-kernel by ticket, 0 by emi_symdefect_combine_kernel
     // host-form staging
     DevBuf s_X, s_U, s_RES, s_VALS, s_COST, s_LF, s_LC, s_H;
+    // adjoint pass (emi_lagr_grad_* / emi_kkt_certificate_*): workspace grown on demand
+    DevBuf d_adjDT;             // [M][ldt] transposed operator without its diagonal (emi_adjoint.hip), rebuilt after emi_set_mesh
+    bool adj_dirty = true;
+    DevBuf d_adj_pvars;         // pvars on the device ...
+    std::vector<int> adj_pvars; // ... and what it holds
+    DevBuf d_adj_c;             // [2][np] path-row bounds of the last certificate call
+    DevBuf d_adj_G;             // G of a certificate call that does not return it
+    DevBuf d_adj_op;            // [B][ns][M] operator term of the side-by-side form (large batches)
+    DevBuf s_G, s_cert, s_zl, s_zu;
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;
     int profile = 0;          // emi_profile_enable level (0 off)
@@ -537,7 +546,7 @@ int emi_destroy(emi_ctx_t c) {
     (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->d_w, &c->d_t, &c->d_Ddiag, &c->d_D, &c->d_De, &c->d_Do, &c->d_path, &c->d_trkx, &c->d_trky,
                       &c->d_cost_part, &c->d_slab, &c->d_tile_ticket, &c->d_cost_part2, &c->d_ticket, &c->s_X, &c->s_U, &c->s_RES, &c->s_VALS, &c->s_COST,
-                      &c->s_LF, &c->s_LC, &c->s_H};
+                      &c->s_LF, &c->s_LC, &c->s_H, &c->d_adjDT, &c->d_adj_pvars, &c->d_adj_c, &c->d_adj_G, &c->d_adj_op, &c->s_G, &c->s_cert, &c->s_zl, &c->s_zu};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& pe : c->prof) {
@@ -607,6 +616,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
         c->symmetric = false;
         c->points_only = true;
         c->delay_dirty = true;
+        c->adj_dirty = true;
         emi::kkt_mesh_changed(c->kkt);
         c->h_tau.assign(tau, tau + M);
         c->h_w.assign(w, w + M);
@@ -677,6 +687,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     c->M = M;
     c->t0 = t0;
     c->tf = tf;
+    c->adj_dirty = true;
     c->delay_dirty = true;      // W(delay) is built for one mesh: [nd][M][M] on these nodes and this horizon
     emi::kkt_mesh_changed(c->kkt);
     // tables sized by M are stale now
@@ -1286,6 +1297,152 @@ int emi_hess_host(emi_ctx_t c, const double* X, const double* U, const double* L
     if ((st = ensure(c, c->s_H, nH * rb))) return st;
     if ((st = emi_hess_dev(c, c->s_X.p, c->s_U.p, c->s_LF.p, c->s_LC.p, sigma, c->s_H.p))) return st;
     return download_real(c, H, c->s_H.p, nH);
+}
+
+// ---- the adjoint pass: Lagrangian gradient and KKT certificate (emi_adjoint.hip) ----
+// a null context on a box without a device is "no device", not a bad argument: there is no host path to fall back to
+static int adj_null_ctx() {
+    int n = 0;
+    return (hipGetDeviceCount(&n) != hipSuccess || n <= 0) ? EMI_ERR_NO_DEVICE : EMI_ERR_ARG;
+}
+
+static int adj_ready(emi_ctx_t c, const char* who) {
+    int st = ready(c);
+    if (st) return st;
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: fp32 contexts have no adjoint pass (the certificate is an fp64 figure)", who);
+    if (c->nch > 0) return fail(c, EMI_ERR_UNSUPPORTED, "%s: contexts with delays (emi_set_delays) are not supported: W as a second operator is not built", who);
+    if (c->points_only) return fail(c, EMI_ERR_STATE, "%s: the mesh has no differentiation matrix (points-only mesh)", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->adj_dirty) {
+        const int M = c->M, ldt = M + (M & 1);
+        if ((st = ensure(c, c->d_adjDT, (size_t)M * ldt * 8))) return st;
+        HIP_TRY(c, emi::launch_adjoint_transpose((const double*)c->d_D.p, (double*)c->d_adjDT.p, M, ldt, c->stream));
+        c->adj_dirty = false;
+    }
+    if (c->adj_pvars != c->pvars || (!c->pvars.empty() && !c->d_adj_pvars.p)) {
+        if ((st = ensure(c, c->d_adj_pvars, c->pvars.size() * sizeof(int)))) return st;
+        if (!c->pvars.empty()) {
+            HIP_TRY(c, hipMemcpyAsync(c->d_adj_pvars.p, c->pvars.data(), c->pvars.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        c->adj_pvars = c->pvars;
+    }
+    return EMI_OK;
+}
+
+int emi_lagr_grad_dev(emi_ctx_t c, const void* dVALS, const void* dLamF, const void* dLamC, double sigma, void* dG) {
+    if (!c) return adj_null_ctx();
+    int st = adj_ready(c, "emi_lagr_grad");
+    if (st) return st;
+    if (!dVALS || !dLamF || !dG || (np_total(c) > 0 && !dLamC)) return fail(c, EMI_ERR_ARG, "emi_lagr_grad: null device pointer");
+    emi::AdjointArgs a;
+    a.VALS = (const double*)dVALS; a.lamF = (const double*)dLamF; a.lamC = np_total(c) > 0 ? (const double*)dLamC : nullptr;
+    a.DT = (const double*)c->d_adjDT.p; a.pvars = (const int*)c->d_adj_pvars.p; a.G = (double*)dG;
+    a.B = c->B; a.M = c->M; a.ldt = c->M + (c->M & 1); a.ns = c->ns; a.nc = c->nc;
+    a.np_table = c->np; a.np_traced = c->np_model; a.pw = c->np_model > 0 ? (int)c->pvars.size() : 0;
+    a.px = c->px; a.py = c->py; a.nvals = nvals_of(c); a.sigma = sigma; a.add_op = 1;
+    if (!emi::adjoint_side_by_side(c->B, c->ns, c->M)) {
+        HIP_TRY(c, emi::launch_adjoint_op(a, c->stream));
+        HIP_TRY(c, emi::launch_adjoint_nodes(a, c->stream));
+        return EMI_OK;
+    }
+    // Large batches: the product (matrix pipe) on the second stream BESIDE the node kernel (HBM) -- they share nothing until the last
+    // addition.  The product writes its own [B][ns][M] block; a third, short kernel adds it onto the state rows: the same last
+    // addition as in the back-to-back form, so both forms give the same bits.
+    if ((st = need_stream2(c))) return st;
+    if ((st = ensure(c, c->d_adj_op, (size_t)c->B * c->ns * c->M * 8))) return st;
+    emi::AdjointArgs op = a;
+    op.G = (double*)c->d_adj_op.p;
+    op.nc = 0;                                       // rows (instance * ns + state) of the block
+    a.add_op = 0;
+    HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));          // the inputs (and the previous call's last addition) are done
+    HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    HIP_TRY(c, emi::launch_adjoint_op(op, c->stream2));
+    HIP_TRY(c, hipEventRecord(c->ev_join, c->stream2));
+    HIP_TRY(c, emi::launch_adjoint_nodes(a, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    HIP_TRY(c, emi::launch_adjoint_add((const double*)c->d_adj_op.p, (double*)dG, c->B, c->ns, c->ns + c->nc, c->M, c->stream));
+    return EMI_OK;
+}
+
+int emi_lagr_grad_host(emi_ctx_t c, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G) {
+    if (!c) return adj_null_ctx();
+    int st = adj_ready(c, "emi_lagr_grad_host");
+    if (st) return st;
+    if (!VALS || !LamF || !G || (np_total(c) > 0 && !LamC)) return fail(c, EMI_ERR_ARG, "emi_lagr_grad_host: null pointer");
+    const size_t M = c->M, B = c->B, nv = c->ns + c->nc;
+    const size_t nV = B * nvals_of(c) * M, nF = B * c->ns * M, nC = B * np_total(c) * M, nG = B * nv * M;
+    if ((st = upload_real(c, c->s_VALS, VALS, nV))) return st;
+    if ((st = upload_real(c, c->s_LF, LamF, nF))) return st;
+    if (nC && (st = upload_real(c, c->s_LC, LamC, nC))) return st;
+    if ((st = ensure(c, c->s_G, nG * 8))) return st;
+    if ((st = emi_lagr_grad_dev(c, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_G.p))) return st;
+    return download_real(c, G, c->s_G.p, nG);
+}
+
+int emi_kkt_certificate_dev(emi_ctx_t c, const void* dX, const void* dU, const void* dRES, const void* dVALS, const void* dLamF,
+                            const void* dLamC, double sigma, const void* dZl, const void* dZu, int nsets, const double* cl,
+                            const double* cu, void* dCert, void* dG) {
+    if (!c) return adj_null_ctx();
+    int st = adj_ready(c, "emi_kkt_certificate");
+    if (st) return st;
+    const int np = np_total(c);
+    if (!dX || !dU || !dRES || !dVALS || !dLamF || !dZl || !dZu || !dCert || (np > 0 && (!dLamC || !cl || !cu)))
+        return fail(c, EMI_ERR_ARG, "emi_kkt_certificate: null pointer");
+    if (nsets != 1 && nsets != c->B) return fail(c, EMI_ERR_ARG, "emi_kkt_certificate: %d bound sets, batch is %d", nsets, c->B);
+    if (!dG) {
+        if ((st = ensure(c, c->d_adj_G, (size_t)c->B * (c->ns + c->nc) * c->M * 8))) return st;
+        dG = c->d_adj_G.p;
+    }
+    if (np > 0) {
+        if ((st = ensure(c, c->d_adj_c, (size_t)2 * np * 8))) return st;
+        // pageable host memory: the copies are staged before the calls return, the caller's arrays are free again
+        HIP_TRY(c, hipMemcpyAsync(c->d_adj_c.p, cl, (size_t)np * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((double*)c->d_adj_c.p + np, cu, (size_t)np * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((st = emi_lagr_grad_dev(c, dVALS, dLamF, dLamC, sigma, dG))) return st;
+    emi::CertArgs a;
+    a.X = (const double*)dX; a.U = (const double*)dU; a.RES = (const double*)dRES; a.VALS = (const double*)dVALS;
+    a.lamF = (const double*)dLamF; a.lamC = np > 0 ? (const double*)dLamC : nullptr; a.G = (const double*)dG;
+    a.zl = (const double*)dZl; a.zu = (const double*)dZu;
+    a.cl = (const double*)c->d_adj_c.p; a.cu = np > 0 ? (const double*)c->d_adj_c.p + np : nullptr;
+    a.cert = (double*)dCert;
+    a.B = c->B; a.M = c->M; a.ns = c->ns; a.nc = c->nc; a.np = np; a.nres = nres_of(c); a.nvals = nvals_of(c); a.nsets = nsets;
+    a.sigma = sigma;
+    HIP_TRY(c, emi::launch_kkt_certificate(a, c->stream));
+    return EMI_OK;
+}
+
+int emi_kkt_certificate_host(emi_ctx_t c, const double* X, const double* U, const double* LamF, const double* LamC, double sigma,
+                             const double* zl, const double* zu, int nsets, const double* cl, const double* cu, double* cert,
+                             double* G) {
+    if (!c) return adj_null_ctx();
+    int st = adj_ready(c, "emi_kkt_certificate_host");
+    if (st) return st;
+    const int np = np_total(c);
+    if (!X || !U || !LamF || !zl || !zu || !cert || (np > 0 && (!LamC || !cl || !cu)))
+        return fail(c, EMI_ERR_ARG, "emi_kkt_certificate_host: null pointer");
+    if (nsets != 1 && nsets != c->B) return fail(c, EMI_ERR_ARG, "emi_kkt_certificate_host: %d bound sets, batch is %d", nsets, c->B);
+    const size_t M = c->M, B = c->B, nv = c->ns + c->nc;
+    const size_t nX = B * c->ns * M, nU = B * c->nc * M, nR = B * nres_of(c) * M, nV = B * nvals_of(c) * M, nC = B * np * M, nG = B * nv * M;
+    if ((st = upload_real(c, c->s_X, X, nX))) return st;
+    if ((st = upload_real(c, c->s_U, U, nU))) return st;
+    if ((st = upload_real(c, c->s_LF, LamF, nX))) return st;
+    if (nC && (st = upload_real(c, c->s_LC, LamC, nC))) return st;
+    if ((st = upload_real(c, c->s_zl, zl, (size_t)nsets * nv * M))) return st;
+    if ((st = upload_real(c, c->s_zu, zu, (size_t)nsets * nv * M))) return st;
+    if ((st = ensure(c, c->s_RES, nR * 8))) return st;
+    if ((st = ensure(c, c->s_VALS, nV * 8))) return st;
+    if ((st = ensure(c, c->s_COST, B * 8))) return st;
+    if ((st = ensure(c, c->s_G, nG * 8))) return st;
+    if ((st = ensure(c, c->s_cert, B * 6 * 8))) return st;
+    if ((st = emi_eval_dev(c, c->s_X.p, c->s_U.p, c->s_RES.p, c->s_VALS.p, c->s_COST.p, EMI_EVAL_ALL))) return st;
+    if ((st = emi_kkt_certificate_dev(c, c->s_X.p, c->s_U.p, c->s_RES.p, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_zl.p, c->s_zu.p,
+                                      nsets, cl, cu, c->s_cert.p, c->s_G.p))) return st;
+    if ((st = download_real(c, cert, c->s_cert.p, B * 6))) return st;
+    if (G && (st = download_real(c, G, c->s_G.p, nG))) return st;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EMI_OK;
 }
 
 int emi_kkt_factor(emi_ctx_t c, const double* Qblk, const double* Jblk, const unsigned char* fixed, double dc,

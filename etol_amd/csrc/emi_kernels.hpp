@@ -51,6 +51,33 @@ hipError_t launch_symdefect(int model, const SymDefectArgs& a, hipStream_t s, bo
 bool pass_supported(int model, int ns, int B, int M, const SymPlan& plan);
 hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& plan);
 
+// the adjoint pass (emi_adjoint.hip): Lagrangian gradient G[B][ns+nc][M] and the per-instance KKT certificate, fp64
+struct AdjointArgs {
+    const double* VALS;     // [B][nvals][M]
+    const double* lamF;     // [B][ns][M]
+    const double* lamC;     // [B][np_table + np_traced][M] (may be null without path rows)
+    const double* DT;       // [M][ldt]: DT[n][j] = D[j][n], zero diagonal, zero padding
+    const int* pvars;       // [pw] node variables of the traced rows' partials (device)
+    double* G;              // [B][ns+nc][M]
+    int B, M, ldt, ns, nc, np_table, np_traced, pw, px, py, nvals;
+    int add_op;             // node kernels: 1 = add the operator term already in the state rows of G, 0 = write the node terms alone
+    double sigma;
+};
+struct CertArgs {
+    const double *X, *U, *RES, *VALS, *lamF, *lamC, *G;
+    const double *zl, *zu;  // [nsets][ns+nc][M]
+    const double *cl, *cu;  // [np] (device)
+    double* cert;           // [B][6]
+    int B, M, ns, nc, np, nres, nvals, nsets;
+    double sigma;
+};
+hipError_t launch_adjoint_transpose(const double* dD, double* dDT, int M, int ldt, hipStream_t s);
+bool adjoint_side_by_side(int B, int ns, int M);                      // batch large enough for the product to run beside the node kernel
+hipError_t launch_adjoint_op(const AdjointArgs& a, hipStream_t s);    // operator term into the state rows of a.G ([B][ns+nc][M])
+hipError_t launch_adjoint_nodes(const AdjointArgs& a, hipStream_t s);
+hipError_t launch_adjoint_add(const double* dGop, double* dG, int B, int ns, int nv, int M, hipStream_t s);
+hipError_t launch_kkt_certificate(const CertArgs& a, hipStream_t s);
+
 // model programs compiled at run time (emi_rtc.hip); the int results are EMI_* status codes
 struct RtcModel;
 int rtc_check(bool f32, const char* struct_name, const char* source, int ns, int nc, int npath, int pw, std::string* log);

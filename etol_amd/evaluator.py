@@ -209,6 +209,46 @@ class Evaluator:
                                          float(sigma), _dp(H)), "emi_hess_host")
         return H
 
+    # ---- adjoint pass: Lagrangian gradient and KKT certificate ------------------
+    CERT_FIELDS = ("stat", "comp", "defect", "viol", "gmax", "lmax")
+
+    def lagr_grad_dev(self, VALS, lamF, lamC, sigma, G):
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self.lib.emi_lagr_grad_dev(self.ctx, ptr(VALS), ptr(lamF), ptr(lamC), float(sigma), ptr(G)), "emi_lagr_grad_dev")
+
+    def lagr_grad_host(self, VALS, lamF, lamC, sigma=1.0):
+        lay = self.layout
+        VALS, lamF = (np.ascontiguousarray(a, dtype=np.float64) for a in (VALS, lamF))
+        lamC = np.ascontiguousarray(lamC if lamC is not None else np.zeros((lay.B, 0, lay.M)), dtype=np.float64)
+        assert VALS.shape == (lay.B, lay.nvals, lay.M) and lamF.shape == (lay.B, lay.ns, lay.M) and lamC.shape == (lay.B, lay.np, lay.M)
+        G = np.zeros((lay.B, lay.ns + lay.nc, lay.M))
+        self._ck(self.lib.emi_lagr_grad_host(self.ctx, _dp(VALS), _dp(lamF), _dp(lamC) if lamC.size else None, float(sigma), _dp(G)),
+                 "emi_lagr_grad_host")
+        return G
+
+    def kkt_certificate_dev(self, X, U, RES, VALS, lamF, lamC, sigma, zl, zu, cl, cu, cert, G=None):
+        """Device tensors, except cl / cu (host arrays [np]); zl / zu: [nsets][ns+nc][M], nsets 1 or B; cert: [B][6]."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        cl, cu = (np.ascontiguousarray(a, dtype=np.float64) for a in (cl, cu))
+        self._ck(self.lib.emi_kkt_certificate_dev(self.ctx, ptr(X), ptr(U), ptr(RES), ptr(VALS), ptr(lamF), ptr(lamC), float(sigma),
+                                                  ptr(zl), ptr(zu), int(zl.shape[0]), _dp(cl) if cl.size else None,
+                                                  _dp(cu) if cu.size else None, ptr(cert), ptr(G)), "emi_kkt_certificate_dev")
+
+    def kkt_certificate_host(self, X, U, lamF, lamC, zl, zu, cl=(), cu=(), sigma=1.0):
+        """Evaluates at (X, U) and certifies; returns (cert [B][6], G [B][ns+nc][M])."""
+        lay = self.layout
+        X, U, lamF, zl, zu, cl, cu = (np.ascontiguousarray(a, dtype=np.float64) for a in (X, U, lamF, zl, zu, cl, cu))
+        lamC = np.ascontiguousarray(lamC if lamC is not None else np.zeros((lay.B, 0, lay.M)), dtype=np.float64)
+        nv = lay.ns + lay.nc
+        if zl.ndim == 2:
+            zl, zu = zl[None], zu[None]
+        assert zl.shape == zu.shape and zl.shape[1:] == (nv, lay.M) and cl.shape == cu.shape == (lay.np,)
+        cert, G = np.zeros((lay.B, 6)), np.zeros((lay.B, nv, lay.M))
+        self._ck(self.lib.emi_kkt_certificate_host(self.ctx, _dp(X), _dp(U), _dp(lamF), _dp(lamC) if lamC.size else None, float(sigma),
+                                                   _dp(zl), _dp(zu), zl.shape[0], _dp(cl) if cl.size else None,
+                                                   _dp(cu) if cu.size else None, _dp(cert), _dp(G)), "emi_kkt_certificate_host")
+        return cert, G
+
     # ---- Newton step (KKT solve) on the device ----------------------------------
     def kkt_factor(self, Qblk, Jblk, fixed, dc=0.0):
         """Assemble and LU-factorise the KKT matrix of one instance; returns rocSOLVER's info (0 = ok)."""

@@ -11,6 +11,12 @@
 //
 //   etol_mi355x_montecarlo <scenarios> <nsteps> <keep-outs per scenario> <threads> [traced]
 //
+// With EMI_MC_CERTIFY=1 every rank certifies its solved scenarios of a mesh size in ONE batched call of the adjoint pass
+// (emi_kkt_certificate_host with B = scenarios, per-instance keep-out tables), writes <out>.cert.csv (columns scenario, stat,
+// comp, defect, viol, gmax, lmax; <out> = EMI_MC_CERT_OUT, else EMI_MC_SAVE/montecarlo, else ./montecarlo, with .rank<r>
+// behind it when there are several ranks) and prints the worst scenario of every column.  The per-solve certificate
+// (Alg::certify) is off in this program either way: nothing else it prints or writes changes.
+//
 // Scenario s draws its discs from SplitMix64(0xE70100 + 0x100*4 + s): centres U([1,9]^2), radii U(0.2,0.6),
 // redrawn while they cover the start or the goal.  Model: the 6-state planar quadrotor, as a built-in
 // device model or (5th argument "traced") written with mi355x::Var arithmetic and compiled at setup().
@@ -73,6 +79,8 @@ struct Result {
     std::string message;
     std::vector<double> states, controls, time;   // [6][nodes], [2][nodes], [nodes] of a solved scenario
     std::vector<mx::Sol::NlpRun> runs;            // the NLP solves of this scenario (ladder rungs, restarts), in order
+    // EMI_MC_CERTIFY: multipliers of the solve and what the batched certificate needs of the transcribed problem
+    std::vector<double> lamF, lamC, recs, zl, zu, cl, cu;
 };
 
 // one gathered record per scenario: header {scenario, rc, nodes, iterations, cost} then X[6][M], U[2][M], t[M]
@@ -212,6 +220,7 @@ Result solve_scenario(int s, int nsteps, int ndiscs, int device, bool traced, co
     if (getenv("EMI_MC_WARM_PUSH")) solver.getAlgorithm()->warm_bound_push = atof(getenv("EMI_MC_WARM_PUSH"));
     solver.getAlgorithm()->print_level = env_int("EMI_MC_PRINT_LEVEL", 0);
     solver.getAlgorithm()->kkt_batcher = batcher;          // the Newton steps of every scenario in flight share their launches
+    solver.getAlgorithm()->certify = false;                // (EMI_MC_CERTIFY certifies the whole rank in one batched call, below)
     t->solve();
     const mx::Sol* sol = solver.getSolution();
     R.rc = sol->error_flag;
@@ -221,9 +230,49 @@ Result solve_scenario(int s, int nsteps, int ndiscs, int device, bool traced, co
     R.runs = sol->nlp_runs;
     R.cost = sol->error_flag ? 0.0 : t->getScore();
     if (!sol->error_flag) { R.states = sol->states; R.controls = sol->controls; R.time = sol->time; }
+    if (!sol->error_flag && !traced && env_int("EMI_MC_CERTIFY", 0) > 0) {
+        const mx::Prob* P = solver.getProblem();
+        const size_t M = sol->nodes;
+        R.lamF = sol->lamF; R.lamC = sol->lamC; R.recs = P->path_records; R.cl = P->path_lower; R.cu = P->path_upper;
+        // variable bounds per node: the state / control boxes, intersected with the event bounds at the first and last node
+        R.zl.resize(8 * M); R.zu.resize(8 * M);
+        for (size_t v = 0; v < 8; ++v)
+            for (size_t k = 0; k < M; ++k) {
+                double l = v < 6 ? P->state_lower[v] : P->control_lower[v - 6], u = v < 6 ? P->state_upper[v] : P->control_upper[v - 6];
+                if (v < 6 && k == 0) { l = std::max(l, P->event_lower[v]); u = std::min(u, P->event_upper[v]); }
+                if (v < 6 && k == M - 1) { l = std::max(l, P->event_lower[6 + v]); u = std::min(u, P->event_upper[6 + v]); }
+                R.zl[v * M + k] = l; R.zu[v * M + k] = u;
+            }
+    }
     t->close();
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return R;
+}
+
+// EMI_MC_CERTIFY: the solved scenarios of one mesh size through ONE call of the adjoint pass (B = scenarios).  cert: [B][6].
+bool certify_batch(const std::vector<const Result*>& rs, int device, int ndiscs, std::vector<double>* cert, std::string* why) {
+    const int B = (int)rs.size(), M = rs[0]->nodes;
+    std::vector<double> tau(M), w(M), D((size_t)M * M), X, U, lamF, lamC, recs;
+    emi_lgl(M, tau.data(), w.data(), D.data());
+    for (const Result* r : rs) {
+        X.insert(X.end(), r->states.begin(), r->states.end());
+        U.insert(U.end(), r->controls.begin(), r->controls.end());
+        lamF.insert(lamF.end(), r->lamF.begin(), r->lamF.end());
+        lamC.insert(lamC.end(), r->lamC.begin(), r->lamC.end());
+        recs.insert(recs.end(), r->recs.begin(), r->recs.end());
+    }
+    const std::vector<double> mp = {1.0, 0.01, 9.81, 1.0, 1.0};
+    emi_ctx_t ctx = nullptr;
+    if (emi_create(device, &ctx) != EMI_OK) { *why = "emi_create: no device"; return false; }
+    cert->assign((size_t)B * 6, 0.0);
+    const bool ok = emi_set_mesh(ctx, M, tau.data(), w.data(), D.data(), 0.0, 4.0) == EMI_OK &&
+                    emi_set_model(ctx, EMI_MODEL_QUADROTOR2D, mp.data(), (int)mp.size(), 0) == EMI_OK && emi_set_batch(ctx, B) == EMI_OK &&
+                    (ndiscs == 0 || emi_set_path(ctx, ndiscs, B, recs.data(), 0, 1) == EMI_OK) &&
+                    emi_kkt_certificate_host(ctx, X.data(), U.data(), lamF.data(), ndiscs ? lamC.data() : nullptr, 1.0, rs[0]->zl.data(),
+                                             rs[0]->zu.data(), 1, rs[0]->cl.data(), rs[0]->cu.data(), cert->data(), nullptr) == EMI_OK;
+    if (!ok) *why = emi_last_error(ctx);
+    emi_destroy(ctx);
+    return ok;
 }
 
 }  // namespace
@@ -334,6 +383,59 @@ int main(int argc, char** argv) {
            "\"model\": \"%s\", \"kkt_batch_groups\": %d, \"wall_s\": %.3f, \"solves_per_s\": %.3f, \"mean_iterations\": %.1f}\n",
            rank, world, hi - lo, ok, nsteps + 1, ndiscs, nthreads, traced ? "traced" : "built-in", groups, wall,
            (hi - lo) / wall, results.empty() ? 0.0 : iters / results.size());
+
+    if (env_int("EMI_MC_CERTIFY", 0) > 0 && traced) printf("EMI_MC_CERTIFY: not available for the traced model\n");
+    if (env_int("EMI_MC_CERTIFY", 0) > 0 && !traced) {
+        std::map<int, std::vector<const Result*>> by_nodes;         // one batched call per mesh size
+        for (const Result& r : results)
+            if (r.rc == 0 && !r.lamF.empty()) by_nodes[r.nodes].push_back(&r);
+        std::string stem = getenv("EMI_MC_CERT_OUT") ? getenv("EMI_MC_CERT_OUT") : (getenv("EMI_MC_SAVE") ? std::string(getenv("EMI_MC_SAVE")) + "/montecarlo" : "montecarlo");
+        if (world > 1) stem += ".rank" + std::to_string(rank);
+        FILE* f = fopen((stem + ".cert.csv").c_str(), "w");
+        if (!f) { fprintf(stderr, "rank %d: cannot write %s.cert.csv\n", rank, stem.c_str()); return EXIT_FAILURE; }
+        fprintf(f, "scenario,stat,comp,defect,viol,gmax,lmax\n");
+        static const char* names[6] = {"stat", "comp", "defect", "viol", "gmax", "lmax"};
+        double worst[6] = {0, 0, 0, 0, 0, 0};
+        int worst_s[6] = {-1, -1, -1, -1, -1, -1}, certified = 0;
+        for (const auto& kv : by_nodes) {
+            std::vector<double> cert;
+            std::string why;
+            const auto c0 = std::chrono::steady_clock::now();
+            if (!certify_batch(kv.second, device, ndiscs, &cert, &why)) { fprintf(stderr, "rank %d: certificate: %s\n", rank, why.c_str()); fclose(f); return EXIT_FAILURE; }
+            printf("certified %zu scenarios of %d nodes in one call (%.1f ms, evaluation and transfers included)\n", kv.second.size(), kv.first,
+                   1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - c0).count());
+            for (size_t b = 0; b < kv.second.size(); ++b) {
+                const double* c = &cert[b * 6];
+                fprintf(f, "%d,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", kv.second[b]->scenario, c[0], c[1], c[2], c[3], c[4], c[5]);
+                for (int q = 0; q < 6; ++q)
+                    if (worst_s[q] < 0 || c[q] > worst[q]) { worst[q] = c[q]; worst_s[q] = kv.second[b]->scenario; }
+                ++certified;
+            }
+        }
+        fclose(f);
+        printf("{\"certified\": %d, \"cert_csv\": \"%s.cert.csv\"", certified, stem.c_str());
+        for (int q = 0; q < 6; ++q) printf(", \"worst_%s\": %.6e, \"worst_%s_scenario\": %d", names[q], worst[q], names[q], worst_s[q]);
+        printf("}\n");
+        if (getenv("EMI_MC_CERT_INPUTS")) {
+            // diagnostics: what went into the batched call, as raw doubles (header B M ns nc np, then per scenario: id, X, U, lamF, lamC,
+            // recs; then zl, zu, cl, cu of the set) -- for an outside check of the certificate at full precision
+            FILE* g = fopen(getenv("EMI_MC_CERT_INPUTS"), "wb");
+            if (g) {
+                for (const auto& kv : by_nodes) {
+                    const double head[5] = {(double)kv.second.size(), (double)kv.first, 6, 2, (double)ndiscs};
+                    fwrite(head, sizeof(double), 5, g);
+                    for (const Result* r : kv.second) {
+                        const double id = r->scenario;
+                        fwrite(&id, sizeof(double), 1, g);
+                        for (const std::vector<double>* v : {&r->states, &r->controls, &r->lamF, &r->lamC, &r->recs}) fwrite(v->data(), sizeof(double), v->size(), g);
+                    }
+                    const Result* r0 = kv.second[0];
+                    for (const std::vector<double>* v : {&r0->zl, &r0->zu, &r0->cl, &r0->cu}) fwrite(v->data(), sizeof(double), v->size(), g);
+                }
+                fclose(g);
+            }
+        }
+    }
 
     // ---- the one collective: every rank's trajectories to rank 0 over RCCL ------------------------------
     if (gather) {

@@ -1263,6 +1263,9 @@ void eMI355X::solve() {
     _solution.mesh_iterations = 0;
     _solution.nlp_iterations_total = 0;
     _solution.nlp_runs.clear();
+    _solution.certificate = mi355x::Sol::Certificate();
+    _solution.lamF.clear();
+    _solution.lamC.clear();
     _solution.ode_error = 0;
     bool sequenced = false;             // the requested mesh is started from the sequencing ladder's solution
     std::function<bool(double, bool)> climb;  // the ladder from its coarsest mesh with the straight-line guess bent by so much: true if every rung converged
@@ -1485,8 +1488,33 @@ void eMI355X::solve() {
     _solution.controls.assign(r.z.begin() + ns * M, r.z.begin() + (ns + nc) * M);      // (a lifted solve carries the delayed values behind them)
     _solution.time.resize(M);
     for (size_t k = 0; k < M; ++k) _solution.time[k] = P.t0 + (P.tf - P.t0) / 2.0 * (P.tau[k] + 1.0);
+    // solve_nlp hands its multipliers back unscaled (row scalings cscale / traced_scale and the variable scales undone; the
+    // jacobian-based defect scaling only weights its merit function) and in the device's row order
+    _solution.lamF.assign(r.lamF.begin(), r.lamF.begin() + std::min(r.lamF.size(), ns * M));
+    _solution.lamC = r.lamC;
+    _solution.certificate = mi355x::Sol::Certificate();
+    if (_algorithm.certify && !lift.on && _solution.lamF.size() == ns * M && _solution.lamC.size() == P.npath * M)
+        _solution.certificate = certify(r.z, _solution.lamF, _solution.lamC);
     setScore(isMaximized() ? -_solution.cost : _solution.cost);
     getTraj();
+}
+
+mi355x::Sol::Certificate eMI355X::certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC) {
+    mi355x::Prob& P = _problem;
+    if (!_dev || !_dev->ctx) die("certify(): setup() must run first");
+    if (P.ndelayed > 0) die("certify(): problems with delayed states / controls have no adjoint pass");
+    const size_t ns = P.nstates, nc = P.ncontrols, M = P.nodes;
+    if (z.size() != (ns + nc) * M || lamF.size() != ns * M || lamC.size() != P.npath * M)
+        die("certify(): z must hold (nstates + ncontrols) x nodes values, lamF nstates x nodes, lamC npath x nodes");
+    const mi355x::NlpProblem nlp = mi355x::make_nlp(P, _dev.get());      // the bounds the iteration works with
+    double c[6];
+    if (emi_kkt_certificate_host(_dev->ctx, z.data(), z.data() + ns * M, lamF.data(), P.npath ? lamC.data() : nullptr, 1.0, nlp.zl.data(),
+                                 nlp.zu.data(), 1, nlp.cl.data(), nlp.cu.data(), c, nullptr) != EMI_OK)
+        die(std::string("certify(): ") + emi_last_error(_dev->ctx));
+    mi355x::Sol::Certificate out;
+    out.stationarity = c[0]; out.complementarity = c[1]; out.defect = c[2]; out.violation = c[3]; out.grad_max = c[4]; out.lam_max = c[5];
+    out.computed = true;
+    return out;
 }
 
 // one (t_k, values) element per LGL node, states and controls (ePSOPT.cpp:157-182)

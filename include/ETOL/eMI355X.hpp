@@ -121,6 +121,9 @@ struct Alg {
                                                    // -- a Monte-Carlo batch waits for its slowest scenario, and the slowest are the ones that wander
                                                    // (profiles/r04_notes.md: median 105 iterations, 90th percentile 411, maximum 1028 at 1024 nodes)
     double nlp_tolerance = 1.e-6;
+    bool certify = true;                           // after a successful non-delayed solve(), one extra evaluation at the returned trajectory fills
+                                                   // Sol::certificate on the device (emi_kkt_certificate_host); false: skipped, computed stays false.
+                                                   // The iteration never sees it: iterates, counts and cost are the same either way
     double max_cpu_time = 1.e9;
     int print_level = 0;
     int device = 0;                                 // HIP device ordinal
@@ -150,6 +153,17 @@ struct Sol {
     std::vector<double> states;     // [nstates][nodes]
     std::vector<double> controls;   // [ncontrols][nodes]
     std::vector<double> time;       // [nodes]  LGL times h (tau_k + 1)
+    // Multipliers of the NLP the trajectory solves, in the caller's units (every scaling of the iteration undone) and in the device's
+    // RES row order (Prob::row_order): L = cost + sum lamF.defect + sum lamC.c is the Lagrangian whose Hessian blocks
+    // emi_hess_host(X, U, lamF, lamC, 1) returns; lamC >= 0 goes with an active upper bound of its row, <= 0 with a lower one
+    std::vector<double> lamF;       // [nstates][nodes]
+    std::vector<double> lamC;       // [npath][nodes]
+    // KKT residuals of (states, controls, lamF, lamC) computed on the device without an activity tolerance (include/emi355x.h,
+    // emi_kkt_certificate_*): maxima over the trajectory, in the caller's units
+    struct Certificate {
+        double stationarity = 0, complementarity = 0, defect = 0, violation = 0, grad_max = 0, lam_max = 0;
+        bool computed = false;
+    } certificate;
 };
 
 // The transcribed problem (what ePSOPT keeps in PSOPT's Prob).
@@ -213,6 +227,10 @@ class eMI355X : public TrajectoryOptimizer {
     // include/emi355x.h.  Needs setup().  With delayed states / controls the node variables of vals are
     // [x | u | delayed values] (emi_set_delays).
     void evaluate(const std::vector<double>& z, std::vector<double>* res, std::vector<double>* vals, double* cost);
+    // KKT certificate of any point on the current mesh (e.g. a trajectory read back from a file): z = [X (nstates x nodes),
+    // U (ncontrols x nodes)], multipliers as Sol::lamF / Sol::lamC.  One evaluation pass and the adjoint pass on the device,
+    // against the bounds of the transcribed problem.  Needs setup(); problems with delayed states / controls are not supported.
+    mi355x::Sol::Certificate certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC);
 
  protected:
     mi355x::Alg _algorithm;

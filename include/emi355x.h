@@ -48,6 +48,11 @@
  *   emi_kkt_*_batch    no counterpart: the reference runs one trajectory per
  *                      process; the Newton steps of several scenarios on one
  *                      mesh go through one sequence of batched launches
+ *   emi_lagr_grad_* / emi_kkt_certificate_*  the derivative checks and the dual_inf / compl_inf figures IPOPT
+ *                      reports behind ePSOPT.cpp:62-67 [IPOPT]: the gradient of the Lagrangian
+ *                      grad f + J^T lambda of a batch of trajectories (the adjoint of the defect pass, D^T on
+ *                      the matrix pipe) and, per trajectory, stationarity / complementarity / feasibility
+ *                      maxima in the caller's units, without an activity tolerance
  *   emi_plan_pass      no counterpart: the launch form emi_eval_* takes for a
  *                      batch size, so that tests and tools query the policy
  *                      instead of restating it
@@ -347,6 +352,36 @@ int emi_hess_dev(emi_ctx_t ctx, const void* dX, const void* dU,
 int emi_hess_host(emi_ctx_t ctx, const double* X, const double* U,
                   const double* LamF, const double* LamC, double sigma,
                   double* H);
+
+/* ---- the adjoint pass: Lagrangian gradient and KKT certificate (f64 contexts without delays) ----
+ * The NLP of one instance: minimise COST subject to defect rows RES[i][k] = 0, path rows cl_j <= RES[ns+j][k] <= cu_j and
+ * variable bounds zl[v][k] <= z[v][k] <= zu[v][k] (zl == zu fixes a variable; |bound| >= 1e19: absent).  Lagrangian
+ * L = sigma COST + sum lamF.defect + sum lamC.c -- the one whose Hessian blocks emi_hess_* returns: lamC >= 0 goes with an
+ * active upper bound, lamC <= 0 with an active lower one.
+ *   G[B][ns+nc][M]:  G[v][k] = sigma VALS[costgrad v][k] + sum_i VALS[i*nv+v][k] lamF[i][k]
+ *                            + (v < ns: sum_{j != k} D[j][k] lamF[v][j])  + sum over path rows and their partials VALS[.][k] lamC[r][k]
+ *                    (partials indexed as emi_jac_structure does).  LamC may be NULL when np == 0.
+ *   cert[B][6] = {stat, comp, defect, viol, gmax, lmax}, each a maximum over the instance; with G+ = max(G,0), G- = max(-G,0),
+ *   lamC+ / lamC- likewise:
+ *     stat    G+ where the variable has no lower bound, G- where it has no upper bound; fixed variables: 0
+ *     comp    G+ max(z-zl,0), G- max(zu-z,0) on bounded sides (not for fixed variables); lamC+ max(cu-c,0), lamC- max(c-cl,0)
+ *             on path rows; lamC+ / lamC- itself on a side without a bound
+ *     defect  |RES| over the ns defect rows;   viol  max(zl-z, z-zu, cl-c, c-cu, 0)
+ *     gmax    max |sigma costgrad|;  lmax  max(|lamF|, |lamC|)   (for relative figures)
+ *   A maximum has no summation order and G is summed in a fixed order: both are bit-reproducible call to call.
+ * zl, zu: [nsets][ns+nc][M], nsets 1 or B;  cl, cu: [np] HOST arrays in both forms.  The _dev forms are asynchronous on the
+ * context's stream (device pointers; dG may be NULL: the gradient then stays in the context's workspace).  The _host form of
+ * the certificate evaluates (EMI_EVAL_ALL) at (X, U) and then certifies; G may be NULL.
+ * EMI_ERR_UNSUPPORTED: f32 context, or delays set (emi_set_delays);  EMI_ERR_STATE: points-only mesh;  a NULL context on a
+ * machine without a device: EMI_ERR_NO_DEVICE.                                                                              */
+int emi_lagr_grad_dev(emi_ctx_t ctx, const void* dVALS, const void* dLamF, const void* dLamC, double sigma, void* dG);
+int emi_lagr_grad_host(emi_ctx_t ctx, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G);
+int emi_kkt_certificate_dev(emi_ctx_t ctx, const void* dX, const void* dU, const void* dRES, const void* dVALS,
+                            const void* dLamF, const void* dLamC, double sigma, const void* dZl, const void* dZu, int nsets,
+                            const double* cl, const double* cu, void* dCert, void* dG);
+int emi_kkt_certificate_host(emi_ctx_t ctx, const double* X, const double* U, const double* LamF, const double* LamC,
+                             double sigma, const double* zl, const double* zu, int nsets, const double* cl, const double* cu,
+                             double* cert, double* G);
 
 /* ---- measurement --------------------------------------------------------- */
 /* HIP-event timers on the context's stream.                                 */
