@@ -15,14 +15,12 @@
 #include <vector>
 
 #include "emi355x.h"
+#include "emi_device_array.hpp"
 #include "emi_kernels.hpp"
 
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
+using DevBuf = emi::DeviceArray<unsigned char>;    // untyped bytes: the context's real type is chosen at run time (f32 / f64)
 
 struct ProfEvents {
     hipEvent_t e[3];        // sequential path: e0 | node | e1 | defect | e2 ; overlapped: e0 fork, e1 join
@@ -146,11 +144,7 @@ int fail(emi_ctx_t c, int code, const char* fmt, ...) {
     } while (0)
 
 int ensure(emi_ctx_t c, DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return EMI_OK;
-    if (b.p) { HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-    if (bytes == 0) return EMI_OK;
-    HIP_TRY(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
+    HIP_TRY(c, b.reserve(bytes));
     return EMI_OK;
 }
 
@@ -544,11 +538,6 @@ int emi_destroy(emi_ctx_t c) {
     if (!c) return EMI_ERR_ARG;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&c->d_w, &c->d_t, &c->d_Ddiag, &c->d_D, &c->d_De, &c->d_Do, &c->d_path, &c->d_trkx, &c->d_trky,
-                      &c->d_cost_part, &c->d_slab, &c->d_tile_ticket, &c->d_cost_part2, &c->d_ticket, &c->s_X, &c->s_U, &c->s_RES, &c->s_VALS, &c->s_COST,
-                      &c->s_LF, &c->s_LC, &c->s_H, &c->d_adjDT, &c->d_adj_pvars, &c->d_adj_c, &c->d_adj_G, &c->d_adj_op, &c->s_G, &c->s_cert, &c->s_zl, &c->s_zu};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
     for (auto& pe : c->prof) {
         for (int i = 0; i < 3; ++i) (void)hipEventDestroy(pe.e[i]);
         for (int i = 0; i < 4; ++i) (void)hipEventDestroy(pe.k[i]);
@@ -1026,16 +1015,16 @@ static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRE
             if (plan.ks > 1) {
                 int est = ensure(c, c->d_slab, plan.slab_bytes);
                 if (est) return est;
-                if (c->d_tile_ticket.bytes < (size_t)plan.tiles * 4) {
+                if (c->d_tile_ticket.bytes() < (size_t)plan.tiles * 4) {
                     est = ensure(c, c->d_tile_ticket, (size_t)plan.tiles * 4);
                     if (est) return est;
-                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes, c->stream));
+                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes(), c->stream));
                 }
                 sa.ksplit = plan.ks;
                 sa.slab = (double*)c->d_slab.p;
                 sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
             }
-            if (c->d_ticket.bytes < (size_t)c->B * 4) {
+            if (c->d_ticket.bytes() < (size_t)c->B * 4) {
                 int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
                 if (est) return est;
                 HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, c->stream));
@@ -1076,10 +1065,10 @@ static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRE
             sa.slab = (double*)c->d_slab.p;
             sa.cpart = plan.cpart; sa.cx = plan.cx;
             if (sa.ksplit > 1 && c->sym_combine) {
-                if (c->d_tile_ticket.bytes < (size_t)plan.tiles * 4) {
+                if (c->d_tile_ticket.bytes() < (size_t)plan.tiles * 4) {
                     int est = ensure(c, c->d_tile_ticket, (size_t)plan.tiles * 4);
                     if (est) return est;
-                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes, s1));
+                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes(), s1));
                 }
                 sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
             }
@@ -1093,7 +1082,7 @@ static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRE
         // COST is finished inside the node kernel (last workgroup of an instance, by ticket, in chunk order): one launch
         // and one kernel boundary less at the end of every pass (emi_cost_finish_kernel alone was 5 us)
         if (c->cost_in_kernel) {
-            if (c->d_ticket.bytes < (size_t)c->B * 4) {
+            if (c->d_ticket.bytes() < (size_t)c->B * 4) {
                 int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
                 if (est) return est;
                 HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, s2));
@@ -1130,7 +1119,7 @@ static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRE
         fill_node_args(c, na, dX, dU, dRES, dVALS, dCOST);
         const size_t rowb = (size_t)c->M * 4;
         HIP_TRY(c, hipMemset2DAsync(dRES, (size_t)nres_of(c) * rowb, 0, (size_t)c->ns * rowb, c->B, c->stream));
-        if (c->d_ticket.bytes < (size_t)c->B * 4) {
+        if (c->d_ticket.bytes() < (size_t)c->B * 4) {
             int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
             if (est) return est;
             HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, c->stream));
@@ -1694,6 +1683,8 @@ int emi_set_option(emi_ctx_t c, const char* name, int value) {
         return EMI_OK;
     }
     if (strncmp(name, "kkt_", 4) == 0 && strcmp(name, "kkt_method") != 0) {
+        if (strcmp(name, "kkt_cholesky") == 0 && value != 1 && value != 2)
+            return fail(c, EMI_ERR_ARG, "kkt_cholesky must be 1 (one-level blocked Cholesky) or 2 (two-level form from 1024 rows)");
         if (emi::kkt_set_option(name, value)) return EMI_OK;
         return fail(c, EMI_ERR_ARG, "unknown option %s", name);
     }

@@ -23,7 +23,6 @@
 //              + Doff o (1 g^T) + (Doff o (1 g'^T))^T + diag(r)    element-wise, from P_k J_k^T and J_k P_k J_k^T
 // -> Cholesky (rocSOLVER potrf: 31 ms at 8192 rows where the LU of the full matrix takes 208 ms at
 // 14336), and a solve is two GEMMs with D, two triangular solves and node-local 8x8 products.
-#include <atomic>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocsolver/rocsolver.h>
@@ -32,11 +31,23 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 #include <vector>
 
+#include "emi_device_array.hpp"
 #include "emi_kernels.hpp"
+
+// error plumbing of the host functions below: they have `std::string* err` in scope and return an EMI_* status
+#define KKT_HIP(call)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) { *err = std::string(#call) + ": " + hipGetErrorString(e_); return EMI_ERR_HIP; } \
+    } while (0)
+#define KKT_RB(call)                                                                       \
+    do {                                                                                   \
+        rocblas_status s_ = (call);                                                        \
+        if (s_ != rocblas_status_success) { *err = std::string(#call) + ": " + rocblas_status_to_string(s_); return EMI_ERR_HIP; } \
+    } while (0)
 
 namespace emi {
 
@@ -44,12 +55,11 @@ namespace emi {
 // every number in profiles/ was measured with)
 struct KktTuning {
     std::atomic<int> chol_outer{768};       // "kkt_chol_outer": columns of an outer panel of the two-level Cholesky
-    std::atomic<int> own_cholesky{2};       // "kkt_cholesky": 2 the library's blocked Cholesky in two-level form from 1024 rows (default), 1 one level, 0 rocsolver_dpotrf (+ confirmation on a copy)
+    std::atomic<int> own_cholesky{2};       // "kkt_cholesky": 2 the library's blocked Cholesky in two-level form from 1024 rows (default), 1 one level
     std::atomic<int> own_diag{2};           // "kkt_chol_diag": 2 the diagonal block by one wave with matrix-pipe updates (default), 1 the 256-thread column-by-column kernel
     std::atomic<int> own_panel{2};          // "kkt_chol_panel": 2 own panel kernel on the matrix pipe (default), 1 its scalar form, 0 rocblas_dtrsm
     std::atomic<int> batched_max_nodes{256};// "kkt_batched_max_nodes": largest mesh with the batched Schur-block build
     std::atomic<int> debug{0};              // "kkt_debug": 1 retries and fallbacks on stderr, 2 also the blocks around a failing pivot
-    std::atomic<int> potrf_lock{0};         // "kkt_potrf_lock": serialise rocsolver_dpotrf calls of different host threads
     std::atomic<int> sticky_reg{1};         // "kkt_sticky_reg": start the Schur path at the regularisation level that worked last on this mesh
     std::atomic<int> block_trsv{1};         // "kkt_block_trsv": 1 single right-hand sides through the block-inverse triangular solves below (gemv form), 2 the same with the library's own diagonal-block kernel, 0 rocsolver_dpotrs (trsv)
     std::atomic<int> primal_levels{1};      // "kkt_primal_levels": 1 primal regularisation levels behind the dual ones before the LU fallback, 0 the round-2 ladder
@@ -69,12 +79,11 @@ struct KktTuning {
 static KktTuning g_tune;
 bool kkt_set_option(const char* name, int value) {
     if (!strcmp(name, "kkt_chol_outer")) { g_tune.chol_outer = value; return true; }
-    if (!strcmp(name, "kkt_cholesky")) { g_tune.own_cholesky = value < 0 ? 0 : (value > 2 ? 2 : value); return true; }
+    if (!strcmp(name, "kkt_cholesky")) { if (value != 1 && value != 2) return false; g_tune.own_cholesky = value; return true; }
     if (!strcmp(name, "kkt_chol_diag")) { g_tune.own_diag = value; return true; }
     if (!strcmp(name, "kkt_chol_panel")) { g_tune.own_panel = value < 0 ? 0 : (value > 2 ? 2 : value); return true; }
     if (!strcmp(name, "kkt_batched_max_nodes")) { g_tune.batched_max_nodes = value; return true; }
     if (!strcmp(name, "kkt_debug")) { g_tune.debug = value; return true; }
-    if (!strcmp(name, "kkt_potrf_lock")) { g_tune.potrf_lock = value != 0; return true; }
     if (!strcmp(name, "kkt_sticky_reg")) { g_tune.sticky_reg = value != 0; return true; }
     if (!strcmp(name, "kkt_block_trsv")) { g_tune.block_trsv = value < 0 ? 0 : (value > 2 ? 2 : value); return true; }
     if (!strcmp(name, "kkt_primal_levels")) { g_tune.primal_levels = value != 0; return true; }
@@ -87,79 +96,63 @@ bool kkt_set_option(const char* name, int value) {
 
 struct KktWorkspace {
     rocblas_handle handle = nullptr;
-    double* K = nullptr;        // [N][N] column-major (symmetric before the factorisation)
-    size_t K_elems = 0;
-    rocblas_int* ipiv = nullptr;
-    rocblas_int* info = nullptr;
-    double* Q = nullptr;        // [nh][M]
-    double* J = nullptr;        // [ns*nv][M]
-    double* rhs = nullptr;      // [N][nrhs] column-major
-    size_t rhs_elems = 0;
-    unsigned char* fixed = nullptr;   // [nv*M]
-    size_t cap_ipiv = 0, cap_Q = 0, cap_J = 0, cap_fixed = 0;     // bytes allocated (contexts are reused across problems)
+    DeviceArray<double> K;              // [N][N] column-major (symmetric before the factorisation)
+    DeviceArray<rocblas_int> ipiv, info;
+    DeviceArray<double> Q;              // [nh][M]
+    DeviceArray<double> J;              // [ns*nv][M]
+    DeviceArray<double> rhs;            // [N][nrhs] column-major
+    DeviceArray<unsigned char> fixed;   // [nv*M]
     int N = 0;
     bool factored = false;
     // method 1 (Schur complement + Cholesky)
     int method_used = 0;        // what the current factorisation is: 0 LU of K, 1 Cholesky of S
     int M = 0, ns = 0, nv = 0;
-    double* S = nullptr;        // [md][md] column-major, lower triangle
-    size_t S_elems = 0;
-    double* Pinv = nullptr;     // [nv*nv][M]  Q_k^-1 (zero rows/columns for fixed variables)
-    double* G = nullptr;        // [ns*ns][M]  (P_k J_k^T) state rows
-    double* Rk = nullptr;       // [ns*ns][M]  J_k P_k J_k^T
-    double* Doff = nullptr;     // [M][M] D without its diagonal (same storage order as D)
-    double* W = nullptr;        // [pairs][M][M] scaled copies of Doff, one per state pair (one [M][M] in the unbatched form)
-    double** gemm_ptrs = nullptr;   // device: [3][pairs] operand pointers of the batched GEMM (A: Doff, B: W_p, C: S block)
+    DeviceArray<double> S;              // [md][md] column-major, lower triangle
+    DeviceArray<double> Pinv;           // [nv*nv][M]  Q_k^-1 (zero rows/columns for fixed variables)
+    DeviceArray<double> G;              // [ns*ns][M]  (P_k J_k^T) state rows
+    DeviceArray<double> Rk;             // [ns*ns][M]  J_k P_k J_k^T
+    DeviceArray<double> Doff;           // [M][M] D without its diagonal (same storage order as D)
+    DeviceArray<double> W;              // [pairs][M][M] scaled copies of Doff, one per state pair (one [M][M] in the unbatched form)
+    DeviceArray<double*> gemm_ptrs;     // device: [3][pairs] operand pointers of the batched GEMM (A: Doff, B: W_p, C: S block)
     const double* ptrs_key[3] = {nullptr, nullptr, nullptr};   // (Doff, W, S) the pointer table was built for
     int ptrs_M = 0, ptrs_ns = 0;
-    double* T = nullptr;        // [nz][nrhs] work
-    double* Cb = nullptr;       // [md][nrhs] work
-    size_t T_elems = 0, Cb_elems = 0;
-    size_t cap_Pinv = 0, cap_G = 0, cap_Rk = 0, cap_Doff = 0, cap_W = 0;
-    int* flag = nullptr;        // node kernel: a block was not positive definite
+    DeviceArray<double> T;              // [nz][nrhs] work
+    DeviceArray<double> Cb;             // [md][nrhs] work
+    DeviceArray<int> flag;              // node kernel: a block was not positive definite
     // dual-regularisation level the Schur path starts from (0: nominal, 1: x1e3, 2: x1e6): late interior-point iterations
     // on one mesh fail at the same levels again and again, and every failed level costs a build of S and a Cholesky.
-    // Kept per mesh shape; after two successes in a row one level lower is tried again.  The LU is never the starting point:
+    // Kept per mesh shape; after four successes in a row one level lower is tried again.  The LU is never the starting point:
     // a wandering solve (inertia search: many trial matrices per iteration) stuck there with 209 of 585 factorisations
     // at 85 ms each where the Cholesky path, tried, takes 10 ms (513 nodes, profiles/r02_notes.md section 12).
     int reg_level = 0, reg_hits = 0, reg_M = 0, reg_ns = 0, reg_nv = 0;
     double reg_dc_applied = 0.0, reg_dw_applied = 0.0;    // what the current factorisation really holds (kkt_last_regularisation)
     // single-right-hand-side solves with the Cholesky factor of S (blk_potrs): inverses of its 512 x 512 diagonal blocks
-    double* Linv = nullptr;        // [nblk][512][512] column-major, zeros above the diagonal
-    size_t cap_Linv = 0;
-    double* LinvT = nullptr;       // the same blocks transposed (the forward sweep multiplies with op T as well)
-    size_t cap_LinvT = 0;
-    int linv_n = 0;                // order of the factor the inverses belong to (0: none -- rocsolver_dpotrs is used)
-    double* trsv_tmp = nullptr;    // [512] x_j while its block is being multiplied
-    size_t cap_trsv_tmp = 0;
-    double* trsv_y = nullptr;      // [n] forward-sweep solution of the gemv form of blk_potrs
-    size_t cap_trsv_y = 0;
-    double* trsm_y = nullptr;      // [n][nrhs] the same for many right-hand sides (blk_potrs_multi)
-    size_t cap_trsm_y = 0;
-    double* chol_blk = nullptr;    // [64][64] + [64]: factorised diagonal block and reciprocal diagonal of the current block column
-    double* chol_copy = nullptr;   // the matrix handed to dpotrf, kept until the factorisation is confirmed (potrf_checked)
-    size_t cap_chol_copy = 0;
+    DeviceArray<double> Linv;           // [nblk][512][512] column-major, zeros above the diagonal
+    DeviceArray<double> LinvT;          // the same blocks transposed (the forward sweep multiplies with op T as well)
+    int linv_n = 0;                     // order of the factor the inverses belong to (0: none -- rocsolver_dpotrs is used)
+    DeviceArray<double> trsv_tmp;       // [512] x_j while its block is being multiplied
+    DeviceArray<double> trsv_y;         // [n] forward-sweep solution of the gemv form of blk_potrs
+    DeviceArray<double> trsm_y;         // [n][nrhs] the same for many right-hand sides (blk_potrs_multi)
+    DeviceArray<double> chol_blk;       // [64][64] + [64]: factorised diagonal block and reciprocal diagonal of the current block column
     // low-rank correction (kkt_lowrank)
     bool lr_active = false;
-    int lr_r = 0, lr_cap = 0, lr_n = 0, lr_nv = 0;   // columns in use, columns allocated, rows of lrY, entries per column of lr_vec
-    double* lrY = nullptr;      // [N][r]  K~^-1 U
-    double* lrC = nullptr;      // [r][r]  Cholesky factor of Delta^-1 - U^T Y
-    double* lrT = nullptr;      // [r][<=64] work
-    int* lr_node = nullptr;
-    double* lr_vec = nullptr;   // [r][nv] (sorted by node, as lr_node and lr_delta)
-    double* lr_delta = nullptr;
+    int lr_r = 0, lr_cap = 0;           // columns in use, columns allocated
+    DeviceArray<double> lrY;            // [N][r]  K~^-1 U
+    DeviceArray<double> lrC;            // [r][r]  Cholesky factor of Delta^-1 - U^T Y
+    DeviceArray<double> lrT;            // [r][<=64] work
+    DeviceArray<int> lr_node;
+    DeviceArray<double> lr_vec;         // [r][nv] (sorted by node, as lr_node and lr_delta)
+    DeviceArray<double> lr_delta;
     // refined solves (kkt_solve_refined_batch): right-hand side, solution, previous solution on the device
-    double *ref_b = nullptr, *ref_x = nullptr, *ref_p = nullptr;
-    size_t cap_ref_b = 0, cap_ref_x = 0, cap_ref_p = 0;
+    DeviceArray<double> ref_b, ref_x, ref_p;
     // Doff is a function of the mesh only: rebuilt when the mesh changes (kkt_mesh_changed), not at every factorisation
     const double* doff_src = nullptr;
     int doff_M = 0;
     // batched entry points (kkt_factor_batch / kkt_solve_batch): scratch of the workspace that LEADS a batch
-    void* b_tab = nullptr;      // device: KktDev[n]
-    double** b_ptrs = nullptr;  // device: pointer arrays of the batched rocBLAS calls
-    int* b_stat = nullptr;      // device: [2 n] info words, then block flags
-    char* b_pin = nullptr;      // pinned host staging of all three
-    size_t cap_b_tab = 0, cap_b_ptrs = 0, cap_b_stat = 0, cap_b_pin = 0;
+    DeviceArray<unsigned char> b_tab;   // device: KktDev[n]
+    DeviceArray<double*> b_ptrs;        // device: pointer arrays of the batched rocBLAS calls
+    DeviceArray<unsigned char> b_stat;  // device: [2 n] info words, then block flags (factorisation); [4 n] doubles (refined solves)
+    PinnedArray<char> b_pin;            // pinned host staging of all three
 };
 
 namespace {
@@ -486,8 +479,6 @@ __global__ void emi_kkt_lr_utx_kernel(double* __restrict__ T, const double* __re
     for (int v = 0; v < nv; ++v) dot += vec[(size_t)a * nv + v] * x[(size_t)v * M];
     T[(size_t)c * r + a] = dot;
 }
-
-const char* rb(rocblas_status s) { return rocblas_status_to_string(s); }
 
 // ---- blocked Cholesky (lower, column-major, in place) ---------------------------------------------------
 // Right-looking with 64-column blocks: the diagonal block is factorised by one workgroup with the rows in registers,
@@ -987,187 +978,102 @@ __global__ void emi_kkt_zero_status_b_kernel(const KktDev* __restrict__ tab, int
     if (b < n) { *tab[b].flag = 0; *tab[b].info = 0; }
 }
 
-// error plumbing of the host functions below: they have `std::string* err` in scope and return an EMI_* status
-#define KKT_HIP(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) { *err = std::string(#call) + ": " + hipGetErrorString(e_); return EMI_ERR_HIP; } \
-    } while (0)
-#define KKT_ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                                   \
-        if ((cap) < (size_t)(bytes)) {                                                     \
-            if (ptr) KKT_HIP(hipFree(ptr));                                                \
-            (ptr) = nullptr;                                                               \
-            (cap) = 0;                                                                     \
-            KKT_HIP(hipMalloc((void**)&(ptr), (bytes)));                                   \
-            (cap) = (bytes);                                                               \
-        }                                                                                  \
-    } while (0)
-#define KKT_RB(call)                                                                       \
-    do {                                                                                   \
-        rocblas_status s_ = (call);                                                        \
-        if (s_ != rocblas_status_success) { *err = std::string(#call) + ": " + rb(s_); return EMI_ERR_HIP; } \
-    } while (0)
-
-// rocsolver_dpotrf (ROCm 7.2) is not reliable while other host threads keep the GPU busy on their own handles and
-// streams: about 1 % of the calls (65-node problems, 6 threads) report a non-positive pivot in an odd 64-column block
-// of a matrix that factorises when the call is repeated on the same data (tools/race_probe.py,
-// profiles/r01_notes.md; dgetrf, dpotrs and the GEMMs showed no such effect).  The solver then took a more
-// regularised step than a single-threaded run, and iteration paths differed from run to run.  Two measures:
-// the calls are serialised across the process (the stream is drained first, so the lock covers the factorisation
-// alone; this alone removes the effect at 65 nodes and leaves 1 in 1000 at 257), and a reported failure is
-// confirmed on a kept copy of the matrix before it is believed.
-std::mutex g_potrf_mutex;
-std::atomic<long> g_potrf_spurious{0};
-
-// A (n x n, lda == n) <- its Cholesky factor; *hinfo = 0, or the position of the first non-positive pivot
-int potrf_checked(KktWorkspace* w, hipStream_t stream, rocblas_int n, double* A, rocblas_int* hinfo, std::string* err) {
-    const size_t bytes = (size_t)n * n * sizeof(double);
-    if (w->cap_chol_copy < bytes) {
-        if (w->chol_copy) KKT_HIP(hipFree(w->chol_copy));
-        w->chol_copy = nullptr;
-        w->cap_chol_copy = 0;
-        KKT_HIP(hipMalloc((void**)&w->chol_copy, bytes));
-        w->cap_chol_copy = bytes;
-    }
-    KKT_HIP(hipMemcpyAsync(w->chol_copy, A, bytes, hipMemcpyDeviceToDevice, stream));
-    rocblas_int first = 0;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        if (attempt > 0) KKT_HIP(hipMemcpyAsync(A, w->chol_copy, bytes, hipMemcpyDeviceToDevice, stream));
-        const bool serialise = g_tune.potrf_lock.load() != 0;
-        std::unique_lock<std::mutex> lk(g_potrf_mutex, std::defer_lock);
-        if (serialise) {
-            KKT_HIP(hipStreamSynchronize(stream));
-            lk.lock();
-        }
-        KKT_RB(rocsolver_dpotrf(w->handle, rocblas_fill_lower, n, A, n, w->info));
-        KKT_HIP(hipMemcpyAsync(hinfo, w->info, sizeof *hinfo, hipMemcpyDeviceToHost, stream));
-        KKT_HIP(hipStreamSynchronize(stream));
-        if (serialise) lk.unlock();
-        if (*hinfo == 0) {
-            if (attempt > 0) {
-                ++g_potrf_spurious;
-                if (g_tune.debug.load())
-                    fprintf(stderr, "emi_kkt: dpotrf reported pivot %d of %d, the same matrix factorised on repeat %d\n", (int)first,
-                            (int)n, attempt);
-            }
-            return EMI_OK;
-        }
-        if (attempt > 0 && *hinfo == first) return EMI_OK;      // the same verdict twice: the matrix is not positive definite
-        first = *hinfo;
-    }
-    return EMI_OK;
-}
-
-// A (n x n, lda == n) <- its lower Cholesky factor with the kernels above; *hinfo as rocsolver_dpotrf reports it
-int chol_blocked(KktWorkspace* w, hipStream_t stream, rocblas_int n, double* A, rocblas_int* hinfo, std::string* err) {
-    KKT_HIP(hipMemsetAsync(w->info, 0, sizeof(rocblas_int), stream));
-    if (!w->chol_blk) KKT_HIP(hipMalloc((void**)&w->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
-    const double one = 1.0, mone = -1.0;
-    for (int j0 = 0; j0 < n; j0 += CHOL_NB) {
-        const int nb = std::min(CHOL_NB, (int)n - j0), rest = (int)n - j0 - nb;
-        if (nb == CHOL_NB && g_tune.own_diag.load() == 2)
-            hipLaunchKernelGGL(emi_chol_diag_mfma_kernel, dim3(1), dim3(64), 0, stream, A, (int)n, j0, (int*)w->info, w->chol_blk);
-        else
-            hipLaunchKernelGGL(emi_chol_diag_kernel, dim3(1), dim3(256), 0, stream, A, (int)n, j0, nb, (int*)w->info, w->chol_blk);
-        if (rest > 0) {
-            double* P = A + (size_t)j0 * n + j0 + nb;
-            // own kernel by default; rocblas_dtrsm (EMI_CHOL_PANEL=0) is 5 % faster on a single 1024-node solve and 20-40 %
-            // slower on eight concurrent 129-node solves (profiles/r01_notes.md)
-            const int own_panel = g_tune.own_panel.load();
-            if (own_panel == 2) {
-                hipLaunchKernelGGL(emi_chol_panel_mfma_kernel, dim3((rest + 63) / 64), dim3(64), 0, stream, A, (int)n, (int)n, j0,
-                                   (const double*)w->chol_blk);
-                KKT_HIP(hipGetLastError());
-            } else if (own_panel) {
-                hipLaunchKernelGGL(emi_chol_panel_kernel, dim3((rest + EMI_PANEL_THREADS - 1) / EMI_PANEL_THREADS), dim3(EMI_PANEL_THREADS), 0, stream, A, (int)n, (int)n, j0,
-                                   (const double*)w->chol_blk);
-                KKT_HIP(hipGetLastError());
-            } else {
-                KKT_RB(rocblas_dtrsm(w->handle, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
-                                     rocblas_diagonal_non_unit, rest, nb, &one, A + (size_t)j0 * n + j0, n, P, n));
-            }
-            double* A22 = A + (size_t)(j0 + nb) * n + j0 + nb;
-            KKT_RB(rocblas_dsyrk(w->handle, rocblas_fill_lower, rocblas_operation_none, rest, nb, &mone, P, n, &one, A22, n));
-        }
-    }
-    KKT_HIP(hipGetLastError());
-    KKT_HIP(hipMemcpyAsync(hinfo, w->info, sizeof *hinfo, hipMemcpyDeviceToHost, stream));
-    KKT_HIP(hipStreamSynchronize(stream));
-    return EMI_OK;
-}
-
-// Two-level form of chol_blocked: the 64-column steps update only the rest of their 512-column OUTER panel (one small dgemm
-// each), and the trailing matrix beyond the outer panel gets one rank-512 dsyrk per outer step instead of eight rank-64 ones
-// (same flops, 12 large updates instead of 96 small ones at 6144 rows).  The inner dgemm writes whole rectangles, so the strict
-// upper triangle inside an outer panel's diagonal block is scratch afterwards -- every consumer of the factor reads its lower
+// The schedule of the blocked Cholesky of an n x n matrix, written once for the single routine and the batched one.
+// Two levels: the 64-column steps update only the rest of their OUTER panel of `outer` columns (one small dgemm each), and the
+// trailing matrix beyond the outer panel gets one rank-`outer` dsyrk per outer panel instead of one rank-64 update per step (same
+// flops, 12 large updates instead of 96 small ones at 6144 rows with 512 columns).  The inner dgemm writes whole rectangles, so the
+// strict upper triangle inside an outer panel's diagonal block is scratch afterwards -- every consumer of the factor reads its lower
 // triangle only (dtrtri / dtrsm / dpotrs with fill_lower, the gemv updates of blk_potrs on blocks below the diagonal).
-int chol_blocked2(KktWorkspace* w, hipStream_t stream, rocblas_int n, double* A, rocblas_int* hinfo, std::string* err) {
-    const int NB2 = std::max(128, (g_tune.chol_outer.load() / CHOL_NB) * CHOL_NB);
-    KKT_HIP(hipMemsetAsync(w->info, 0, sizeof(rocblas_int), stream));
-    if (!w->chol_blk) KKT_HIP(hipMalloc((void**)&w->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
-    const double one = 1.0, mone = -1.0;
-    for (int J0 = 0; J0 < n; J0 += NB2) {
-        const int Jend = std::min((int)n, J0 + NB2);
+// outer == 64 is the one-level form: a step has nothing right of it in its panel (wc == 0, no dgemm) and the outer update IS the
+// step's rank-64 dsyrk of everything below and right of it.
+struct CholStep { int j0, nb, rest, wc; };     // diagonal block at j0 of nb <= 64 columns, rows below it, columns of the outer panel right of it
+struct CholOuter { int J0, Jend, rest2; };     // columns [J0, Jend) done, rest2 rows and columns beyond them
+template <class StepFn, class OuterFn>
+int chol_walk(int n, int outer, StepFn&& step, OuterFn&& outer_update) {
+    for (int J0 = 0; J0 < n; J0 += outer) {
+        const int Jend = std::min(n, J0 + outer);
         for (int j0 = J0; j0 < Jend; j0 += CHOL_NB) {
-            const int nb = std::min(CHOL_NB, (int)n - j0), rest = (int)n - j0 - nb;
-            if (nb == CHOL_NB && g_tune.own_diag.load() == 2)
-            hipLaunchKernelGGL(emi_chol_diag_mfma_kernel, dim3(1), dim3(64), 0, stream, A, (int)n, j0, (int*)w->info, w->chol_blk);
-        else
-            hipLaunchKernelGGL(emi_chol_diag_kernel, dim3(1), dim3(256), 0, stream, A, (int)n, j0, nb, (int*)w->info, w->chol_blk);
-            if (rest <= 0) continue;
-            if (g_tune.own_panel.load() == 2)
-                hipLaunchKernelGGL(emi_chol_panel_mfma_kernel, dim3((rest + 63) / 64), dim3(64), 0, stream, A, (int)n, (int)n, j0,
-                                   (const double*)w->chol_blk);
-            else
-                hipLaunchKernelGGL(emi_chol_panel_kernel, dim3((rest + EMI_PANEL_THREADS - 1) / EMI_PANEL_THREADS), dim3(EMI_PANEL_THREADS), 0, stream, A, (int)n, (int)n, j0,
-                               (const double*)w->chol_blk);
-            const int wc = Jend - (j0 + nb);            // columns of the outer panel right of this step
-            if (wc > 0) {
-                double* P = A + (size_t)j0 * n + j0 + nb;                 // rest x nb, the step's panel below its diagonal block
-                double* A22 = A + (size_t)(j0 + nb) * n + j0 + nb;        // rest x wc
-                KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_transpose, rest, wc, nb, &mone, P, n, P, n, &one,
-                                     A22, n));
-            }
+            const int nb = std::min(CHOL_NB, n - j0);
+            if (int st = step(CholStep{j0, nb, n - j0 - nb, Jend - (j0 + nb)})) return st;
         }
-        const int rest2 = (int)n - Jend, W = Jend - J0;
-        if (rest2 > 0) {
-            double* P2 = A + (size_t)J0 * n + Jend;                       // rest2 x W
-            double* A33 = A + (size_t)Jend * n + Jend;
-            KKT_RB(rocblas_dsyrk(w->handle, rocblas_fill_lower, rocblas_operation_none, rest2, W, &mone, P2, n, &one, A33, n));
-        }
+        if (int st = outer_update(CholOuter{J0, Jend, n - Jend})) return st;
     }
+    return EMI_OK;
+}
+// "kkt_chol_outer": columns of an outer panel of the two-level form (whole 64-column steps, at least two)
+int chol_outer_panel() { return std::max(128, (g_tune.chol_outer.load() / CHOL_NB) * CHOL_NB); }
+
+// A (n x n, lda == n) <- its lower Cholesky factor with the kernels above, outer panels of `outer` columns; *hinfo = 0, or the
+// position of the first non-positive pivot (1-based)
+int chol_single(KktWorkspace* w, hipStream_t stream, int n, double* A, int outer, rocblas_int* hinfo, std::string* err) {
+    KKT_HIP(hipMemsetAsync(w->info.p, 0, sizeof(rocblas_int), stream));
+    KKT_HIP(w->chol_blk.reserve(CHOL_NB * CHOL_NB + CHOL_NB));
+    const double one = 1.0, mone = -1.0;
+    const int own_diag = g_tune.own_diag.load(), own_panel = g_tune.own_panel.load();
+    auto step = [&](const CholStep& s) -> int {
+        const int j0 = s.j0, nb = s.nb, rest = s.rest;
+        if (nb == CHOL_NB && own_diag == 2)
+            hipLaunchKernelGGL(emi_chol_diag_mfma_kernel, dim3(1), dim3(64), 0, stream, A, n, j0, (int*)w->info.p, w->chol_blk.p);
+        else
+            hipLaunchKernelGGL(emi_chol_diag_kernel, dim3(1), dim3(256), 0, stream, A, n, j0, nb, (int*)w->info.p, w->chol_blk.p);
+        if (rest <= 0) return EMI_OK;
+        double* P = A + (size_t)j0 * n + j0 + nb;                     // rest x nb, the step's panel below its diagonal block
+        // own kernel by default; rocblas_dtrsm ("kkt_chol_panel" 0) is 5 % faster on a single 1024-node solve and 20-40 %
+        // slower on eight concurrent 129-node solves (profiles/r01_notes.md)
+        if (own_panel == 2)
+            hipLaunchKernelGGL(emi_chol_panel_mfma_kernel, dim3((rest + 63) / 64), dim3(64), 0, stream, A, n, n, j0, (const double*)w->chol_blk.p);
+        else if (own_panel)
+            hipLaunchKernelGGL(emi_chol_panel_kernel, dim3((rest + EMI_PANEL_THREADS - 1) / EMI_PANEL_THREADS), dim3(EMI_PANEL_THREADS), 0, stream,
+                               A, n, n, j0, (const double*)w->chol_blk.p);
+        else
+            KKT_RB(rocblas_dtrsm(w->handle, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, rest,
+                                 nb, &one, A + (size_t)j0 * n + j0, n, P, n));
+        if (s.wc > 0) {
+            double* A22 = A + (size_t)(j0 + nb) * n + j0 + nb;        // rest x wc
+            KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_transpose, rest, s.wc, nb, &mone, P, n, P, n, &one, A22, n));
+        }
+        return EMI_OK;
+    };
+    auto outer_update = [&](const CholOuter& o) -> int {
+        if (o.rest2 <= 0) return EMI_OK;
+        double* P2 = A + (size_t)o.J0 * n + o.Jend;                   // rest2 x (Jend - J0)
+        double* A33 = A + (size_t)o.Jend * n + o.Jend;
+        KKT_RB(rocblas_dsyrk(w->handle, rocblas_fill_lower, rocblas_operation_none, o.rest2, o.Jend - o.J0, &mone, P2, n, &one, A33, n));
+        return EMI_OK;
+    };
+    if (int st = chol_walk(n, outer, step, outer_update)) return st;
     KKT_HIP(hipGetLastError());
-    KKT_HIP(hipMemcpyAsync(hinfo, w->info, sizeof *hinfo, hipMemcpyDeviceToHost, stream));
+    KKT_HIP(hipMemcpyAsync(hinfo, w->info.p, sizeof *hinfo, hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;
 }
 
-// which Cholesky ("kkt_cholesky"): 2 (default) the two-level form from 1024 rows (below: the one-level one), 1 one level always,
-// 0 rocsolver_dpotrf with the confirmation on a copy.  Factorisation of the 1024 / 512 / 256-node Schur complement (S build
-// included; tools/scratch/chol_time.py, one box): one level 16.85 / 7.38 / 3.36 ms, outer panels of 256 / 512 / 768 / 1024
-// columns 14.68 / 13.96 / 13.36 / 13.28 ms at 1024 nodes, 5.79 and 2.64 ms with 768 at 512 and 256 nodes.
+// which Cholesky ("kkt_cholesky"): 2 (default) the two-level form from 1024 rows (below: the one-level one), 1 one level always.
+// Factorisation of the 1024 / 512 / 256-node Schur complement (S build included; tools/scratch/chol_time.py, one box): one level
+// 16.85 / 7.38 / 3.36 ms, outer panels of 256 / 512 / 768 / 1024 columns 14.68 / 13.96 / 13.36 / 13.28 ms at 1024 nodes, 5.79 and
+// 2.64 ms with 768 at 512 and 256 nodes.
+// rocsolver_dpotrf is not used: in ROCm 7.2 about 1 % of its calls reported a non-positive pivot in a matrix that factorises when the
+// call is repeated, while other host threads kept the GPU busy (profiles/r01_notes.md); iteration paths then differed from run to run.
 int cholesky(KktWorkspace* w, hipStream_t stream, rocblas_int n, double* A, rocblas_int* hinfo, std::string* err) {
-    const int own = g_tune.own_cholesky.load();
-    if (own == 2 && n >= 2 * 512) return chol_blocked2(w, stream, n, A, hinfo, err);
-    return own ? chol_blocked(w, stream, n, A, hinfo, err) : potrf_checked(w, stream, n, A, hinfo, err);
+    const bool two_level = g_tune.own_cholesky.load() == 2 && n >= 2 * 512;
+    return chol_single(w, stream, (int)n, A, two_level ? chol_outer_panel() : CHOL_NB, hinfo, err);
 }
 
 
-// inverses of the diagonal TRSV_NB blocks of the factor L (n x n, lda == n) -> w->Linv; call after a successful Cholesky
+// inverses of the diagonal TRSV_NB blocks of the factor L (n x n, lda == n) -> w->Linv.p; call after a successful Cholesky
 int blk_invert(KktWorkspace* w, hipStream_t stream, rocblas_int n, const double* L, std::string* err) {
     w->linv_n = 0;
     if (!g_tune.block_trsv.load() || n < 2 * TRSV_NB) return EMI_OK;
     const int nblk = (n + TRSV_NB - 1) / TRSV_NB, full = n / TRSV_NB, tail = n - full * TRSV_NB;
-    KKT_ENSURE(w->Linv, w->cap_Linv, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double));
-    KKT_HIP(hipMemsetAsync(w->Linv, 0, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double), stream));
+    KKT_HIP(w->Linv.reserve((size_t)nblk * TRSV_NB * TRSV_NB));
+    KKT_HIP(hipMemsetAsync(w->Linv.p, 0, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double), stream));
     KKT_RB(rocblas_dtrtri_strided_batched(w->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, TRSV_NB, L, n,
-                                          (rocblas_stride)TRSV_NB * (n + 1), w->Linv, TRSV_NB, (rocblas_stride)TRSV_NB * TRSV_NB, full));
+                                          (rocblas_stride)TRSV_NB * (n + 1), w->Linv.p, TRSV_NB, (rocblas_stride)TRSV_NB * TRSV_NB, full));
     if (tail > 0)
         KKT_RB(rocblas_dtrtri(w->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, tail, L + (size_t)full * TRSV_NB * (n + 1), n,
-                              w->Linv + (size_t)full * TRSV_NB * TRSV_NB, TRSV_NB));
-    KKT_ENSURE(w->LinvT, w->cap_LinvT, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double));
-    hipLaunchKernelGGL(emi_trsv_transpose_kernel, dim3(TRSV_NB / 32, TRSV_NB / 32, nblk), dim3(256), 0, stream, (const double*)w->Linv, w->LinvT);
+                              w->Linv.p + (size_t)full * TRSV_NB * TRSV_NB, TRSV_NB));
+    KKT_HIP(w->LinvT.reserve((size_t)nblk * TRSV_NB * TRSV_NB));
+    hipLaunchKernelGGL(emi_trsv_transpose_kernel, dim3(TRSV_NB / 32, TRSV_NB / 32, nblk), dim3(256), 0, stream, (const double*)w->Linv.p, w->LinvT.p);
     KKT_HIP(hipGetLastError());
     w->linv_n = n;
     return EMI_OK;
@@ -1182,33 +1088,33 @@ int blk_potrs(KktWorkspace* w, hipStream_t stream, rocblas_int n, const double* 
     const int nblk = (n + TRSV_NB - 1) / TRSV_NB;
     const double one = 1.0, mone = -1.0, zero = 0.0;
     if (g_tune.block_trsv.load() == 2) {
-        KKT_ENSURE(w->trsv_tmp, w->cap_trsv_tmp, (size_t)TRSV_NB * sizeof(double));
+        KKT_HIP(w->trsv_tmp.reserve((size_t)TRSV_NB));
         for (int j = 0; j < nblk; ++j) {            // forward: L y = b
             const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0), rest = (int)n - j0 - bs;
-            hipLaunchKernelGGL(emi_trsv_diag_kernel, dim3((bs + 63) / 64), dim3(64), 0, stream, (const double*)w->Linv + (size_t)j * TRSV_NB * TRSV_NB,
-                               bs, 0, x + j0, w->trsv_tmp);
-            hipLaunchKernelGGL(emi_trsv_copy_kernel, dim3((bs + 255) / 256), dim3(256), 0, stream, (const double*)w->trsv_tmp, x + j0, bs);
+            hipLaunchKernelGGL(emi_trsv_diag_kernel, dim3((bs + 63) / 64), dim3(64), 0, stream, (const double*)w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB,
+                               bs, 0, x + j0, w->trsv_tmp.p);
+            hipLaunchKernelGGL(emi_trsv_copy_kernel, dim3((bs + 255) / 256), dim3(256), 0, stream, (const double*)w->trsv_tmp.p, x + j0, bs);
             if (rest > 0)           // b_rest -= L[rest rows, block j] y_j
                 KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_none, rest, bs, &mone, L + (size_t)j0 * n + j0 + bs, n, x + j0, 1, &one,
                                      x + j0 + bs, 1));
         }
         for (int j = nblk - 1; j >= 0; --j) {       // backward: L^T x = y
             const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0);
-            hipLaunchKernelGGL(emi_trsv_diag_kernel, dim3((bs + 63) / 64), dim3(64), 0, stream, (const double*)w->Linv + (size_t)j * TRSV_NB * TRSV_NB,
-                               bs, 1, x + j0, w->trsv_tmp);
-            hipLaunchKernelGGL(emi_trsv_copy_kernel, dim3((bs + 255) / 256), dim3(256), 0, stream, (const double*)w->trsv_tmp, x + j0, bs);
+            hipLaunchKernelGGL(emi_trsv_diag_kernel, dim3((bs + 63) / 64), dim3(64), 0, stream, (const double*)w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB,
+                               bs, 1, x + j0, w->trsv_tmp.p);
+            hipLaunchKernelGGL(emi_trsv_copy_kernel, dim3((bs + 255) / 256), dim3(256), 0, stream, (const double*)w->trsv_tmp.p, x + j0, bs);
             if (j0 > 0)             // y_(0 .. j0) -= L[block row j, 0 .. j0)^T x_j
                 KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, j0, &mone, L + j0, n, x + j0, 1, &one, x, 1));
         }
         KKT_HIP(hipGetLastError());
         return EMI_OK;
     }
-    KKT_ENSURE(w->trsv_y, w->cap_trsv_y, (size_t)n * sizeof(double));
-    double* y = w->trsv_y;
+    KKT_HIP(w->trsv_y.reserve((size_t)n));
+    double* y = w->trsv_y.p;
     for (int j = 0; j < nblk; ++j) {                // forward: L y = b (b in x, consumed block by block)
         const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0), rest = (int)n - j0 - bs;
         // y_j = Linv_j b_j as a product with the TRANSPOSE of the transposed copy (gemvt: 5 us, gemvn 22 us on 512 x 512)
-        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, bs, &one, w->LinvT + (size_t)j * TRSV_NB * TRSV_NB, TRSV_NB, x + j0, 1,
+        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, bs, &one, w->LinvT.p + (size_t)j * TRSV_NB * TRSV_NB, TRSV_NB, x + j0, 1,
                              &zero, y + j0, 1));
         if (rest > 0)               // b_rest -= L[rest rows, block j] y_j
             hipLaunchKernelGGL(emi_trsv_update_kernel, dim3((rest + 63) / 64), dim3(256), 0, stream, L + (size_t)j0 * n + j0 + bs, (int)n, rest, bs,
@@ -1216,7 +1122,7 @@ int blk_potrs(KktWorkspace* w, hipStream_t stream, rocblas_int n, const double* 
     }
     for (int j = nblk - 1; j >= 0; --j) {           // backward: L^T x = y (y consumed block by block)
         const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0);
-        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, bs, &one, w->Linv + (size_t)j * TRSV_NB * TRSV_NB, TRSV_NB, y + j0, 1, &zero,
+        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, bs, &one, w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB, TRSV_NB, y + j0, 1, &zero,
                              x + j0, 1));
         if (j0 > 0)                 // y_(0 .. j0) -= L[block row j, 0 .. j0)^T x_j
             KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_transpose, bs, j0, &mone, L + j0, n, x + j0, 1, &one, y, 1));
@@ -1234,11 +1140,11 @@ int blk_potrs_multi(KktWorkspace* w, hipStream_t stream, rocblas_int n, const do
                     std::string* err) {
     const int nblk = (n + TRSV_NB - 1) / TRSV_NB;
     const double one = 1.0, mone = -1.0, zero = 0.0;
-    KKT_ENSURE(w->trsm_y, w->cap_trsm_y, (size_t)n * nrhs * sizeof(double));
-    double* Y = w->trsm_y;                              // n x nrhs, leading dimension n
+    KKT_HIP(w->trsm_y.reserve((size_t)n * nrhs));
+    double* Y = w->trsm_y.p;                              // n x nrhs, leading dimension n
     for (int j = 0; j < nblk; ++j) {                    // forward: L Y = B (B in X, consumed block row by block row)
         const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0), rest = (int)n - j0 - bs;
-        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, bs, nrhs, bs, &one, w->Linv + (size_t)j * TRSV_NB * TRSV_NB,
+        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, bs, nrhs, bs, &one, w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB,
                              TRSV_NB, X + j0, ldx, &zero, Y + j0, n));
         if (rest > 0)
             KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, rest, nrhs, bs, &mone, L + (size_t)j0 * n + j0 + bs, n,
@@ -1246,7 +1152,7 @@ int blk_potrs_multi(KktWorkspace* w, hipStream_t stream, rocblas_int n, const do
     }
     for (int j = nblk - 1; j >= 0; --j) {               // backward: L^T X = Y (Y consumed block row by block row)
         const int j0 = j * TRSV_NB, bs = std::min(TRSV_NB, (int)n - j0);
-        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_transpose, rocblas_operation_none, bs, nrhs, bs, &one, w->Linv + (size_t)j * TRSV_NB * TRSV_NB,
+        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_transpose, rocblas_operation_none, bs, nrhs, bs, &one, w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB,
                              TRSV_NB, Y + j0, n, &zero, X + j0, ldx));
         if (j0 > 0)
             KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_transpose, rocblas_operation_none, j0, nrhs, bs, &mone, L + j0, n, X + j0, ldx, &one, Y,
@@ -1255,23 +1161,151 @@ int blk_potrs_multi(KktWorkspace* w, hipStream_t stream, rocblas_int n, const do
     return EMI_OK;
 }
 
+// A new factorisation of an (M, ns, nv) problem begins in w: what it held is void; the handle and every buffer the factorisation
+// needs.  schur: the Schur path will run -- its buffers too (W: w_blocks blocks of [M][M]) and Doff for the mesh; a problem that
+// goes to the LU (more than KKT_NV_MAX variables per node, or method 0) does not start allocating an S it never uses.
+int ws_prepare(KktWorkspace* w, hipStream_t stream, const double* dD, int M, int ns, int nv, double dc, bool schur, int w_blocks,
+               std::string* err) {
+    const int nh = nv * (nv + 1) / 2, N = (nv + ns) * M, nz = nv * M;
+    w->factored = false;
+    w->lr_active = false;
+    w->linv_n = 0;
+    w->reg_dc_applied = dc;
+    w->reg_dw_applied = 0.0;
+    if (!w->handle) {
+        KKT_RB(rocblas_create_handle(&w->handle));
+        // split-K kernels that accumulate with atomics make the factorisation, and with it the iteration path of
+        // the NLP solver, differ from run to run: a solver has to be reproducible
+        KKT_RB(rocblas_set_atomics_mode(w->handle, rocblas_atomics_not_allowed));
+    }
+    KKT_HIP(w->info.reserve(1));
+    KKT_HIP(w->ipiv.reserve((size_t)N));
+    KKT_HIP(w->Q.reserve((size_t)nh * M));
+    KKT_HIP(w->J.reserve((size_t)ns * nv * M));
+    KKT_HIP(w->fixed.reserve((size_t)nz));
+    w->N = N; w->M = M; w->ns = ns; w->nv = nv;
+    if (!schur) return EMI_OK;
+    const size_t md = (size_t)ns * M;
+    KKT_HIP(w->flag.reserve(1));
+    KKT_HIP(w->chol_blk.reserve(CHOL_NB * CHOL_NB + CHOL_NB));
+    KKT_HIP(w->S.reserve(md * md));
+    KKT_HIP(w->Pinv.reserve((size_t)nv * nv * M));
+    KKT_HIP(w->G.reserve((size_t)ns * ns * M));
+    KKT_HIP(w->Rk.reserve((size_t)ns * ns * M));
+    bool doff_moved = false;
+    KKT_HIP(w->Doff.reserve((size_t)M * M, &doff_moved));
+    if (doff_moved) w->doff_M = 0;
+    KKT_HIP(w->W.reserve((size_t)w_blocks * M * M));
+    if (w->doff_M != M || w->doff_src != dD) {
+        hipLaunchKernelGGL(emi_kkt_doff_kernel, dim3((unsigned)(((size_t)M * M + 255) / 256)), dim3(256), 0, stream, dD, w->Doff.p, M);
+        KKT_HIP(hipGetLastError());
+        w->doff_M = M;
+        w->doff_src = dD;
+    }
+    return EMI_OK;
+}
+
+// the caller's node blocks (host) into the prepared workspace
+int upload_blocks(KktWorkspace* w, hipStream_t stream, const double* Qblk, const double* Jblk, const unsigned char* fixed, std::string* err) {
+    const size_t M = (size_t)w->M, nh = (size_t)w->nv * (w->nv + 1) / 2;
+    KKT_HIP(hipMemcpyAsync(w->Q.p, Qblk, nh * M * sizeof(double), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->J.p, Jblk, (size_t)w->ns * w->nv * M * sizeof(double), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->fixed.p, fixed, (size_t)w->nv * M, hipMemcpyHostToDevice, stream));
+    return EMI_OK;
+}
+
+// Regularisation ladder of the Schur path (kkt_factor and kkt_factor_batch).
+// S = J Q^-1 J^T squares the conditioning of J; late interior-point iterations (barrier terms of 1e10 in Q) leave it numerically
+// semidefinite.  A dual regularisation of IPOPT's size (its delta_c is 1e-8 mu^1/4), raised x1000 on a failed Cholesky, keeps the
+// factorisation alive; the caller's iterative refinement works against the matrix with the nominal dc.
+// Level l factorises S with the dual regularisation dc_l and the node blocks with a primal regularisation dw_l on their free
+// diagonal (IPOPT's delta_c / delta_w, here applied ONLY to make the factorisation exist: the caller's iterative refinement works
+// against the nominal matrix and takes the difference out again).  Round 2 had the dual levels only and sent what failed all three
+// to an LU of the whole assembled KKT matrix (rocSOLVER getrf, one launch per column: 43 000 launches and ~210 ms at 1024 nodes of
+// the 6-state model, two or three times per solve).  Those matrices come from late iterations (mu <= 1e-7): state variables away
+// from their bounds carry ~1e-9 of curvature, P = Q^-1 ~ 1e9, and S = J P J^T ~ 1e19 at the clustered end nodes loses its positive
+// definiteness to rounding whatever the dual shift.  A primal shift bounds P instead (profiles/r03_notes.md) -- on the STATE
+// variables only: they are pinned by the defect equations, so the shift barely moves the step, whereas the controls' own curvature
+// (h w_k L_uu ~ 1e-5 .. 1e-2) would drown in it (shifting every variable: 24 factorisations on the last mesh of scenario 0 instead
+// of 13).
+// (Tried: raising the diagonal relatively, S_ii (1 + 1e-12 .. 1e-6), on the retries.  At the clustered end nodes of a 1000-node
+// mesh the entries of S reach 1e16 and an absolute 1e-3 no longer rescues the Cholesky -- the relative shift does, but the factor of
+// such an S is too inaccurate for the refinement to repair: the 1024-node solve went from 12 to 174 iterations.  Those few matrices
+// belong to the LU.)
+struct RegLadder {
+    static constexpr int NLV = 5;
+    static constexpr double DC[NLV] = {1.0, 1e3, 1e3, 1e3, 1e6}, DW[NLV] = {0.0, 0.0, 1e-7, 1e-5, 1e-3};
+    const int max_lv = g_tune.primal_levels.load() ? NLV : 2;      // "kkt_primal_levels" 0: the round-2 ladder (dual levels, then the LU)
+
+    // the level this factorisation starts at: the one that worked last on this mesh shape (KktWorkspace::reg_level), one lower
+    // after four successes in a row at it; the nominal one on a new shape or with "kkt_sticky_reg" 0
+    int start(KktWorkspace* w, int M, int ns, int nv) const {
+        if (w->reg_M != M || w->reg_ns != ns || w->reg_nv != nv || !g_tune.sticky_reg.load()) {
+            w->reg_level = w->reg_hits = 0;
+            w->reg_M = M; w->reg_ns = ns; w->reg_nv = nv;
+        } else if (w->reg_level > 0 && w->reg_hits >= 4) {
+            --w->reg_level;
+            w->reg_hits = 0;
+        }
+        return std::min(w->reg_level, max_lv - 1);
+    }
+    double dc(int level, double dc_caller) const { return (dc_caller > 1e-9 ? dc_caller : 1e-9) * DC[level]; }
+    double dw(int level) const { return DW[level]; }
+    // the Schur path factorised at `level`, having started at `first`
+    void succeeded(KktWorkspace* w, int level, int first, double dc_caller) const {
+        if (level == first) ++w->reg_hits; else { w->reg_level = level; w->reg_hits = 0; }
+        w->reg_dc_applied = dc(level, dc_caller);
+        w->reg_dw_applied = dw(level);
+        w->factored = true;
+        w->method_used = 1;
+    }
+    // S was not positive definite at any level (the next factorisation starts at the last level, not at the LU)
+    void exhausted(KktWorkspace* w) const {
+        w->reg_level = max_lv - 1;
+        w->reg_hits = 0;
+    }
+};
+
+// P_k = Q_k^-1, G_k, R_k of every node with the primal shift dw, by the kernel that knows the block sizes at compile time where there
+// is one.  tab == nullptr: the one workspace w; else the na scenarios of the device table (their shifts are in it).
+void launch_node_inverse(hipStream_t stream, int M, int ns, int nv, const KktWorkspace* w, double dw, const KktDev* tab, int na) {
+    const dim3 grid((M + 63) / 64, tab ? na : 1), block(64);
+    auto launch = [&](auto* plain, auto* table, auto... shape) {       // shape: (ns, nv), for the generic kernels only
+        if (tab)
+            hipLaunchKernelGGL(table, grid, block, 0, stream, tab, M, shape...);
+        else
+            hipLaunchKernelGGL(plain, grid, block, 0, stream, w->Q.p, w->J.p, w->fixed.p, M, shape..., w->Pinv.p, w->G.p, w->Rk.p, w->flag.p, dw);
+    };
+    if (ns == 6 && nv == 8) launch(emi_kkt_node_inverse_fixed_kernel<6, 8>, emi_kkt_node_inverse_fixed_b_kernel<6, 8>);
+    else if (ns == 2 && nv == 4) launch(emi_kkt_node_inverse_fixed_kernel<2, 4>, emi_kkt_node_inverse_fixed_b_kernel<2, 4>);
+    else launch(emi_kkt_node_inverse_kernel, emi_kkt_node_inverse_b_kernel, ns, nv);
+}
+
+// "kkt_debug" 2: the node blocks around a failing pivot of S (diagonals of Q as uploaded and of P = Q^-1)
+void dump_failing_pivot(const KktWorkspace* w, int pivot) {
+    const int M = w->M, nv = w->nv, nh = nv * (nv + 1) / 2;
+    const int kf = (pivot - 1) % M, i_f = (pivot - 1) / M;
+    std::vector<double> hq((size_t)nh * M), hp((size_t)nv * nv * M);
+    std::vector<unsigned char> hf((size_t)nv * M);
+    (void)hipMemcpy(hq.data(), w->Q.p, hq.size() * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hp.data(), w->Pinv.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hf.data(), w->fixed.p, hf.size(), hipMemcpyDeviceToHost);
+    fprintf(stderr, "  failing pivot: state row %d, node %d of %d\n", i_f, kf, M);
+    for (int k = std::max(0, kf - 2); k <= std::min(M - 1, kf + 2); ++k) {
+        fprintf(stderr, "  node %4d  Qdiag", k);
+        for (int v = 0; v < nv; ++v) fprintf(stderr, " %9.2e%s", hq[(size_t)(v * (v + 1) / 2 + v) * M + k], hf[(size_t)v * M + k] ? "f" : "");
+        fprintf(stderr, "   Pdiag");
+        for (int v = 0; v < nv; ++v) fprintf(stderr, " %9.2e", hp[(size_t)(v * nv + v) * M + k]);
+        fprintf(stderr, "\n");
+    }
+}
+
 }  // namespace
 
 void kkt_destroy(KktWorkspace* w) {
     if (!w) return;
     if (w->handle) (void)rocblas_destroy_handle(w->handle);
-    void* bufs[] = {w->K, w->ipiv, w->info, w->Q, w->J, w->rhs, w->fixed, w->S, w->Pinv, w->G, w->Rk, w->Doff, w->W, w->gemm_ptrs, w->T,
-                    w->Cb, w->flag, w->chol_blk, w->chol_copy, w->Linv, w->LinvT, w->trsv_tmp, w->trsv_y, w->trsm_y, w->lrY, w->lrC, w->lrT, w->lr_node, w->lr_vec, w->lr_delta};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (w->ref_b) (void)hipFree(w->ref_b);
-    if (w->ref_x) (void)hipFree(w->ref_x);
-    if (w->ref_p) (void)hipFree(w->ref_p);
-    if (w->b_tab) (void)hipFree(w->b_tab);
-    if (w->b_ptrs) (void)hipFree(w->b_ptrs);
-    if (w->b_stat) (void)hipFree(w->b_stat);
-    if (w->b_pin) (void)hipHostFree(w->b_pin);
-    delete w;
+    delete w;       // (every buffer is a DeviceArray member)
 }
 
 bool kkt_is_schur(const KktWorkspace* w) { return w && w->factored && w->method_used == 1; }
@@ -1285,150 +1319,74 @@ void kkt_mesh_changed(KktWorkspace* w) {
 // Returns an EMI_* status; *info = 0 factorised, > 0 exactly singular (zero pivot at that position).
 int kkt_factor(KktWorkspace** pw, hipStream_t stream, const double* dD, int M, int ns, int nv, const double* Qblk,
                const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err) {
-    const int nh = nv * (nv + 1) / 2, N = (nv + ns) * M, nz = nv * M;
+    const int N = (nv + ns) * M;
     if (!*pw) *pw = new KktWorkspace();
     KktWorkspace* w = *pw;
-    w->factored = false;
-    w->lr_active = false;
-    w->linv_n = 0;
-    w->reg_dc_applied = dc;
-    w->reg_dw_applied = 0.0;
-    if (!w->handle) {
-        KKT_RB(rocblas_create_handle(&w->handle));
-        // split-K kernels that accumulate with atomics make the factorisation, and with it the iteration path of
-        // the NLP solver, differ from run to run: a solver has to be reproducible
-        KKT_RB(rocblas_set_atomics_mode(w->handle, rocblas_atomics_not_allowed));
-    }
+    const bool schur = method == 1 && nv <= KKT_NV_MAX;
+    // one batched GEMM for all state pairs where the build is launch-bound (measured: +5-10 % Monte-Carlo throughput
+    // at 65 nodes, +3 % at 129; no gain per factorisation at 1024 nodes, where the unbatched form is kept)
+    const bool batched = M <= g_tune.batched_max_nodes.load();
+    const int npairs = ns * (ns + 1) / 2;
+    if (int st = ws_prepare(w, stream, dD, M, ns, nv, dc, schur, batched ? npairs : 1, err)) return st;
     KKT_RB(rocblas_set_stream(w->handle, stream));
-    if (!w->info) KKT_HIP(hipMalloc(&w->info, sizeof(rocblas_int)));
-    KKT_ENSURE(w->ipiv, w->cap_ipiv, (size_t)N * sizeof(rocblas_int));
-    KKT_ENSURE(w->Q, w->cap_Q, (size_t)nh * M * sizeof(double));
-    KKT_ENSURE(w->J, w->cap_J, (size_t)ns * nv * M * sizeof(double));
-    KKT_ENSURE(w->fixed, w->cap_fixed, (size_t)nz);
-    w->N = N;
-    KKT_HIP(hipMemcpyAsync(w->Q, Qblk, (size_t)nh * M * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->J, Jblk, (size_t)ns * nv * M * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->fixed, fixed, (size_t)nz, hipMemcpyHostToDevice, stream));
-    w->M = M; w->ns = ns; w->nv = nv;
-    if (method == 1 && nv <= KKT_NV_MAX) {
+    if (int st = upload_blocks(w, stream, Qblk, Jblk, fixed, err)) return st;
+    if (schur) {
         const size_t md = (size_t)ns * M;
-        if (w->S_elems < md * md) {
-            if (w->S) KKT_HIP(hipFree(w->S));
-            w->S = nullptr;
-            w->S_elems = 0;
-            KKT_HIP(hipMalloc(&w->S, md * md * sizeof(double)));
-            w->S_elems = md * md;
-        }
-        KKT_ENSURE(w->Pinv, w->cap_Pinv, (size_t)nv * nv * M * sizeof(double));
-        KKT_ENSURE(w->G, w->cap_G, (size_t)ns * ns * M * sizeof(double));
-        KKT_ENSURE(w->Rk, w->cap_Rk, (size_t)ns * ns * M * sizeof(double));
-        if (w->cap_Doff < (size_t)M * M * sizeof(double)) w->doff_M = 0;
-        KKT_ENSURE(w->Doff, w->cap_Doff, (size_t)M * M * sizeof(double));
-        // one batched GEMM for all state pairs where the build is launch-bound (measured: +5-10 % Monte-Carlo throughput
-        // at 65 nodes, +3 % at 129; no gain per factorisation at 1024 nodes, where the unbatched form is kept)
-        const int batched_max_m = g_tune.batched_max_nodes.load();
-        const bool batched = M <= batched_max_m;
-        const int npairs = ns * (ns + 1) / 2;
-        KKT_ENSURE(w->W, w->cap_W, (size_t)(batched ? npairs : 1) * M * M * sizeof(double));
-        if (!w->flag) KKT_HIP(hipMalloc(&w->flag, sizeof(int)));
-        // S = J Q^-1 J^T squares the conditioning of J; late interior-point iterations (barrier terms of 1e10 in Q)
-        // leave it numerically semidefinite.  A dual regularisation of IPOPT's size (its delta_c is 1e-8 mu^1/4),
-        // raised x1000 on a failed Cholesky, keeps the factorisation alive; the caller's iterative refinement
-        // works against the matrix with the nominal dc.
-        KKT_HIP(hipMemsetAsync(w->flag, 0, sizeof(int), stream));
+        KKT_HIP(hipMemsetAsync(w->flag.p, 0, sizeof(int), stream));
         const unsigned nb2 = (unsigned)(((size_t)M * M + 255) / 256);
-        if (w->doff_M != M || w->doff_src != dD) {
-            hipLaunchKernelGGL(emi_kkt_doff_kernel, dim3(nb2), dim3(256), 0, stream, dD, w->Doff, M);
-            w->doff_M = M;
-            w->doff_src = dD;
-        }
         // Doff is stored [k][j] row-major, i.e. as the column-major matrix Dc = Doff^T:  Doff diag(p) Doff^T = Dc^T (diag(p) Dc)
         const double one = 1.0, zero = 0.0;
         rocblas_int hinfo = 0;
         int hflag = 0;
-        // (Tried: raising the diagonal relatively, S_ii (1 + 1e-12 .. 1e-6), on the retries.  At the clustered end nodes of
-        // a 1000-node mesh the entries of S reach 1e16 and an absolute 1e-3 no longer rescues the Cholesky -- the relative
-        // shift does, but the factor of such an S is too inaccurate for the refinement to repair: the 1024-node solve went
-        // from 12 to 174 iterations.  Those few matrices belong to the LU below.)
-        // Regularisation ladder of the Schur path.  Level l factorises S with the dual regularisation dc_l and the node blocks
-        // with a primal regularisation dw_l on their free diagonal (IPOPT's delta_c / delta_w, here applied ONLY to make the
-        // factorisation exist: the caller's iterative refinement works against the nominal matrix and takes the difference
-        // out again).  Round 2 had the dual levels only and sent what failed all three to an LU of the whole assembled KKT
-        // matrix (rocSOLVER getrf, one launch per column: 43 000 launches and ~210 ms at 1024 nodes of the 6-state model, two
-        // or three times per solve).  Those matrices come from late iterations (mu <= 1e-7): state variables away from their
-        // bounds carry ~1e-9 of curvature, P = Q^-1 ~ 1e9, and S = J P J^T ~ 1e19 at the clustered end nodes loses its positive
-        // definiteness to rounding whatever the dual shift.  A primal shift bounds P instead (profiles/r03_notes.md) -- on the
-        // STATE variables only: they are pinned by the defect equations, so the shift barely moves the step, whereas the
-        // controls' own curvature (h w_k L_uu ~ 1e-5 .. 1e-2) would drown in it (shifting every variable: 24 factorisations on
-        // the last mesh of scenario 0 instead of 13).
-        static const double LV_DC[5] = {1.0, 1e3, 1e3, 1e3, 1e6}, LV_DW[5] = {0.0, 0.0, 1e-7, 1e-5, 1e-3};
-        constexpr int NLV = 5;
-        const double dc_base = dc > 1e-9 ? dc : 1e-9;
-        double dc_schur = dc_base;
-        if (w->reg_M != M || w->reg_ns != ns || w->reg_nv != nv || !g_tune.sticky_reg.load()) {
-            w->reg_level = w->reg_hits = 0;
-            w->reg_M = M; w->reg_ns = ns; w->reg_nv = nv;
-        } else if (w->reg_level > 0 && w->reg_hits >= 4) {
-            --w->reg_level;
-            w->reg_hits = 0;
-        }
-        const int max_lv = g_tune.primal_levels.load() ? NLV : 2;      // "kkt_primal_levels" 0: the round-2 ladder (dual levels, then the LU)
-        const int first_attempt = std::min(w->reg_level, max_lv - 1);
-        if (batched && (w->ptrs_key[0] != w->Doff || w->ptrs_key[1] != w->W || w->ptrs_key[2] != w->S || w->ptrs_M != M ||
+        const RegLadder ladder{};
+        const int first_attempt = ladder.start(w, M, ns, nv);
+        if (batched && (w->ptrs_key[0] != w->Doff.p || w->ptrs_key[1] != w->W.p || w->ptrs_key[2] != w->S.p || w->ptrs_M != M ||
                         w->ptrs_ns != ns)) {
             std::vector<double*> hp(3 * (size_t)npairs);
             for (int i = 0, p = 0; i < ns; ++i)
                 for (int ip = 0; ip <= i; ++ip, ++p) {
-                    hp[p] = w->Doff;
-                    hp[npairs + p] = w->W + (size_t)p * M * M;
-                    hp[2 * npairs + p] = w->S + ((size_t)ip * M) * md + (size_t)i * M;
+                    hp[p] = w->Doff.p;
+                    hp[npairs + p] = w->W.p + (size_t)p * M * M;
+                    hp[2 * npairs + p] = w->S.p + ((size_t)ip * M) * md + (size_t)i * M;
                 }
-            if (!w->gemm_ptrs) KKT_HIP(hipMalloc((void**)&w->gemm_ptrs, 3 * 136 * sizeof(double*)));   // ns <= 16
-            KKT_HIP(hipMemcpyAsync(w->gemm_ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, stream));
+            KKT_HIP(w->gemm_ptrs.reserve(3 * 136));   // ns <= 16
+            KKT_HIP(hipMemcpyAsync(w->gemm_ptrs.p, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, stream));
             KKT_HIP(hipStreamSynchronize(stream));
-            w->ptrs_key[0] = w->Doff; w->ptrs_key[1] = w->W; w->ptrs_key[2] = w->S;
+            w->ptrs_key[0] = w->Doff.p; w->ptrs_key[1] = w->W.p; w->ptrs_key[2] = w->S.p;
             w->ptrs_M = M; w->ptrs_ns = ns;
         }
         int attempt = first_attempt;
-        double dw_done = -1.0;
-        for (; attempt < max_lv; ++attempt) {
-            dc_schur = dc_base * LV_DC[attempt];
-            if (LV_DW[attempt] != dw_done) {        // node blocks (re)inverted with this level's primal shift
-                dw_done = LV_DW[attempt];
-                KKT_HIP(hipMemsetAsync(w->flag, 0, sizeof(int), stream));
-                if (ns == 6 && nv == 8)
-                    hipLaunchKernelGGL((emi_kkt_node_inverse_fixed_kernel<6, 8>), dim3((M + 63) / 64), dim3(64), 0, stream, w->Q, w->J, w->fixed, M,
-                                   w->Pinv, w->G, w->Rk, w->flag, dw_done);
-                else if (ns == 2 && nv == 4)
-                    hipLaunchKernelGGL((emi_kkt_node_inverse_fixed_kernel<2, 4>), dim3((M + 63) / 64), dim3(64), 0, stream, w->Q, w->J, w->fixed, M,
-                                   w->Pinv, w->G, w->Rk, w->flag, dw_done);
-                else
-                    hipLaunchKernelGGL(emi_kkt_node_inverse_kernel, dim3((M + 63) / 64), dim3(64), 0, stream, w->Q, w->J, w->fixed, M, ns, nv,
-                                   w->Pinv, w->G, w->Rk, w->flag, dw_done);
+        double dc_schur = 0.0, dw_done = -1.0;
+        for (; attempt < ladder.max_lv; ++attempt) {
+            dc_schur = ladder.dc(attempt, dc);
+            if (ladder.dw(attempt) != dw_done) {        // node blocks (re)inverted with this level's primal shift
+                dw_done = ladder.dw(attempt);
+                KKT_HIP(hipMemsetAsync(w->flag.p, 0, sizeof(int), stream));
+                launch_node_inverse(stream, M, ns, nv, w, dw_done, nullptr, 1);
                 KKT_HIP(hipGetLastError());
             }
             if (batched) {
                 // three launches for all ns (ns + 1) / 2 state pairs: small meshes are launch-bound here
-                hipLaunchKernelGGL(emi_kkt_scale_all_kernel, dim3(nb2, npairs), dim3(256), 0, stream, w->Doff, w->Pinv, w->W, M, nv);
+                hipLaunchKernelGGL(emi_kkt_scale_all_kernel, dim3(nb2, npairs), dim3(256), 0, stream, w->Doff.p, w->Pinv.p, w->W.p, M, nv);
                 KKT_RB(rocblas_dgemm_batched(w->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one,
-                                             (const double* const*)w->gemm_ptrs, M, (const double* const*)(w->gemm_ptrs + npairs), M,
-                                             &zero, w->gemm_ptrs + 2 * npairs, (rocblas_int)md, npairs));
-                hipLaunchKernelGGL(emi_kkt_sblock_terms_kernel, dim3(nb2, npairs), dim3(256), 0, stream, w->S, w->Doff, w->G, w->Rk,
+                                             (const double* const*)w->gemm_ptrs.p, M, (const double* const*)(w->gemm_ptrs.p + npairs), M,
+                                             &zero, w->gemm_ptrs.p + 2 * npairs, (rocblas_int)md, npairs));
+                hipLaunchKernelGGL(emi_kkt_sblock_terms_kernel, dim3(nb2, npairs), dim3(256), 0, stream, w->S.p, w->Doff.p, w->G.p, w->Rk.p,
                                    M, ns, -1, -1, dc_schur, 0.0);
             } else
             for (int i = 0; i < ns; ++i)
                 for (int ip = 0; ip <= i; ++ip) {
-                    hipLaunchKernelGGL(emi_kkt_scale_kernel, dim3(nb2), dim3(256), 0, stream, w->Doff,
-                                       w->Pinv + (size_t)(i * nv + ip) * M, w->W, M);
-                    double* Sblk = w->S + ((size_t)ip * M) * md + (size_t)i * M;
-                    KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, w->Doff, M,
-                                         w->W, M, &zero, Sblk, (rocblas_int)md));
-                    hipLaunchKernelGGL(emi_kkt_sblock_terms_kernel, dim3(nb2), dim3(256), 0, stream, w->S, w->Doff, w->G, w->Rk, M,
+                    hipLaunchKernelGGL(emi_kkt_scale_kernel, dim3(nb2), dim3(256), 0, stream, w->Doff.p,
+                                       w->Pinv.p + (size_t)(i * nv + ip) * M, w->W.p, M);
+                    double* Sblk = w->S.p + ((size_t)ip * M) * md + (size_t)i * M;
+                    KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, w->Doff.p, M,
+                                         w->W.p, M, &zero, Sblk, (rocblas_int)md));
+                    hipLaunchKernelGGL(emi_kkt_sblock_terms_kernel, dim3(nb2), dim3(256), 0, stream, w->S.p, w->Doff.p, w->G.p, w->Rk.p, M,
                                        ns, i, ip, dc_schur, 0.0);
                 }
             KKT_HIP(hipGetLastError());
-            if (int st = cholesky(w, stream, (rocblas_int)md, w->S, &hinfo, err)) return st;
-            KKT_HIP(hipMemcpyAsync(&hflag, w->flag, sizeof hflag, hipMemcpyDeviceToHost, stream));
+            if (int st = cholesky(w, stream, (rocblas_int)md, w->S.p, &hinfo, err)) return st;
+            KKT_HIP(hipMemcpyAsync(&hflag, w->flag.p, sizeof hflag, hipMemcpyDeviceToHost, stream));
             KKT_HIP(hipStreamSynchronize(stream));
             if (hinfo == 0 || hflag != 0) break;      // factorised, or hopeless (a Q block is not positive definite)
             if (g_tune.debug.load())
@@ -1436,55 +1394,26 @@ int kkt_factor(KktWorkspace** pw, hipStream_t stream, const double* dD, int M, i
                         (int)hinfo, dc_schur, dw_done, M);
         }
         if (hinfo == 0 && hflag == 0) {
-            if (int st = blk_invert(w, stream, (rocblas_int)md, w->S, err)) return st;
-            if (attempt == first_attempt) ++w->reg_hits; else { w->reg_level = attempt; w->reg_hits = 0; }
-            w->reg_dc_applied = dc_schur;
-            w->reg_dw_applied = dw_done;
+            if (int st = blk_invert(w, stream, (rocblas_int)md, w->S.p, err)) return st;
+            ladder.succeeded(w, attempt, first_attempt, dc);
             *info = 0;
-            w->factored = true;
-            w->method_used = 1;
             return EMI_OK;
         }
-        if (hflag == 0) {                           // S not positive definite at any level
-            w->reg_level = max_lv - 1;                  // (the next factorisation starts at the last level, not at the LU)
-            w->reg_hits = 0;
-        }
+        if (hflag == 0) ladder.exhausted(w);        // S not positive definite at any level
         // a block was not positive definite or S is not: not the quasi-definite case -- general path below
-        if (g_tune.debug.load() >= 2 && hinfo > 0) {
-            // diagnosis: the node blocks around the failing pivot (diagonals of Q as uploaded and of P = Q^-1)
-            const int kf = ((int)hinfo - 1) % M, i_f = ((int)hinfo - 1) / M;
-            std::vector<double> hq((size_t)nh * M), hp((size_t)nv * nv * M);
-            std::vector<unsigned char> hf((size_t)nz);
-            (void)hipMemcpy(hq.data(), w->Q, hq.size() * sizeof(double), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hp.data(), w->Pinv, hp.size() * sizeof(double), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hf.data(), w->fixed, hf.size(), hipMemcpyDeviceToHost);
-            fprintf(stderr, "  failing pivot: state row %d, node %d of %d\n", i_f, kf, M);
-            for (int k = std::max(0, kf - 2); k <= std::min(M - 1, kf + 2); ++k) {
-                fprintf(stderr, "  node %4d  Qdiag", k);
-                for (int v = 0; v < nv; ++v) fprintf(stderr, " %9.2e%s", hq[(size_t)(v * (v + 1) / 2 + v) * M + k], hf[(size_t)v * M + k] ? "f" : "");
-                fprintf(stderr, "   Pdiag");
-                for (int v = 0; v < nv; ++v) fprintf(stderr, " %9.2e", hp[(size_t)(v * nv + v) * M + k]);
-                fprintf(stderr, "\n");
-            }
-        }
+        if (g_tune.debug.load() >= 2 && hinfo > 0) dump_failing_pivot(w, (int)hinfo);
         if (g_tune.debug.load())
             fprintf(stderr, "emi_kkt_factor: Schur path gave up (block flag %d, potrf info %d, M %d, dc %.3g) -> LU\n", hflag,
                     (int)hinfo, M, dc);
     }
     w->method_used = 0;
-    if (w->K_elems < (size_t)N * N) {
-        if (w->K) KKT_HIP(hipFree(w->K));
-        w->K = nullptr;
-        w->K_elems = 0;
-        KKT_HIP(hipMalloc(&w->K, (size_t)N * N * sizeof(double)));
-        w->K_elems = (size_t)N * N;
-    }
+    KKT_HIP(w->K.reserve((size_t)N * N));
     dim3 grid((N + 255) / 256, N), block(256);
-    hipLaunchKernelGGL(emi_kkt_assemble_kernel, grid, block, 0, stream, w->K, w->Q, w->J, dD, w->fixed, M, ns, nv, dc);
+    hipLaunchKernelGGL(emi_kkt_assemble_kernel, grid, block, 0, stream, w->K.p, w->Q.p, w->J.p, dD, w->fixed.p, M, ns, nv, dc);
     KKT_HIP(hipGetLastError());
-    KKT_RB(rocsolver_dgetrf(w->handle, N, N, w->K, N, w->ipiv, w->info));
+    KKT_RB(rocsolver_dgetrf(w->handle, N, N, w->K.p, N, w->ipiv.p, w->info.p));
     rocblas_int hinfo = 0;
-    KKT_HIP(hipMemcpyAsync(&hinfo, w->info, sizeof hinfo, hipMemcpyDeviceToHost, stream));
+    KKT_HIP(hipMemcpyAsync(&hinfo, w->info.p, sizeof hinfo, hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     *info = (int)hinfo;
     w->factored = hinfo == 0;
@@ -1501,63 +1430,53 @@ void kkt_last_regularisation(const KktWorkspace* w, double* dc, double* dw) {
 // X [N][nrhs] on the device, in place: X <- K~^-1 X with the current factorisation
 static int solve_dev(KktWorkspace* w, hipStream_t stream, int nz, double* X, int nrhs, std::string* err) {
     const int N = w->N;
-    hipLaunchKernelGGL(emi_kkt_mask_rhs_kernel, dim3((nz + 255) / 256, nrhs), dim3(256), 0, stream, X, w->fixed, nz, N);
+    hipLaunchKernelGGL(emi_kkt_mask_rhs_kernel, dim3((nz + 255) / 256, nrhs), dim3(256), 0, stream, X, w->fixed.p, nz, N);
     KKT_HIP(hipGetLastError());
     KKT_RB(rocblas_set_stream(w->handle, stream));
     if (w->method_used == 1) {
         const int M = w->M, ns = w->ns, nv = w->nv, md = ns * M;
-        if (w->T_elems < (size_t)nz * nrhs) {
-            if (w->T) KKT_HIP(hipFree(w->T));
-            w->T = nullptr; w->T_elems = 0;
-            KKT_HIP(hipMalloc(&w->T, (size_t)nz * nrhs * sizeof(double)));
-            w->T_elems = (size_t)nz * nrhs;
-        }
-        if (w->Cb_elems < (size_t)md * nrhs) {
-            if (w->Cb) KKT_HIP(hipFree(w->Cb));
-            w->Cb = nullptr; w->Cb_elems = 0;
-            KKT_HIP(hipMalloc(&w->Cb, (size_t)md * nrhs * sizeof(double)));
-            w->Cb_elems = (size_t)md * nrhs;
-        }
+        KKT_HIP(w->T.reserve((size_t)nz * nrhs));
+        KKT_HIP(w->Cb.reserve((size_t)md * nrhs));
         const double one = 1.0, zero = 0.0, mone = -1.0;
         dim3 gk((M + 127) / 128, nrhs), bk(128);
         // t = P a
-        hipLaunchKernelGGL(emi_kkt_apply_p_kernel, gk, bk, 0, stream, w->Pinv, X, (size_t)N, w->T, (size_t)nz, M, nv);
+        hipLaunchKernelGGL(emi_kkt_apply_p_kernel, gk, bk, 0, stream, w->Pinv.p, X, (size_t)N, w->T.p, (size_t)nz, M, nv);
         // Cb = Doff t_states            (Doff = Dc^T in column-major terms).  One right-hand side: an M x ns panel.  Many (the r columns of
         // the low-rank correction, r ~ 800 at 1024 nodes): batched over the STATES instead -- state i of every right-hand side is the
         // M x nrhs matrix at T + i M with leading dimension nz, so the product is ns large GEMMs (M x nrhs x M) rather than nrhs GEMMs
         // with ns columns each (which ran at a few percent of the matrix pipe)
         if (nrhs >= 8)
             KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_transpose, rocblas_operation_none, M, nrhs, M, &one,
-                                                 w->Doff, M, 0, w->T, nz, (rocblas_stride)M, &zero, w->Cb, md, (rocblas_stride)M, ns));
+                                                 w->Doff.p, M, 0, w->T.p, nz, (rocblas_stride)M, &zero, w->Cb.p, md, (rocblas_stride)M, ns));
         else
             KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_transpose, rocblas_operation_none, M, ns, M, &one,
-                                                 w->Doff, M, 0, w->T, M, (rocblas_stride)nz, &zero, w->Cb, M, (rocblas_stride)md,
+                                                 w->Doff.p, M, 0, w->T.p, M, (rocblas_stride)nz, &zero, w->Cb.p, M, (rocblas_stride)md,
                                                  nrhs));
         // Cb += J_node t - b
-        hipLaunchKernelGGL(emi_kkt_jnode_minus_b_kernel, gk, bk, 0, stream, w->J, w->T, (size_t)nz, X + nz, (size_t)N, w->Cb,
+        hipLaunchKernelGGL(emi_kkt_jnode_minus_b_kernel, gk, bk, 0, stream, w->J.p, w->T.p, (size_t)nz, X + nz, (size_t)N, w->Cb.p,
                            (size_t)md, M, ns, nv);
         KKT_HIP(hipGetLastError());
         // lambda = S^-1 Cb
-        if (nrhs == 1 && w->linv_n == md) { if (int st = blk_potrs(w, stream, md, w->S, w->Cb, err)) return st; }
-        else if (nrhs >= 16 && w->linv_n == md) { if (int st = blk_potrs_multi(w, stream, md, w->S, w->Cb, md, nrhs, err)) return st; }
-        else KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, md, nrhs, w->S, md, w->Cb, md));
+        if (nrhs == 1 && w->linv_n == md) { if (int st = blk_potrs(w, stream, md, w->S.p, w->Cb.p, err)) return st; }
+        else if (nrhs >= 16 && w->linv_n == md) { if (int st = blk_potrs_multi(w, stream, md, w->S.p, w->Cb.p, md, nrhs, err)) return st; }
+        else KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, md, nrhs, w->S.p, md, w->Cb.p, md));
         // y = a - J^T lambda  (in place in the primal part of X), then x = P y
         if (nrhs >= 8)
-            KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_none, rocblas_operation_none, M, nrhs, M, &mone, w->Doff,
-                                                 M, 0, w->Cb, md, (rocblas_stride)M, &one, X, N, (rocblas_stride)M, ns));
+            KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_none, rocblas_operation_none, M, nrhs, M, &mone, w->Doff.p,
+                                                 M, 0, w->Cb.p, md, (rocblas_stride)M, &one, X, N, (rocblas_stride)M, ns));
         else
-            KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_none, rocblas_operation_none, M, ns, M, &mone, w->Doff,
-                                                 M, 0, w->Cb, M, (rocblas_stride)md, &one, X, M, (rocblas_stride)N, nrhs));
-        hipLaunchKernelGGL(emi_kkt_jnode_t_kernel, gk, bk, 0, stream, w->J, w->Cb, (size_t)md, X, (size_t)N, M, ns, nv);
-        hipLaunchKernelGGL(emi_kkt_apply_p_kernel, gk, bk, 0, stream, w->Pinv, X, (size_t)N, w->T, (size_t)nz, M, nv);
+            KKT_RB(rocblas_dgemm_strided_batched(w->handle, rocblas_operation_none, rocblas_operation_none, M, ns, M, &mone, w->Doff.p,
+                                                 M, 0, w->Cb.p, M, (rocblas_stride)md, &one, X, M, (rocblas_stride)N, nrhs));
+        hipLaunchKernelGGL(emi_kkt_jnode_t_kernel, gk, bk, 0, stream, w->J.p, w->Cb.p, (size_t)md, X, (size_t)N, M, ns, nv);
+        hipLaunchKernelGGL(emi_kkt_apply_p_kernel, gk, bk, 0, stream, w->Pinv.p, X, (size_t)N, w->T.p, (size_t)nz, M, nv);
         KKT_HIP(hipGetLastError());
-        KKT_HIP(hipMemcpy2DAsync(X, (size_t)N * sizeof(double), w->T, (size_t)nz * sizeof(double), (size_t)nz * sizeof(double),
+        KKT_HIP(hipMemcpy2DAsync(X, (size_t)N * sizeof(double), w->T.p, (size_t)nz * sizeof(double), (size_t)nz * sizeof(double),
                                  nrhs, hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(emi_kkt_copy_lambda_kernel, dim3((md + 255) / 256, nrhs), dim3(256), 0, stream, w->Cb, (size_t)md, X,
+        hipLaunchKernelGGL(emi_kkt_copy_lambda_kernel, dim3((md + 255) / 256, nrhs), dim3(256), 0, stream, w->Cb.p, (size_t)md, X,
                            (size_t)N, nz, md);
         KKT_HIP(hipGetLastError());
     } else {
-        KKT_RB(rocsolver_dgetrs(w->handle, rocblas_operation_none, N, nrhs, w->K, N, w->ipiv, X, N));
+        KKT_RB(rocsolver_dgetrs(w->handle, rocblas_operation_none, N, nrhs, w->K.p, N, w->ipiv.p, X, N));
     }
     return EMI_OK;
 }
@@ -1574,36 +1493,18 @@ int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* n
     *exact = r == 0 ? 1 : 0;
     if (r == 0) return EMI_OK;
     const int N = w->N, nv = w->nv, M = w->M;
-    if (w->lr_cap < r) {
-        void** bufs[] = {(void**)&w->lrY, (void**)&w->lrC, (void**)&w->lr_node, (void**)&w->lr_vec, (void**)&w->lr_delta,
-                         (void**)&w->lrT};
-        for (void** b : bufs)
-            if (*b) { KKT_HIP(hipFree(*b)); *b = nullptr; }
-        w->lr_cap = 0;
-        w->lr_nv = 0;
-        const int cap = r + r / 4 + 16;
-        KKT_HIP(hipMalloc(&w->lrY, (size_t)N * cap * sizeof(double)));
-        KKT_HIP(hipMalloc(&w->lrC, (size_t)cap * cap * sizeof(double)));
-        KKT_HIP(hipMalloc(&w->lr_node, (size_t)cap * sizeof(int)));
-        KKT_HIP(hipMalloc(&w->lr_vec, (size_t)cap * nv * sizeof(double)));
-        KKT_HIP(hipMalloc(&w->lr_delta, (size_t)cap * sizeof(double)));
-        KKT_HIP(hipMalloc(&w->lrT, (size_t)cap * 64 * sizeof(double)));
-        w->lr_cap = cap;
-        w->lr_n = N;
-        w->lr_nv = nv;
-    } else if (w->lr_n < N) {
-        if (w->lrY) KKT_HIP(hipFree(w->lrY));
-        w->lrY = nullptr;
-        KKT_HIP(hipMalloc(&w->lrY, (size_t)N * w->lr_cap * sizeof(double)));
-        w->lr_n = N;
+    if (w->lr_cap < r) {            // more columns than ever: room to grow; lrY and lr_vec anew at this problem's N and nv
+        KKT_HIP(w->lrY.release());
+        KKT_HIP(w->lr_vec.release());
+        w->lr_cap = r + r / 4 + 16;
     }
-    if (w->lr_nv < nv) {            // (the LU path takes node blocks of any size: traced models up to 64 variables per node)
-        if (w->lr_vec) KKT_HIP(hipFree(w->lr_vec));
-        w->lr_vec = nullptr;
-        w->lr_nv = 0;
-        KKT_HIP(hipMalloc(&w->lr_vec, (size_t)w->lr_cap * nv * sizeof(double)));
-        w->lr_nv = nv;
-    }
+    const size_t cap = (size_t)w->lr_cap;
+    KKT_HIP(w->lrY.reserve((size_t)N * cap));
+    KKT_HIP(w->lrC.reserve(cap * cap));
+    KKT_HIP(w->lr_node.reserve(cap));
+    KKT_HIP(w->lr_vec.reserve(cap * nv));      // (the LU path takes node blocks of any size: traced models up to 64 variables per node)
+    KKT_HIP(w->lr_delta.reserve(cap));
+    KKT_HIP(w->lrT.reserve(cap * 64));
     // the columns sorted by node (stable: an order that already is, as solve_nlp's, stays as it is) -- the residual of the refined
     // solves gives each node's columns to one thread (emi_kkt_residual_lr_b_kernel)
     std::vector<int> perm(r), s_node(r);
@@ -1615,20 +1516,20 @@ int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* n
         s_delta[a] = delta[perm[a]];
         std::memcpy(&s_vec[(size_t)a * nv], vec + (size_t)perm[a] * nv, (size_t)nv * sizeof(double));
     }
-    KKT_HIP(hipMemcpyAsync(w->lr_node, s_node.data(), (size_t)r * sizeof(int), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->lr_vec, s_vec.data(), (size_t)r * nv * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->lr_delta, s_delta.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemsetAsync(w->lrY, 0, (size_t)N * r * sizeof(double), stream));
-    hipLaunchKernelGGL(emi_kkt_lr_scatter_kernel, dim3((r + 63) / 64), dim3(64), 0, stream, w->lrY, w->lr_node, w->lr_vec, r, N, M,
+    KKT_HIP(hipMemcpyAsync(w->lr_node.p, s_node.data(), (size_t)r * sizeof(int), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->lr_vec.p, s_vec.data(), (size_t)r * nv * sizeof(double), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemcpyAsync(w->lr_delta.p, s_delta.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, stream));
+    KKT_HIP(hipMemsetAsync(w->lrY.p, 0, (size_t)N * r * sizeof(double), stream));
+    hipLaunchKernelGGL(emi_kkt_lr_scatter_kernel, dim3((r + 63) / 64), dim3(64), 0, stream, w->lrY.p, w->lr_node.p, w->lr_vec.p, r, N, M,
                        nv);
     KKT_HIP(hipGetLastError());
-    int st = solve_dev(w, stream, nz, w->lrY, r, err);
+    int st = solve_dev(w, stream, nz, w->lrY.p, r, err);
     if (st) return st;
-    hipLaunchKernelGGL(emi_kkt_lr_c_kernel, dim3((r + 15) / 16, (r + 15) / 16), dim3(16, 16), 0, stream, w->lrC, w->lrY, w->lr_node,
-                       w->lr_vec, w->lr_delta, r, N, M, nv);
+    hipLaunchKernelGGL(emi_kkt_lr_c_kernel, dim3((r + 15) / 16, (r + 15) / 16), dim3(16, 16), 0, stream, w->lrC.p, w->lrY.p, w->lr_node.p,
+                       w->lr_vec.p, w->lr_delta.p, r, N, M, nv);
     KKT_HIP(hipGetLastError());
     rocblas_int hinfo = 0;
-    if (int st2 = cholesky(w, stream, r, w->lrC, &hinfo, err)) return st2;
+    if (int st2 = cholesky(w, stream, r, w->lrC.p, &hinfo, err)) return st2;
     if (hinfo == 0) {
         w->lr_active = true;
         w->lr_r = r;
@@ -1641,29 +1542,23 @@ int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs
     if (!w || !w->factored) { *err = "emi_kkt_solve: no factorisation (emi_kkt_factor must succeed first)"; return EMI_ERR_STATE; }
     const int N = w->N;
     const size_t elems = (size_t)N * nrhs;
-    if (w->rhs_elems < elems) {
-        if (w->rhs) KKT_HIP(hipFree(w->rhs));
-        w->rhs = nullptr;
-        w->rhs_elems = 0;
-        KKT_HIP(hipMalloc(&w->rhs, elems * sizeof(double)));
-        w->rhs_elems = elems;
-    }
-    KKT_HIP(hipMemcpyAsync(w->rhs, rhs, elems * sizeof(double), hipMemcpyHostToDevice, stream));
-    int st = solve_dev(w, stream, nz, w->rhs, nrhs, err);
+    KKT_HIP(w->rhs.reserve(elems));
+    KKT_HIP(hipMemcpyAsync(w->rhs.p, rhs, elems * sizeof(double), hipMemcpyHostToDevice, stream));
+    int st = solve_dev(w, stream, nz, w->rhs.p, nrhs, err);
     if (st) return st;
     if (w->lr_active) {
         // x <- x + Y C^-1 (U^T x)
         const int r = w->lr_r;
         if (nrhs > 64) { *err = "emi_kkt_solve: at most 64 right-hand sides while a low-rank correction is active"; return EMI_ERR_ARG; }
-        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, nrhs), dim3(64), 0, stream, w->lrT, w->rhs, w->lr_node,
-                           w->lr_vec, r, N, w->M, w->nv);
+        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, nrhs), dim3(64), 0, stream, w->lrT.p, w->rhs.p, w->lr_node.p,
+                           w->lr_vec.p, r, N, w->M, w->nv);
         KKT_HIP(hipGetLastError());
-        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, nrhs, w->lrC, r, w->lrT, r));
+        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, nrhs, w->lrC.p, r, w->lrT.p, r));
         const double one = 1.0;
-        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, N, nrhs, r, &one, w->lrY, N, w->lrT, r,
-                             &one, w->rhs, N));
+        KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, N, nrhs, r, &one, w->lrY.p, N, w->lrT.p, r,
+                             &one, w->rhs.p, N));
     }
-    KKT_HIP(hipMemcpyAsync(rhs, w->rhs, elems * sizeof(double), hipMemcpyDeviceToHost, stream));
+    KKT_HIP(hipMemcpyAsync(rhs, w->rhs.p, elems * sizeof(double), hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;
 }
@@ -1687,128 +1582,74 @@ int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs
 namespace {
 
 int batch_scratch(KktWorkspace* L, size_t tab_bytes, size_t ptr_bytes, size_t stat_bytes, std::string* err) {
-    KKT_ENSURE(L->b_tab, L->cap_b_tab, tab_bytes);
-    KKT_ENSURE(L->b_ptrs, L->cap_b_ptrs, ptr_bytes);
-    KKT_ENSURE(L->b_stat, L->cap_b_stat, stat_bytes);
+    KKT_HIP(L->b_tab.reserve(tab_bytes));
+    KKT_HIP(L->b_ptrs.reserve(ptr_bytes / sizeof(double*)));
+    KKT_HIP(L->b_stat.reserve(stat_bytes));
     const size_t pin = tab_bytes + ptr_bytes + stat_bytes;
-    if (L->cap_b_pin < pin) {
-        if (L->b_pin) KKT_HIP(hipHostFree(L->b_pin));
-        L->b_pin = nullptr;
-        L->cap_b_pin = 0;
-        KKT_HIP(hipHostMalloc((void**)&L->b_pin, pin + pin / 2, hipHostMallocDefault));
-        L->cap_b_pin = pin + pin / 2;
-    }
+    if (L->b_pin.cap < pin) KKT_HIP(L->b_pin.reserve(pin + pin / 2));
     return EMI_OK;
 }
 
-// handle + every buffer a Schur factorisation of (M, ns, nv) needs, Doff for the mesh
-int ws_prepare(KktWorkspace* w, hipStream_t stream, const double* dD, int M, int ns, int nv, std::string* err) {
-    const int nh = nv * (nv + 1) / 2, N = (nv + ns) * M, nz = nv * M;
-    const size_t md = (size_t)ns * M;
-    if (!w->handle) {
-        KKT_RB(rocblas_create_handle(&w->handle));
-        KKT_RB(rocblas_set_atomics_mode(w->handle, rocblas_atomics_not_allowed));
-    }
-    if (!w->info) KKT_HIP(hipMalloc(&w->info, sizeof(rocblas_int)));
-    if (!w->flag) KKT_HIP(hipMalloc(&w->flag, sizeof(int)));
-    if (!w->chol_blk) KKT_HIP(hipMalloc((void**)&w->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
-    KKT_ENSURE(w->ipiv, w->cap_ipiv, (size_t)N * sizeof(rocblas_int));
-    KKT_ENSURE(w->Q, w->cap_Q, (size_t)nh * M * sizeof(double));
-    KKT_ENSURE(w->J, w->cap_J, (size_t)ns * nv * M * sizeof(double));
-    KKT_ENSURE(w->fixed, w->cap_fixed, (size_t)nz);
-    if (w->S_elems < md * md) {
-        if (w->S) KKT_HIP(hipFree(w->S));
-        w->S = nullptr;
-        w->S_elems = 0;
-        KKT_HIP(hipMalloc(&w->S, md * md * sizeof(double)));
-        w->S_elems = md * md;
-    }
-    KKT_ENSURE(w->Pinv, w->cap_Pinv, (size_t)nv * nv * M * sizeof(double));
-    KKT_ENSURE(w->G, w->cap_G, (size_t)ns * ns * M * sizeof(double));
-    KKT_ENSURE(w->Rk, w->cap_Rk, (size_t)ns * ns * M * sizeof(double));
-    if (w->cap_Doff < (size_t)M * M * sizeof(double)) w->doff_M = 0;
-    KKT_ENSURE(w->Doff, w->cap_Doff, (size_t)M * M * sizeof(double));
-    KKT_ENSURE(w->W, w->cap_W, (size_t)M * M * sizeof(double));
-    if (w->doff_M != M || w->doff_src != dD) {
-        hipLaunchKernelGGL(emi_kkt_doff_kernel, dim3((unsigned)(((size_t)M * M + 255) / 256)), dim3(256), 0, stream, dD, w->Doff, M);
-        KKT_HIP(hipGetLastError());
-        w->doff_M = M;
-        w->doff_src = dD;
-    }
-    w->N = N; w->M = M; w->ns = ns; w->nv = nv;
-    return EMI_OK;
-}
-
-// Blocked Cholesky of na matrices at once (two-level form of chol_blocked2; lower, column-major, lda = n): per 64-column step one
-// diagonal-block launch of na workgroups, one panel launch, one batched dgemm for the rest of the outer panel; per outer panel one
-// batched dsyrk.  ptrs: device pointer arrays laid out by the caller as  [step][0 = panel, 1 = trailing][na]  for the steps, then
-// [outer][0 = panel, 1 = trailing][na]  for the outer updates (host copy hp: the same layout, filled here).
+// Blocked Cholesky of na matrices at once (the schedule of chol_walk in its two-level form at every size, the matrix-pipe diagonal
+// and panel kernels; lower, column-major, lda = n): per 64-column step one diagonal-block launch of na workgroups, one panel launch,
+// one batched dgemm for the rest of the outer panel; per outer panel one batched dsyrk.  ptrs: device pointer arrays, in the order
+// of the walk  [0 = panel, 1 = trailing][na]  for every step that has an update and every outer panel that has one (host copy hp:
+// the same layout, filled here).
 int chol_batched(KktWorkspace* L, hipStream_t stream, const KktDev* d_tab, int na, double* const* Sptr, int n, double** hp, double** dp,
                  size_t* used, std::string* err) {
-    const int NB2 = std::max(128, (g_tune.chol_outer.load() / CHOL_NB) * CHOL_NB);
+    const int outer = chol_outer_panel();
     const double one = 1.0, mone = -1.0;
+    // pass 1: every pointer array on the host and to the device, before the first launch that reads one
     size_t q = 0;
-    // pass 1: every pointer array on the host (the launches below read them from dp, which the caller uploads AFTER this function
-    // has filled hp?  No: the arrays must be on the device before the first launch that uses them, so they are filled first ...)
-    struct Step { int j0, nb, rest, wc; size_t at; };
-    struct Outer { int J0, Jend, rest2; size_t at; };
-    std::vector<Step> steps;
-    std::vector<Outer> outers;
-    for (int J0 = 0; J0 < n; J0 += NB2) {
-        const int Jend = std::min(n, J0 + NB2);
-        for (int j0 = J0; j0 < Jend; j0 += CHOL_NB) {
-            const int nb = std::min(CHOL_NB, n - j0), rest = n - j0 - nb, wc = Jend - (j0 + nb);
-            Step st{j0, nb, rest, wc, q};
-            if (rest > 0 && wc > 0) {
-                for (int a = 0; a < na; ++a) hp[q + a] = Sptr[a] + (size_t)j0 * n + j0 + nb;                 // panel below the diagonal block
-                for (int a = 0; a < na; ++a) hp[q + na + a] = Sptr[a] + (size_t)(j0 + nb) * n + j0 + nb;     // rest of the outer panel
-                q += 2 * (size_t)na;
-            }
-            steps.push_back(st);
-        }
-        const int rest2 = n - Jend;
-        Outer o{J0, Jend, rest2, q};
-        if (rest2 > 0) {
-            for (int a = 0; a < na; ++a) hp[q + a] = Sptr[a] + (size_t)J0 * n + Jend;
-            for (int a = 0; a < na; ++a) hp[q + na + a] = Sptr[a] + (size_t)Jend * n + Jend;
-            q += 2 * (size_t)na;
-        }
-        outers.push_back(o);
-    }
+    auto push = [&](size_t panel, size_t trailing) {        // positions in every matrix -> [0 = panel][na], [1 = trailing][na]
+        for (int a = 0; a < na; ++a) hp[q + a] = Sptr[a] + panel;
+        for (int a = 0; a < na; ++a) hp[q + na + a] = Sptr[a] + trailing;
+        q += 2 * (size_t)na;
+    };
+    chol_walk(n, outer,
+              [&](const CholStep& s) {            // panel below the diagonal block, rest of the outer panel
+                  if (s.rest > 0 && s.wc > 0) push((size_t)s.j0 * n + s.j0 + s.nb, (size_t)(s.j0 + s.nb) * n + s.j0 + s.nb);
+                  return EMI_OK;
+              },
+              [&](const CholOuter& o) {
+                  if (o.rest2 > 0) push((size_t)o.J0 * n + o.Jend, (size_t)o.Jend * n + o.Jend);
+                  return EMI_OK;
+              });
     *used = q;
     KKT_HIP(hipMemcpyAsync(dp, hp, q * sizeof(double*), hipMemcpyHostToDevice, stream));
-    // ... then the launches
-    size_t si = 0;
-    for (const Outer& o : outers) {
-        for (; si < steps.size() && steps[si].j0 < o.Jend; ++si) {
-            const Step& st = steps[si];
-            if (st.nb == CHOL_NB)
-                hipLaunchKernelGGL(emi_chol_diag_mfma_b_kernel, dim3(na), dim3(64), 0, stream, d_tab, n, st.j0);
-            else
-                hipLaunchKernelGGL(emi_chol_diag_b_kernel, dim3(na), dim3(256), 0, stream, d_tab, n, st.j0, st.nb);
-            if (st.rest <= 0) continue;
-            hipLaunchKernelGGL(emi_chol_panel_mfma_b_kernel, dim3((st.rest + 63) / 64, na), dim3(64), 0, stream, d_tab, n, n, st.j0);
-            if (st.wc > 0) {
-                if (n < g_tune.batch_gemm_rows.load())
-                    KKT_RB(rocblas_dgemm_batched(L->handle, rocblas_operation_none, rocblas_operation_transpose, st.rest, st.wc, st.nb, &mone,
-                                                 (const double* const*)(dp + st.at), n, (const double* const*)(dp + st.at), n, &one,
-                                                 dp + st.at + na, n, na));
-                else
-                    for (int a = 0; a < na; ++a)
-                        KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_none, rocblas_operation_transpose, st.rest, st.wc, st.nb, &mone, hp[st.at + a], n,
-                                             hp[st.at + a], n, &one, hp[st.at + na + a], n));
-            }
-        }
-        if (o.rest2 > 0) {
-            if (n < g_tune.batch_syrk_rows.load())
-                KKT_RB(rocblas_dsyrk_batched(L->handle, rocblas_fill_lower, rocblas_operation_none, o.rest2, o.Jend - o.J0, &mone,
-                                             (const double* const*)(dp + o.at), n, &one, dp + o.at + na, n, na));
-            else
-                for (int a = 0; a < na; ++a)
-                    KKT_RB(rocblas_dsyrk(L->handle, rocblas_fill_lower, rocblas_operation_none, o.rest2, o.Jend - o.J0, &mone, hp[o.at + a], n, &one,
-                                         hp[o.at + na + a], n));
-        }
-    }
+    // pass 2: the launches (`at` walks the arrays as pass 1 laid them out)
+    size_t at = 0;
+    auto step = [&](const CholStep& s) -> int {
+        if (s.nb == CHOL_NB)
+            hipLaunchKernelGGL(emi_chol_diag_mfma_b_kernel, dim3(na), dim3(64), 0, stream, d_tab, n, s.j0);
+        else
+            hipLaunchKernelGGL(emi_chol_diag_b_kernel, dim3(na), dim3(256), 0, stream, d_tab, n, s.j0, s.nb);
+        if (s.rest <= 0) return EMI_OK;
+        hipLaunchKernelGGL(emi_chol_panel_mfma_b_kernel, dim3((s.rest + 63) / 64, na), dim3(64), 0, stream, d_tab, n, n, s.j0);
+        if (s.wc <= 0) return EMI_OK;
+        if (n < g_tune.batch_gemm_rows.load())
+            KKT_RB(rocblas_dgemm_batched(L->handle, rocblas_operation_none, rocblas_operation_transpose, s.rest, s.wc, s.nb, &mone,
+                                         (const double* const*)(dp + at), n, (const double* const*)(dp + at), n, &one, dp + at + na, n, na));
+        else
+            for (int a = 0; a < na; ++a)
+                KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_none, rocblas_operation_transpose, s.rest, s.wc, s.nb, &mone, hp[at + a], n,
+                                     hp[at + a], n, &one, hp[at + na + a], n));
+        at += 2 * (size_t)na;
+        return EMI_OK;
+    };
+    auto outer_update = [&](const CholOuter& o) -> int {
+        if (o.rest2 <= 0) return EMI_OK;
+        if (n < g_tune.batch_syrk_rows.load())
+            KKT_RB(rocblas_dsyrk_batched(L->handle, rocblas_fill_lower, rocblas_operation_none, o.rest2, o.Jend - o.J0, &mone,
+                                         (const double* const*)(dp + at), n, &one, dp + at + na, n, na));
+        else
+            for (int a = 0; a < na; ++a)
+                KKT_RB(rocblas_dsyrk(L->handle, rocblas_fill_lower, rocblas_operation_none, o.rest2, o.Jend - o.J0, &mone, hp[at + a], n, &one,
+                                     hp[at + na + a], n));
+        at += 2 * (size_t)na;
+        return EMI_OK;
+    };
+    if (int st = chol_walk(n, outer, step, outer_update)) return st;
     KKT_HIP(hipGetLastError());
     return EMI_OK;
 }
@@ -1827,20 +1668,13 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
         for (int b = 0; b < n; ++b) info[b] = -1;
         return EMI_OK;
     }
-    const int nh = nv * (nv + 1) / 2, nz = nv * M, md = ns * M, npairs = ns * (ns + 1) / 2;
+    const int md = ns * M, npairs = ns * (ns + 1) / 2;
     std::vector<KktWorkspace*> W(n);
     for (int b = 0; b < n; ++b) {
         if (!*pws[b]) *pws[b] = new KktWorkspace();
         KktWorkspace* w = W[b] = *pws[b];
-        w->factored = false;
-        w->lr_active = false;
-        w->linv_n = 0;
-        w->reg_dc_applied = dc[b];
-        w->reg_dw_applied = 0.0;
-        if (int st = ws_prepare(w, stream, dD[b], M, ns, nv, err)) return st;
-        KKT_HIP(hipMemcpyAsync(w->Q, Qblk[b], (size_t)nh * M * sizeof(double), hipMemcpyHostToDevice, stream));
-        KKT_HIP(hipMemcpyAsync(w->J, Jblk[b], (size_t)ns * nv * M * sizeof(double), hipMemcpyHostToDevice, stream));
-        KKT_HIP(hipMemcpyAsync(w->fixed, fixed[b], (size_t)nz, hipMemcpyHostToDevice, stream));
+        if (int st = ws_prepare(w, stream, dD[b], M, ns, nv, dc[b], true, 1, err)) return st;
+        if (int st = upload_blocks(w, stream, Qblk[b], Jblk[b], fixed[b], err)) return st;
         info[b] = -1;
     }
     KktWorkspace* L = W[0];
@@ -1851,32 +1685,21 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
     const size_t ptr_count = (size_t)n * (2 + npairs + 2 * (nsteps + nsteps / 2 + 2) + 2 * nblk + 8);
     const size_t tab_bytes = (size_t)n * sizeof(KktDev), ptr_bytes = ptr_count * sizeof(double*), stat_bytes = (size_t)2 * n * sizeof(int);
     if (int st = batch_scratch(L, tab_bytes, ptr_bytes, stat_bytes, err)) return st;
-    KktDev* h_tab = reinterpret_cast<KktDev*>(L->b_pin);
-    double** h_ptr = reinterpret_cast<double**>(L->b_pin + tab_bytes);
-    int* h_stat = reinterpret_cast<int*>(L->b_pin + tab_bytes + ptr_bytes);
-    KktDev* d_tab = reinterpret_cast<KktDev*>(L->b_tab);
+    KktDev* h_tab = reinterpret_cast<KktDev*>(L->b_pin.p);
+    double** h_ptr = reinterpret_cast<double**>(L->b_pin.p + tab_bytes);
+    int* h_stat = reinterpret_cast<int*>(L->b_pin.p + tab_bytes + ptr_bytes);
+    KktDev* d_tab = reinterpret_cast<KktDev*>(L->b_tab.p);
+    int* d_stat = reinterpret_cast<int*>(L->b_stat.p);
 
-    static const double LV_DC[5] = {1.0, 1e3, 1e3, 1e3, 1e6}, LV_DW[5] = {0.0, 0.0, 1e-7, 1e-5, 1e-3};       // the ladder of kkt_factor
-    constexpr int NLV = 5;
-    const int max_lv = g_tune.primal_levels.load() ? NLV : 2;
+    const RegLadder ladder{};
     std::vector<int> level(n), first(n);
     std::vector<char> done(n, 0);
-    for (int b = 0; b < n; ++b) {
-        KktWorkspace* w = W[b];
-        if (w->reg_M != M || w->reg_ns != ns || w->reg_nv != nv || !g_tune.sticky_reg.load()) {
-            w->reg_level = w->reg_hits = 0;
-            w->reg_M = M; w->reg_ns = ns; w->reg_nv = nv;
-        } else if (w->reg_level > 0 && w->reg_hits >= 4) {
-            --w->reg_level;
-            w->reg_hits = 0;
-        }
-        level[b] = first[b] = std::min(w->reg_level, max_lv - 1);
-    }
+    for (int b = 0; b < n; ++b) level[b] = first[b] = ladder.start(W[b], M, ns, nv);
     const unsigned nb2 = (unsigned)(((size_t)M * M + 255) / 256);
     const double one = 1.0, zero = 0.0;
     std::vector<int> act;
     std::vector<double*> Sptr(n);
-    for (int round = 0; round < NLV + 1; ++round) {
+    for (int round = 0; round < RegLadder::NLV + 1; ++round) {
         act.clear();
         for (int b = 0; b < n; ++b)
             if (!done[b]) act.push_back(b);
@@ -1884,53 +1707,47 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
         if (na == 0) break;
         for (int a = 0; a < na; ++a) {
             KktWorkspace* w = W[act[a]];
-            const double dc_base = dc[act[a]] > 1e-9 ? dc[act[a]] : 1e-9;
             KktDev t{};
-            t.Q = w->Q; t.J = w->J; t.Pinv = w->Pinv; t.G = w->G; t.Rk = w->Rk; t.S = w->S; t.W = w->W; t.chol_blk = w->chol_blk;
-            t.Doff = w->Doff;
-            t.fixed = w->fixed;
-            t.info = L->b_stat + a;
-            t.flag = L->b_stat + na + a;
-            t.dw = LV_DW[level[act[a]]];
-            t.dc = dc_base * LV_DC[level[act[a]]];
+            t.Q = w->Q.p; t.J = w->J.p; t.Pinv = w->Pinv.p; t.G = w->G.p; t.Rk = w->Rk.p; t.S = w->S.p; t.W = w->W.p; t.chol_blk = w->chol_blk.p;
+            t.Doff = w->Doff.p;
+            t.fixed = w->fixed.p;
+            t.info = d_stat + a;
+            t.flag = d_stat + na + a;
+            t.dw = ladder.dw(level[act[a]]);
+            t.dc = ladder.dc(level[act[a]], dc[act[a]]);
             h_tab[a] = t;
-            Sptr[a] = w->S;
+            Sptr[a] = w->S.p;
         }
         // pointer arrays of the S build
         size_t q = 0;
-        const size_t at_A = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Doff;
-        const size_t at_B = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->W;
+        const size_t at_A = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Doff.p;
+        const size_t at_B = q;  for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->W.p;
         const size_t at_C = q;
         for (int i = 0; i < ns; ++i)
             for (int ip = 0; ip <= i; ++ip)
-                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S + ((size_t)ip * M) * md + (size_t)i * M;
+                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S.p + ((size_t)ip * M) * md + (size_t)i * M;
         KKT_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)na * sizeof(KktDev), hipMemcpyHostToDevice, stream));
-        KKT_HIP(hipMemcpyAsync(L->b_ptrs, h_ptr, q * sizeof(double*), hipMemcpyHostToDevice, stream));
+        KKT_HIP(hipMemcpyAsync(L->b_ptrs.p, h_ptr, q * sizeof(double*), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(emi_kkt_zero_status_b_kernel, dim3((na + 63) / 64), dim3(64), 0, stream, (const KktDev*)d_tab, na);
-        if (ns == 6 && nv == 8)
-            hipLaunchKernelGGL((emi_kkt_node_inverse_fixed_b_kernel<6, 8>), dim3((M + 63) / 64, na), dim3(64), 0, stream, (const KktDev*)d_tab, M);
-        else if (ns == 2 && nv == 4)
-            hipLaunchKernelGGL((emi_kkt_node_inverse_fixed_b_kernel<2, 4>), dim3((M + 63) / 64, na), dim3(64), 0, stream, (const KktDev*)d_tab, M);
-        else
-            hipLaunchKernelGGL(emi_kkt_node_inverse_b_kernel, dim3((M + 63) / 64, na), dim3(64), 0, stream, (const KktDev*)d_tab, M, ns, nv);
+        launch_node_inverse(stream, M, ns, nv, nullptr, 0.0, d_tab, na);
         KKT_HIP(hipGetLastError());
         for (int i = 0, p = 0; i < ns; ++i)
             for (int ip = 0; ip <= i; ++ip, ++p) {
                 hipLaunchKernelGGL(emi_kkt_scale_b_kernel, dim3(nb2, na), dim3(256), 0, stream, (const KktDev*)d_tab, M, (i * nv + ip) * M);
                 if (md < g_tune.batch_gemm_rows.load())
                     KKT_RB(rocblas_dgemm_batched(L->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one,
-                                                 (const double* const*)(L->b_ptrs + at_A), M, (const double* const*)(L->b_ptrs + at_B), M, &zero,
-                                                 L->b_ptrs + at_C + (size_t)p * na, (rocblas_int)md, na));
+                                                 (const double* const*)(L->b_ptrs.p + at_A), M, (const double* const*)(L->b_ptrs.p + at_B), M, &zero,
+                                                 L->b_ptrs.p + at_C + (size_t)p * na, (rocblas_int)md, na));
                 else
                     for (int a = 0; a < na; ++a)
-                        KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, W[act[a]]->Doff, M, W[act[a]]->W, M, &zero,
+                        KKT_RB(rocblas_dgemm(L->handle, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, W[act[a]]->Doff.p, M, W[act[a]]->W.p, M, &zero,
                                              h_ptr[at_C + (size_t)p * na + a], (rocblas_int)md));
                 hipLaunchKernelGGL(emi_kkt_sblock_terms_b_kernel, dim3(nb2, na), dim3(256), 0, stream, (const KktDev*)d_tab, M, ns, i, ip);
             }
         KKT_HIP(hipGetLastError());
         size_t used = 0;
-        if (int st = chol_batched(L, stream, d_tab, na, Sptr.data(), md, h_ptr + q, L->b_ptrs + q, &used, err)) return st;
-        KKT_HIP(hipMemcpyAsync(h_stat, L->b_stat, (size_t)2 * na * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (int st = chol_batched(L, stream, d_tab, na, Sptr.data(), md, h_ptr + q, L->b_ptrs.p + q, &used, err)) return st;
+        KKT_HIP(hipMemcpyAsync(h_stat, d_stat, (size_t)2 * na * sizeof(int), hipMemcpyDeviceToHost, stream));
         KKT_HIP(hipStreamSynchronize(stream));
         for (int a = 0; a < na; ++a) {
             const int b = act[a], hinfo = h_stat[a], hflag = h_stat[na + a];
@@ -1938,15 +1755,11 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
             if (hinfo == 0 && hflag == 0) {
                 done[b] = 1;
                 info[b] = 0;
-                if (level[b] == first[b]) ++w->reg_hits; else { w->reg_level = level[b]; w->reg_hits = 0; }
-                w->reg_dc_applied = h_tab[a].dc;
-                w->reg_dw_applied = h_tab[a].dw;
-                w->factored = true;
-                w->method_used = 1;
-            } else if (hflag != 0 || level[b] + 1 >= max_lv) {
+                ladder.succeeded(w, level[b], first[b], dc[b]);
+            } else if (hflag != 0 || level[b] + 1 >= ladder.max_lv) {
                 done[b] = 1;                        // not the quasi-definite case, or no level helps: the single path (and its LU) decides
                 info[b] = -1;
-                if (hflag == 0) { w->reg_level = max_lv - 1; w->reg_hits = 0; }
+                if (hflag == 0) ladder.exhausted(w);
                 if (g_tune.debug.load())
                     fprintf(stderr, "emi_kkt_factor_batch: scenario %d of %d leaves the batch (block flag %d, potrf info %d, M %d)\n", b, n, hflag, hinfo, M);
             } else {
@@ -1968,37 +1781,37 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
             size_t q = 0;
             for (int a = 0; a < na; ++a) {
                 KktWorkspace* w = W[act[a]];
-                KKT_ENSURE(w->Linv, w->cap_Linv, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double));
-                KKT_ENSURE(w->LinvT, w->cap_LinvT, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double));
-                KKT_HIP(hipMemsetAsync(w->Linv, 0, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double), stream));
+                KKT_HIP(w->Linv.reserve((size_t)nblk * TRSV_NB * TRSV_NB));
+                KKT_HIP(w->LinvT.reserve((size_t)nblk * TRSV_NB * TRSV_NB));
+                KKT_HIP(hipMemsetAsync(w->Linv.p, 0, (size_t)nblk * TRSV_NB * TRSV_NB * sizeof(double), stream));
                 KktDev t{};
-                t.Linv = w->Linv;
-                t.LinvT = w->LinvT;
+                t.Linv = w->Linv.p;
+                t.LinvT = w->LinvT.p;
                 h_tab[a] = t;
             }
             const size_t at_LA = q;
             for (int j = 0; j < full; ++j)
-                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S + (size_t)j * TRSV_NB * ((size_t)md + 1);
+                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S.p + (size_t)j * TRSV_NB * ((size_t)md + 1);
             const size_t at_LI = q;
             for (int j = 0; j < full; ++j)
-                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Linv + (size_t)j * TRSV_NB * TRSV_NB;
+                for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Linv.p + (size_t)j * TRSV_NB * TRSV_NB;
             const size_t at_TA = q;
-            for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S + (size_t)full * TRSV_NB * ((size_t)md + 1);
+            for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->S.p + (size_t)full * TRSV_NB * ((size_t)md + 1);
             const size_t at_TI = q;
-            for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Linv + (size_t)full * TRSV_NB * TRSV_NB;
+            for (int a = 0; a < na; ++a) h_ptr[q++] = W[act[a]]->Linv.p + (size_t)full * TRSV_NB * TRSV_NB;
             KKT_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)na * sizeof(KktDev), hipMemcpyHostToDevice, stream));
-            KKT_HIP(hipMemcpyAsync(L->b_ptrs, h_ptr, q * sizeof(double*), hipMemcpyHostToDevice, stream));
+            KKT_HIP(hipMemcpyAsync(L->b_ptrs.p, h_ptr, q * sizeof(double*), hipMemcpyHostToDevice, stream));
             if (full > 0 && md < g_tune.batch_trtri_rows.load())
                 KKT_RB(rocblas_dtrtri_batched(L->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, TRSV_NB,
-                                              (const double* const*)(L->b_ptrs + at_LA), md, L->b_ptrs + at_LI, TRSV_NB, full * na));
+                                              (const double* const*)(L->b_ptrs.p + at_LA), md, L->b_ptrs.p + at_LI, TRSV_NB, full * na));
             else if (full > 0)
                 for (int a = 0; a < na; ++a)
-                    KKT_RB(rocblas_dtrtri_strided_batched(L->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, TRSV_NB, W[act[a]]->S, md,
-                                                          (rocblas_stride)TRSV_NB * (md + 1), W[act[a]]->Linv, TRSV_NB,
+                    KKT_RB(rocblas_dtrtri_strided_batched(L->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, TRSV_NB, W[act[a]]->S.p, md,
+                                                          (rocblas_stride)TRSV_NB * (md + 1), W[act[a]]->Linv.p, TRSV_NB,
                                                           (rocblas_stride)TRSV_NB * TRSV_NB, full));
             if (tail > 0)
                 KKT_RB(rocblas_dtrtri_batched(L->handle, rocblas_fill_lower, rocblas_diagonal_non_unit, tail,
-                                              (const double* const*)(L->b_ptrs + at_TA), md, L->b_ptrs + at_TI, TRSV_NB, na));
+                                              (const double* const*)(L->b_ptrs.p + at_TA), md, L->b_ptrs.p + at_TI, TRSV_NB, na));
             hipLaunchKernelGGL(emi_trsv_transpose_b_kernel, dim3(TRSV_NB / 32, TRSV_NB / 32, nblk * na), dim3(256), 0, stream, (const KktDev*)d_tab, nblk);
             KKT_HIP(hipGetLastError());
             KKT_HIP(hipStreamSynchronize(stream));          // (the pinned table is reused by the next call)
@@ -2090,12 +1903,12 @@ __global__ void emi_kkt_vecop_b_kernel(const KktDev* __restrict__ tab, int N, in
 struct SolveShape { int M, ns, nv, N, nz, md, nblk; bool blk; };
 
 void fill_solve_entry(KktDev& t, KktWorkspace* w) {
-    t.Q = w->Q; t.J = w->J; t.Pinv = w->Pinv; t.S = w->S; t.Linv = w->Linv; t.LinvT = w->LinvT; t.T = w->T; t.Cb = w->Cb; t.rhs = w->rhs;
-    t.y = w->trsv_y; t.bb = w->ref_b; t.xx = w->ref_x; t.xp = w->ref_p;
-    t.fixed = w->fixed;
-    t.Doff = w->Doff;
+    t.Q = w->Q.p; t.J = w->J.p; t.Pinv = w->Pinv.p; t.S = w->S.p; t.Linv = w->Linv.p; t.LinvT = w->LinvT.p; t.T = w->T.p; t.Cb = w->Cb.p; t.rhs = w->rhs.p;
+    t.y = w->trsv_y.p; t.bb = w->ref_b.p; t.xx = w->ref_x.p; t.xp = w->ref_p.p;
+    t.fixed = w->fixed.p;
+    t.Doff = w->Doff.p;
     t.lr_r = w->lr_active ? w->lr_r : 0;
-    t.lr_node = w->lr_node; t.lr_vec = w->lr_vec; t.lr_delta = w->lr_delta;
+    t.lr_node = w->lr_node.p; t.lr_vec = w->lr_vec.p; t.lr_delta = w->lr_delta.p;
 }
 
 // table + the pointer arrays every batched call below needs, for the n workspaces of this step
@@ -2109,10 +1922,10 @@ int solve_arrays(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int 
     const size_t ptr_count = (size_t)n * (8 + (sh.blk ? 5 * sh.nblk : 0));
     const size_t tab_bytes = (size_t)n * sizeof(KktDev), ptr_bytes = ptr_count * sizeof(double*), stat_bytes = (size_t)4 * n * sizeof(double);
     if (int st = batch_scratch(L, tab_bytes, ptr_bytes, stat_bytes, err)) return st;
-    KktDev* h_tab = reinterpret_cast<KktDev*>(L->b_pin);
-    double** h_ptr = reinterpret_cast<double**>(L->b_pin + tab_bytes);
-    A->d_tab = reinterpret_cast<KktDev*>(L->b_tab);
-    A->P = L->b_ptrs;
+    KktDev* h_tab = reinterpret_cast<KktDev*>(L->b_pin.p);
+    double** h_ptr = reinterpret_cast<double**>(L->b_pin.p + tab_bytes);
+    A->d_tab = reinterpret_cast<KktDev*>(L->b_tab.p);
+    A->P = L->b_ptrs.p;
     for (int b = 0; b < n; ++b) {
         KktDev t{};
         fill_solve_entry(t, ws[b]);
@@ -2120,23 +1933,23 @@ int solve_arrays(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int 
     }
     size_t q = 0;
     auto arr = [&](auto f) { const size_t at = q; for (int b = 0; b < n; ++b) h_ptr[q++] = f(ws[b]); return at; };
-    A->at_D = arr([](KktWorkspace* w) { return w->Doff; });
-    A->at_T = arr([](KktWorkspace* w) { return w->T; });
-    A->at_Cb = arr([](KktWorkspace* w) { return w->Cb; });
-    A->at_X = arr([](KktWorkspace* w) { return w->rhs; });
-    A->at_S = arr([](KktWorkspace* w) { return w->S; });
-    A->at_Y = arr([](KktWorkspace* w) { return w->trsv_y; });
-    A->at_XX = arr([](KktWorkspace* w) { return w->ref_x; });
-    A->at_lam = arr([&](KktWorkspace* w) { return w->ref_x + sh.nz; });
+    A->at_D = arr([](KktWorkspace* w) { return w->Doff.p; });
+    A->at_T = arr([](KktWorkspace* w) { return w->T.p; });
+    A->at_Cb = arr([](KktWorkspace* w) { return w->Cb.p; });
+    A->at_X = arr([](KktWorkspace* w) { return w->rhs.p; });
+    A->at_S = arr([](KktWorkspace* w) { return w->S.p; });
+    A->at_Y = arr([](KktWorkspace* w) { return w->trsv_y.p; });
+    A->at_XX = arr([](KktWorkspace* w) { return w->ref_x.p; });
+    A->at_lam = arr([&](KktWorkspace* w) { return w->ref_x.p + sh.nz; });
     A->at_LT.assign(sh.nblk, 0); A->at_LI.assign(sh.nblk, 0); A->at_xj.assign(sh.nblk, 0); A->at_yj.assign(sh.nblk, 0); A->at_Sr.assign(sh.nblk, 0);
     if (sh.blk)
         for (int j = 0; j < sh.nblk; ++j) {
             const size_t j0 = (size_t)j * TRSV_NB;
-            A->at_LT[j] = arr([&](KktWorkspace* w) { return w->LinvT + (size_t)j * TRSV_NB * TRSV_NB; });
-            A->at_LI[j] = arr([&](KktWorkspace* w) { return w->Linv + (size_t)j * TRSV_NB * TRSV_NB; });
-            A->at_xj[j] = arr([&](KktWorkspace* w) { return w->Cb + j0; });
-            A->at_yj[j] = arr([&](KktWorkspace* w) { return w->trsv_y + j0; });
-            A->at_Sr[j] = arr([&](KktWorkspace* w) { return w->S + j0; });
+            A->at_LT[j] = arr([&](KktWorkspace* w) { return w->LinvT.p + (size_t)j * TRSV_NB * TRSV_NB; });
+            A->at_LI[j] = arr([&](KktWorkspace* w) { return w->Linv.p + (size_t)j * TRSV_NB * TRSV_NB; });
+            A->at_xj[j] = arr([&](KktWorkspace* w) { return w->Cb.p + j0; });
+            A->at_yj[j] = arr([&](KktWorkspace* w) { return w->trsv_y.p + j0; });
+            A->at_Sr[j] = arr([&](KktWorkspace* w) { return w->S.p + j0; });
         }
     // the previous step's launches read the device copies: they are done before the pinned staging is overwritten, because every
     // step of the callers ends with a stream synchronisation (status words) -- except the first, which has nothing in flight
@@ -2145,7 +1958,7 @@ int solve_arrays(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int 
     return EMI_OK;
 }
 
-// rhs <- K~^-1 rhs (+ Woodbury term of the scenarios that hold a low-rank correction), in place on every ws[b]->rhs
+// rhs <- K~^-1 rhs (+ Woodbury term of the scenarios that hold a low-rank correction), in place on every ws[b]->rhs.p
 int solve_core(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int n, KktWorkspace* const* ws, const SolveArrays& A, std::string* err) {
     const int M = sh.M, ns = sh.ns, nv = sh.nv, N = sh.N, nz = sh.nz, md = sh.md, nblk = sh.nblk;
     const KktDev* d_tab = A.d_tab;
@@ -2190,10 +2003,10 @@ int solve_core(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int n,
         if (!w->lr_active) continue;    // x <- x + Y C^-1 (U^T x), with the scenario's own handle on this stream
         const int r = w->lr_r;
         KKT_RB(rocblas_set_stream(w->handle, stream));
-        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, 1), dim3(64), 0, stream, w->lrT, w->rhs, w->lr_node, w->lr_vec, r, N, M, nv);
+        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, 1), dim3(64), 0, stream, w->lrT.p, w->rhs.p, w->lr_node.p, w->lr_vec.p, r, N, M, nv);
         KKT_HIP(hipGetLastError());
-        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, 1, w->lrC, r, w->lrT, r));
-        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_none, N, r, &one, w->lrY, N, w->lrT, 1, &one, w->rhs, 1));
+        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, 1, w->lrC.p, r, w->lrT.p, r));
+        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_none, N, r, &one, w->lrY.p, N, w->lrT.p, 1, &one, w->rhs.p, 1));
     }
     return EMI_OK;
 }
@@ -2218,29 +2031,14 @@ int residual_core(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int
 }
 
 int solve_buffers(KktWorkspace* w, int N, int nz, int md, bool refine, std::string* err) {
-    if (w->rhs_elems < (size_t)N) {
-        if (w->rhs) KKT_HIP(hipFree(w->rhs));
-        w->rhs = nullptr; w->rhs_elems = 0;
-        KKT_HIP(hipMalloc(&w->rhs, (size_t)N * sizeof(double)));
-        w->rhs_elems = (size_t)N;
-    }
-    if (w->T_elems < (size_t)nz) {
-        if (w->T) KKT_HIP(hipFree(w->T));
-        w->T = nullptr; w->T_elems = 0;
-        KKT_HIP(hipMalloc(&w->T, (size_t)nz * sizeof(double)));
-        w->T_elems = (size_t)nz;
-    }
-    if (w->Cb_elems < (size_t)md) {
-        if (w->Cb) KKT_HIP(hipFree(w->Cb));
-        w->Cb = nullptr; w->Cb_elems = 0;
-        KKT_HIP(hipMalloc(&w->Cb, (size_t)md * sizeof(double)));
-        w->Cb_elems = (size_t)md;
-    }
-    KKT_ENSURE(w->trsv_y, w->cap_trsv_y, (size_t)md * sizeof(double));
+    KKT_HIP(w->rhs.reserve((size_t)N));
+    KKT_HIP(w->T.reserve((size_t)nz));
+    KKT_HIP(w->Cb.reserve((size_t)md));
+    KKT_HIP(w->trsv_y.reserve((size_t)md));
     if (refine) {
-        KKT_ENSURE(w->ref_b, w->cap_ref_b, (size_t)N * sizeof(double));
-        KKT_ENSURE(w->ref_x, w->cap_ref_x, (size_t)N * sizeof(double));
-        KKT_ENSURE(w->ref_p, w->cap_ref_p, (size_t)N * sizeof(double));
+        KKT_HIP(w->ref_b.reserve((size_t)N));
+        KKT_HIP(w->ref_x.reserve((size_t)N));
+        KKT_HIP(w->ref_p.reserve((size_t)N));
     }
     return EMI_OK;
 }
@@ -2273,13 +2071,13 @@ int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, 
     KktWorkspace* L = ws[0];
     for (int b = 0; b < n; ++b) {
         if (int st = solve_buffers(ws[b], sh.N, sh.nz, sh.md, false, err)) return st;
-        KKT_HIP(hipMemcpyAsync(ws[b]->rhs, rhs[b], (size_t)sh.N * sizeof(double), hipMemcpyHostToDevice, stream));
+        KKT_HIP(hipMemcpyAsync(ws[b]->rhs.p, rhs[b], (size_t)sh.N * sizeof(double), hipMemcpyHostToDevice, stream));
     }
     KKT_RB(rocblas_set_stream(L->handle, stream));
     SolveArrays A;
     if (int st = solve_arrays(L, stream, sh, n, ws, &A, err)) return st;
     if (int st = solve_core(L, stream, sh, n, ws, A, err)) return st;
-    for (int b = 0; b < n; ++b) KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->rhs, (size_t)sh.N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    for (int b = 0; b < n; ++b) KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->rhs.p, (size_t)sh.N * sizeof(double), hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;
 }
@@ -2300,11 +2098,11 @@ int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, 
     const double refine_rel = std::pow(10.0, -(double)g_tune.refine_exp.load());
     for (int b = 0; b < n; ++b) {
         if (int st = solve_buffers(ws[b], sh.N, sh.nz, sh.md, true, err)) return st;
-        KKT_HIP(hipMemcpyAsync(ws[b]->ref_b, rhs[b], (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
+        KKT_HIP(hipMemcpyAsync(ws[b]->ref_b.p, rhs[b], (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
         rel[b] = 0.0; nsolve[b] = 0; reverted[b] = 0; status[b] = 0;
     }
     KKT_RB(rocblas_set_stream(L->handle, stream));
-    double* d_stat = reinterpret_cast<double*>(L->b_stat);              // (batch_scratch sizes it for 4 n doubles)
+    double* d_stat = reinterpret_cast<double*>(L->b_stat.p);              // (batch_scratch sizes it for 4 n doubles)
     std::vector<double> h_max(n), bmax(n), prev(n, 1e300), rlast(n, 0.0);
     std::vector<char> have_prev(n, 0);
     std::vector<KktWorkspace*> act(ws, ws + n);
@@ -2312,7 +2110,7 @@ int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, 
     for (int b = 0; b < n; ++b) idx[b] = b;
     SolveArrays A;
     if (int st = solve_arrays(L, stream, sh, n, act.data(), &A, err)) return st;
-    d_stat = reinterpret_cast<double*>(L->b_stat);
+    d_stat = reinterpret_cast<double*>(L->b_stat.p);
     // mask the right-hand sides as the single path does (fixed variables: 0), |b|, first solve
     dim3 gN((N + 255) / 256, n);
     hipLaunchKernelGGL(emi_kkt_vecop_b_kernel, gN, dim3(256), 0, stream, (const KktDev*)A.d_tab, N, 0);                 // rhs <- bb
@@ -2385,13 +2183,10 @@ int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, 
     }
     for (int b = 0; b < n; ++b) {
         rel[b] = rlast[b] / std::max(1.0, bmax[b]);
-        KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->ref_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream));
+        KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->ref_x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream));
     }
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;
-#undef KKT_ENSURE
-#undef KKT_HIP
-#undef KKT_RB
 }
 
 }  // namespace emi

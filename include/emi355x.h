@@ -441,10 +441,10 @@ int emi_profile_read(emi_ctx_t ctx, float* node_ms, int* node_launches,
  * dual ones before the LU fallback; "kkt_sticky_reg" 1 (default):
  * the Schur path starts at the dual regularisation level that worked last on this
  * mesh; "kkt_cholesky" 2 (default): the library's blocked Cholesky in two-level form from 1024 rows
- * (outer panels of "kkt_chol_outer" columns, default 768), 1: one level, 0: rocsolver_dpotrf;
+ * (outer panels of "kkt_chol_outer" columns, default 768), 1: one level (any other value: EMI_ERR_ARG);
  * "kkt_chol_diag" 2 (default): the 64 x 64 diagonal block of a Cholesky step by one wave with matrix-pipe block updates, 1: column by column by 256 threads;
  * "kkt_chol_panel" 2 (default): the panel solve of a Cholesky step as 16 x 16 block products on the matrix pipe, 1: one row per thread, 0: rocblas_dtrsm;
- * "kkt_debug", "kkt_batched_max_nodes", "kkt_potrf_lock": diagnostics, see csrc/emi_kkt.hip).
+ * "kkt_debug", "kkt_batched_max_nodes": diagnostics, see csrc/emi_kkt.hip).
  * "slice": > 0: batches above 2 * slice instances are evaluated in pieces of `slice` instances; 0 (default): a batch above
  * 2048 instances goes as one launch over its multiple of 256 instances plus one for the remainder.
  * "sym_ablate": diagnostics only, results invalid.                             */

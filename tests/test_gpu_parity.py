@@ -471,6 +471,26 @@ def test_abi_error_paths(built):
     assert lib.emi_destroy(None) == 1
 
 
+def test_removed_cholesky_options_are_refused(built):
+    """"kkt_cholesky" 0 (rocsolver_dpotrf behind a lock and a confirmation on a copy) and its "kkt_potrf_lock" are gone: the option
+    takes 1 and 2, anything else is an argument error with a message; the lock is an unknown option."""
+    import ctypes as C
+    from etol_amd import _lib as L
+    lib = L.load()
+    ctx = C.c_void_p()
+    assert lib.emi_create(0, C.byref(ctx)) == 0
+    try:
+        for bad in (0, -1, 3):
+            assert lib.emi_set_option(ctx, b"kkt_cholesky", bad) == 1, bad
+            assert b"kkt_cholesky" in lib.emi_last_error(ctx)
+        assert lib.emi_set_option(ctx, b"kkt_potrf_lock", 1) == 1
+        assert b"unknown option" in lib.emi_last_error(ctx)
+        assert lib.emi_set_option(ctx, b"kkt_cholesky", 1) == 0
+    finally:
+        assert lib.emi_set_option(ctx, b"kkt_cholesky", 2) == 0      # (process-wide: back to the default)
+        assert lib.emi_destroy(ctx) == 0
+
+
 @pytest.mark.parametrize("inputs", ["smooth", "bench"])
 def test_f32_defect_survives_single_precision_at_4096_nodes(built, inputs):
     """Config 5 shape: M = 4096, 12 states, f32, against the CPU ORACLE (oracle/emi_oracle.c: D.X accumulated in
