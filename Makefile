@@ -77,8 +77,9 @@ $(LIBDIR)/etol_mi355x_example1: etol_amd/examples/etol_mi355x_example1.cpp $(LIB
 $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $(LIBDIR)/libetol_mi355x.so
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
-tests/harness/libetol_harness.so: tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp $(LIBDIR)/libetol_mi355x.so $(HOST_HDR)
-	$(CXX) $(CXXFLAGS) -I$(HOST) -shared -o $@ tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
+HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp
+tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR)
+	$(CXX) $(CXXFLAGS) -I$(HOST) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 oracle:

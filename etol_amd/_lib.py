@@ -91,6 +91,10 @@ SYMBOLS = {
     "emi_lagr_grad_host": (C.c_int, [_P, _D, _D, _D, C.c_double, _D]),
     "emi_kkt_certificate_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P, C.c_int, _D, _D, _P, _P]),
     "emi_kkt_certificate_host": (C.c_int, [_P, _D, _D, _D, _D, C.c_double, _D, _D, C.c_int, _D, _D, _D, _D]),
+    "emi_lagr_grad_total_dev": (C.c_int, [_P, _P, _P, _P, C.c_double, _P, _P]),
+    "emi_lagr_grad_total_host": (C.c_int, [_P, _D, _D, _D, C.c_double, _D, _D]),
+    "emi_kkt_certificate_total_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P, C.c_int, _D, _D, _P, _P, _P]),
+    "emi_kkt_certificate_total_host": (C.c_int, [_P, _D, _D, _D, _D, C.c_double, _D, _D, C.c_int, _D, _D, _D, _D, _D]),
     "emi_timer_start": (C.c_int, [_P]),
     "emi_timer_stop": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "emi_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -5,9 +5,12 @@
 //              + (v < ns ? sum_{j != k} D[j][k] * lamF[v][j] : 0)           off-diagonal part of D^T: the operator
 //              + sum over path rows and their partials  VALS[..][k] * lamC[r][k]
 //
-//   KA  emi_adjoint_transpose_kernel   once per mesh: DT[n][j] = D[j][n], zero on the diagonal, rows padded to an even length
+//   KA  emi_adjoint_transpose_kernel   once per mesh: DT[n][j] = D[j][n], zero on the diagonal, rows padded to an even length; with delays
+//                                      also WT[n][s*ldt + j] = W_(s+1)[j][n], the transposed stack of the interpolation operators (diagonal kept)
 //   KB  emi_adjoint_op_kernel          operator term: [R = B*ns][M] x [M][M] on v_mfma_f64_16x16x4_f64, plain stores into the state rows of G;
-//                                      two tile shapes, by the number of workgroups the batch gives
+//                                      two tile shapes, by the number of workgroups the batch gives.  The same kernel folds the adjoints
+//                                      of the delayed values onto their sources (emi_lagr_grad_total_*): rows (instance, source variable),
+//                                      K = the delay indices' node ranges one after the other, the last addition is Gx[source] + product
 //   KC  emi_adjoint_node_all_kernel /  node terms, threads along the node index: one thread per (instance, node) with the nv sums in registers,
 //       emi_adjoint_node_kernel        or per (instance, variable, node) for small batches; both read every VALS entry exactly once
 //                                      (coalesced), sum in the same order and ADD the operator term already in G (state rows)
@@ -36,24 +39,32 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int ADJ_CUS = 256;
 constexpr double ADJ_INF_BOUND = 1e19;      // |bound| >= this: the bound is absent (INF_BOUND of the NLP iteration)
 
-__global__ __launch_bounds__(256) void emi_adjoint_transpose_kernel(const double* __restrict__ D, double* __restrict__ DT, int M, int ldt) {
+// grid.z = segment: source matrix blockIdx.z, columns blockIdx.z * ldt .. of the ld_dst long rows of DT
+__global__ __launch_bounds__(256) void emi_adjoint_transpose_kernel(const double* __restrict__ D, double* __restrict__ DT, int M, int ldt,
+                                                                    int ld_dst, int keep_diag) {
     __shared__ double t[16][17];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int j0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+    D += (size_t)blockIdx.z * M * M;
+    DT += (size_t)blockIdx.z * ldt;
     {
         const int j = j0 + ty, n = n0 + tx;
-        t[ty][tx] = (j < M && n < M && j != n) ? D[(size_t)j * M + n] : 0.0;
+        t[ty][tx] = (j < M && n < M && (keep_diag || j != n)) ? D[(size_t)j * M + n] : 0.0;
     }
     __syncthreads();
     const int n = n0 + ty, j = j0 + tx;
-    if (n < M && j < ldt) DT[(size_t)n * ldt + j] = t[tx][ty];     // j == M (padding of an odd M) gets the zero staged above
+    if (n < M && j < ldt) DT[(size_t)n * ld_dst + j] = t[tx][ty];     // j == M (padding of an odd M) gets the zero staged above
 }
 
 // out[r][n] = sum_j lamF[r][j] * DT[n][j];  r = (instance, state): lamF viewed as [R][M]; G rows (instance * nv + state).
+// In general (AdjointOpArgs): row r = (instance, j) of A is found through a row map, the K range is nseg segments of ldt (M padded
+// to even) each -- segment s reads the A row a_seg * s further down and columns s * ldt .. of Bop -- and the epilogue either stores
+// the product or adds one more row to it (add[r][n] + product, one rounding) before the store.
+// FOLD = false compiles the operator term alone (A rows contiguous, one segment, plain stores: nothing of the map is evaluated).
 // lane l supplies A[l&15][l>>4], B[l>>4][l&15]; result reg i of lane l is out[(l>>4) + 4i][l&15] (as emi_defect_f64_kernel).
 // Edge tiles are padded with zeros (rows beyond R, nodes beyond M, K beyond M); every M >= 2.
-template <bool ALIGNED, int TM, int TN, int BK>
-__global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
+template <bool ALIGNED, bool FOLD, int TM, int TN, int BK>
+__global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointOpArgs a) {
     constexpr int LDK = BK + 2;
     constexpr int RT = TM / 16, CT = TN / 64;
     constexpr int A_PASS = TM * BK / 2 / 256, B_PASS = TN * BK / 2 / 256;
@@ -62,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
     double* As = smem;                        // [2][TM][LDK]
     double* Bs = smem + 2 * TM * LDK;         // [2][TN][LDK]
 
-    const int M = a.M, R = a.B * a.ns, ldt = a.ldt;
+    const int M = a.M, R = a.R, ldt = a.ldt, kend = a.nseg * a.ldt;
     const int nwg = gridDim.x;
     int bid = blockIdx.x;
     {   // blocks that share a column panel of DT share blockIdx % 8, i.e. one XCD's L2
@@ -82,14 +93,29 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
         for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
 
     double2 pa[A_PASS], pb[B_PASS];
+    long long arow[A_PASS];                   // A row (segment 0) of the tile rows this thread stages; -1 beyond R
+#pragma unroll
+    for (int p = 0; p < A_PASS; ++p) {
+        const int r = m0 + (tid + 256 * p) / (BK / 2);
+        if (FOLD) {
+            const int inst = r / a.rpi;
+            arow[p] = r < R ? (long long)inst * a.a_inst + a.a_row0 + (r - inst * a.rpi) : -1;
+        } else {
+            arow[p] = r < R ? r : -1;
+        }
+    }
     auto gload = [&](int k0) {
 #pragma unroll
         for (int p = 0; p < A_PASS; ++p) {
-            const int idx = tid + 256 * p, row = idx / (BK / 2), c2 = idx % (BK / 2);
-            const int r = m0 + row, k = k0 + 2 * c2;
+            const int c2 = (tid + 256 * p) % (BK / 2);
+            int k = k0 + 2 * c2, seg = 0;
+            if (FOLD && a.nseg > 1) {
+                seg = k / ldt;
+                k -= seg * ldt;
+            }
             double2 v = make_double2(0.0, 0.0);
-            if (r < R) {
-                const double* src = a.lamF + (size_t)r * M + k;
+            if (arow[p] >= 0 && (!FOLD || seg < a.nseg)) {
+                const double* src = a.A + (size_t)(arow[p] + (FOLD ? (long long)seg * a.a_seg : 0)) * M + k;
                 if (ALIGNED) {
                     if (k < M) v = *reinterpret_cast<const double2*>(src);
                 } else {
@@ -104,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
             const int idx = tid + 256 * p, row = idx / (BK / 2), c2 = idx % (BK / 2);
             const int n = n0 + row, k = k0 + 2 * c2;
             double2 v = make_double2(0.0, 0.0);
-            if (n < M && k < ldt) v = *reinterpret_cast<const double2*>(a.DT + (size_t)n * ldt + k);   // ldt is even and zero padded
+            if (n < M && k < kend) v = *reinterpret_cast<const double2*>(a.Bop + (size_t)n * a.ldb + k);   // ldt and ldb are even, segments zero padded
             pb[p] = v;
         }
     };
@@ -121,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
         }
     };
 
-    const int nkt = (M + BK - 1) / BK;
+    const int nkt = (kend + BK - 1) / BK;
     gload(0);
     lstore(0);
     __syncthreads();
@@ -150,7 +176,6 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
         }
     }
 
-    const int nv = a.ns + a.nc;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -160,8 +185,10 @@ __global__ __launch_bounds__(256, 2) void emi_adjoint_op_kernel(AdjointArgs a) {
             for (int i = 0; i < 4; ++i) {
                 const int r = m0 + rt * 16 + kq + 4 * i;
                 if (r < R && n < M) {
-                    const int inst = r / a.ns, st = r - inst * a.ns;
-                    a.G[((size_t)inst * nv + st) * M + n] = acc[rt][ct][i];
+                    const int inst = r / a.rpi, j = r - inst * a.rpi;
+                    double g = acc[rt][ct][i];
+                    if (FOLD && a.add) g = a.add[((size_t)inst * a.add_inst + a.add_row0 + j) * M + n] + g;
+                    a.out[((size_t)inst * a.out_inst + a.out_row0 + j) * M + n] = g;
                 }
             }
         }
@@ -262,7 +289,7 @@ __global__ __launch_bounds__(256) void emi_kkt_certificate_kernel(CertArgs a) {
     double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const double* __restrict__ G = a.G + (size_t)b * nv * M;
     const double* __restrict__ R = a.RES + (size_t)b * a.nres * M;
-    const double* __restrict__ cg = a.VALS + ((size_t)b * a.nvals + (a.nvals - nv)) * M;
+    const double* __restrict__ cg = a.VALS + ((size_t)b * a.nvals + (a.nvals - a.ncg)) * M;
     const double* __restrict__ zl = a.zl + (a.nsets > 1 ? (size_t)b * nv * M : 0);
     const double* __restrict__ zu = a.zu + (a.nsets > 1 ? (size_t)b * nv * M : 0);
     for (int e = tid; e < nv * M; e += 256) {
@@ -280,6 +307,7 @@ __global__ __launch_bounds__(256) void emi_kkt_certificate_kernel(CertArgs a) {
         if (has_up) m[3] = adj_max(m[3], z - up);
         m[4] = adj_max(m[4], fabs(a.sigma * cg[e]));
     }
+    for (int e = nv * M + tid; e < a.ncg * M; e += 256) m[4] = adj_max(m[4], fabs(a.sigma * cg[e]));     // delayed inputs: gmax alone
     for (int e = tid; e < ns * M; e += 256) {
         m[2] = adj_max(m[2], fabs(R[e]));
         m[5] = adj_max(m[5], fabs(a.lamF[(size_t)b * ns * M + e]));
@@ -310,9 +338,9 @@ __global__ __launch_bounds__(256) void emi_kkt_certificate_kernel(CertArgs a) {
 
 }  // namespace
 
-hipError_t launch_adjoint_transpose(const double* dD, double* dDT, int M, int ldt, hipStream_t s) {
-    dim3 grid((ldt + 15) / 16, (ldt + 15) / 16);
-    hipLaunchKernelGGL(emi_adjoint_transpose_kernel, grid, dim3(256), 0, s, dD, dDT, M, ldt);
+hipError_t launch_adjoint_transpose(const double* dSrc, double* dDst, int M, int ldt, int ld_dst, int nseg, bool keep_diag, hipStream_t s) {
+    dim3 grid((ldt + 15) / 16, (ldt + 15) / 16, nseg);
+    hipLaunchKernelGGL(emi_adjoint_transpose_kernel, grid, dim3(256), 0, s, dSrc, dDst, M, ldt, ld_dst, keep_diag ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -342,16 +370,33 @@ static bool launch_adjoint_node_rows(const AdjointArgs& a, hipStream_t s, hipErr
 bool adjoint_side_by_side(int B, int ns, int M) { return ((B * ns + 95) / 96) * ((M + 127) / 128) >= ADJ_CUS; }
 
 hipError_t launch_adjoint_op(const AdjointArgs& a, hipStream_t s) {
-    const int R = a.B * a.ns;
+    AdjointOpArgs o;
+    o.A = a.lamF; o.Bop = a.DT; o.add = nullptr; o.out = a.G;
+    o.R = a.B * a.ns; o.rpi = a.ns; o.M = a.M; o.ldt = a.ldt; o.nseg = 1; o.ldb = a.ldt;
+    o.a_inst = a.ns; o.a_row0 = 0; o.a_seg = 0; o.out_inst = a.ns + a.nc; o.out_row0 = 0; o.add_inst = 0; o.add_row0 = 0;
+    return launch_adjoint_product(o, 0, s);
+}
+
+hipError_t launch_adjoint_product(const AdjointOpArgs& a, int tile, hipStream_t s) {
+    const int R = a.R;
     const int big = ((R + 95) / 96) * ((a.M + 127) / 128), small = ((R + 47) / 48) * ((a.M + 63) / 64);
     const bool al = a.M % 2 == 0;
-    if (big >= ADJ_CUS) {
-        if (al) hipLaunchKernelGGL((emi_adjoint_op_kernel<true, 96, 128, 16>), dim3(big), dim3(256), 0, s, a);
-        else    hipLaunchKernelGGL((emi_adjoint_op_kernel<false, 96, 128, 16>), dim3(big), dim3(256), 0, s, a);
+    // the operator term: rows of A one after the other, one segment, plain stores
+    const bool fold = a.nseg != 1 || a.add || a.a_row0 != 0 || a.a_inst != a.rpi;
+    const bool large = tile == 2 || (tile == 0 && big >= ADJ_CUS);
+#define EMI_ADJ_LAUNCH(AL, FO)                                                                                                      \
+    do {                                                                                                                            \
+        if (large) hipLaunchKernelGGL((emi_adjoint_op_kernel<AL, FO, 96, 128, 16>), dim3(big), dim3(256), 0, s, a);                 \
+        else hipLaunchKernelGGL((emi_adjoint_op_kernel<AL, FO, 48, 64, 32>), dim3(small), dim3(256), 0, s, a);                      \
+    } while (0)
+    if (fold) {
+        if (al) EMI_ADJ_LAUNCH(true, true);
+        else EMI_ADJ_LAUNCH(false, true);
     } else {
-        if (al) hipLaunchKernelGGL((emi_adjoint_op_kernel<true, 48, 64, 32>), dim3(small), dim3(256), 0, s, a);
-        else    hipLaunchKernelGGL((emi_adjoint_op_kernel<false, 48, 64, 32>), dim3(small), dim3(256), 0, s, a);
+        if (al) EMI_ADJ_LAUNCH(true, false);
+        else EMI_ADJ_LAUNCH(false, false);
     }
+#undef EMI_ADJ_LAUNCH
     return hipGetLastError();
 }
 

@@ -65,15 +65,31 @@ struct AdjointArgs {
 };
 struct CertArgs {
     const double *X, *U, *RES, *VALS, *lamF, *lamC, *G;
-    const double *zl, *zu;  // [nsets][ns+nc][M]
+    const double *zl, *zu;  // [nsets][ns+nc][M]   (nc: the controls G, U, zl and zu hold -- the free ones of a context with delays)
     const double *cl, *cu;  // [np] (device)
     double* cert;           // [B][6]
     int B, M, ns, nc, np, nres, nvals, nsets;
+    int ncg;                // cost-gradient entries at the end of VALS that gmax runs over (>= ns + nc: the delayed inputs' too)
     double sigma;
 };
-hipError_t launch_adjoint_transpose(const double* dD, double* dDT, int M, int ldt, hipStream_t s);
+// One product of the adjoint pass on the matrix pipe (emi_adjoint_op_kernel): out rows r = (instance, j), j < rpi,
+//     out[r][n] = (epilogue: add[r][n] +) sum over segments s < nseg, k < M of A[r, s][k] * Bop[n][s * ldt + k].
+// The operator term of G takes one segment (A = lamF, Bop = DT), the fold of the delayed values one segment per delay index
+// (A = the rows of the delayed copies in Gx, Bop = the transposed stack of W).
+struct AdjointOpArgs {
+    const double* A;        // row (r, s) at A + ((size_t)instance * a_inst + a_row0 + s * a_seg + j) * M
+    const double* Bop;      // [M][ldb], ldb even, rows zero padded: segment s in columns s * ldt .. s * ldt + ldt - 1
+    const double* add;      // epilogue 1: add + ((size_t)instance * add_inst + add_row0 + j) * M is added last (null: plain stores)
+    double* out;            // out + ((size_t)instance * out_inst + out_row0 + j) * M
+    int R, rpi, M, ldt, nseg, ldb;
+    int a_inst, a_row0, a_seg, out_inst, out_row0, add_inst, add_row0;
+};
+// dst[n][seg * ldt + j] = src[seg][j][n] (diagonal kept or zeroed), rows of dst ld_dst long, each segment padded with zeros to ldt
+hipError_t launch_adjoint_transpose(const double* dSrc, double* dDst, int M, int ldt, int ld_dst, int nseg, bool keep_diag, hipStream_t s);
 bool adjoint_side_by_side(int B, int ns, int M);                      // batch large enough for the product to run beside the node kernel
 hipError_t launch_adjoint_op(const AdjointArgs& a, hipStream_t s);    // operator term into the state rows of a.G ([B][ns+nc][M])
+// tile: 0 = by the number of workgroups the rows give (as the operator term), 1 = 48 x 64, 2 = 96 x 128
+hipError_t launch_adjoint_product(const AdjointOpArgs& a, int tile, hipStream_t s);
 hipError_t launch_adjoint_nodes(const AdjointArgs& a, hipStream_t s);
 hipError_t launch_adjoint_add(const double* dGop, double* dG, int B, int ns, int nv, int M, hipStream_t s);
 hipError_t launch_kkt_certificate(const CertArgs& a, hipStream_t s);

@@ -249,6 +249,52 @@ class Evaluator:
                                                    _dp(cu) if cu.size else None, _dp(cert), _dp(G)), "emi_kkt_certificate_host")
         return cert, G
 
+    # ... for the trajectory of a context with delays: G on the ns + ncf free variables, Gdel the adjoints of the delayed values
+    def lagr_grad_total_dev(self, VALS, lamF, lamC, sigma, G, Gdel=None):
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self.lib.emi_lagr_grad_total_dev(self.ctx, ptr(VALS), ptr(lamF), ptr(lamC), float(sigma), ptr(G), ptr(Gdel)),
+                 "emi_lagr_grad_total_dev")
+
+    def lagr_grad_total_host(self, VALS, lamF, lamC, sigma=1.0):
+        """Returns (G [B][ns+ncf][M], Gdel [B][n_delayed][M])."""
+        lay = self.layout
+        VALS, lamF = (np.ascontiguousarray(a, dtype=np.float64) for a in (VALS, lamF))
+        lamC = np.ascontiguousarray(lamC if lamC is not None else np.zeros((lay.B, 0, lay.M)), dtype=np.float64)
+        assert VALS.shape == (lay.B, lay.nvals, lay.M) and lamF.shape == (lay.B, lay.ns, lay.M) and lamC.shape == (lay.B, lay.np, lay.M)
+        nd = self.n_delayed
+        G, Gdel = np.zeros((lay.B, lay.ns + lay.nc - nd, lay.M)), np.zeros((lay.B, nd, lay.M))
+        self._ck(self.lib.emi_lagr_grad_total_host(self.ctx, _dp(VALS), _dp(lamF), _dp(lamC) if lamC.size else None, float(sigma), _dp(G),
+                                                   _dp(Gdel) if nd else None), "emi_lagr_grad_total_host")
+        return G, Gdel
+
+    def kkt_certificate_total_dev(self, X, U, RES, VALS, lamF, lamC, sigma, zl, zu, cl, cu, cert, G=None, Gdel=None):
+        """As kkt_certificate_dev with U, zl, zu, G on the free variables ([.][ns+ncf][M]); Gdel: [B][n_delayed][M] or None."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        cl, cu = (np.ascontiguousarray(a, dtype=np.float64) for a in (cl, cu))
+        self._ck(self.lib.emi_kkt_certificate_total_dev(self.ctx, ptr(X), ptr(U), ptr(RES), ptr(VALS), ptr(lamF), ptr(lamC), float(sigma),
+                                                        ptr(zl), ptr(zu), int(zl.shape[0]), _dp(cl) if cl.size else None,
+                                                        _dp(cu) if cu.size else None, ptr(cert), ptr(G), ptr(Gdel)),
+                 "emi_kkt_certificate_total_dev")
+
+    def kkt_certificate_total_host(self, X, U, lamF, lamC, zl, zu, cl=(), cu=(), sigma=1.0):
+        """Evaluates at (X, U) (the delayed values formed on the device) and certifies; returns (cert [B][6], G [B][ns+ncf][M],
+        Gdel [B][n_delayed][M])."""
+        lay = self.layout
+        X, U, lamF, zl, zu, cl, cu = (np.ascontiguousarray(a, dtype=np.float64) for a in (X, U, lamF, zl, zu, cl, cu))
+        lamC = np.ascontiguousarray(lamC if lamC is not None else np.zeros((lay.B, 0, lay.M)), dtype=np.float64)
+        nd = self.n_delayed
+        nf = lay.ns + lay.nc - nd
+        if zl.ndim == 2:
+            zl, zu = zl[None], zu[None]
+        assert X.shape == (lay.B, lay.ns, lay.M) and U.shape == (lay.B, nf - lay.ns, lay.M)
+        assert zl.shape == zu.shape and zl.shape[1:] == (nf, lay.M) and cl.shape == cu.shape == (lay.np,)
+        cert, G, Gdel = np.zeros((lay.B, 6)), np.zeros((lay.B, nf, lay.M)), np.zeros((lay.B, nd, lay.M))
+        self._ck(self.lib.emi_kkt_certificate_total_host(self.ctx, _dp(X), _dp(U), _dp(lamF), _dp(lamC) if lamC.size else None,
+                                                         float(sigma), _dp(zl), _dp(zu), zl.shape[0], _dp(cl) if cl.size else None,
+                                                         _dp(cu) if cu.size else None, _dp(cert), _dp(G), _dp(Gdel) if nd else None),
+                 "emi_kkt_certificate_total_host")
+        return cert, G, Gdel
+
     # ---- Newton step (KKT solve) on the device ----------------------------------
     def kkt_factor(self, Qblk, Jblk, fixed, dc=0.0):
         """Assemble and LU-factorise the KKT matrix of one instance; returns rocSOLVER's info (0 = ok)."""

@@ -1097,11 +1097,13 @@ void eMI355X::solve() {
     struct Lift {
         eMI355X* self;
         bool on;
-        ~Lift() {
+        void end() {
             if (!on) return;
+            on = false;
             self->_problem.lifted = false;
             self->configureDevice(self->_dev.get());          // evaluate() forms the delayed values on the device again
         }
+        ~Lift() { end(); }
     } lift{this, P.ndelayed > 0};
     if (lift.on) {
         const size_t rows = (2 * P.nstates + P.ncontrols + 2 * P.ndelayed) * P.nodes;
@@ -1492,25 +1494,36 @@ void eMI355X::solve() {
     // jacobian-based defect scaling only weights its merit function) and in the device's row order
     _solution.lamF.assign(r.lamF.begin(), r.lamF.begin() + std::min(r.lamF.size(), ns * M));
     _solution.lamC = r.lamC;
+    _solution.lamL = r.lamL;                       // coupling rows of a delayed problem, in the order of the delayed slots
+    _solution.adjDelayed.clear();
     _solution.certificate = mi355x::Sol::Certificate();
-    if (_algorithm.certify && !lift.on && _solution.lamF.size() == ns * M && _solution.lamC.size() == P.npath * M)
-        _solution.certificate = certify(r.z, _solution.lamF, _solution.lamC);
+    // the certificate is taken of the problem the caller stated: the lifted form ends here and the device forms the delayed values itself
+    lift.end();
+    if (_algorithm.certify && _solution.lamF.size() == ns * M && _solution.lamC.size() == P.npath * M)
+        _solution.certificate = certify(std::vector<double>(r.z.begin(), r.z.begin() + (ns + nc) * M), _solution.lamF, _solution.lamC,
+                                        &_solution.adjDelayed);
     setScore(isMaximized() ? -_solution.cost : _solution.cost);
     getTraj();
 }
 
-mi355x::Sol::Certificate eMI355X::certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC) {
+mi355x::Sol::Certificate eMI355X::certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC,
+                                          std::vector<double>* adj_delayed) {
     mi355x::Prob& P = _problem;
     if (!_dev || !_dev->ctx) die("certify(): setup() must run first");
-    if (P.ndelayed > 0) die("certify(): problems with delayed states / controls have no adjoint pass");
+    if (P.lifted) die("certify(): the context is lifted (a solve() of a delayed problem is running); certify the stated problem after it");
     const size_t ns = P.nstates, nc = P.ncontrols, M = P.nodes;
     if (z.size() != (ns + nc) * M || lamF.size() != ns * M || lamC.size() != P.npath * M)
         die("certify(): z must hold (nstates + ncontrols) x nodes values, lamF nstates x nodes, lamC npath x nodes");
     const mi355x::NlpProblem nlp = mi355x::make_nlp(P, _dev.get());      // the bounds the iteration works with
     double c[6];
-    if (emi_kkt_certificate_host(_dev->ctx, z.data(), z.data() + ns * M, lamF.data(), P.npath ? lamC.data() : nullptr, 1.0, nlp.zl.data(),
-                                 nlp.zu.data(), 1, nlp.cl.data(), nlp.cu.data(), c, nullptr) != EMI_OK)
+    // the _total_ form: on a problem without delays it is emi_kkt_certificate_host bit for bit; with delays the device forms the delayed
+    // values, and the gradient on the trajectory carries their adjoints folded through the interpolation operators
+    std::vector<double> gdel(P.ndelayed * M);
+    if (emi_kkt_certificate_total_host(_dev->ctx, z.data(), z.data() + ns * M, lamF.data(), P.npath ? lamC.data() : nullptr, 1.0,
+                                       nlp.zl.data(), nlp.zu.data(), 1, nlp.cl.data(), nlp.cu.data(), c, nullptr,
+                                       gdel.empty() ? nullptr : gdel.data()) != EMI_OK)
         die(std::string("certify(): ") + emi_last_error(_dev->ctx));
+    if (adj_delayed) *adj_delayed = gdel;
     mi355x::Sol::Certificate out;
     out.stationarity = c[0]; out.complementarity = c[1]; out.defect = c[2]; out.violation = c[3]; out.grad_max = c[4]; out.lam_max = c[5];
     out.computed = true;

@@ -547,6 +547,8 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             for (int k = 0; k < M; ++k) S.z[(size_t)v * M + k] *= P.vscale[v];
         for (int i = 0; i < ns && (int)S.lamF.size() == md; ++i)
             for (int k = 0; k < M; ++k) S.lamF[(size_t)i * M + k] /= P.vscale[i];
+        for (size_t l = 0; l < P.links.size() && S.lamL.size() == P.links.size() * M; ++l)      // row (d - W z) / s: multiplier / s
+            for (int k = 0; k < M; ++k) S.lamL[l * M + k] /= P.vscale[P.links[l].dst];
         return S;
     }
     if (!P.ev || (int)P.zl.size() != nz || (int)P.zu.size() != nz || (int)P.D.size() != M * M ||

@@ -121,8 +121,10 @@ struct Alg {
                                                    // -- a Monte-Carlo batch waits for its slowest scenario, and the slowest are the ones that wander
                                                    // (profiles/r04_notes.md: median 105 iterations, 90th percentile 411, maximum 1028 at 1024 nodes)
     double nlp_tolerance = 1.e-6;
-    bool certify = true;                           // after a successful non-delayed solve(), one extra evaluation at the returned trajectory fills
-                                                   // Sol::certificate on the device (emi_kkt_certificate_host); false: skipped, computed stays false.
+    bool certify = true;                           // after a successful solve(), one extra evaluation at the returned trajectory fills
+                                                   // Sol::certificate on the device (emi_kkt_certificate_total_host; a delayed problem is certified
+                                                   // as stated, the delayed values formed on the device, after the lifted form of the solve has
+                                                   // ended); false: skipped, computed stays false.
                                                    // The iteration never sees it: iterates, counts and cost are the same either way
     double max_cpu_time = 1.e9;
     int print_level = 0;
@@ -158,6 +160,13 @@ struct Sol {
     // emi_hess_host(X, U, lamF, lamC, 1) returns; lamC >= 0 goes with an active upper bound of its row, <= 0 with a lower one
     std::vector<double> lamF;       // [nstates][nodes]
     std::vector<double> lamC;       // [npath][nodes]
+    // Delayed problems (Prob::ndelayed > 0; slot order of emi_set_delays: x(t - dt) of every state, .., then u(t - dt) of every control, ..).
+    // lamL: multipliers of the coupling rows  z_q - W(i(q) dt) z_src(q) = 0  the solve ties the delayed values to their sources with,
+    // L = .. + sum lamL (z_q - W z_src).  adjDelayed: d L / d (delayed value) at the returned point from the device (Gdel of
+    // emi_kkt_certificate_total_host; filled with the certificate).  Stationarity in z_q reads adjDelayed + lamL = 0: at a KKT point
+    // adjDelayed = -lamL, up to the tolerance of the solve.
+    std::vector<double> lamL;       // [ndelayed][nodes]
+    std::vector<double> adjDelayed; // [ndelayed][nodes]
     // KKT residuals of (states, controls, lamF, lamC) computed on the device without an activity tolerance (include/emi355x.h,
     // emi_kkt_certificate_*): maxima over the trajectory, in the caller's units
     struct Certificate {
@@ -229,8 +238,12 @@ class eMI355X : public TrajectoryOptimizer {
     void evaluate(const std::vector<double>& z, std::vector<double>* res, std::vector<double>* vals, double* cost);
     // KKT certificate of any point on the current mesh (e.g. a trajectory read back from a file): z = [X (nstates x nodes),
     // U (ncontrols x nodes)], multipliers as Sol::lamF / Sol::lamC.  One evaluation pass and the adjoint pass on the device,
-    // against the bounds of the transcribed problem.  Needs setup(); problems with delayed states / controls are not supported.
-    mi355x::Sol::Certificate certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC);
+    // against the bounds of the transcribed problem.  Needs setup().  A problem with delayed states / controls is certified as stated:
+    // the device forms the delayed values from z, and stationarity is that of the gradient with respect to the trajectory (the adjoints
+    // of the delayed values folded onto their sources, emi_lagr_grad_total_*); adj_delayed, if given, receives those adjoints
+    // [ndelayed][nodes] (Sol::adjDelayed).
+    mi355x::Sol::Certificate certify(const std::vector<double>& z, const std::vector<double>& lamF, const std::vector<double>& lamC,
+                                     std::vector<double>* adj_delayed = nullptr);
 
  protected:
     mi355x::Alg _algorithm;

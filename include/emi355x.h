@@ -53,6 +53,9 @@
  *                      grad f + J^T lambda of a batch of trajectories (the adjoint of the defect pass, D^T on
  *                      the matrix pipe) and, per trajectory, stationarity / complementarity / feasibility
  *                      maxima in the caller's units, without an activity tolerance
+ *   emi_lagr_grad_total_* / emi_kkt_certificate_total_*  the same for a problem with delayed states / controls
+ *                      (ePSOPT.cpp:231-248): the adjoints of the delayed values folded onto the trajectory
+ *                      through the transposes of the interpolation operators W(i dt), on the matrix pipe
  *   emi_plan_pass      no counterpart: the launch form emi_eval_* takes for a
  *                      batch size, so that tests and tools query the policy
  *                      instead of restating it
@@ -212,7 +215,7 @@ int emi_set_batch(emi_ctx_t ctx, int B);
  * reference tree, and this build takes the history of a delayed variable before t0 to be its value at t0.
  * VALS / H then hold partials with respect to the delayed inputs as they hold those of the controls (entries of the extended
  * node-variable vector); the total derivative with respect to the trajectory is (d . / d delayed) . W -- W stays an operator,
- * like the off-diagonal part of I (x) D.  emi_get_layout reports nc = nc_model; emi_get_delays the split.  Must follow
+ * like the off-diagonal part of I (x) D; emi_lagr_grad_total_* applies it to the Lagrangian gradient.  emi_get_layout reports nc = nc_model; emi_get_delays the split.  Must follow
  * emi_set_model_source (a model change drops the delays).  Horizons 0 / 1 and 0: no delayed values, as the reference.    */
 int emi_set_delays(emi_ctx_t ctx, int x_horizon, int u_horizon, double dt);
 int emi_get_delays(emi_ctx_t ctx, int* x_horizon, int* u_horizon, int* n_delayed);
@@ -353,7 +356,7 @@ int emi_hess_host(emi_ctx_t ctx, const double* X, const double* U,
                   const double* LamF, const double* LamC, double sigma,
                   double* H);
 
-/* ---- the adjoint pass: Lagrangian gradient and KKT certificate (f64 contexts without delays) ----
+/* ---- the adjoint pass: Lagrangian gradient and KKT certificate (f64 contexts; with delays: the _total_ forms below) ----
  * The NLP of one instance: minimise COST subject to defect rows RES[i][k] = 0, path rows cl_j <= RES[ns+j][k] <= cu_j and
  * variable bounds zl[v][k] <= z[v][k] <= zu[v][k] (zl == zu fixes a variable; |bound| >= 1e19: absent).  Lagrangian
  * L = sigma COST + sum lamF.defect + sum lamC.c -- the one whose Hessian blocks emi_hess_* returns: lamC >= 0 goes with an
@@ -372,7 +375,7 @@ int emi_hess_host(emi_ctx_t ctx, const double* X, const double* U,
  * zl, zu: [nsets][ns+nc][M], nsets 1 or B;  cl, cu: [np] HOST arrays in both forms.  The _dev forms are asynchronous on the
  * context's stream (device pointers; dG may be NULL: the gradient then stays in the context's workspace).  The _host form of
  * the certificate evaluates (EMI_EVAL_ALL) at (X, U) and then certifies; G may be NULL.
- * EMI_ERR_UNSUPPORTED: f32 context, or delays set (emi_set_delays);  EMI_ERR_STATE: points-only mesh;  a NULL context on a
+ * EMI_ERR_UNSUPPORTED: f32 context, or delays set (emi_set_delays: the _total_ forms below take those);  EMI_ERR_STATE: points-only mesh;  a NULL context on a
  * machine without a device: EMI_ERR_NO_DEVICE.                                                                              */
 int emi_lagr_grad_dev(emi_ctx_t ctx, const void* dVALS, const void* dLamF, const void* dLamC, double sigma, void* dG);
 int emi_lagr_grad_host(emi_ctx_t ctx, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G);
@@ -382,6 +385,32 @@ int emi_kkt_certificate_dev(emi_ctx_t ctx, const void* dX, const void* dU, const
 int emi_kkt_certificate_host(emi_ctx_t ctx, const double* X, const double* U, const double* LamF, const double* LamC,
                              double sigma, const double* zl, const double* zu, int nsets, const double* cl, const double* cu,
                              double* cert, double* G);
+/* The same for the TRAJECTORY of a context with delays (emi_set_delays).  ncf = nc - n_delayed free controls; the node variables
+ * of the model are [x | u | delayed slots q = 0 .. n_delayed-1], slot q the copy of source variable src(q) (a state or a free
+ * control) at delay index i(q), in the order of emi_set_delays.  With Gx[B][ns+nc][M] the formula above on those extended
+ * variables (the D term on the state rows):
+ *   Gdel[B][n_delayed][M]:  Gdel[q][k] = Gx[ns+ncf+q][k]      the adjoint of the delayed value: d Lagrangian / d (delayed input)
+ *   G[B][ns+ncf][M]:        G[v][k] = Gx[v][k] + sum_{q: src(q) = v} sum_j Gdel[q][j] W(i(q) dt)[j][k]
+ * -- a row vector times W: j runs over the ROWS of emi_delay_matrix's W.  Per class of sources (states, controls) one product on
+ * the matrix pipe, K = the node ranges of the delay indices one after the other, last addition Gx[v] + product; one writer per
+ * entry, fixed order, no atomics: bit-reproducible.  Gdel may be NULL.  A solver that carries the delayed values as variables
+ * z_q tied to their sources by rows z_q - W z_src(q) = 0 with multipliers lamL (L = .. + sum lamL (z_q - W z_src)) has
+ * Gdel = -lamL at a KKT point.
+ * The certificate takes U, zl, zu and G on the FREE variables ([.][ns+ncf][M]; delayed values carry no bounds of their own) and
+ * certifies the folded G; gmax runs over all ns+nc cost-gradient entries of VALS (a scale figure).  The _host form evaluates
+ * first, so it forms the delayed values on the device.  An adjoint call may be the first use of a mesh: it builds W itself.
+ * On a context WITHOUT delays these calls are the ones above, bit for bit (Gdel is not touched).  Statuses as above, except
+ * that delays are supported.                                                                                                   */
+int emi_lagr_grad_total_dev(emi_ctx_t ctx, const void* dVALS, const void* dLamF, const void* dLamC, double sigma, void* dG,
+                            void* dGdel);
+int emi_lagr_grad_total_host(emi_ctx_t ctx, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G,
+                             double* Gdel);
+int emi_kkt_certificate_total_dev(emi_ctx_t ctx, const void* dX, const void* dU, const void* dRES, const void* dVALS,
+                                  const void* dLamF, const void* dLamC, double sigma, const void* dZl, const void* dZu, int nsets,
+                                  const double* cl, const double* cu, void* dCert, void* dG, void* dGdel);
+int emi_kkt_certificate_total_host(emi_ctx_t ctx, const double* X, const double* U, const double* LamF, const double* LamC,
+                                   double sigma, const double* zl, const double* zu, int nsets, const double* cl, const double* cu,
+                                   double* cert, double* G, double* Gdel);
 
 /* ---- measurement --------------------------------------------------------- */
 /* HIP-event timers on the context's stream.                                 */
@@ -447,6 +476,9 @@ int emi_profile_read(emi_ctx_t ctx, float* node_ms, int* node_launches,
  * "kkt_debug", "kkt_batched_max_nodes": diagnostics, see csrc/emi_kkt.hip).
  * "slice": > 0: batches above 2 * slice instances are evaluated in pieces of `slice` instances; 0 (default): a batch above
  * 2048 instances goes as one launch over its multiple of 256 instances plus one for the remainder.
+ * "adj_fold_tile": tile shape of the fold product of emi_lagr_grad_total_*: 0 (default) by the number of workgroups the rows give
+ * (as the operator term: 96 x 128 where that gives every CU a workgroup, else 48 x 64), 1 = 48 x 64, 2 = 96 x 128; the
+ * summation order of an entry is the same either way.
  * "sym_ablate": diagnostics only, results invalid.                             */
 int emi_set_option(emi_ctx_t ctx, const char* name, int value);
 /* 1 if emi_eval(EMI_EVAL_ALL) currently takes the overlapped path             */
