@@ -22,11 +22,13 @@ namespace {
 
 using DevBuf = emi::DeviceArray<unsigned char>;    // untyped bytes: the context's real type is chosen at run time (f32 / f64)
 
+// the events of one profiled launch.  Sequential form: E0 | node | E1 | defect | E2; overlapped forms: E0 fork, E1 join, the MFMA
+// kernel K0..K1 (its stream), the node kernel K2..K3 (its stream)
+enum ProfMark { E0, E1, E2, K0, K1, K2, K3, PROF_MARKS };
 struct ProfEvents {
-    hipEvent_t e[3];        // sequential path: e0 | node | e1 | defect | e2 ; overlapped: e0 fork, e1 join
-    hipEvent_t k[4];        // overlapped path: MFMA kernel k0..k1 (main stream), node kernel k2..k3 (stream 2)
-    bool has_node, has_defect, fused;
-    int level;              // 1: every bracket; 2: the defect (MFMA) kernel only; 3: the node kernel only
+    hipEvent_t ev[PROF_MARKS] = {};     // null until created (next_prof_record); the context's destructor destroys what is not
+    bool has_node = false, has_defect = false, fused = false;
+    int level = 0;          // 1: every bracket; 2: the defect (MFMA) kernel only; 3: the node kernel only; -1: one bracket K0..K1, the pass kernel
 };
 
 }  // namespace
@@ -50,7 +52,7 @@ struct emi_ctx_s {
     DevBuf d_w, d_t, d_Ddiag, d_D, d_De, d_Do;
     bool symmetric = false;   // D is exactly centro-antisymmetric and M is even: De/Do are valid
     bool points_only = false; // emi_set_mesh(D = NULL): abscissae without a differentiation matrix
-    bool allow_fused = true;      // "overlap" option: even/odd MFMA defect kernel || node kernel on two streams
+    int allow_fused = 1;          // "overlap" option: even/odd MFMA defect kernel || node kernel on two streams
     int sym_ct = 0;               // MFMA kernel variant (emi_symdefect.hip): 0 = chosen from the batch, 3 = LDS-DMA ring, 5..8 state-split ring, 1/2 = register-staged
     int sym_order = 1;
     int sym_ablate = 0;
@@ -79,7 +81,7 @@ struct emi_ctx_s {
     DevBuf d_tile_ticket;       // ... and the tickets of its in-kernel combine (zero between launches)
     DevBuf d_cost_part2;        // cost partials of the values-only pre-kernel of the overlapped f32 pass (discarded)
     DevBuf d_ticket;            // [B] arrival counters of the in-kernel COST finish (zeroed once, self-resetting)
-    bool cost_in_kernel = true; // "cost_in_kernel": the node kernel of the overlapped pass finishes COST itself (ticket), no emi_cost_finish_kernel
+    int cost_in_kernel = 1;     // "cost_in_kernel": the node kernel of the overlapped pass finishes COST itself (ticket), no emi_cost_finish_kernel
     int sym_nst = 3;            // "sym_nst": ring stages of the one-launch pass (3 or 4)
     int sym_hs = 0;             // "sym_hs": 2: K range of a tile in two halves inside the workgroup (512 threads); 1: undivided; 0: by batch size
     int sym_ctc = 0;            // "sym_ctc": 64-column sub-tiles per MFMA workgroup of the one-launch pass (1 or 2; 0: by batch size, plan_pass)
@@ -101,7 +103,6 @@ struct emi_ctx_s {
                                 // Off: measured at config 5 (256 instances, 4096 nodes) 1.12 - 1.26 ms per pass in every block order against
                                 // 1.04 ms for the node kernel followed by the MFMA kernel (profiles/r03_notes.md section 6)
     int slice = 0;              // "slice" option: > 0: batches above 2 * slice instances are evaluated in pieces of this many; 0: one launch (see emi_eval_dev)
-    int slice_first = 0;        // first instance of the slice emi_eval_dev is working on (per-instance tables are offset by it)
     int sym_ksplit = 0;         // "sym_ksplit" option: K slices per tile of the state-split ring kernel (0: by batch size)
     int sym_cpart = 0;          // "sym_cpart" option: column partitions of the tile order (0: by mesh size, -1: plain order, 1/2/4/8)
     int sym_gblk = 0, sym_cx = 0;   // "sym_gblk" / "sym_cx" options: grouped tile order, instance groups per super-block (0: off) and column tiles per block (0: 2)
@@ -125,6 +126,23 @@ struct emi_ctx_s {
     std::vector<ProfEvents> prof;
     size_t prof_used = 0;
     bool attr_set = false;
+
+    // everything above that is a handle: streams drained and destroyed (the caller's own stream is only drained), then the events,
+    // the run-time compiled model and the Newton-step workspace; the buffers free themselves after this body
+    ~emi_ctx_s() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (ProfEvents& pe : prof)
+            for (hipEvent_t e : pe.ev)
+                if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {stream2, s_mfma, s_node})
+            if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        for (hipEvent_t e : {ev_join2, ev_fork, ev_join, t_start, t_stop})
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+        emi::rtc_destroy(rtc);
+        emi::kkt_destroy(kkt);
+    }
 };
 
 namespace {
@@ -147,40 +165,50 @@ int fail(emi_ctx_t c, int code, const char* fmt, ...) {
                         hipGetErrorString(e_), __FILE__, __LINE__);                   \
     } while (0)
 
+// a step that returns an EMI_* status: anything but EMI_OK ends the calling function with it
+#define EMI_TRY(call)              \
+    do {                           \
+        const int st_ = (call);    \
+        if (st_) return st_;       \
+    } while (0)
+
 int ensure(emi_ctx_t c, DevBuf& b, size_t bytes) {
     HIP_TRY(c, b.reserve(bytes));
     return EMI_OK;
 }
 
+// the tickets of the in-kernel combines are zero between launches (a kernel resets what it draws), so a buffer is zeroed when it
+// is made and again whenever it grows (reserve keeps no contents), on the stream its next reader runs on
+int ensure_zeroed(emi_ctx_t c, DevBuf& b, size_t bytes, hipStream_t s) {
+    if (b.bytes() >= bytes) return EMI_OK;
+    EMI_TRY(ensure(c, b, bytes));
+    HIP_TRY(c, hipMemsetAsync(b.p, 0, bytes, s));
+    return EMI_OK;
+}
+
+// host -> context buffer on the context's stream, complete on return (the source may be a local of the caller)
+int upload_bytes(emi_ctx_t c, DevBuf& b, const void* src, size_t bytes) {
+    EMI_TRY(ensure(c, b, bytes));
+    if (bytes == 0) return EMI_OK;
+    HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EMI_OK;
+}
+
 // upload a host double array in the context's real type
 int upload_real(emi_ctx_t c, DevBuf& b, const double* src, size_t n) {
-    const size_t rb = c->f32 ? 4 : 8;
-    int st = ensure(c, b, n * rb);
-    if (st) return st;
-    if (n == 0) return EMI_OK;
-    if (c->f32) {
-        std::vector<float> tmp(n);
-        for (size_t i = 0; i < n; ++i) tmp[i] = (float)src[i];
-        HIP_TRY(c, hipMemcpyAsync(b.p, tmp.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(b.p, src, n * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return EMI_OK;
+    if (!c->f32) return upload_bytes(c, b, src, n * 8);
+    std::vector<float> tmp(n);
+    for (size_t i = 0; i < n; ++i) tmp[i] = (float)src[i];
+    return upload_bytes(c, b, tmp.data(), n * 4);
 }
 
 int download_real(emi_ctx_t c, double* dst, const void* dsrc, size_t n) {
     if (!dst || n == 0) return EMI_OK;
-    if (c->f32) {
-        std::vector<float> tmp(n);
-        HIP_TRY(c, hipMemcpyAsync(tmp.data(), dsrc, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < n; ++i) dst[i] = tmp[i];
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(dst, dsrc, n * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    std::vector<float> tmp(c->f32 ? n : 0);
+    HIP_TRY(c, hipMemcpyAsync(c->f32 ? (void*)tmp.data() : (void*)dst, dsrc, n * (c->f32 ? 4 : 8), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < tmp.size(); ++i) dst[i] = tmp[i];
     return EMI_OK;
 }
 
@@ -192,11 +220,11 @@ bool overlapped_path(emi_ctx_t c) {
 }
 
 // the one-launch pass in its small-batch form (SW = 1, plain stores) is available to this context by the default dispatch
-bool pass_takes_small_batches(emi_ctx_t c) {
+bool pass_takes_small_batches(emi_ctx_t c, int B) {
     if (!overlapped_path(c) || (c->overlap_mode != 0 && c->overlap_mode != 3) || c->M % 128 != 0) return false;
-    if (c->rtc) return emi::rtc_pass_supported(c->rtc, c->B, c->M, 1, 1, 0);
-    const emi::SymPlan p = emi::plan_symdefect(c->ns, c->B, c->M, 7, 1, c->sym_cpart, c->sym_gblk, c->sym_cx);
-    return emi::pass_supported(c->model, c->ns, c->B, c->M, p);
+    if (c->rtc) return emi::rtc_pass_supported(c->rtc, B, c->M, 1, 1, 0);
+    const emi::SymPlan p = emi::plan_symdefect(c->ns, B, c->M, 7, 1, c->sym_cpart, c->sym_gblk, c->sym_cx);
+    return emi::pass_supported(c->model, c->ns, B, c->M, p);
 }
 
 int np_total(emi_ctx_t c) { return c->np + c->np_model; }     // rows of the record table, then the model's own (traced) rows
@@ -237,7 +265,7 @@ int store_mode_for(emi_ctx_t c, int B) {
 }
 
 // Everything the default dispatch decides about ONE launch of the evaluation pass as emi_pass_f64_kernel, in one place:
-// plan_pass() is what eval_dev_slice launches by and what emi_plan_pass reports (tests and tools read the policy from the
+// plan_pass() is what choose_form / form_pass_f64 launch by and what emi_plan_pass reports (tests and tools read the policy from the
 // library instead of restating it).
 struct PassPlan {
     bool one_launch = false;    // the pass goes out as ONE launch (MFMA-role + node-role workgroups)
@@ -367,32 +395,43 @@ PassPlan plan_pass(emi_ctx_t c, int B, bool jac) {
 // something forces them: the "slice" option (> 0: pieces of that many instances once B > 2 slice), the 32-bit operand offsets of
 // the MFMA role (X of a launch below 4 GB), and a remainder that is not a multiple of 256 instances (the grouped order wants whole
 // super-blocks on every XCD) as a second launch.
-int plan_piece(emi_ctx_t c) {
+int plan_piece(emi_ctx_t c, int B) {
     const long long cap = ((0xFFFFFFFFLL / ((long long)c->ns * c->M * 8)) / 256) * 256;     // instances whose X stays below 4 GB
     int piece = 0;
-    if (c->slice > 0) { if (c->B > 2 * c->slice) piece = c->slice; }
-    else if (c->B > 2048) piece = (int)std::min<long long>(cap > 0 ? cap : 256, c->B - c->B % 256);
-    return piece >= c->B ? 0 : piece;
+    if (c->slice > 0) { if (B > 2 * c->slice) piece = c->slice; }
+    else if (B > 2048) piece = (int)std::min<long long>(cap > 0 ? cap : 256, B - B % 256);
+    return piece >= B ? 0 : piece;
+}
+
+// One launch of the evaluation pass: instances [first, first + B) of the context's batch.  The whole batch as a rule; pieces of it
+// where plan_piece says so.  The context is not written to on the way: the batch of a launch is this argument.
+struct Launch { int first, B; };
+// ... and its arrays (device memory, in the context's real type), already at the launch's first instance
+struct PassIO { const void *X, *U; void *RES, *VALS, *COST; };
+
+PassIO io_at(emi_ctx_t c, const PassIO& io, int first) {
+    const size_t row = (size_t)first * c->M * (c->f32 ? 4 : 8);
+    return PassIO{(const char*)io.X + row * c->ns, (const char*)io.U + row * c->nc, (char*)io.RES + row * nres_of(c),
+                  io.VALS ? (char*)io.VALS + row * nvals_of(c) : nullptr, (char*)io.COST + (size_t)first * (c->f32 ? 4 : 8)};
 }
 
 template <typename T>
-void fill_node_args(emi_ctx_t c, emi::NodeArgs<T>& a, const void* dX, const void* dU, void* dRES,
-                    void* dVALS, void* dCOST) {
-    a.X = (const T*)dX;
-    a.U = (const T*)dU;
-    a.RES = (T*)dRES;
-    a.VALS = (T*)dVALS;
-    a.cost_part = (T*)c->d_cost_part.p + (size_t)c->slice_first * emi::node_chunks(c->M);
-    a.cost = (T*)dCOST;
+void fill_node_args(emi_ctx_t c, Launch L, emi::NodeArgs<T>& a, const PassIO& io) {
+    a.X = (const T*)io.X;
+    a.U = (const T*)io.U;
+    a.RES = (T*)io.RES;
+    a.VALS = (T*)io.VALS;
+    a.cost_part = (T*)c->d_cost_part.p + (size_t)L.first * emi::node_chunks(c->M);
+    a.cost = (T*)io.COST;
     a.cost_ticket = nullptr;
     a.w = (const T*)c->d_w.p;
     a.node_t = (const T*)c->d_t.p;
     a.Ddiag = (const T*)c->d_Ddiag.p;
-    a.path = (const T*)c->d_path.p + (c->path_sets > 1 ? (size_t)c->slice_first * c->np * EMI_PATH_REC : 0);
-    a.track_x = (const T*)c->d_trkx.p + (c->track_sets > 1 ? (size_t)c->slice_first * c->ntracks * c->M : 0);
-    a.track_y = (const T*)c->d_trky.p + (c->track_sets > 1 ? (size_t)c->slice_first * c->ntracks * c->M : 0);
+    a.path = (const T*)c->d_path.p + (c->path_sets > 1 ? (size_t)L.first * c->np * EMI_PATH_REC : 0);
+    a.track_x = (const T*)c->d_trkx.p + (c->track_sets > 1 ? (size_t)L.first * c->ntracks * c->M : 0);
+    a.track_y = (const T*)c->d_trky.p + (c->track_sets > 1 ? (size_t)L.first * c->ntracks * c->M : 0);
     a.M = c->M;
-    a.B = c->B;
+    a.B = L.B;
     a.np = np_total(c);
     a.nres = nres_of(c);
     a.nvals = nvals_of(c);
@@ -401,7 +440,7 @@ void fill_node_args(emi_ctx_t c, emi::NodeArgs<T>& a, const void* dX, const void
     a.ntracks = c->ntracks;
     a.px = c->px;
     a.py = c->py;
-    a.store_mode = store_mode_for(c, c->B);
+    a.store_mode = store_mode_for(c, L.B);
     a.h = (T)((c->tf - c->t0) / 2.0);
     a.sgn = c->maximize ? T(-1) : T(1);
     for (int i = 0; i < EMI_MAX_PARAMS; ++i) a.P.p[i] = (T)c->params[i];
@@ -446,9 +485,7 @@ int ensure_delay_matrices(emi_ctx_t c) {
     const int M = c->M, nd = std::max(c->xh - 1, c->uh);
     std::vector<double> W((size_t)nd * M * M);
     for (int d = 0; d < nd; ++d) delay_matrix(c->h_tau, c->h_w, c->t0, c->tf, (d + 1) * c->delay_dt, W.data() + (size_t)d * M * M);
-    int st;
-    if ((st = upload_real(c, c->d_W, W.data(), W.size()))) return st;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));        // W is a local: the copy must be done before it goes
+    EMI_TRY(upload_real(c, c->d_W, W.data(), W.size()));       // (complete on return: W is a local)
     c->delay_dirty = false;
     return EMI_OK;
 }
@@ -486,6 +523,389 @@ int extend_controls(emi_ctx_t c, const void* dX, const void* dU_free, const void
     return EMI_OK;
 }
 
+// ---- emi_set_option: the plain options, one row each (what the name means is said at the member it sets) -------------------
+struct OptionRow {
+    const char* name;
+    int emi_ctx_s::*member;
+    bool (*accepts)(int);       // the range or set of values taken ...
+    int (*stored)(int);         // ... what an accepted value is stored as ...
+    const char* message;        // ... and what emi_last_error says about any other
+};
+template <int LO, int HI> bool within(int v) { return v >= LO && v <= HI; }
+template <int... VS> bool one_of(int v) { return ((v == VS) || ...); }
+bool any_value(int) { return true; }
+bool at_least_0(int v) { return v >= 0; }
+bool whole_tiles(int v) { return v >= 0 && v % 16 == 0; }
+int as_given(int v) { return v; }
+int as_flag(int v) { return v != 0; }
+int ring_wgs(int v) { return v == 1 ? 1 : 2; }
+int block_order(int v) { return v < 0 ? -1 : (v >= 100 ? v : (v != 0)); }
+
+const OptionRow OPTIONS[] = {
+    {"overlap", &emi_ctx_s::allow_fused, any_value, as_flag, nullptr},
+    {"fused", &emi_ctx_s::allow_fused, any_value, as_flag, nullptr},
+    {"sym_ct", &emi_ctx_s::sym_ct, within<0, 8>, as_given,
+     "sym_ct must be 0..8 (0/4 = chosen from the batch, 3 = LDS-DMA ring, 5..8 = state-split ring with SW = NS/2/1/3)"},
+    {"small_rows", &emi_ctx_s::small_rows, at_least_0, as_given, "small_rows must be >= 0 (0 disables the skinny defect kernel)"},
+    {"sym_order", &emi_ctx_s::sym_order, any_value, as_flag, nullptr},
+    {"f32_ring", &emi_ctx_s::f32_ring, any_value, as_flag, nullptr},
+    {"f32_ring_wgs", &emi_ctx_s::f32_ring_wgs, any_value, ring_wgs, nullptr},
+    {"f32_one_launch", &emi_ctx_s::f32_one_launch, any_value, as_flag, nullptr},
+    {"slice", &emi_ctx_s::slice, whole_tiles, as_given, "slice must be 0 (never) or a multiple of 16 instances"},
+    {"pass_order", &emi_ctx_s::pass_order, any_value, block_order, nullptr},
+    {"sym_ablate", &emi_ctx_s::sym_ablate, any_value, as_given, nullptr},   // diagnostics only
+    {"adj_fold_tile", &emi_ctx_s::adj_fold_tile, within<0, 2>, as_given, "adj_fold_tile must be 0 (by size), 1 (48 x 64) or 2 (96 x 128)"},
+    {"cost_in_kernel", &emi_ctx_s::cost_in_kernel, any_value, as_flag, nullptr},
+    {"sym_nst", &emi_ctx_s::sym_nst, one_of<3, 4>, as_given, "sym_nst must be 3 or 4"},
+    {"sym_hs", &emi_ctx_s::sym_hs, within<0, 2>, as_given, "sym_hs must be 0 (by batch size), 1 or 2"},
+    {"sym_ctc", &emi_ctx_s::sym_ctc, within<0, 2>, as_given, "sym_ctc must be 0 (by batch size), 1 or 2"},
+    {"sym_bk", &emi_ctx_s::sym_bk, one_of<0, 8, 16>, as_given, "sym_bk must be 0 (by batch size), 8 or 16"},
+    {"sym_cpart", &emi_ctx_s::sym_cpart, one_of<-1, 0, 1, 2, 4, 8>, as_given, "sym_cpart must be -1 (plain order), 0 (by mesh size), 1, 2, 4 or 8"},
+    {"sym_gblk", &emi_ctx_s::sym_gblk, within<0, 64>, as_given, "sym_gblk must be 0 (off) .. 64 instance groups per super-block"},
+    {"sym_cx", &emi_ctx_s::sym_cx, within<0, 64>, as_given, "sym_cx must be 0 (default) .. 64 column tiles per block"},
+    {"sym_combine", &emi_ctx_s::sym_combine, any_value, as_flag, nullptr},
+    {"sym_ksplit", &emi_ctx_s::sym_ksplit, one_of<0, 1, 2, 4, 8>, as_given, "sym_ksplit must be 0 (by batch size), 1, 2, 4 or 8"},
+    {"node_store", &emi_ctx_s::node_store, within<-1, 3>, as_given,
+     "node_store must be -1 (by size), 0 (plain), 1 (write-through sc1), 2 (non-temporal) or 3 (nt sc1; the one-launch pass only)"},
+    {"overlap_mode", &emi_ctx_s::overlap_mode, within<0, 3>, as_given,
+     "overlap_mode must be 0 (by batch size), 1 (one stream), 2 (two streams) or 3 (one launch)"},
+};
+
+// ---- the evaluation pass: one chooser (choose_form), one function per launch form ------------------------------------------
+
+// the second stream of the two-stream forms (node kernel beside the MFMA defect kernel), created on first use
+int need_stream2(emi_ctx_t c) {
+    if (c->stream2) return EMI_OK;
+    if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) {
+        c->stream2 = nullptr;
+        return fail(c, EMI_ERR_HIP, "cannot create the second stream of the two-stream pass");
+    }
+    return EMI_OK;
+}
+
+// The forms a launch of the pass can take.  choose_form is the one place that picks among them; emi_last_path asks it too.
+enum class Form {
+    PassF64,        // form_pass_f64: emi_pass_f64_kernel, MFMA-role and node-role workgroups in one grid
+    TwoKernelF64,   // form_two_kernel_f64: even/odd MFMA defect kernel and node kernel, on one or two streams or on CU-split streams
+    PassF32,        // form_pass_f32: emi_pass_f32_kernel, the fp32 pass as one launch
+    TwoStreamF32,   // form_two_stream_f32: fp32 MFMA defect kernel beside the full node kernel ("overlap_mode" 2)
+    Sequential,     // form_sequential: node kernel, then the general (or skinny) defect kernel, on the context's stream
+};
+struct FormChoice {
+    Form form = Form::Sequential;
+    bool small = false;     // Sequential: the skinny streaming defect kernel instead of the MFMA one
+    PassPlan plan;          // PassF64 (and TwoKernelF64, which it declined): what plan_pass decided
+    bool overlapped() const { return form == Form::PassF64 || form == Form::TwoKernelF64; }
+};
+
+FormChoice choose_form(emi_ctx_t c, Launch L, unsigned flags) {
+    const bool nodes = flags & EMI_EVAL_NODES, defect = flags & EMI_EVAL_DEFECT, jac = !(flags & EMI_EVAL_NOJAC);
+    FormChoice ch;
+    // a handful of instances: the stand-alone MFMA kernels would have a few workgroups to run and a skinny streaming product wins
+    // (21 us at B = 1) -- unless the whole pass can go as ONE launch with its K range sliced, which is faster still (13 - 15 us for
+    // any batch up to 16 instances: profiles/r03_notes.md section 7)
+    ch.small = defect && !c->f32 && L.B > 0 && L.B * c->ns <= c->small_rows && emi::defect_small_supported(L.B * c->ns) &&
+               !(nodes && jac && pass_takes_small_batches(c, L.B));
+    if (nodes && defect && !ch.small && overlapped_path(c)) {
+        ch.plan = plan_pass(c, L.B, jac);
+        ch.form = ch.plan.one_launch ? Form::PassF64 : Form::TwoKernelF64;
+    } else if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused) {
+        if ((c->overlap_mode == 3 || (c->overlap_mode == 0 && c->f32_one_launch)) && emi::pass_f32_supported(c->model, L.B * c->ns, c->M, L.B))
+            ch.form = Form::PassF32;
+        else if (c->overlap_mode == 2 && emi::defect_f32_mfma_supported(c->M))
+            ch.form = Form::TwoStreamF32;
+    }
+    return ch;
+}
+
+// the record of the next profiled launch; the list owns every event from the moment it exists (a record whose events could not
+// all be created is completed by the next call)
+int next_prof_record(emi_ctx_t c, ProfEvents** out) {
+    if (c->prof_used == c->prof.size()) c->prof.emplace_back();
+    ProfEvents& pe = c->prof[c->prof_used];
+    for (hipEvent_t& e : pe.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    ++c->prof_used;
+    *out = &pe;
+    return EMI_OK;
+}
+
+// One side of a profiling bracket: event `which` of the launch's record on stream s, when the launch is profiled (pe) at one of
+// the levels in `levels` (emi_profile_enable: AT1 every bracket, AT2 the defect kernel only, AT3 the node kernel only)
+constexpr unsigned AT1 = 1u << 1, AT2 = 1u << 2, AT3 = 1u << 3, AT_ANY = AT1 | AT2 | AT3;
+int prof_mark(emi_ctx_t c, ProfEvents* pe, ProfMark which, unsigned levels, hipStream_t s) {
+    if (pe && pe->level > 0 && ((levels >> pe->level) & 1u)) HIP_TRY(c, hipEventRecord(pe->ev[which], s));
+    return EMI_OK;
+}
+
+// ---- what emi_last_defect_kernel reports (the names a rocprofv3 kernel trace shows), each built here and nowhere else
+const char* const NAME_PASS_F32 = "emi_pass_f32_kernel (MFMA + node roles, one launch)";
+const char* const NAME_RING1_F64 = "emi_symdefect_ring_f64_kernel";
+const char* name_defect_f32(emi_ctx_t c, bool mfma) {
+    return !mfma ? "emi_defect_f32_kernel" : (c->f32_ring ? "emi_defect_f32_ring_kernel" : "emi_defect_f32_mfma_kernel");
+}
+const char* name_defect_f64(bool small) { return small ? "emi_defect_small_f64_kernel" : "emi_defect_f64_kernel"; }
+std::string name_pass_f64(const emi::SymPlan& plan) {
+    return "emi_pass_f64_kernel<SW=" + std::to_string(plan.sw) + "> (MFMA + node roles, one launch" +
+           (plan.ks > 1 ? ", " + std::to_string(plan.ks) + " K slices per tile" : "") + ")" +
+           (plan.bk == 16 ? " [K tiles of 16]" : "") + (plan.ct == 2 ? " [128-column tiles]" : "") + (plan.hs == 2 ? " [K range in two halves per workgroup]" : "");
+}
+std::string name_symdefect(emi_ctx_t c, const emi::SymPlan& plan, bool in_kernel_combine) {
+    if (plan.ring1) return c->sym_ct == 1 || c->sym_ct == 2 ? "emi_symdefect_f64_kernel" : NAME_RING1_F64;
+    return "emi_symdefect_ring2_f64_kernel<SW=" + std::to_string(plan.sw) + ">" +
+           (plan.ks > 1 ? " x" + std::to_string(plan.ks) + (in_kernel_combine ? " K slices (in-kernel combine)" : " K slices + emi_symdefect_combine_kernel") : "");
+}
+
+// arguments of the even/odd MFMA role for a launch, unsplit and in the plain tile order (the forms set what their plan changes)
+emi::SymDefectArgs sym_defect_args(emi_ctx_t c, Launch L, const PassIO& io) {
+    emi::SymDefectArgs sa;
+    sa.X = (const double*)io.X;
+    sa.U = (const double*)io.U;
+    sa.RES = (double*)io.RES;
+    sa.node_t = (const double*)c->d_t.p;
+    sa.De = (const double*)c->d_De.p;
+    sa.Do = (const double*)c->d_Do.p;
+    sa.M = c->M;
+    sa.B = L.B;
+    sa.nres = nres_of(c);
+    sa.h = (c->tf - c->t0) / 2.0;
+    sa.order = c->sym_order;
+    sa.ablate = c->sym_ablate;
+    sa.ksplit = 1;
+    sa.slab = nullptr;
+    sa.tile_ticket = nullptr;
+    sa.cpart = sa.cx = 0;
+    sa.mfma_first = 0;
+    for (int i = 0; i < EMI_MAX_PARAMS; ++i) sa.P.p[i] = c->params[i];
+    return sa;
+}
+
+emi::DefectArgsF32 defect_args_f32(emi_ctx_t c, Launch L, const PassIO& io) {
+    return emi::DefectArgsF32{(const float*)io.X, (const float*)c->d_D.p, (float*)io.RES, L.B * c->ns, c->M, c->ns, nres_of(c)};
+}
+
+// The fp64 pass as ONE launch, by the plan the chooser made: MFMA-role and node-role workgroups in one grid, K slices combined
+// and COST finished in-kernel by ticket.
+int form_pass_f64(emi_ctx_t c, Launch L, const PassIO& io, const PassPlan& pp, ProfEvents* pe) {
+    const emi::SymPlan& plan = pp.sym;
+    emi::SymDefectArgs sa = sym_defect_args(c, L, io);
+    emi::NodeArgs<double> na;
+    fill_node_args(c, L, na, io);
+    sa.mfma_first = pp.mfma_first;
+    sa.cpart = plan.cpart;
+    sa.cx = plan.cx;
+    if (plan.ks > 1) {
+        EMI_TRY(ensure(c, c->d_slab, plan.slab_bytes));
+        EMI_TRY(ensure_zeroed(c, c->d_tile_ticket, (size_t)plan.tiles * 4, c->stream));
+        sa.ksplit = plan.ks;
+        sa.slab = (double*)c->d_slab.p;
+        sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
+    }
+    EMI_TRY(ensure_zeroed(c, c->d_ticket, (size_t)L.B * 4, c->stream));
+    na.cost_ticket = (unsigned*)c->d_ticket.p;
+    EMI_TRY(prof_mark(c, pe, K0, AT_ANY, c->stream));
+    if (c->rtc) HIP_TRY(c, emi::rtc_launch_pass(c->rtc, sa, na, plan.sw, c->stream));
+    else HIP_TRY(c, emi::launch_pass(c->model, sa, na, c->stream, plan));
+    EMI_TRY(prof_mark(c, pe, K1, AT_ANY, c->stream));
+    if (pe) pe->level = -1;                 // one bracket: the pass kernel
+    c->last_defect_kernel = name_pass_f64(plan);
+    return EMI_OK;
+}
+
+// the stand-alone even/odd MFMA defect kernel of the two-kernel form on stream s, K slices by "sym_ksplit"
+int launch_symdefect_f64(emi_ctx_t c, Launch L, emi::SymDefectArgs& sa, hipStream_t s) {
+    if (c->rtc) {
+        HIP_TRY(c, emi::rtc_launch_symdefect(c->rtc, sa, s));
+        c->last_defect_kernel = NAME_RING1_F64;
+        return EMI_OK;
+    }
+    const emi::SymPlan plan = emi::plan_symdefect(c->ns, L.B, c->M, c->sym_ct, c->sym_ksplit, c->sym_cpart, c->sym_gblk, c->sym_cx);
+    if (plan.slab_bytes) EMI_TRY(ensure(c, c->d_slab, plan.slab_bytes));
+    sa.ksplit = plan.ring1 ? 1 : plan.ks;
+    sa.slab = (double*)c->d_slab.p;
+    sa.cpart = plan.cpart;
+    sa.cx = plan.cx;
+    if (sa.ksplit > 1 && c->sym_combine) {
+        EMI_TRY(ensure_zeroed(c, c->d_tile_ticket, (size_t)plan.tiles * 4, s));
+        sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
+    }
+    const unsigned bit = 1u << c->sym_ct;
+    HIP_TRY(c, emi::launch_symdefect(c->model, sa, s, !(c->fused_attr_mask & bit), c->sym_ct, plan));
+    c->fused_attr_mask |= bit;
+    c->last_defect_kernel = name_symdefect(c, plan, sa.tile_ticket != nullptr);
+    return EMI_OK;
+}
+
+// The fp64 pass as two kernels that read X, U and write disjoint outputs.  "overlap_mode" 1: back to back on the context's stream;
+// otherwise forked onto a second stream (or, with "cu_split", onto two CU-masked streams) and joined again.  The MFMA kernel goes
+// first and takes one workgroup per CU (LDS-shaped); the streaming kernel's waves fill the rest of every CU.
+int form_two_kernel_f64(emi_ctx_t c, Launch L, const PassIO& io, bool jac, ProfEvents* pe) {
+    emi::SymDefectArgs sa = sym_defect_args(c, L, io);
+    emi::NodeArgs<double> na;
+    fill_node_args(c, L, na, io);
+    const bool two = c->overlap_mode != 1;
+    const bool split = two && c->cu_split > 0;
+    if (two && !split) EMI_TRY(need_stream2(c));
+    hipStream_t s1 = split ? c->s_mfma : c->stream;
+    hipStream_t s2 = split ? c->s_node : (two ? c->stream2 : c->stream);
+    if (two) {
+        HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
+        if (split) HIP_TRY(c, hipStreamWaitEvent(s1, c->ev_fork, 0));
+    }
+    EMI_TRY(prof_mark(c, pe, K0, AT1 | AT2, s1));
+    EMI_TRY(launch_symdefect_f64(c, L, sa, s1));
+    EMI_TRY(prof_mark(c, pe, K1, AT1 | AT2, s1));
+    // COST is finished inside the node kernel (last workgroup of an instance, by ticket, in chunk order): one launch
+    // and one kernel boundary less at the end of every pass (emi_cost_finish_kernel alone was 5 us)
+    if (c->cost_in_kernel) {
+        EMI_TRY(ensure_zeroed(c, c->d_ticket, (size_t)L.B * 4, s2));
+        na.cost_ticket = (unsigned*)c->d_ticket.p;
+    }
+    EMI_TRY(prof_mark(c, pe, K2, AT1 | AT3, s2));
+    if (c->rtc && jac && na.store_mode == 2 && c->M % 2 == 0) HIP_TRY(c, emi::rtc_launch_nodes_nt(c->rtc, na, s2));
+    else if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<double>(c->rtc, na, jac, false, s2));
+    else HIP_TRY(c, emi::launch_nodes<double>(c->model, na, jac, false, s2));
+    EMI_TRY(prof_mark(c, pe, K3, AT1 | AT3, s2));
+    if (!c->cost_in_kernel) HIP_TRY(c, emi::launch_cost_finish<double>(na.cost_part, na.cost, L.B, emi::node_chunks(c->M), na.sgn * na.h, s2));
+    if (two) {
+        HIP_TRY(c, hipEventRecord(c->ev_join, s2));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        if (split) {
+            HIP_TRY(c, hipEventRecord(c->ev_join2, s1));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join2, 0));
+        }
+    }
+    EMI_TRY(prof_mark(c, pe, E1, AT1, c->stream));
+    EMI_TRY(prof_mark(c, pe, E2, AT1, c->stream));
+    return EMI_OK;
+}
+
+// fp32 contexts (config 5): the pass as ONE launch -- MFMA-role and node-role workgroups in one grid, the defect rows zeroed
+// here and completed by float atomics from both roles (emi_defect_f32.hip), COST finished in-kernel by ticket
+int form_pass_f32(emi_ctx_t c, Launch L, const PassIO& io, ProfEvents* pe) {
+    emi::NodeArgs<float> na;
+    fill_node_args(c, L, na, io);
+    const size_t rowb = (size_t)c->M * 4;
+    HIP_TRY(c, hipMemset2DAsync(io.RES, (size_t)nres_of(c) * rowb, 0, (size_t)c->ns * rowb, L.B, c->stream));
+    EMI_TRY(ensure_zeroed(c, c->d_ticket, (size_t)L.B * 4, c->stream));
+    na.cost_ticket = (unsigned*)c->d_ticket.p;
+    EMI_TRY(prof_mark(c, pe, K0, AT_ANY, c->stream));
+    HIP_TRY(c, emi::launch_pass_f32(c->model, defect_args_f32(c, L, io), na, c->pass_order >= 0 ? c->pass_order : 0, c->stream));
+    EMI_TRY(prof_mark(c, pe, K1, AT_ANY, c->stream));
+    if (pe) { pe->level = -1; pe->fused = true; }
+    c->last_defect_kernel = NAME_PASS_F32;
+    return EMI_OK;
+}
+
+// fp32 contexts (config 5), only when asked for ("overlap_mode" 2): the f32 MFMA defect kernel ACCUMULATES onto
+// -h f, so a values-only node kernel writes -h f first and the MFMA kernel follows it on the context's stream, while
+// the full node kernel (Jacobian values, cost; no defect rows) runs beside them on the second stream.  Measured at
+// B = 256, M = 4096: 1.076 ms against 1.082 ms back to back -- both kernels stretch (MFMA 0.93 -> 1.03 ms, node
+// 0.16 -> 0.80 ms), nothing is gained, so the default stays sequential (profiles/r02_notes.md)
+int form_two_stream_f32(emi_ctx_t c, Launch L, const PassIO& io, ProfEvents* pe) {
+    emi::NodeArgs<float> pre, full;
+    PassIO values_only = io;
+    values_only.VALS = nullptr;
+    fill_node_args(c, L, pre, values_only);
+    fill_node_args(c, L, full, io);
+    EMI_TRY(ensure(c, c->d_cost_part2, (size_t)L.B * emi::node_chunks(c->M) * 4));
+    EMI_TRY(need_stream2(c));
+    pre.cost_part = (float*)c->d_cost_part2.p;      // its cost partials go nowhere
+    pre.np = 0;                                      // ... and it leaves the path rows to the full kernel
+    // (round 4, "f32_ring_wgs" 1: the ring kernel at one workgroup per CU, which costs it nothing, leaves the node kernel's waves
+    // room on every SIMD; the node kernel is then released only once the values-only kernel is through, so that it does not fill the
+    // chip before the ring kernel's workgroups arrive)
+    const bool fork_late = c->f32_ring_wgs == 1;
+    if (!fork_late) {
+        HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    }
+    HIP_TRY(c, emi::launch_nodes<float>(c->model, pre, false, true, c->stream));
+    if (fork_late) {
+        HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    }
+    EMI_TRY(prof_mark(c, pe, K0, AT1 | AT2, c->stream));
+    HIP_TRY(c, emi::launch_defect_f32_mfma(defect_args_f32(c, L, io), c->stream, c->f32_ring, c->f32_ring_wgs));
+    EMI_TRY(prof_mark(c, pe, K1, AT1 | AT2, c->stream));
+    c->last_defect_kernel = name_defect_f32(c, true);
+    EMI_TRY(prof_mark(c, pe, K2, AT1 | AT3, c->stream2));
+    HIP_TRY(c, emi::launch_nodes<float>(c->model, full, true, false, c->stream2));
+    EMI_TRY(prof_mark(c, pe, K3, AT1 | AT3, c->stream2));
+    HIP_TRY(c, emi::launch_cost_finish<float>(full.cost_part, full.cost, L.B, emi::node_chunks(c->M), full.sgn * full.h, c->stream2));
+    HIP_TRY(c, hipEventRecord(c->ev_join, c->stream2));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    if (pe) pe->fused = true;
+    EMI_TRY(prof_mark(c, pe, E1, AT1, c->stream));
+    EMI_TRY(prof_mark(c, pe, E2, AT1, c->stream));
+    return EMI_OK;
+}
+
+// the node kernel by itself (it writes -h f into the defect rows, which the defect kernel then adds D X onto), then COST
+template <typename T>
+int launch_nodes_alone(emi_ctx_t c, Launch L, const PassIO& io, bool jac) {
+    emi::NodeArgs<T> a;
+    fill_node_args(c, L, a, io);
+    if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<T>(c->rtc, a, jac, true, c->stream));
+    else HIP_TRY(c, emi::launch_nodes<T>(c->model, a, jac, true, c->stream));
+    HIP_TRY(c, emi::launch_cost_finish<T>(a.cost_part, a.cost, L.B, emi::node_chunks(c->M), a.sgn * a.h, c->stream));
+    return EMI_OK;
+}
+
+// The general sequence on the context's stream: node kernel, then defect kernel (either alone where the flags ask for one).
+int form_sequential(emi_ctx_t c, Launch L, const PassIO& io, unsigned flags, bool small, ProfEvents* pe) {
+    const bool jac = !(flags & EMI_EVAL_NOJAC);
+    if (flags & EMI_EVAL_NODES) EMI_TRY(c->f32 ? launch_nodes_alone<float>(c, L, io, jac) : launch_nodes_alone<double>(c, L, io, jac));
+    EMI_TRY(prof_mark(c, pe, E1, AT_ANY, c->stream));
+    if ((flags & EMI_EVAL_DEFECT) && c->f32) {
+        const bool mfma = emi::defect_f32_mfma_supported(c->M) && c->allow_fused;
+        if (mfma) HIP_TRY(c, emi::launch_defect_f32_mfma(defect_args_f32(c, L, io), c->stream, c->f32_ring, c->f32_ring_wgs));
+        else HIP_TRY(c, emi::launch_defect_f32(defect_args_f32(c, L, io), c->stream));
+        c->last_defect_kernel = name_defect_f32(c, mfma);
+    } else if (flags & EMI_EVAL_DEFECT) {
+        emi::DefectArgs a{(const double*)io.X, (const double*)c->d_D.p, (double*)io.RES, L.B * c->ns, c->M, c->ns, nres_of(c)};
+        if (small) HIP_TRY(c, emi::launch_defect_small_f64(a, c->stream));
+        else HIP_TRY(c, emi::launch_defect_f64(a, c->stream));
+        c->last_defect_kernel = name_defect_f64(small);
+    }
+    EMI_TRY(prof_mark(c, pe, E2, AT1 | AT2, c->stream));
+    return EMI_OK;
+}
+
+// One launch of the pass: the argument checks, the profiling record, then the form the chooser names.
+int eval_launch(emi_ctx_t c, Launch L, const PassIO& io, unsigned flags) {
+    const bool nodes = flags & EMI_EVAL_NODES, defect = flags & EMI_EVAL_DEFECT;
+    const bool jac = !(flags & EMI_EVAL_NOJAC);
+    if (!nodes && !defect) return fail(c, EMI_ERR_ARG, "emi_eval: empty flags");
+    if (defect && c->points_only) return fail(c, EMI_ERR_STATE, "emi_eval: the mesh has no differentiation matrix (points-only mesh): EMI_EVAL_NODES only");
+    if (!io.X || !io.RES || (nodes && (!io.U || !io.COST || (jac && !io.VALS))))
+        return fail(c, EMI_ERR_ARG, "emi_eval: null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->attr_set) {
+        HIP_TRY(c, emi::defect_f64_set_attr());
+        c->attr_set = true;
+    }
+    const FormChoice ch = choose_form(c, L, flags);
+    ProfEvents* pe = nullptr;
+    if (c->profile) {
+        EMI_TRY(next_prof_record(c, &pe));
+        pe->has_node = nodes;
+        pe->has_defect = defect;
+        pe->fused = ch.overlapped();
+        pe->level = c->profile;
+        EMI_TRY(prof_mark(c, pe, E0, pe->fused ? AT1 : AT1 | AT3, c->stream));
+    }
+    switch (ch.form) {
+        case Form::PassF64: return form_pass_f64(c, L, io, ch.plan, pe);
+        case Form::TwoKernelF64: return form_two_kernel_f64(c, L, io, jac, pe);
+        case Form::PassF32: return form_pass_f32(c, L, io, pe);
+        case Form::TwoStreamF32: return form_two_stream_f32(c, L, io, pe);
+        case Form::Sequential: break;
+    }
+    return form_sequential(c, L, io, flags, ch.small, pe);
+}
+
 }  // namespace
 
 extern "C" {
@@ -512,20 +932,14 @@ static int create_impl(int device_id, bool f32, emi_ctx_t* out) {
     emi_ctx_t c = new emi_ctx_s();
     c->device = device_id;
     c->f32 = f32;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return EMI_ERR_HIP;
-    }
     c->own_stream = true;
     // (stream2 is created when a two-stream form first asks for it, need_stream2: every stream takes a share of one of the runtime's few
     // hardware queues, and a Monte-Carlo run has a context per host thread)
-    if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-        delete c;
-        return EMI_ERR_HIP;
-    }
-    if (hipEventCreate(&c->t_start) != hipSuccess || hipEventCreate(&c->t_stop) != hipSuccess) {
-        delete c;
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreate(&c->t_start) != hipSuccess || hipEventCreate(&c->t_stop) != hipSuccess) {
+        delete c;               // (the destructor releases what was created before the failure)
         return EMI_ERR_HIP;
     }
     *out = c;
@@ -535,35 +949,8 @@ static int create_impl(int device_id, bool f32, emi_ctx_t* out) {
 int emi_create(int device_id, emi_ctx_t* out) { return create_impl(device_id, false, out); }
 int emi_create_f32(int device_id, emi_ctx_t* out) { return create_impl(device_id, true, out); }
 
-// the second stream of the two-stream forms (node kernel beside the MFMA defect kernel), created on first use
-static int need_stream2(emi_ctx_t c) {
-    if (c->stream2) return EMI_OK;
-    if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) {
-        c->stream2 = nullptr;
-        return fail(c, EMI_ERR_HIP, "cannot create the second stream of the two-stream pass");
-    }
-    return EMI_OK;
-}
-
 int emi_destroy(emi_ctx_t c) {
     if (!c) return EMI_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    for (auto& pe : c->prof) {
-        for (int i = 0; i < 3; ++i) (void)hipEventDestroy(pe.e[i]);
-        for (int i = 0; i < 4; ++i) (void)hipEventDestroy(pe.k[i]);
-    }
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-    if (c->s_mfma) { (void)hipStreamSynchronize(c->s_mfma); (void)hipStreamDestroy(c->s_mfma); }
-    if (c->s_node) { (void)hipStreamSynchronize(c->s_node); (void)hipStreamDestroy(c->s_node); }
-    if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->t_start) (void)hipEventDestroy(c->t_start);
-    if (c->t_stop) (void)hipEventDestroy(c->t_stop);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    emi::rtc_destroy(c->rtc);
-    emi::kkt_destroy(c->kkt);
     delete c;
     return EMI_OK;
 }
@@ -598,50 +985,9 @@ int emi_synchronize(emi_ctx_t c) {
     return EMI_OK;
 }
 
-int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const double* D, double t0,
-                 double tf) {
-    if (!c || M < 2 || !tau || !w) return fail(c, EMI_ERR_ARG, "emi_set_mesh: bad argument");
-    if (!D) {
-        // points-only mesh: the node functions are evaluated at arbitrary abscissae (the ODE-error estimate between
-        // the collocation nodes); there is no differentiation matrix, so EMI_EVAL_DEFECT and the KKT entry points refuse
-        HIP_TRY(c, hipSetDevice(c->device));
-        const double hh = (tf - t0) / 2.0;
-        if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_set_mesh: tf must exceed t0");
-        std::vector<double> nt(M), zero(M, 0.0);
-        for (int k = 0; k < M; ++k) nt[k] = t0 + hh * (tau[k] + 1.0);
-        int st;
-        if ((st = upload_real(c, c->d_w, w, M))) return st;
-        if ((st = upload_real(c, c->d_t, nt.data(), M))) return st;
-        if ((st = upload_real(c, c->d_Ddiag, zero.data(), M))) return st;
-        c->symmetric = false;
-        c->points_only = true;
-        c->delay_dirty = true;
-        c->adjw_dirty = true;
-        c->adj_dirty = true;
-        emi::kkt_mesh_changed(c->kkt);
-        c->h_tau.assign(tau, tau + M);
-        c->h_w.assign(w, w + M);
-        c->M = M; c->t0 = t0; c->tf = tf;
-        c->ntracks = 0; c->track_sets = 0;
-        if (c->B > 0) {
-            const size_t rb = c->f32 ? 4 : 8;
-            if ((st = ensure(c, c->d_cost_part, (size_t)c->B * emi::node_chunks(M) * rb))) return st;
-        }
-        return EMI_OK;
-    }
-    c->points_only = false;
-    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_set_mesh: tf must exceed t0");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const double h = (tf - t0) / 2.0;
-    std::vector<double> nt(M), dd(M);
-    for (int k = 0; k < M; ++k) {
-        nt[k] = t0 + h * (tau[k] + 1.0);
-        dd[k] = D[(size_t)k * M + k];
-    }
-    int st;
-    if ((st = upload_real(c, c->d_w, w, M))) return st;
-    if ((st = upload_real(c, c->d_t, nt.data(), M))) return st;
-    if ((st = upload_real(c, c->d_Ddiag, dd.data(), M))) return st;
+// the differentiation matrix of a collocation mesh on the device: D itself (fp32 contexts: a copy whose rows sum to zero), and for
+// an exactly centro-antisymmetric D on an even number of nodes its even/odd halves De / Do (c->symmetric says whether they are valid)
+static int upload_operator(emi_ctx_t c, int M, const double* D) {
     if (c->f32) {
         // f32 copy of D whose rows sum to EXACTLY zero in f32 arithmetic terms: off-diagonals rounded,
         // diagonal = -(f64 sum of the rounded off-diagonals), rounded.  The shifted-difference form of
@@ -656,33 +1002,47 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
             }
             Df[(size_t)i * M + i] = (float)(-rs);
         }
-        if ((st = ensure(c, c->d_D, Df.size() * 4))) return st;
-        HIP_TRY(c, hipMemcpyAsync(c->d_D.p, Df.data(), Df.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if ((st = upload_real(c, c->d_D, D, (size_t)M * M))) {
-        return st;
+        return upload_bytes(c, c->d_D, Df.data(), Df.size() * 4);
     }
+    EMI_TRY(upload_real(c, c->d_D, D, (size_t)M * M));
     // even/odd split of D for the fused kernel: valid only for an exactly centro-antisymmetric D
-    c->symmetric = false;
-    if (M % 2 == 0 && !c->f32) {
-        const int N = M - 1, Hh = M / 2;
-        bool sym = true;
-        for (int i = 0; i < M && sym; ++i)
-            for (int j = 0; j < M; ++j)
-                if (D[(size_t)i * M + j] != -D[(size_t)(N - i) * M + (N - j)]) { sym = false; break; }
-        if (sym) {
-            std::vector<double> De((size_t)Hh * Hh), Do((size_t)Hh * Hh);
-            for (int i = 0; i < Hh; ++i)
-                for (int j = 0; j < Hh; ++j) {
-                    const double p = D[(size_t)i * M + j], q = D[(size_t)i * M + (N - j)];
-                    De[(size_t)i * Hh + j] = 0.5 * (p + q);
-                    Do[(size_t)i * Hh + j] = 0.5 * (p - q);
-                }
-            if ((st = upload_real(c, c->d_De, De.data(), De.size()))) return st;
-            if ((st = upload_real(c, c->d_Do, Do.data(), Do.size()))) return st;
-            c->symmetric = true;
+    if (M % 2 != 0) return EMI_OK;
+    const int N = M - 1, Hh = M / 2;
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < M; ++j)
+            if (D[(size_t)i * M + j] != -D[(size_t)(N - i) * M + (N - j)]) return EMI_OK;
+    std::vector<double> De((size_t)Hh * Hh), Do((size_t)Hh * Hh);
+    for (int i = 0; i < Hh; ++i)
+        for (int j = 0; j < Hh; ++j) {
+            const double p = D[(size_t)i * M + j], q = D[(size_t)i * M + (N - j)];
+            De[(size_t)i * Hh + j] = 0.5 * (p + q);
+            Do[(size_t)i * Hh + j] = 0.5 * (p - q);
         }
+    EMI_TRY(upload_real(c, c->d_De, De.data(), De.size()));
+    EMI_TRY(upload_real(c, c->d_Do, Do.data(), Do.size()));
+    c->symmetric = true;
+    return EMI_OK;
+}
+
+int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const double* D, double t0,
+                 double tf) {
+    if (!c || M < 2 || !tau || !w) return fail(c, EMI_ERR_ARG, "emi_set_mesh: bad argument");
+    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_set_mesh: tf must exceed t0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // D == NULL is a points-only mesh: the node functions are evaluated at arbitrary abscissae (the ODE-error estimate between
+    // the collocation nodes); there is no differentiation matrix, so EMI_EVAL_DEFECT and the KKT entry points refuse
+    const double h = (tf - t0) / 2.0;
+    std::vector<double> nt(M), dd(M, 0.0);
+    for (int k = 0; k < M; ++k) {
+        nt[k] = t0 + h * (tau[k] + 1.0);
+        if (D) dd[k] = D[(size_t)k * M + k];
     }
+    EMI_TRY(upload_real(c, c->d_w, w, M));
+    EMI_TRY(upload_real(c, c->d_t, nt.data(), M));
+    EMI_TRY(upload_real(c, c->d_Ddiag, dd.data(), M));
+    c->symmetric = false;
+    if (D) EMI_TRY(upload_operator(c, M, D));
+    c->points_only = !D;
     c->h_tau.assign(tau, tau + M);
     c->h_w.assign(w, w + M);
     c->M = M;
@@ -696,11 +1056,26 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     c->ntracks = 0;
     c->track_sets = 0;
     // the per-block cost partials are sized B * node_chunks(M): keep them valid for the batch already set
-    if (c->B > 0) {
-        const size_t rb = c->f32 ? 4 : 8;
-        if ((st = ensure(c, c->d_cost_part, (size_t)c->B * emi::node_chunks(M) * rb))) return st;
-    }
+    if (c->B > 0) EMI_TRY(ensure(c, c->d_cost_part, (size_t)c->B * emi::node_chunks(M) * (c->f32 ? 4 : 8)));
     return EMI_OK;
+}
+
+// A new model is in force: its dimensions, the traced rows it computes itself (run-time compiled models) and its parameters.
+// What was declared for the previous model goes: delayed values (emi_set_delays again) and the path rows, which name states
+// (px, py) that this model may not have.
+static void model_in_force(emi_ctx_t c, int model, int ns, int nc, int npath, const int* path_vars, int n_path_vars,
+                           const double* params, int nparams, int maximize) {
+    c->model = model;
+    c->ns = ns;
+    c->nc = nc;
+    c->xh = c->uh = c->nch = 0;
+    c->np_model = npath;
+    c->pvars.assign(path_vars, path_vars + n_path_vars);
+    c->maximize = maximize ? 1 : 0;
+    memset(c->params, 0, sizeof c->params);
+    for (int i = 0; i < nparams; ++i) c->params[i] = params[i];
+    c->np = 0;
+    c->path_sets = 0;
 }
 
 int emi_set_model(emi_ctx_t c, int model, const double* params, int nparams, int maximize) {
@@ -714,18 +1089,7 @@ int emi_set_model(emi_ctx_t c, int model, const double* params, int nparams, int
         emi::rtc_destroy(c->rtc);
         c->rtc = nullptr;
     }
-    c->model = model;
-    c->ns = ns;
-    c->nc = nc;
-    c->xh = c->uh = c->nch = 0;
-    c->np_model = 0;
-    c->pvars.clear();
-    c->maximize = maximize ? 1 : 0;
-    memset(c->params, 0, sizeof c->params);
-    for (int i = 0; i < nparams; ++i) c->params[i] = params[i];
-    // path rows name states (px, py) of the previous model, which this one may not have
-    c->np = 0;
-    c->path_sets = 0;
+    model_in_force(c, model, ns, nc, 0, nullptr, 0, params, nparams, maximize);
     return EMI_OK;
 }
 
@@ -751,18 +1115,7 @@ int emi_set_model_source(emi_ctx_t c, const char* struct_name, const char* sourc
     }
     emi::rtc_destroy(c->rtc);
     c->rtc = m;
-    c->model = EMI_MODEL_SOURCE;
-    c->ns = ns;
-    c->nc = nc;
-    c->xh = c->uh = c->nch = 0;     // delayed values belong to the model they were declared for: emi_set_delays again
-    c->np_model = npath;
-    c->pvars.assign(path_vars, path_vars + (npath > 0 ? n_path_vars : 0));
-    c->maximize = maximize ? 1 : 0;
-    memset(c->params, 0, sizeof c->params);
-    for (int i = 0; i < nparams; ++i) c->params[i] = params[i];
-    // path rows name states of the previous model
-    c->np = 0;
-    c->path_sets = 0;
+    model_in_force(c, EMI_MODEL_SOURCE, ns, nc, npath, path_vars, npath > 0 ? n_path_vars : 0, params, nparams, maximize);
     return EMI_OK;
 }
 
@@ -930,8 +1283,6 @@ int emi_d2h(emi_ctx_t c, void* dst, const void* src, size_t bytes) {
     return EMI_OK;
 }
 
-static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* dVALS, void* dCOST, unsigned flags);
-
 int emi_eval_dev(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* dVALS, void* dCOST,
                  unsigned flags) {
     int st = ready(c);
@@ -941,289 +1292,12 @@ int emi_eval_dev(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* 
     int piece = 0;
     if (!c->profile && !c->f32 && (flags & EMI_EVAL_ALL) == EMI_EVAL_ALL && overlapped_path(c) && dX && dU && dRES && dCOST &&
         (dVALS || (flags & EMI_EVAL_NOJAC)))
-        piece = plan_piece(c);
-    if (piece > 0) {
-        const int SL = piece;
-        const int Btot = c->B;
-        const size_t rb = 8, M = c->M;
-        const size_t nres = nres_of(c), nvals = nvals_of(c);
-        for (int first = 0; first < Btot && st == EMI_OK; first += SL) {
-            c->B = std::min(SL, Btot - first);
-            c->slice_first = first;
-            st = eval_dev_slice(c, (const char*)dX + (size_t)first * c->ns * M * rb, (const char*)dU + (size_t)first * c->nc * M * rb,
-                                (char*)dRES + (size_t)first * nres * M * rb, dVALS ? (char*)dVALS + (size_t)first * nvals * M * rb : nullptr,
-                                (char*)dCOST + (size_t)first * rb, flags);
-        }
-        c->B = Btot;
-        c->slice_first = 0;
-        return st;
-    }
-    return eval_dev_slice(c, dX, dU, dRES, dVALS, dCOST, flags);
-}
-
-static int eval_dev_slice(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* dVALS, void* dCOST, unsigned flags) {
-    const bool nodes = flags & EMI_EVAL_NODES, defect = flags & EMI_EVAL_DEFECT;
-    const bool jac = !(flags & EMI_EVAL_NOJAC);
-    if (!nodes && !defect) return fail(c, EMI_ERR_ARG, "emi_eval: empty flags");
-    if (defect && c->points_only) return fail(c, EMI_ERR_STATE, "emi_eval: the mesh has no differentiation matrix (points-only mesh): EMI_EVAL_NODES only");
-    if (!dX || !dRES || (nodes && (!dU || !dCOST || (jac && !dVALS))))
-        return fail(c, EMI_ERR_ARG, "emi_eval: null device pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->attr_set) {
-        HIP_TRY(c, emi::defect_f64_set_attr());
-        c->attr_set = true;
-    }
-    // a handful of instances: the stand-alone MFMA kernels would have a few workgroups to run and a skinny streaming product wins
-    // (21 us at B = 1) -- unless the whole pass can go as ONE launch with its K range sliced, which is faster still (13 - 15 us for
-    // any batch up to 16 instances: profiles/r03_notes.md section 7)
-    const bool small = defect && !c->f32 && c->B * c->ns <= c->small_rows && emi::defect_small_supported(c->B * c->ns) &&
-                       !(nodes && jac && pass_takes_small_batches(c));
-    const bool fused = nodes && defect && !small && overlapped_path(c);
-    ProfEvents* pe = nullptr;
-    if (c->profile) {
-        if (c->prof_used == c->prof.size()) {
-            ProfEvents n;
-            for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventCreate(&n.e[i]));
-            for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventCreate(&n.k[i]));
-            c->prof.push_back(n);
-        }
-        pe = &c->prof[c->prof_used++];
-        pe->has_node = nodes;
-        pe->has_defect = defect;
-        pe->fused = fused;
-        pe->level = c->profile;
-        if (pe->level == 1 || (!fused && pe->level == 3)) HIP_TRY(c, hipEventRecord(pe->e[0], c->stream));
-    }
-    const int plv = pe ? pe->level : 0;
-    if (fused) {
-        // fork: the two kernels read X,U and write disjoint outputs, so they run concurrently.
-        // The MFMA kernel goes first and takes one workgroup per CU (LDS-shaped); the streaming
-        // kernel's waves fill the rest of every CU.
-        emi::SymDefectArgs sa;
-        sa.X = (const double*)dX;
-        sa.U = (const double*)dU;
-        sa.RES = (double*)dRES;
-        sa.node_t = (const double*)c->d_t.p;
-        sa.De = (const double*)c->d_De.p;
-        sa.Do = (const double*)c->d_Do.p;
-        sa.M = c->M;
-        sa.B = c->B;
-        sa.nres = nres_of(c);
-        sa.h = (c->tf - c->t0) / 2.0;
-        sa.order = c->sym_order;
-        sa.ablate = c->sym_ablate;
-        sa.ksplit = 1;
-        sa.slab = nullptr;
-        sa.tile_ticket = nullptr;
-        sa.cpart = sa.cx = 0;
-        sa.mfma_first = 0;
-        for (int i = 0; i < EMI_MAX_PARAMS; ++i) sa.P.p[i] = c->params[i];
-        emi::NodeArgs<double> na;
-        fill_node_args(c, na, dX, dU, dRES, dVALS, dCOST);
-        const PassPlan pp = plan_pass(c, c->B, jac);
-        if (pp.one_launch) {
-            const emi::SymPlan& plan = pp.sym;
-            sa.mfma_first = pp.mfma_first;
-            sa.cpart = plan.cpart;
-            sa.cx = plan.cx;
-            if (plan.ks > 1) {
-                int est = ensure(c, c->d_slab, plan.slab_bytes);
-                if (est) return est;
-                if (c->d_tile_ticket.bytes() < (size_t)plan.tiles * 4) {
-                    est = ensure(c, c->d_tile_ticket, (size_t)plan.tiles * 4);
-                    if (est) return est;
-                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes(), c->stream));
-                }
-                sa.ksplit = plan.ks;
-                sa.slab = (double*)c->d_slab.p;
-                sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
-            }
-            if (c->d_ticket.bytes() < (size_t)c->B * 4) {
-                int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
-                if (est) return est;
-                HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, c->stream));
-            }
-            na.cost_ticket = (unsigned*)c->d_ticket.p;
-            if (plv) HIP_TRY(c, hipEventRecord(pe->k[0], c->stream));
-            if (c->rtc) HIP_TRY(c, emi::rtc_launch_pass(c->rtc, sa, na, plan.sw, c->stream));
-            else HIP_TRY(c, emi::launch_pass(c->model, sa, na, c->stream, plan));
-            if (plv) HIP_TRY(c, hipEventRecord(pe->k[1], c->stream));
-            if (pe) pe->level = -1;                 // one bracket: the pass kernel
-            c->last_defect_kernel = "emi_pass_f64_kernel<SW=" + std::to_string(plan.sw) + "> (MFMA + node roles, one launch" +
-                                    (plan.ks > 1 ? ", " + std::to_string(plan.ks) + " K slices per tile" : "") + ")" +
-                                    (plan.bk == 16 ? " [K tiles of 16]" : "") + (plan.ct == 2 ? " [128-column tiles]" : "") + (plan.hs == 2 ? " [K range in two halves per workgroup]" : "");
-            return EMI_OK;
-        }
-        const bool two = c->overlap_mode != 1;
-        const bool split = two && c->cu_split > 0;
-        if (two && !split) { if (int st = need_stream2(c)) return st; }
-        hipStream_t s1 = split ? c->s_mfma : c->stream;
-        hipStream_t s2 = split ? c->s_node : (two ? c->stream2 : c->stream);
-        const unsigned bit = 1u << c->sym_ct;
-        if (two) {
-            HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
-            if (split) HIP_TRY(c, hipStreamWaitEvent(s1, c->ev_fork, 0));
-        }
-        if (plv == 1 || plv == 2) HIP_TRY(c, hipEventRecord(pe->k[0], s1));
-        if (c->rtc) {
-            HIP_TRY(c, emi::rtc_launch_symdefect(c->rtc, sa, s1));
-            c->last_defect_kernel = "emi_symdefect_ring_f64_kernel";
-        } else {
-            const emi::SymPlan plan = emi::plan_symdefect(c->ns, c->B, c->M, c->sym_ct, c->sym_ksplit, c->sym_cpart, c->sym_gblk, c->sym_cx);
-            if (plan.slab_bytes) {
-                int est = ensure(c, c->d_slab, plan.slab_bytes);
-                if (est) return est;
-            }
-            sa.ksplit = plan.ring1 ? 1 : plan.ks;
-            sa.slab = (double*)c->d_slab.p;
-            sa.cpart = plan.cpart; sa.cx = plan.cx;
-            if (sa.ksplit > 1 && c->sym_combine) {
-                if (c->d_tile_ticket.bytes() < (size_t)plan.tiles * 4) {
-                    int est = ensure(c, c->d_tile_ticket, (size_t)plan.tiles * 4);
-                    if (est) return est;
-                    HIP_TRY(c, hipMemsetAsync(c->d_tile_ticket.p, 0, c->d_tile_ticket.bytes(), s1));
-                }
-                sa.tile_ticket = (unsigned*)c->d_tile_ticket.p;
-            }
-            HIP_TRY(c, emi::launch_symdefect(c->model, sa, s1, !(c->fused_attr_mask & bit), c->sym_ct, plan));
-            c->fused_attr_mask |= bit;
-            c->last_defect_kernel = !plan.ring1 ? "emi_symdefect_ring2_f64_kernel<SW=" + std::to_string(plan.sw) + ">" +
-                                                      (plan.ks > 1 ? " x" + std::to_string(plan.ks) + (sa.tile_ticket ? " K slices (in-kernel combine)" : " K slices + emi_symdefect_combine_kernel") : "")
-                                                : (c->sym_ct == 1 || c->sym_ct == 2 ? "emi_symdefect_f64_kernel" : "emi_symdefect_ring_f64_kernel");
-        }
-        if (plv == 1 || plv == 2) HIP_TRY(c, hipEventRecord(pe->k[1], s1));
-        // COST is finished inside the node kernel (last workgroup of an instance, by ticket, in chunk order): one launch
-        // and one kernel boundary less at the end of every pass (emi_cost_finish_kernel alone was 5 us)
-        if (c->cost_in_kernel) {
-            if (c->d_ticket.bytes() < (size_t)c->B * 4) {
-                int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
-                if (est) return est;
-                HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, s2));
-            }
-            na.cost_ticket = (unsigned*)c->d_ticket.p;
-        }
-        if (plv == 1 || plv == 3) HIP_TRY(c, hipEventRecord(pe->k[2], s2));
-        if (c->rtc && jac && na.store_mode == 2 && c->M % 2 == 0) HIP_TRY(c, emi::rtc_launch_nodes_nt(c->rtc, na, s2));
-        else if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<double>(c->rtc, na, jac, false, s2));
-        else HIP_TRY(c, emi::launch_nodes<double>(c->model, na, jac, false, s2));
-        if (plv == 1 || plv == 3) HIP_TRY(c, hipEventRecord(pe->k[3], s2));
-        if (!c->cost_in_kernel)
-            HIP_TRY(c, emi::launch_cost_finish<double>(na.cost_part, na.cost, c->B, emi::node_chunks(c->M),
-                                                       na.sgn * na.h, s2));
-        if (two) {
-            HIP_TRY(c, hipEventRecord(c->ev_join, s2));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            if (split) {
-                HIP_TRY(c, hipEventRecord(c->ev_join2, s1));
-                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join2, 0));
-            }
-        }
-        if (plv == 1) {
-            HIP_TRY(c, hipEventRecord(pe->e[1], c->stream));
-            HIP_TRY(c, hipEventRecord(pe->e[2], c->stream));
-        }
-        return EMI_OK;
-    }
-    if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused && (c->overlap_mode == 3 || (c->overlap_mode == 0 && c->f32_one_launch)) &&
-        emi::pass_f32_supported(c->model, c->B * c->ns, c->M, c->B)) {
-        // fp32 contexts (config 5): the pass as ONE launch -- MFMA-role and node-role workgroups in one grid, the defect rows zeroed
-        // here and completed by float atomics from both roles (emi_defect_f32.hip), COST finished in-kernel by ticket
-        emi::NodeArgs<float> na;
-        fill_node_args(c, na, dX, dU, dRES, dVALS, dCOST);
-        const size_t rowb = (size_t)c->M * 4;
-        HIP_TRY(c, hipMemset2DAsync(dRES, (size_t)nres_of(c) * rowb, 0, (size_t)c->ns * rowb, c->B, c->stream));
-        if (c->d_ticket.bytes() < (size_t)c->B * 4) {
-            int est = ensure(c, c->d_ticket, (size_t)c->B * 4);
-            if (est) return est;
-            HIP_TRY(c, hipMemsetAsync(c->d_ticket.p, 0, (size_t)c->B * 4, c->stream));
-        }
-        na.cost_ticket = (unsigned*)c->d_ticket.p;
-        emi::DefectArgsF32 da{(const float*)dX, (const float*)c->d_D.p, (float*)dRES, c->B * c->ns, c->M, c->ns, nres_of(c)};
-        if (plv) HIP_TRY(c, hipEventRecord(pe->k[0], c->stream));
-        HIP_TRY(c, emi::launch_pass_f32(c->model, da, na, c->pass_order >= 0 ? c->pass_order : 0, c->stream));
-        if (plv) HIP_TRY(c, hipEventRecord(pe->k[1], c->stream));
-        if (pe) { pe->level = -1; pe->fused = true; }
-        c->last_defect_kernel = "emi_pass_f32_kernel (MFMA + node roles, one launch)";
-        return EMI_OK;
-    }
-    if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused && c->overlap_mode == 2 && emi::defect_f32_mfma_supported(c->M)) {
-        // fp32 contexts (config 5), only when asked for ("overlap_mode" 2): the f32 MFMA defect kernel ACCUMULATES onto
-        // -h f, so a values-only node kernel writes -h f first and the MFMA kernel follows it on the context's stream, while
-        // the full node kernel (Jacobian values, cost; no defect rows) runs beside them on the second stream.  Measured at
-        // B = 256, M = 4096: 1.076 ms against 1.082 ms back to back -- both kernels stretch (MFMA 0.93 -> 1.03 ms, node
-        // 0.16 -> 0.80 ms), nothing is gained, so the default stays sequential (profiles/r02_notes.md)
-        emi::NodeArgs<float> pre, full;
-        fill_node_args(c, pre, dX, dU, dRES, nullptr, dCOST);
-        fill_node_args(c, full, dX, dU, dRES, dVALS, dCOST);
-        int est = ensure(c, c->d_cost_part2, (size_t)c->B * emi::node_chunks(c->M) * 4);
-        if (est) return est;
-        if (int st2 = need_stream2(c)) return st2;
-        pre.cost_part = (float*)c->d_cost_part2.p;      // its cost partials go nowhere
-        pre.np = 0;                                      // ... and it leaves the path rows to the full kernel
-        // (round 4, "f32_ring_wgs" 1: the ring kernel at one workgroup per CU, which costs it nothing, leaves the node kernel's waves
-        // room on every SIMD; the node kernel is then released only once the values-only kernel is through, so that it does not fill the
-        // chip before the ring kernel's workgroups arrive)
-        if (c->f32_ring_wgs != 1) {
-            HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        }
-        HIP_TRY(c, emi::launch_nodes<float>(c->model, pre, false, true, c->stream));
-        if (c->f32_ring_wgs == 1) {
-            HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        }
-        emi::DefectArgsF32 da{(const float*)dX, (const float*)c->d_D.p, (float*)dRES, c->B * c->ns, c->M, c->ns, nres_of(c)};
-        if (plv == 1 || plv == 2) HIP_TRY(c, hipEventRecord(pe->k[0], c->stream));
-        HIP_TRY(c, emi::launch_defect_f32_mfma(da, c->stream, c->f32_ring, c->f32_ring_wgs));
-        if (plv == 1 || plv == 2) HIP_TRY(c, hipEventRecord(pe->k[1], c->stream));
-        c->last_defect_kernel = c->f32_ring ? "emi_defect_f32_ring_kernel" : "emi_defect_f32_mfma_kernel";
-        if (plv == 1 || plv == 3) HIP_TRY(c, hipEventRecord(pe->k[2], c->stream2));
-        HIP_TRY(c, emi::launch_nodes<float>(c->model, full, true, false, c->stream2));
-        if (plv == 1 || plv == 3) HIP_TRY(c, hipEventRecord(pe->k[3], c->stream2));
-        HIP_TRY(c, emi::launch_cost_finish<float>(full.cost_part, full.cost, c->B, emi::node_chunks(c->M), full.sgn * full.h, c->stream2));
-        HIP_TRY(c, hipEventRecord(c->ev_join, c->stream2));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        if (pe) pe->fused = true;
-        if (plv == 1) {
-            HIP_TRY(c, hipEventRecord(pe->e[1], c->stream));
-            HIP_TRY(c, hipEventRecord(pe->e[2], c->stream));
-        }
-        return EMI_OK;
-    }
-    if (nodes) {
-        if (c->f32) {
-            emi::NodeArgs<float> a;
-            fill_node_args(c, a, dX, dU, dRES, dVALS, dCOST);
-            if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<float>(c->rtc, a, jac, true, c->stream));
-            else HIP_TRY(c, emi::launch_nodes<float>(c->model, a, jac, true, c->stream));
-            HIP_TRY(c, emi::launch_cost_finish<float>(a.cost_part, a.cost, c->B, emi::node_chunks(c->M), a.sgn * a.h,
-                                                      c->stream));
-        } else {
-            emi::NodeArgs<double> a;
-            fill_node_args(c, a, dX, dU, dRES, dVALS, dCOST);
-            if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<double>(c->rtc, a, jac, true, c->stream));
-            else HIP_TRY(c, emi::launch_nodes<double>(c->model, a, jac, true, c->stream));
-            HIP_TRY(c, emi::launch_cost_finish<double>(a.cost_part, a.cost, c->B, emi::node_chunks(c->M), a.sgn * a.h,
-                                                       c->stream));
-        }
-    }
-    if (plv) HIP_TRY(c, hipEventRecord(pe->e[1], c->stream));
-    if (defect) {
-        if (c->f32) {
-            emi::DefectArgsF32 a{(const float*)dX, (const float*)c->d_D.p, (float*)dRES, c->B * c->ns,
-                                 c->M, c->ns, nres_of(c)};
-            if (emi::defect_f32_mfma_supported(c->M) && c->allow_fused) { HIP_TRY(c, emi::launch_defect_f32_mfma(a, c->stream, c->f32_ring, c->f32_ring_wgs)); c->last_defect_kernel = c->f32_ring ? "emi_defect_f32_ring_kernel" : "emi_defect_f32_mfma_kernel"; }
-            else { HIP_TRY(c, emi::launch_defect_f32(a, c->stream)); c->last_defect_kernel = "emi_defect_f32_kernel"; }
-        } else {
-            emi::DefectArgs a{(const double*)dX, (const double*)c->d_D.p, (double*)dRES, c->B * c->ns,
-                              c->M, c->ns, nres_of(c)};
-            if (small) { HIP_TRY(c, emi::launch_defect_small_f64(a, c->stream)); c->last_defect_kernel = "emi_defect_small_f64_kernel"; }
-            else { HIP_TRY(c, emi::launch_defect_f64(a, c->stream)); c->last_defect_kernel = "emi_defect_f64_kernel"; }
-        }
-    }
-    if (plv == 1 || plv == 2) HIP_TRY(c, hipEventRecord(pe->e[2], c->stream));
-    return EMI_OK;
+        piece = plan_piece(c, c->B);
+    const PassIO io{dX, dU, dRES, dVALS, dCOST};
+    if (piece <= 0) return eval_launch(c, Launch{0, c->B}, io, flags);
+    for (int first = 0; first < c->B && st == EMI_OK; first += piece)
+        st = eval_launch(c, Launch{first, std::min(piece, c->B - first)}, io_at(c, io, first), flags);
+    return st;
 }
 
 int emi_eval_host(emi_ctx_t c, const double* X, const double* U, double* RES, double* VALS,
@@ -1333,11 +1407,7 @@ static int adj_ready(emi_ctx_t c, const char* who, bool total = false) {
         c->adjw_dirty = false;
     }
     if (c->adj_pvars != c->pvars || (!c->pvars.empty() && !c->d_adj_pvars.p)) {
-        if ((st = ensure(c, c->d_adj_pvars, c->pvars.size() * sizeof(int)))) return st;
-        if (!c->pvars.empty()) {
-            HIP_TRY(c, hipMemcpyAsync(c->d_adj_pvars.p, c->pvars.data(), c->pvars.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
+        if ((st = upload_bytes(c, c->d_adj_pvars, c->pvars.data(), c->pvars.size() * sizeof(int)))) return st;
         c->adj_pvars = c->pvars;
     }
     return EMI_OK;
@@ -1420,37 +1490,36 @@ int emi_lagr_grad_total_dev(emi_ctx_t c, const void* dVALS, const void* dLamF, c
     return EMI_OK;
 }
 
-int emi_lagr_grad_total_host(emi_ctx_t c, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G, double* Gdel) {
+// total: emi_lagr_grad_total_host (G on the free variables, Gdel the adjoints of the delayed values); a context the plain form
+// accepts has no delayed values, so the sizes below are the same figures for both
+static int lagr_grad_host(emi_ctx_t c, bool total, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G,
+                          double* Gdel) {
     if (!c) return adj_null_ctx();
-    int st = adj_ready(c, "emi_lagr_grad_total_host", true);
+    const char* who = total ? "emi_lagr_grad_total_host" : "emi_lagr_grad_host";
+    int st = adj_ready(c, who, total);
     if (st) return st;
-    if (!VALS || !LamF || !G || (np_total(c) > 0 && !LamC)) return fail(c, EMI_ERR_ARG, "emi_lagr_grad_total_host: null pointer");
+    if (!VALS || !LamF || !G || (np_total(c) > 0 && !LamC)) return fail(c, EMI_ERR_ARG, "%s: null pointer", who);
     const size_t M = c->M, B = c->B, nf = c->ns + c->nc - c->nch;
     const size_t nV = B * nvals_of(c) * M, nF = B * c->ns * M, nC = B * np_total(c) * M, nG = B * nf * M, nGd = B * c->nch * M;
     if ((st = upload_real(c, c->s_VALS, VALS, nV))) return st;
     if ((st = upload_real(c, c->s_LF, LamF, nF))) return st;
     if (nC && (st = upload_real(c, c->s_LC, LamC, nC))) return st;
     if ((st = ensure(c, c->s_G, nG * 8))) return st;
-    const bool del = Gdel && nGd > 0;
+    const bool del = total && Gdel && nGd > 0;
     if (del && (st = ensure(c, c->s_Gdel, nGd * 8))) return st;
-    if ((st = emi_lagr_grad_total_dev(c, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_G.p, del ? c->s_Gdel.p : nullptr))) return st;
+    if ((st = total ? emi_lagr_grad_total_dev(c, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_G.p, del ? c->s_Gdel.p : nullptr)
+                    : emi_lagr_grad_dev(c, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_G.p)))
+        return st;
     if (del && (st = download_real(c, Gdel, c->s_Gdel.p, nGd))) return st;
     return download_real(c, G, c->s_G.p, nG);
 }
 
+int emi_lagr_grad_total_host(emi_ctx_t c, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G, double* Gdel) {
+    return lagr_grad_host(c, true, VALS, LamF, LamC, sigma, G, Gdel);
+}
+
 int emi_lagr_grad_host(emi_ctx_t c, const double* VALS, const double* LamF, const double* LamC, double sigma, double* G) {
-    if (!c) return adj_null_ctx();
-    int st = adj_ready(c, "emi_lagr_grad_host");
-    if (st) return st;
-    if (!VALS || !LamF || !G || (np_total(c) > 0 && !LamC)) return fail(c, EMI_ERR_ARG, "emi_lagr_grad_host: null pointer");
-    const size_t M = c->M, B = c->B, nv = c->ns + c->nc;
-    const size_t nV = B * nvals_of(c) * M, nF = B * c->ns * M, nC = B * np_total(c) * M, nG = B * nv * M;
-    if ((st = upload_real(c, c->s_VALS, VALS, nV))) return st;
-    if ((st = upload_real(c, c->s_LF, LamF, nF))) return st;
-    if (nC && (st = upload_real(c, c->s_LC, LamC, nC))) return st;
-    if ((st = ensure(c, c->s_G, nG * 8))) return st;
-    if ((st = emi_lagr_grad_dev(c, c->s_VALS.p, c->s_LF.p, c->s_LC.p, sigma, c->s_G.p))) return st;
-    return download_real(c, G, c->s_G.p, nG);
+    return lagr_grad_host(c, false, VALS, LamF, LamC, sigma, G, nullptr);
 }
 
 // the certificate on the free variables: G, U, zl, zu hold nf = ns + nc - n_delayed variables (total: the folded gradient)
@@ -1726,35 +1795,35 @@ int emi_profile_read(emi_ctx_t c, float* node_ms, int* node_launches, float* def
         ProfEvents& pe = c->prof[i];
         float ms = 0;
         if (pe.fused && pe.level == -1) {
-            HIP_TRY(c, hipEventElapsedTime(&ms, pe.k[0], pe.k[1]));
+            HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[K0], pe.ev[K1]));
             dm += ms; ++dl; fm += ms; ++fl;
             continue;
         }
         if (pe.fused) {
             if (pe.level == 1) {
-                HIP_TRY(c, hipEventElapsedTime(&ms, pe.e[0], pe.e[1]));
+                HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[E0], pe.ev[E1]));
                 fm += ms;
             }
             ++fl;
             if (pe.level == 1 || pe.level == 2) {
-                HIP_TRY(c, hipEventElapsedTime(&ms, pe.k[0], pe.k[1]));
+                HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[K0], pe.ev[K1]));
                 dm += ms;
                 ++dl;
             }
             if (pe.level == 1 || pe.level == 3) {
-                HIP_TRY(c, hipEventElapsedTime(&ms, pe.k[2], pe.k[3]));
+                HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[K2], pe.ev[K3]));
                 nm += ms;
                 ++nl;
             }
             continue;
         }
         if (pe.has_node && pe.level != 2) {
-            HIP_TRY(c, hipEventElapsedTime(&ms, pe.e[0], pe.e[1]));
+            HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[E0], pe.ev[E1]));
             nm += ms;
             ++nl;
         }
         if (pe.has_defect && pe.level != 3) {
-            HIP_TRY(c, hipEventElapsedTime(&ms, pe.e[1], pe.e[2]));
+            HIP_TRY(c, hipEventElapsedTime(&ms, pe.ev[E1], pe.ev[E2]));
             dm += ms;
             ++dl;
         }
@@ -1771,12 +1840,6 @@ int emi_profile_read(emi_ctx_t c, float* node_ms, int* node_launches, float* def
 
 int emi_set_option(emi_ctx_t c, const char* name, int value) {
     if (!c || !name) return EMI_ERR_ARG;
-    if (strcmp(name, "overlap") == 0 || strcmp(name, "fused") == 0) { c->allow_fused = value != 0; return EMI_OK; }
-    if (strcmp(name, "sym_ct") == 0) {
-        if (value < 0 || value > 8) return fail(c, EMI_ERR_ARG, "sym_ct must be 0..8 (0/4 = chosen from the batch, 3 = LDS-DMA ring, 5..8 = state-split ring with SW = NS/2/1/3)");
-        c->sym_ct = value;
-        return EMI_OK;
-    }
     if (strcmp(name, "cu_split") == 0) {
         // experiment: spatial instead of temporal sharing of the chip between the MFMA and the streaming kernel
         hipDeviceProp_t prop;
@@ -1797,88 +1860,21 @@ int emi_set_option(emi_ctx_t c, const char* name, int value) {
         }
         return EMI_OK;
     }
-    if (strncmp(name, "kkt_", 4) == 0 && strcmp(name, "kkt_method") != 0) {
-        if (strcmp(name, "kkt_cholesky") == 0 && value != 1 && value != 2)
-            return fail(c, EMI_ERR_ARG, "kkt_cholesky must be 1 (one-level blocked Cholesky) or 2 (two-level form from 1024 rows)");
-        if (emi::kkt_set_option(name, value)) return EMI_OK;
-        return fail(c, EMI_ERR_ARG, "unknown option %s", name);
-    }
     if (strcmp(name, "kkt_method") == 0) {
         if (value != 0 && value != 1) return fail(c, EMI_ERR_ARG, "kkt_method must be 0 (LU) or 1 (Schur complement + Cholesky)");
         c->kkt_method = value;
         return EMI_OK;
     }
-    if (strcmp(name, "small_rows") == 0) {
-        if (value < 0) return fail(c, EMI_ERR_ARG, "small_rows must be >= 0 (0 disables the skinny defect kernel)");
-        c->small_rows = value;
-        return EMI_OK;
+    if (strncmp(name, "kkt_", 4) == 0) {        // the process-wide switches of the Newton step (emi_kkt.hip)
+        if (strcmp(name, "kkt_cholesky") == 0 && value != 1 && value != 2)
+            return fail(c, EMI_ERR_ARG, "kkt_cholesky must be 1 (one-level blocked Cholesky) or 2 (two-level form from 1024 rows)");
+        if (emi::kkt_set_option(name, value)) return EMI_OK;
+        return fail(c, EMI_ERR_ARG, "unknown option %s", name);
     }
-    if (strcmp(name, "sym_order") == 0) { c->sym_order = value != 0; return EMI_OK; }
-    if (strcmp(name, "f32_ring") == 0) { c->f32_ring = value != 0; return EMI_OK; }
-    if (strcmp(name, "f32_ring_wgs") == 0) { c->f32_ring_wgs = value == 1 ? 1 : 2; return EMI_OK; }
-    if (strcmp(name, "f32_one_launch") == 0) { c->f32_one_launch = value != 0; return EMI_OK; }
-    if (strcmp(name, "slice") == 0) {
-        if (value < 0 || (value > 0 && value % 16 != 0)) return fail(c, EMI_ERR_ARG, "slice must be 0 (never) or a multiple of 16 instances");
-        c->slice = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "pass_order") == 0) { c->pass_order = value < 0 ? -1 : (value >= 100 ? value : (value != 0)); return EMI_OK; }
-    if (strcmp(name, "sym_ablate") == 0) { c->sym_ablate = value; return EMI_OK; }   // diagnostics only
-    if (strcmp(name, "adj_fold_tile") == 0) {
-        if (value < 0 || value > 2) return fail(c, EMI_ERR_ARG, "adj_fold_tile must be 0 (by size), 1 (48 x 64) or 2 (96 x 128)");
-        c->adj_fold_tile = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "cost_in_kernel") == 0) { c->cost_in_kernel = value != 0; return EMI_OK; }
-    if (strcmp(name, "sym_nst") == 0) {
-        if (value != 3 && value != 4) return fail(c, EMI_ERR_ARG, "sym_nst must be 3 or 4");
-        c->sym_nst = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_hs") == 0) {
-        if (value < 0 || value > 2) return fail(c, EMI_ERR_ARG, "sym_hs must be 0 (by batch size), 1 or 2");
-        c->sym_hs = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_ctc") == 0) {
-        if (value < 0 || value > 2) return fail(c, EMI_ERR_ARG, "sym_ctc must be 0 (by batch size), 1 or 2");
-        c->sym_ctc = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_bk") == 0) {
-        if (value != 0 && value != 8 && value != 16) return fail(c, EMI_ERR_ARG, "sym_bk must be 0 (by batch size), 8 or 16");
-        c->sym_bk = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_cpart") == 0) {
-        if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(c, EMI_ERR_ARG, "sym_cpart must be -1 (plain order), 0 (by mesh size), 1, 2, 4 or 8");
-        c->sym_cpart = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_gblk") == 0) {
-        if (value < 0 || value > 64) return fail(c, EMI_ERR_ARG, "sym_gblk must be 0 (off) .. 64 instance groups per super-block");
-        c->sym_gblk = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_cx") == 0) {
-        if (value < 0 || value > 64) return fail(c, EMI_ERR_ARG, "sym_cx must be 0 (default) .. 64 column tiles per block");
-        c->sym_cx = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "sym_combine") == 0) { c->sym_combine = value != 0; return EMI_OK; }
-    if (strcmp(name, "sym_ksplit") == 0) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(c, EMI_ERR_ARG, "sym_ksplit must be 0 (by batch size), 1, 2, 4 or 8");
-        c->sym_ksplit = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "node_store") == 0) {
-        if (value < -1 || value > 3) return fail(c, EMI_ERR_ARG, "node_store must be -1 (by size), 0 (plain), 1 (write-through sc1), 2 (non-temporal) or 3 (nt sc1; the one-launch pass only)");
-        c->node_store = value;
-        return EMI_OK;
-    }
-    if (strcmp(name, "overlap_mode") == 0) {
-        if (value < 0 || value > 3) return fail(c, EMI_ERR_ARG, "overlap_mode must be 0 (by batch size), 1 (one stream), 2 (two streams) or 3 (one launch)");
-        c->overlap_mode = value;
+    for (const OptionRow& o : OPTIONS) {
+        if (strcmp(name, o.name) != 0) continue;
+        if (!o.accepts(value)) return fail(c, EMI_ERR_ARG, "%s", o.message);
+        c->*o.member = o.stored(value);
         return EMI_OK;
     }
     return fail(c, EMI_ERR_ARG, "unknown option '%s'", name);
@@ -1888,9 +1884,7 @@ int emi_plan_pass(emi_ctx_t c, int B, emi_pass_plan_t* out) {
     if (!c || !out || B < 1) return EMI_ERR_ARG;
     if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "emi_plan_pass: mesh and model must be set");
     memset(out, 0, sizeof *out);
-    const int Bkeep = c->B;
-    c->B = B;                                   // the policy reads the batch from the context (piece sizes, per-instance tables)
-    const int piece = (!c->f32 && overlapped_path(c)) ? plan_piece(c) : 0;
+    const int piece = (!c->f32 && overlapped_path(c)) ? plan_piece(c, B) : 0;
     const int first = piece > 0 ? piece : B;    // instances of the first launch
     out->piece = piece;
     out->tail = piece > 0 ? B % piece : 0;
@@ -1910,19 +1904,15 @@ int emi_plan_pass(emi_ctx_t c, int B, emi_pass_plan_t* out) {
         out->block_order = p.mfma_first;
         out->tiles16 = p.tiles16;
     }
-    c->B = Bkeep;
     return EMI_OK;
 }
 
 int emi_last_path(emi_ctx_t c, int* fused) {
     if (!c || !fused) return EMI_ERR_ARG;
-    const bool small = !c->f32 && c->B > 0 && c->B * c->ns <= c->small_rows && emi::defect_small_supported(c->B * c->ns) &&
-                       !pass_takes_small_batches(c);
-    *fused = (!small && overlapped_path(c)) ? 1 : 0;
+    *fused = choose_form(c, Launch{0, c->B}, EMI_EVAL_ALL).overlapped() ? 1 : 0;
     return EMI_OK;
 }
 
-/* name of the kernel that produced the defect rows in the last emi_eval_dev of this context (for reports) */
 int emi_debug_pass_roles(int nm, int nn, int order, int* out_role, int out_cap) {
     if (nm < 0 || nn < 0 || nm + nn < 1 || !out_role || out_cap < nm + nn) return EMI_ERR_ARG;
     for (int j = 0; j < nm + nn; ++j) {
@@ -1953,6 +1943,7 @@ int emi_debug_tile_order2(int ns, int B, int M, int sym_ct, int sym_cpart, int s
     return EMI_OK;
 }
 
+/* name of the kernel that produced the defect rows in the last emi_eval_dev of this context (for reports) */
 const char* emi_last_defect_kernel(emi_ctx_t c) {
     if (!c) return "";
     return c->last_defect_kernel.c_str();

@@ -471,6 +471,52 @@ def test_abi_error_paths(built):
     assert lib.emi_destroy(None) == 1
 
 
+# emi_set_option as include/emi355x.h documents it: name -> (an accepted value, values outside the range or set the header or the
+# message gives; empty where every integer is taken).  The "kkt_*" switches are process-wide, so their accepted value is the default.
+DOCUMENTED_OPTIONS = {
+    "overlap": (1, ()), "sym_ct": (0, (-1, 9)), "node_store": (-1, (-2, 4)), "sym_order": (1, ()),
+    "overlap_mode": (0, (-1, 4)), "sym_ksplit": (0, (-1, 3, 16)), "small_rows": (24, (-1,)), "sym_combine": (1, ()),
+    "sym_cpart": (0, (-2, 3, 16)), "sym_gblk": (0, (-1, 65)), "sym_cx": (0, (-1, 65)), "sym_nst": (3, (2, 5)),
+    "pass_order": (-1, ()), "slice": (0, (-16, 24)), "adj_fold_tile": (0, (-1, 3)), "sym_ablate": (0, ()),
+    "kkt_method": (1, (-1, 2)), "kkt_block_trsv": (1, ()), "kkt_primal_levels": (1, ()), "kkt_sticky_reg": (1, ()),
+    "kkt_cholesky": (2, (0, 3)), "kkt_chol_outer": (768, ()), "kkt_chol_diag": (2, ()), "kkt_chol_panel": (2, ()),
+    "kkt_debug": (0, ()), "kkt_batched_max_nodes": (256, ()),
+}
+# ... and the names the header does not list but bench.py, the tools and the other tests set
+OTHER_OPTIONS = {
+    "fused": (1, ()), "cu_split": (0, (-1, 1 << 20)), "f32_ring": (1, ()), "f32_ring_wgs": (2, ()), "f32_one_launch": (0, ()),
+    "cost_in_kernel": (1, ()), "sym_hs": (0, (-1, 3)), "sym_ctc": (0, (-1, 3)), "sym_bk": (0, (4, 32)),
+}
+
+
+def test_every_documented_option_is_taken_and_checked(built):
+    """Every option name include/emi355x.h documents for emi_set_option takes an accepted value; a value outside the documented range
+    or set is an argument error whose message names the option; a name nobody documents is an "unknown option"."""
+    import ctypes as C
+    import re
+    from etol_amd import _lib as L
+    lib = L.load()
+    header = open(os.path.join(ROOT, "include", "emi355x.h")).read()
+    doc = header[header.index("---- kernel selection"):header.index("int emi_set_option")]
+    named = set(re.findall(r'"([a-z0-9_]+)"', doc)) | set(re.findall(r'Option "([a-z0-9_]+)" \(emi_set_option\)', header))
+    assert named == set(DOCUMENTED_OPTIONS), named ^ set(DOCUMENTED_OPTIONS)    # the table above follows the header
+    ctx = C.c_void_p()
+    assert lib.emi_create(0, C.byref(ctx)) == 0
+    try:
+        for name, (good, bad) in {**DOCUMENTED_OPTIONS, **OTHER_OPTIONS}.items():
+            for v in bad:
+                assert lib.emi_set_option(ctx, name.encode(), v) == 1, (name, v)
+                assert name.encode() in lib.emi_last_error(ctx), (name, v, lib.emi_last_error(ctx))
+            assert lib.emi_set_option(ctx, name.encode(), good) == 0, (name, lib.emi_last_error(ctx))
+        for name in ("no_such_option", "kkt_no_such_option", "sym", "sym_ct2", ""):
+            assert lib.emi_set_option(ctx, name.encode(), 1) == 1, name
+            assert b"unknown option" in lib.emi_last_error(ctx), name
+        assert lib.emi_set_option(ctx, None, 1) == 1
+        assert lib.emi_set_option(None, b"sym_ct", 0) == 1
+    finally:
+        assert lib.emi_destroy(ctx) == 0
+
+
 def test_removed_cholesky_options_are_refused(built):
     """"kkt_cholesky" 0 (rocsolver_dpotrf behind a lock and a confirmation on a copy) and its "kkt_potrf_lock" are gone: the option
     takes 1 and 2, anything else is an argument error with a message; the lock is an unknown option."""

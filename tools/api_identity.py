@@ -1,0 +1,291 @@
+#!/usr/bin/env python3
+"""Does a change to the host side of the C ABI (csrc/emi_api.hip) leave the library as it was?  Run in two trees -- the parent
+commit's and the changed one, each with its own built library -- and compare what they write:
+
+   python tools/api_identity.py plan    OUT.json   emi_plan_pass (all fields) and emi_last_path over a grid; launches no kernel
+   python tools/api_identity.py results OUT.json   SHA-256 of what every launch form computes, the kernel name, launch counts
+   python tools/api_identity.py times   OUT.json   ms per default-dispatch pass at B = 1, 16, 128, 1024 (quadrotor, 1024 nodes)
+   python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case
+
+The library is the one of the tree the script lies in."""
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+# every threshold of plan_pass / plan_piece: 16-instance x 128-node tiles (last below, first above), then instances
+TILE_STEPS = [(32, 33), (48, 49), (127, 128), (143, 144), (207, 208), (383, 384), (767, 768), (1024, 1025)]
+INSTANCES = [1, 16, 64, 2048, 2049, 4096, 16384]
+FORCED = {"sym_ct": range(0, 9), "sym_ksplit": (0, 1, 2, 4, 8), "sym_bk": (0, 8, 16), "sym_ctc": (0, 1, 2), "sym_hs": (0, 1, 2),
+          "sym_nst": (3, 4), "sym_cpart": (-1, 0, 1, 2, 4, 8), "sym_gblk": (0, 1, 2, 4, 8, 64), "pass_order": (-1, 0, 1, 100, 125, 150),
+          "node_store": (-1, 0, 1, 2, 3), "overlap_mode": (0, 1, 2, 3), "slice": (0, 16, 256, 1024)}
+DEFAULTS = {"sym_nst": 3, "sym_cpart": 0, "pass_order": -1, "node_store": -1}
+
+
+def batches(M):
+    per = M // 128
+    out = set(INSTANCES)
+    for lo, _ in TILE_STEPS:
+        out.update((16 * (lo // per), 16 * (lo // per) + 1))      # the last batch within `lo` tiles and the first beyond
+    return sorted((b for b in out if b >= 1), reverse=True)        # (descending: the context's buffers are sized once)
+
+
+def plan_grid():
+    import etol_amd as E
+    from etol_amd import workloads as W
+    models = {"pointmass2": (E.MODEL_POINTMASS2D, ()), "quadrotor6": (E.MODEL_QUADROTOR2D, W.QUAD_PARAMS),
+              "fixedwing12": (E.MODEL_FIXEDWING12, W.FW_PARAMS)}
+    out = {}
+    for mname, (model, params) in models.items():
+        for M in (128, 256, 1024):
+            ev = E.Evaluator(0)
+            ev.set_mesh(M, 0.0, 2.0)
+            ev.set_model(model, params)
+            for opt, value in [(None, None)] + [(o, v) for o, vs in FORCED.items() for v in vs]:
+                if opt:
+                    ev.set_option(opt, value)
+                for B in batches(M):
+                    ev.set_batch(B)
+                    out[f"{mname} M={M} {opt}={value} B={B}"] = dict(ev.plan(B), last_path=int(ev.uses_fused_kernel))
+                if opt:
+                    ev.set_option(opt, DEFAULTS.get(opt, 0))
+            ev.close()
+    return out
+
+
+def sha(a):
+    import numpy as np
+    import torch
+    if isinstance(a, torch.Tensor):
+        a = a.cpu().numpy()
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def traced_quadrotor():
+    import ctypes as C
+    lib = C.CDLL(os.path.join(ROOT, "tests", "harness", "libetol_harness.so"))
+    lib.harness_traced_model_source.restype = C.c_char_p
+    return lib.harness_traced_model_source(0).decode()
+
+
+Q = dict(model="quad", M=1024)
+CASES = {
+    # fp64, the one-launch pass
+    "pass K slices": dict(Q, B=16), "pass unsplit": dict(Q, B=256), "pass 16-deep K tiles": dict(Q, B=128),
+    "pass 128-column tiles": dict(Q, B=64, opts=dict(sym_ct=6, sym_ksplit=1, sym_ctc=2)),
+    "pass halved K": dict(Q, B=64, opts=dict(sym_ksplit=1, sym_hs=2)),
+    "pass pointmass": dict(model="pm", M=256, B=16), "pass one instance": dict(Q, B=1),
+    # fp64, two kernels
+    **{f"two kernels mode {m} combine {sc} cost_in_kernel {ck}": dict(Q, B=32, opts=dict(overlap_mode=m, sym_ct=7, sym_ksplit=2, sym_combine=sc,
+                                                                                         cost_in_kernel=ck))
+       for m in (1, 2) for sc in (0, 1) for ck in (0, 1)},
+    "two kernels ring": dict(Q, B=256, opts=dict(overlap_mode=2, sym_ct=3)),
+    "skinny": dict(Q, B=2, opts=dict(overlap_mode=2)),
+    "sliced large batch": dict(model="quad", M=128, B=2320, paths=True), "slice option": dict(Q, B=64, opts=dict(slice=16), paths=True),
+    "delays": dict(model="quad", M=128, B=8, delays=(0, 1, 0.1)),
+    "run-time compiled": dict(model="rtc", M=1024, B=16), "run-time compiled two kernels": dict(model="rtc", M=1024, B=16, opts=dict(overlap_mode=2)),
+    "sequential": dict(Q, B=16, opts=dict(overlap=0)), "sequential 33 nodes": dict(model="quad", M=33, B=3),
+    "defect only": dict(Q, B=16, flags=2), "nodes only": dict(Q, B=16, flags=1), "no Jacobian": dict(Q, B=16, flags=7),
+    # fp32
+    "f32 ring": dict(model="fw", M=1024, B=16, f32=True), "f32 register-staged": dict(model="fw", M=1024, B=16, f32=True, opts=dict(f32_ring=0)),
+    "f32 one launch": dict(model="fw", M=512, B=64, f32=True, opts=dict(overlap_mode=3, f32_ring=0), atomics=True),
+    "f32 two streams": dict(model="fw", M=512, B=64, f32=True, opts=dict(overlap_mode=2), atomics=True),
+}
+
+
+def run_case(c):
+    import numpy as np
+    import torch
+    import etol_amd as E
+    import oracle_lib as O
+    from etol_amd import workloads as W
+    f32, M, B, flags = c.get("f32", False), c["M"], c["B"], c.get("flags", 3)
+    ev = E.Evaluator(0, f32=f32)
+    ev.set_mesh(M, 0.0, 20.0 if c["model"] == "fw" else 2.0)
+    if c["model"] == "rtc":
+        ev.set_model_source("TracedModel", traced_quadrotor(), 6, 2)
+    else:
+        ev.set_model(*{"quad": (E.MODEL_QUADROTOR2D, W.QUAD_PARAMS), "pm": (E.MODEL_POINTMASS2D, ()), "fw": (E.MODEL_FIXEDWING12, W.FW_PARAMS)}[c["model"]])
+    if c.get("delays"):
+        ev.set_delays(*c["delays"])
+    ev.set_batch(B)
+    gen = min(B, 16)
+    recs = None
+    if c["model"] == "fw":
+        X, U = W.fixedwing_batch(4, gen, M)
+    elif c["model"] == "pm":
+        X, U = W.pointmass_batch(1, gen, M)
+    else:
+        X, U, recs = W.quadrotor_batch(2, gen, M, 3 if c.get("paths") else 0)
+    rep = lambda a: np.concatenate([a] * (B // gen) + [a[:B % gen]])
+    X, U = rep(X), rep(U)[:, :ev.layout.nc - ev.n_delayed]
+    if f32:
+        X, U = (a.astype(np.float32).astype(np.float64) for a in (X, U))
+    if c.get("paths"):
+        recs = rep(recs)
+        recs[:, :, 1] += 0.001 * np.arange(B)[:, None]           # a table per instance: a piece must read its own
+        ev.set_path(recs, 0, 1)
+    for k, v in c.get("opts", {}).items():
+        ev.set_option(k, v)
+    lay = ev.layout
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if f32 else np.float64)).cuda()
+    dX, dU = dev(X), dev(U)
+    out = dict(last_path=int(ev.uses_fused_kernel))
+
+    def evaluate(tag):
+        outs = ev.alloc_outputs()
+        for t in outs:
+            t.zero_()
+        torch.cuda.synchronize()
+        ev.eval_dev(dX, dU, outs[0], outs[1] if flags & 1 else None, outs[2] if flags & 1 else None, flags)
+        ev.synchronize()
+        out[tag] = dict(RES=sha(outs[0]), VALS=sha(outs[1]), COST=sha(outs[2]), kernel=ev.last_defect_kernel)
+        return outs
+
+    outs = evaluate("eval_dev")
+    if c.get("atomics"):                    # float atomics from two roles: does one library agree with itself?  And with the oracle?
+        out["repeats"] = []
+        for _ in range(3):
+            evaluate("eval_dev_again")
+            out["repeats"].append(out["eval_dev_again"]["RES"])
+        sub = slice(0, 4)
+        rRES, rVALS, rCOST = O.evaluate(E.MODEL_FIXEDWING12, W.FW_PARAMS, M, (ev.tau, ev.w, ev.D), 0.0, 20.0, X[sub], U[sub])
+        got = [o.cpu().numpy().astype(np.float64) for o in outs]
+        scale = np.einsum("kj,bij->bik", np.abs(ev.D), np.abs(X[sub])) + np.abs(rRES) + 1.0
+        errs = dict(RES=float((np.abs(got[0][sub] - rRES) / scale).max()),
+                    VALS=float(max(np.abs(got[1][sub][:, e] - rVALS[:, e]).max() / (np.abs(rVALS[:, e]).max() + 1.0) for e in range(rVALS.shape[1]))),
+                    COST=float(np.abs(got[2][sub] - rCOST).max() / np.abs(rCOST).max()))
+        # the bounds of tests/test_gpu_parity.py::test_f32_pass_as_one_launch_matches_the_sequential_pair_and_the_oracle at M <= 512
+        out["oracle"] = dict(errs, bound=2e-6, within=all(v < 2e-6 for v in errs.values()))
+    ev.profile(1)
+    evaluate("eval_dev_profiled")
+    counts = ev.profile_read()
+    out["launch_counts"] = {k: v for k, v in counts.items() if not k.endswith("_ms")}
+    ev.profile(0)
+    if flags != 3:
+        ev.close()
+        return out
+    rng = np.random.default_rng(7)
+    lamF, lamC = rng.standard_normal((B, lay.ns, M)), rng.standard_normal((B, lay.np, M))
+    H = torch.zeros((B, lay.nhess, M), dtype=ev.dtype, device="cuda")
+    ev.hess_dev(dX, dU, dev(lamF), dev(lamC) if lay.np else None, 0.7, H)
+    ev.synchronize()
+    out["hess_dev"] = sha(H)
+    small = slice(0, min(B, 32))           # the host forms on a batch of their own (they stage through the context's buffers)
+    if B > 32:
+        ev.set_batch(32)
+        if c.get("paths"):
+            ev.set_path(recs[small], 0, 1)
+    hX, hU, hF, hC = X[small], U[small], lamF[small], lamC[small] if lay.np else None
+    hRES, hVALS, hCOST = ev.eval_host(hX, hU)
+    out["eval_host"] = dict(RES=sha(hRES), VALS=sha(hVALS), COST=sha(hCOST), kernel=ev.last_defect_kernel)
+    out["hess_host"] = sha(ev.hess_host(hX, hU, hF, hC, 0.7))
+    if not f32:
+        nf = lay.ns + lay.nc - ev.n_delayed
+        z = np.concatenate([hX, hU], axis=1)
+        zl, zu = z - 0.5 * rng.random(z.shape), z + 0.5 * rng.random(z.shape)
+        cl, cu = -np.ones(lay.np), np.ones(lay.np)
+        total = ev.n_delayed > 0
+        if B > 32:
+            ev.set_batch(B)
+            if c.get("paths"):
+                ev.set_path(recs, 0, 1)
+        G = torch.zeros((B, nf, M), dtype=torch.float64, device="cuda")
+        cert = torch.zeros((B, 6), dtype=torch.float64, device="cuda")
+        dzl, dzu = dev(np.concatenate([X, U], axis=1) - 0.25), dev(np.concatenate([X, U], axis=1) + 0.25)
+        args = (outs[1], dev(lamF), dev(lamC) if lay.np else None, 0.7)
+        if total:
+            Gdel = torch.zeros((B, ev.n_delayed, M), dtype=torch.float64, device="cuda")
+            ev.lagr_grad_total_dev(*args, G, Gdel)
+            ev.synchronize()
+            out["lagr_grad_total_dev"] = dict(G=sha(G), Gdel=sha(Gdel))
+            ev.kkt_certificate_total_dev(dX, dU, outs[0], *args, dzl, dzu, cl, cu, cert, G, Gdel)
+            ev.synchronize()
+            out["kkt_certificate_total_dev"] = dict(cert=sha(cert), G=sha(G), Gdel=sha(Gdel))
+        else:
+            ev.lagr_grad_dev(*args, G)
+            ev.synchronize()
+            out["lagr_grad_dev"] = sha(G)
+            ev.kkt_certificate_dev(dX, dU, outs[0], *args, dzl, dzu, cl, cu, cert, G)
+            ev.synchronize()
+            out["kkt_certificate_dev"] = dict(cert=sha(cert), G=sha(G))
+        if B > 32:
+            ev.set_batch(32)
+            if c.get("paths"):
+                ev.set_path(recs[small], 0, 1)
+        if total:
+            out["lagr_grad_total_host"] = [sha(a) for a in ev.lagr_grad_total_host(hVALS, hF, hC, 0.7)]
+            out["kkt_certificate_total_host"] = [sha(a) for a in ev.kkt_certificate_total_host(hX, hU, hF, hC, zl, zu, cl, cu, 0.7)]
+        else:
+            out["lagr_grad_host"] = sha(ev.lagr_grad_host(hVALS, hF, hC, 0.7))
+            out["kkt_certificate_host"] = [sha(a) for a in ev.kkt_certificate_host(hX, hU, hF, hC, zl, zu, cl, cu, 0.7)]
+    ev.close()
+    return out
+
+
+def times():
+    import torch
+    import etol_amd as E
+    from etol_amd import workloads as W
+    out = {}
+    for B in (1, 16, 128, 1024):
+        ev = E.Evaluator(0)
+        ev.set_mesh(1024, 0.0, 2.0)
+        ev.set_model(E.MODEL_QUADROTOR2D, W.QUAD_PARAMS)
+        ev.set_batch(B)
+        X, U, _ = W.quadrotor_batch(2, min(B, 16), 1024, 0)
+        dX, dU = (torch.from_numpy(a).cuda().repeat((B + 15) // 16, 1, 1)[:B].contiguous() for a in (X, U))
+        outs = ev.alloc_outputs()
+        import ctypes as C
+        p = [C.c_void_p(t.data_ptr()) for t in (dX, dU, *outs)]
+        call = lambda: ev.lib.emi_eval_dev(ev.ctx, *p, 3)
+        for _ in range(2000):
+            call()
+        ev.synchronize()
+        n, ms = 2000, 0.0
+        while ms < 1100.0:                  # enough passes to fill a second
+            n = int(n * max(1.5, 1300.0 / ms)) if ms else n
+            ev.timer_start()
+            for _ in range(n):
+                call()
+            ms = ev.timer_stop()
+        out[str(B)] = dict(passes=n, ms_per_pass=ms / n, kernel=ev.last_defect_kernel)
+        ev.close()
+    return out
+
+
+def compare(pa, br):
+    report = dict(equal=[], different=[], self_disagreeing=[])
+    for name in sorted(set(pa) | set(br)):
+        a, b = pa.get(name), br.get(name)
+        unstable = isinstance(a, dict) and "repeats" in a and len(set(a["repeats"]) | {a["eval_dev"]["RES"]}) > 1
+        if unstable:        # the parent does not reproduce its own bits here: the oracle decides, at the existing test's bounds
+            strip = lambda d: {k: v for k, v in d.items() if k in ("last_path", "launch_counts", "oracle")}
+            ok = a["oracle"]["within"] and b["oracle"]["within"] and strip(a)["launch_counts"] == strip(b)["launch_counts"]
+            report["self_disagreeing"].append(dict(case=name, parent=a, branch=b, both_within_oracle_bound=ok))
+            if not ok:
+                report["different"].append(name)
+        elif a == b:
+            report["equal"].append(name)
+        else:
+            report["different"].append(name)
+    report["verdict"] = "identical" if not report["different"] else "DIFFERENT"
+    return report
+
+
+if __name__ == "__main__":
+    mode = sys.argv[1]
+    if mode == "compare":
+        pa, br = (json.load(open(f)) for f in sys.argv[2:4])
+        rep = compare(pa, br)
+        print(json.dumps({k: (v if k == "verdict" or k == "self_disagreeing" else len(v)) for k, v in rep.items()} | {"different": rep["different"][:20]}))
+        if len(sys.argv) > 4:
+            json.dump(dict(rep, cases={k: dict(parent=pa.get(k), branch=br.get(k)) for k in sorted(set(pa) | set(br))}), open(sys.argv[4], "w"), indent=1)
+        sys.exit(0 if rep["verdict"] == "identical" else 1)
+    res = plan_grid() if mode == "plan" else times() if mode == "times" else {name: run_case(c) for name, c in CASES.items()}
+    json.dump(res, open(sys.argv[2], "w"), indent=1 if mode != "plan" else None, sort_keys=True)
+    print(mode, len(res), "entries ->", sys.argv[2], hashlib.sha256(json.dumps(res, sort_keys=True).encode()).hexdigest()[:16])
