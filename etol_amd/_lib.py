@@ -66,6 +66,10 @@ SYMBOLS = {
     "emi_set_model_source": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, _I, C.c_int, _D, C.c_int, C.c_int]),
     "emi_check_model_source": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "emi_kkt_factor": (C.c_int, [_P, _D, _D, C.POINTER(C.c_ubyte), C.c_double, C.POINTER(C.c_int)]),
+    "emi_kkt_factor_dev": (C.c_int, [_P, _P, _P, _P, C.c_double, C.POINTER(C.c_int)]),
+    "emi_kkt_blocks_rows": (C.c_int, [_P, C.c_int, _I, _I, _I]),
+    "emi_kkt_blocks_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "emi_kkt_blocks_host": (C.c_int, [_P, _D, _D, _D, _D, C.POINTER(C.c_ubyte), C.c_double, _D, _D, C.c_int, _I, _I, _D, _D, _D]),
     "emi_kkt_solve": (C.c_int, [_P, _D, C.c_int]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),

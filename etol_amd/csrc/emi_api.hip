@@ -120,6 +120,15 @@ struct emi_ctx_s {
     DevBuf d_adj_G;             // G of a certificate call that does not return it
     DevBuf d_adj_op;            // [B][ns][M] operator term of the side-by-side form (large batches)
     DevBuf s_G, s_cert, s_zl, s_zu, s_Gdel;
+    // node blocks of the Newton step (emi_kkt_blocks_*): the (variable, VALS entry) pairs of the path rows, the per-entry term
+    // lists built from them (uploaded once per list) and the workspace of the kernels, grown on demand
+    bool blk_rows_set = false;          // emi_kkt_blocks_rows was called (else: the layout's default for table rows)
+    std::vector<int> blk_row_ptr, blk_var, blk_entry;
+    std::vector<int> blk_key;           // what the uploaded term lists were built from ({} = nothing uploaded)
+    emi::DeviceArray<int> blk_term_ptr, blk_term_row, blk_term_ea, blk_term_eb, blk_flag, blk_list, blk_nflag, blk_cnt;
+    emi::DeviceArray<double> blk_tdelta, blk_tvec, blk_tworst;
+    int blk_generic = 0;                // "blocks_generic": 1 = the run-time-nv assembly kernel also where a templated one exists
+    DevBuf sb_H, sb_V, sb_Sg, sb_St, sb_fx, sb_Qx, sb_Q, sb_cnt, sb_node, sb_delta, sb_vec, sb_worst;   // host-form staging
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;
     int profile = 0;          // emi_profile_enable level (0 off)
@@ -1618,19 +1627,197 @@ int emi_kkt_certificate_total_host(emi_ctx_t c, const double* X, const double* U
     return kkt_certificate_host(c, true, X, U, LamF, LamC, sigma, zl, zu, nsets, cl, cu, cert, G, Gdel);
 }
 
-int emi_kkt_factor(emi_ctx_t c, const double* Qblk, const double* Jblk, const unsigned char* fixed, double dc,
-                   int* info) {
+// emi_kkt_factor / emi_kkt_factor_dev: the blocks in host or in device memory, everything else the same
+static int kkt_factor_from(emi_ctx_t c, const char* what, const void* Qblk, const void* Jblk, const void* fixed, double dc, int* info,
+                           bool blocks_on_device) {
     if (!c) return EMI_ERR_ARG;
-    if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "emi_kkt_factor: mesh and model must be set");
-    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_kkt_factor: f64 contexts only");
-    if (c->points_only) return fail(c, EMI_ERR_STATE, "emi_kkt_factor: the mesh has no differentiation matrix");
-    if (!Qblk || !Jblk || !fixed || !info || !(dc >= 0.0)) return fail(c, EMI_ERR_ARG, "emi_kkt_factor: bad argument");
+    if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "%s: mesh and model must be set", what);
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: f64 contexts only", what);
+    if (c->points_only) return fail(c, EMI_ERR_STATE, "%s: the mesh has no differentiation matrix", what);
+    if (!Qblk || !Jblk || !fixed || !info || !(dc >= 0.0)) return fail(c, EMI_ERR_ARG, "%s: bad argument", what);
     HIP_TRY(c, hipSetDevice(c->device));
     std::string err;
-    const int st = emi::kkt_factor(&c->kkt, c->stream, (const double*)c->d_D.p, c->M, c->ns, c->ns + c->nc, Qblk, Jblk,
-                                   fixed, dc, c->kkt_method, info, &err);
+    const int st = emi::kkt_factor(&c->kkt, c->stream, (const double*)c->d_D.p, c->M, c->ns, c->ns + c->nc, (const double*)Qblk,
+                                   (const double*)Jblk, (const unsigned char*)fixed, dc, c->kkt_method, info, &err, blocks_on_device);
     if (st) c->err = err;
     return st;
+}
+
+int emi_kkt_factor(emi_ctx_t c, const double* Qblk, const double* Jblk, const unsigned char* fixed, double dc,
+                   int* info) {
+    return kkt_factor_from(c, "emi_kkt_factor", Qblk, Jblk, fixed, dc, info, false);
+}
+
+int emi_kkt_factor_dev(emi_ctx_t c, const void* dQblk, const void* dJblk, const void* dFixed, double dc, int* info) {
+    return kkt_factor_from(c, "emi_kkt_factor_dev", dQblk, dJblk, dFixed, dc, info, true);
+}
+
+// ---- node blocks of the Newton step: assembly, screen and eigen-fix over [instance][node] (emi_kkt_blocks.hip) -----------------
+int emi_kkt_blocks_rows(emi_ctx_t c, int np, const int* row_ptr, const int* var, const int* entry) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->model < 0) return fail(c, EMI_ERR_STATE, "emi_kkt_blocks_rows: the model must be set");
+    if (np < 0 || !row_ptr || row_ptr[0] != 0) return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_rows: bad argument");
+    const int nv = c->ns + c->nc, nvals = nvals_of(c);
+    for (int j = 0; j < np; ++j)
+        if (row_ptr[j + 1] < row_ptr[j]) return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_rows: row_ptr decreases at row %d", j);
+    const int n = row_ptr[np];
+    if (n > 0 && (!var || !entry)) return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_rows: bad argument");
+    for (int a = 0; a < n; ++a)
+        if (var[a] < 0 || var[a] >= nv || entry[a] < 0 || entry[a] >= nvals)
+            return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_rows: pair %d (variable %d, VALS entry %d) is out of range (%d variables, %d entries)",
+                        a, var[a], entry[a], nv, nvals);
+    c->blk_row_ptr.assign(row_ptr, row_ptr + np + 1);
+    c->blk_var.assign(var, var + n);
+    c->blk_entry.assign(entry, entry + n);
+    c->blk_rows_set = true;
+    c->blk_key.clear();
+    return EMI_OK;
+}
+
+namespace {
+
+// the per-entry term lists of the assembly kernel on the device: for every packed entry of the block, the products
+// SigT[row] VALS[ea] VALS[eb] that the host loop adds to it, in that loop's order (rows ascending, pairs (a, b <= a) in list order)
+int blocks_terms(emi_ctx_t c, const char* what) {
+    const int nv = c->ns + c->nc, nh = nv * (nv + 1) / 2, np = np_total(c), nvals = nvals_of(c);
+    std::vector<int> ptr, var, ent;
+    if (c->blk_rows_set) {
+        if ((int)c->blk_row_ptr.size() != np + 1)
+            return fail(c, EMI_ERR_STATE, "%s: the row list (emi_kkt_blocks_rows) has %d rows, the context %d", what, (int)c->blk_row_ptr.size() - 1, np);
+        ptr = c->blk_row_ptr; var = c->blk_var; ent = c->blk_entry;
+        for (size_t a = 0; a < var.size(); ++a)         // (the model may have changed since the list was given)
+            if (var[a] >= nv || ent[a] >= nvals) return fail(c, EMI_ERR_STATE, "%s: the row list does not fit the context's layout any more", what);
+    } else {
+        if (c->np_model > 0)
+            return fail(c, EMI_ERR_STATE, "%s: the context has traced path rows and no row list (emi_kkt_blocks_rows)", what);
+        ptr.push_back(0);
+        for (int j = 0; j < c->np; ++j) {
+            var.push_back(c->px); ent.push_back(c->ns * nv + 2 * j);
+            var.push_back(c->py); ent.push_back(c->ns * nv + 2 * j + 1);
+            ptr.push_back((int)var.size());
+        }
+    }
+    std::vector<int> key = {nv, np, nvals, (int)c->blk_rows_set};
+    key.insert(key.end(), ptr.begin(), ptr.end());
+    key.insert(key.end(), var.begin(), var.end());
+    key.insert(key.end(), ent.begin(), ent.end());
+    if (key == c->blk_key) return EMI_OK;
+    std::vector<std::vector<int>> per(nh);      // (row, ea, eb) triples of every entry
+    for (int j = 0; j < np; ++j)
+        for (int a = ptr[j]; a < ptr[j + 1]; ++a)
+            for (int b = ptr[j]; b <= a; ++b) {
+                const int hi = std::max(var[a], var[b]), lo = std::min(var[a], var[b]);
+                std::vector<int>& t = per[hi * (hi + 1) / 2 + lo];
+                t.push_back(j); t.push_back(ent[a]); t.push_back(ent[b]);
+            }
+    std::vector<int> tp(nh + 1, 0), tr, ta, tb;
+    for (int e = 0; e < nh; ++e) {
+        for (size_t i = 0; i < per[e].size(); i += 3) { tr.push_back(per[e][i]); ta.push_back(per[e][i + 1]); tb.push_back(per[e][i + 2]); }
+        tp[e + 1] = (int)tr.size();
+    }
+    const size_t nt = std::max<size_t>(tr.size(), 1);
+    tr.resize(nt); ta.resize(nt); tb.resize(nt);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // a launch in flight may still read the old lists
+    HIP_TRY(c, c->blk_term_ptr.reserve(tp.size()));
+    HIP_TRY(c, c->blk_term_row.reserve(nt));
+    HIP_TRY(c, c->blk_term_ea.reserve(nt));
+    HIP_TRY(c, c->blk_term_eb.reserve(nt));
+    HIP_TRY(c, hipMemcpyAsync(c->blk_term_ptr.p, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->blk_term_row.p, tr.data(), nt * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->blk_term_ea.p, ta.data(), nt * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->blk_term_eb.p, tb.data(), nt * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (the sources are locals)
+    c->blk_key = key;
+    return EMI_OK;
+}
+
+int blocks_check(emi_ctx_t c, const char* what) {
+    if (c->M <= 0 || c->model < 0 || c->B <= 0) return fail(c, EMI_ERR_STATE, "%s: mesh, model and batch must be set", what);
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: f64 contexts only", what);
+    if (c->ns + c->nc > 16) return fail(c, EMI_ERR_UNSUPPORTED, "%s: node blocks of up to 16 variables (this model has %d)", what, c->ns + c->nc);
+    return EMI_OK;
+}
+
+}  // namespace
+
+int emi_kkt_blocks_dev(emi_ctx_t c, const void* dH, const void* dVALS, const void* dSigma, const void* dSigT, const void* dFixed,
+                       double dw_shift, void* dQexact, void* dQ, int max_mods, void* dCount, void* dNode, void* dDelta, void* dVec,
+                       void* dWorst) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(blocks_check(c, "emi_kkt_blocks_dev"));
+    const int nv = c->ns + c->nc, np = np_total(c);
+    if (!dH || !dVALS || !dSigma || !dFixed || !dQ || !dCount || !dWorst || max_mods < 0 || (np > 0 && !dSigT) ||
+        (max_mods > 0 && (!dNode || !dDelta || !dVec)) || !(dw_shift >= 0.0))
+        return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_dev: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    EMI_TRY(blocks_terms(c, "emi_kkt_blocks_dev"));
+    const size_t BM = (size_t)c->B * c->M;
+    HIP_TRY(c, c->blk_flag.reserve(BM));
+    HIP_TRY(c, c->blk_list.reserve(BM));
+    HIP_TRY(c, c->blk_cnt.reserve(BM));
+    HIP_TRY(c, c->blk_nflag.reserve((size_t)c->B));
+    HIP_TRY(c, c->blk_tworst.reserve(BM));
+    HIP_TRY(c, c->blk_tdelta.reserve(BM * nv));
+    // (room for EVERY block failing with all nv eigenvalues negative: how many fail is known on the device only, and a host
+    //  round trip to size it is what this call avoids.  B M nv^2 doubles: 34 MB at 64 x 1024 nodes x 8, 2 GiB at 1024 x 1024 x 16)
+    HIP_TRY(c, c->blk_tvec.reserve(BM * nv * nv));
+    emi::BlocksArgs a{};
+    a.H = (const double*)dH; a.VALS = (const double*)dVALS; a.Sigma = (const double*)dSigma; a.SigT = (const double*)dSigT;
+    a.fixed = (const unsigned char*)dFixed; a.dw_shift = dw_shift; a.Qexact = (double*)dQexact; a.Q = (double*)dQ;
+    a.max_mods = max_mods; a.count = (int*)dCount; a.node = (int*)dNode; a.delta = (double*)dDelta; a.vec = (double*)dVec;
+    a.worst = (double*)dWorst;
+    a.B = c->B; a.M = c->M; a.nv = nv; a.np = np; a.nvals = nvals_of(c); a.generic = c->blk_generic;
+    a.term_ptr = c->blk_term_ptr.p; a.term_row = c->blk_term_row.p; a.term_ea = c->blk_term_ea.p; a.term_eb = c->blk_term_eb.p;
+    a.flag = c->blk_flag.p; a.list = c->blk_list.p; a.nflag = c->blk_nflag.p; a.cnt = c->blk_cnt.p;
+    a.tdelta = c->blk_tdelta.p; a.tvec = c->blk_tvec.p; a.tworst = c->blk_tworst.p;
+    HIP_TRY(c, emi::launch_kkt_blocks(a, c->stream));
+    return EMI_OK;
+}
+
+int emi_kkt_blocks_host(emi_ctx_t c, const double* H, const double* VALS, const double* Sigma, const double* SigT,
+                        const unsigned char* fixed, double dw_shift, double* Qexact, double* Q, int max_mods, int* count, int* node,
+                        double* delta, double* vec, double* worst) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(blocks_check(c, "emi_kkt_blocks_host"));
+    const size_t B = (size_t)c->B, M = (size_t)c->M, nv = (size_t)(c->ns + c->nc), nh = nv * (nv + 1) / 2, np = (size_t)np_total(c);
+    if (!H || !VALS || !Sigma || !fixed || !Q || !count || !worst || max_mods < 0 || (np > 0 && !SigT) ||
+        (max_mods > 0 && (!node || !delta || !vec)))
+        return fail(c, EMI_ERR_ARG, "emi_kkt_blocks_host: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t mm = (size_t)max_mods;
+    EMI_TRY(upload_bytes(c, c->sb_H, H, B * nh * M * 8));
+    EMI_TRY(upload_bytes(c, c->sb_V, VALS, B * nvals_of(c) * M * 8));
+    EMI_TRY(upload_bytes(c, c->sb_Sg, Sigma, B * nv * M * 8));
+    if (np) EMI_TRY(upload_bytes(c, c->sb_St, SigT, B * np * M * 8));
+    EMI_TRY(upload_bytes(c, c->sb_fx, fixed, B * nv * M));
+    EMI_TRY(ensure(c, c->sb_Qx, B * nh * M * 8));
+    EMI_TRY(ensure(c, c->sb_Q, B * nh * M * 8));
+    EMI_TRY(ensure(c, c->sb_cnt, B * sizeof(int)));
+    EMI_TRY(ensure(c, c->sb_worst, B * 8));
+    EMI_TRY(ensure(c, c->sb_node, std::max<size_t>(B * mm, 1) * sizeof(int)));
+    EMI_TRY(ensure(c, c->sb_delta, std::max<size_t>(B * mm, 1) * 8));
+    EMI_TRY(ensure(c, c->sb_vec, std::max<size_t>(B * mm * nv, 1) * 8));
+    EMI_TRY(emi_kkt_blocks_dev(c, c->sb_H.p, c->sb_V.p, c->sb_Sg.p, np ? c->sb_St.p : nullptr, c->sb_fx.p, dw_shift,
+                               Qexact ? c->sb_Qx.p : nullptr, c->sb_Q.p, max_mods, c->sb_cnt.p, c->sb_node.p, c->sb_delta.p, c->sb_vec.p,
+                               c->sb_worst.p));
+    auto down = [&](void* dst, const DevBuf& src, size_t bytes) {
+        return !dst || !bytes ? hipSuccess : hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    };
+    HIP_TRY(c, down(Qexact, c->sb_Qx, B * nh * M * 8));
+    HIP_TRY(c, down(Q, c->sb_Q, B * nh * M * 8));
+    HIP_TRY(c, down(count, c->sb_cnt, B * sizeof(int)));
+    HIP_TRY(c, down(worst, c->sb_worst, B * 8));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // only what the kernels wrote: the first min(count, max_mods) entries of every instance
+    for (size_t b = 0; b < B && mm > 0; ++b) {
+        const size_t n = std::min<size_t>((size_t)std::max(count[b], 0), mm);
+        if (n == 0) continue;
+        HIP_TRY(c, hipMemcpyAsync(node + b * mm, (const int*)c->sb_node.p + b * mm, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(delta + b * mm, (const double*)c->sb_delta.p + b * mm, n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(vec + b * mm * nv, (const double*)c->sb_vec.p + b * mm * nv, n * nv * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EMI_OK;
 }
 
 int emi_kkt_lowrank(emi_ctx_t c, int r, const int* node, const double* vec, const double* delta, int* exact) {
@@ -1858,6 +2045,11 @@ int emi_set_option(emi_ctx_t c, const char* name, int value) {
             HIP_TRY(c, hipExtStreamCreateWithCUMask(&c->s_node, words, m2.data()));
             if (!c->ev_join2) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
         }
+        return EMI_OK;
+    }
+    if (strcmp(name, "blocks_generic") == 0) {      // emi_kkt_blocks_*: the run-time-nv assembly kernel also where a templated one exists
+        if (value != 0 && value != 1) return fail(c, EMI_ERR_ARG, "blocks_generic must be 0 or 1");
+        c->blk_generic = value;
         return EMI_OK;
     }
     if (strcmp(name, "kkt_method") == 0) {

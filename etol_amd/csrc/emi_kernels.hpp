@@ -94,6 +94,27 @@ hipError_t launch_adjoint_nodes(const AdjointArgs& a, hipStream_t s);
 hipError_t launch_adjoint_add(const double* dGop, double* dG, int B, int ns, int nv, int M, hipStream_t s);
 hipError_t launch_kkt_certificate(const CertArgs& a, hipStream_t s);
 
+// node blocks of the Newton step, assembled and made positive definite over [instance][node] (emi_kkt_blocks.hip)
+struct BlocksArgs {
+    const double *H, *VALS, *Sigma, *SigT;      // [B][nh][M], [B][nvals][M], [B][nv][M], [B][np][M]
+    const unsigned char* fixed;                 // [B][nv][M]
+    double dw_shift;
+    double *Qexact, *Q;                         // [B][nh][M]; Qexact may be null
+    int max_mods;
+    int* count;                                 // [B] recorded pairs (the true number, also beyond max_mods)
+    int* node;                                  // [B][max_mods]
+    double *delta, *vec, *worst;                // [B][max_mods], [B][max_mods][nv], [B]
+    int B, M, nv, np, nvals;
+    int generic;                                // 1: the run-time-nv assembly kernel whatever nv is
+    // path-row terms of every packed entry e, in row order then pair order: Q[e] += SigT[row] VALS[ea] VALS[eb]
+    const int *term_ptr, *term_row, *term_ea, *term_eb;
+    // workspace: [B][M] screen flags, flagged nodes (ascending), their number [B], pairs per flagged node; per flagged node the
+    // pairs in eigenvalue order [B][M][nv] / [B][M][nv][nv] and the node's worst shift [B][M]
+    int *flag, *list, *nflag, *cnt;
+    double *tdelta, *tvec, *tworst;
+};
+hipError_t launch_kkt_blocks(const BlocksArgs& a, hipStream_t s);
+
 // model programs compiled at run time (emi_rtc.hip); the int results are EMI_* status codes
 struct RtcModel;
 int rtc_check(bool f32, const char* struct_name, const char* source, int ns, int nc, int npath, int pw, std::string* log);
@@ -114,7 +135,8 @@ hipError_t rtc_launch_nodes_nt(RtcModel* m, const NodeArgs<double>& a, hipStream
 // Newton step on the device (emi_kkt.hip)
 struct KktWorkspace;
 int kkt_factor(KktWorkspace** w, hipStream_t stream, const double* dD, int M, int ns, int nv, const double* Qblk,
-               const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err);
+               const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err,
+               bool blocks_on_device = false);      // Qblk, Jblk, fixed in device memory (copied on `stream`)
 int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs, std::string* err);
 bool kkt_set_option(const char* name, int value);   // process-wide diagnostics of the factorisation ("kkt_cholesky", ...)
 int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* node, const double* vec, const double* delta,

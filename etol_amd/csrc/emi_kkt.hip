@@ -1205,12 +1205,14 @@ int ws_prepare(KktWorkspace* w, hipStream_t stream, const double* dD, int M, int
     return EMI_OK;
 }
 
-// the caller's node blocks (host) into the prepared workspace
-int upload_blocks(KktWorkspace* w, hipStream_t stream, const double* Qblk, const double* Jblk, const unsigned char* fixed, std::string* err) {
+// the caller's node blocks (host memory, or device memory: emi_kkt_factor_dev) into the prepared workspace
+int upload_blocks(KktWorkspace* w, hipStream_t stream, const double* Qblk, const double* Jblk, const unsigned char* fixed, std::string* err,
+                  bool on_device = false) {
     const size_t M = (size_t)w->M, nh = (size_t)w->nv * (w->nv + 1) / 2;
-    KKT_HIP(hipMemcpyAsync(w->Q.p, Qblk, nh * M * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->J.p, Jblk, (size_t)w->ns * w->nv * M * sizeof(double), hipMemcpyHostToDevice, stream));
-    KKT_HIP(hipMemcpyAsync(w->fixed.p, fixed, (size_t)w->nv * M, hipMemcpyHostToDevice, stream));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    KKT_HIP(hipMemcpyAsync(w->Q.p, Qblk, nh * M * sizeof(double), kind, stream));
+    KKT_HIP(hipMemcpyAsync(w->J.p, Jblk, (size_t)w->ns * w->nv * M * sizeof(double), kind, stream));
+    KKT_HIP(hipMemcpyAsync(w->fixed.p, fixed, (size_t)w->nv * M, kind, stream));
     return EMI_OK;
 }
 
@@ -1318,7 +1320,7 @@ void kkt_mesh_changed(KktWorkspace* w) {
 
 // Returns an EMI_* status; *info = 0 factorised, > 0 exactly singular (zero pivot at that position).
 int kkt_factor(KktWorkspace** pw, hipStream_t stream, const double* dD, int M, int ns, int nv, const double* Qblk,
-               const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err) {
+               const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err, bool blocks_on_device) {
     const int N = (nv + ns) * M;
     if (!*pw) *pw = new KktWorkspace();
     KktWorkspace* w = *pw;
@@ -1329,7 +1331,7 @@ int kkt_factor(KktWorkspace** pw, hipStream_t stream, const double* dD, int M, i
     const int npairs = ns * (ns + 1) / 2;
     if (int st = ws_prepare(w, stream, dD, M, ns, nv, dc, schur, batched ? npairs : 1, err)) return st;
     KKT_RB(rocblas_set_stream(w->handle, stream));
-    if (int st = upload_blocks(w, stream, Qblk, Jblk, fixed, err)) return st;
+    if (int st = upload_blocks(w, stream, Qblk, Jblk, fixed, err, blocks_on_device)) return st;
     if (schur) {
         const size_t md = (size_t)ns * M;
         KKT_HIP(hipMemsetAsync(w->flag.p, 0, sizeof(int), stream));

@@ -309,6 +309,53 @@ class Evaluator:
                                          float(dc), C.byref(info)), "emi_kkt_factor")
         return info.value
 
+    def kkt_factor_dev(self, Qblk, Jblk, fixed, dc=0.0):
+        """kkt_factor on device tensors (Qblk [nhess][M] and Jblk [>= ns*nv][M] float64, fixed [nv*M] uint8); returns info."""
+        info = C.c_int(-1)
+        self._ck(self.lib.emi_kkt_factor_dev(self.ctx, C.c_void_p(Qblk.data_ptr()), C.c_void_p(Jblk.data_ptr()),
+                                             C.c_void_p(fixed.data_ptr()), float(dc), C.byref(info)), "emi_kkt_factor_dev")
+        return info.value
+
+    # ---- node blocks of the Newton step: assembly, Cholesky screen, eigen-fix (emi_kkt_blocks_*) ------------------------
+    def kkt_blocks_rows(self, rows):
+        """rows: per path row a list of (variable, VALS entry) pairs"""
+        ptr, var, ent = [0], [], []
+        for r in rows:
+            var += [int(v) for v, _ in r]
+            ent += [int(e) for _, e in r]
+            ptr.append(len(var))
+        ia = lambda a: (C.c_int * max(len(a), 1))(*a)
+        self._ck(self.lib.emi_kkt_blocks_rows(self.ctx, len(rows), ia(ptr), ia(var), ia(ent)), "emi_kkt_blocks_rows")
+
+    def kkt_blocks_dev(self, H, VALS, Sigma, SigT, fixed, dw_shift, Q, max_mods, count, node, delta, vec, worst, Qexact=None):
+        """Device tensors in the layouts of include/emi355x.h (SigT, Qexact, and with max_mods 0 node / delta / vec may be None);
+        asynchronous on the context's stream."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self.lib.emi_kkt_blocks_dev(self.ctx, ptr(H), ptr(VALS), ptr(Sigma), ptr(SigT), ptr(fixed), float(dw_shift), ptr(Qexact),
+                                             ptr(Q), int(max_mods), ptr(count), ptr(node), ptr(delta), ptr(vec), ptr(worst)),
+                 "emi_kkt_blocks_dev")
+
+    def kkt_blocks_host(self, H, VALS, Sigma, SigT, fixed, dw_shift=0.0, max_mods=None):
+        """numpy in / numpy out: dict Qexact, Q [B][nhess][M], count [B], node [B][max_mods], delta, vec [B][max_mods][nv], worst [B]
+        (max_mods defaults to nv * M: every pair fits; entries beyond count keep -1 / nan)."""
+        lay = self.layout
+        nv = lay.ns + lay.nc
+        mm = nv * lay.M if max_mods is None else int(max_mods)
+        H, VALS, Sigma = (np.ascontiguousarray(a, dtype=np.float64) for a in (H, VALS, Sigma))
+        SigT = np.ascontiguousarray(SigT if SigT is not None else np.zeros((lay.B, 0, lay.M)), dtype=np.float64)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        assert H.shape == (lay.B, lay.nhess, lay.M) and VALS.shape == (lay.B, lay.nvals, lay.M) and Sigma.shape == (lay.B, nv, lay.M)
+        assert SigT.shape == (lay.B, lay.np, lay.M) and fixed.shape == (lay.B, nv, lay.M)
+        out = dict(Qexact=np.zeros_like(H), Q=np.zeros_like(H), count=np.zeros(lay.B, dtype=np.int32),
+                   node=np.full((lay.B, mm), -1, dtype=np.int32), delta=np.full((lay.B, mm), np.nan),
+                   vec=np.full((lay.B, mm, nv), np.nan), worst=np.zeros(lay.B))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._ck(self.lib.emi_kkt_blocks_host(self.ctx, _dp(H), _dp(VALS), _dp(Sigma), _dp(SigT) if SigT.size else None,
+                                              fixed.ctypes.data_as(C.POINTER(C.c_ubyte)), float(dw_shift), _dp(out["Qexact"]), _dp(out["Q"]),
+                                              mm, ip(out["count"]), ip(out["node"]) if mm else None, _dp(out["delta"]) if mm else None,
+                                              _dp(out["vec"]) if mm else None, _dp(out["worst"])), "emi_kkt_blocks_host")
+        return out
+
     def kkt_lowrank(self, node, vec, delta):
         """K = K~ - sum delta_c u_c u_c^T; returns True iff K has the inertia of K~ (solves are then with K)."""
         node = np.ascontiguousarray(node, dtype=np.int32)

@@ -100,8 +100,76 @@ struct eMI355X::Device : public mi355x::NlpEvaluator, public mi355x::KktBackend 
     int nodes = 0;                       // mesh size the context holds (configureDevice)
     std::string installed_source;        // text of the traced model whose code object is loaded in ctx ("" = none)
     bool installed_maximize = false;     // ... and the objective sign it was installed with
+    // device memory of factor_terms (Alg::node_blocks = "device"), grown on demand
+    struct DevMem {
+        void* p = nullptr;
+        size_t cap = 0;
+    };
+    enum { MH, MV, MSG, MST, MFX, MQX, MQ, MCNT, MNODE, MDELTA, MVEC, MWORST, NMEM };
+    DevMem mem[NMEM];
+    std::vector<std::vector<std::pair<int, int>>> rows_sent;    // the row list the context holds (emi_kkt_blocks_rows)
+    bool rows_valid = false;
     ~Device() override {
+        for (DevMem& m : mem)
+            if (m.p) (void)emi_dev_free(ctx, m.p);
         if (ctx) emi_destroy(ctx);
+    }
+    bool room(int which, size_t bytes) {
+        DevMem& m = mem[which];
+        if (m.cap >= bytes) return true;
+        if (m.p) (void)emi_dev_free(ctx, m.p);
+        m.p = nullptr; m.cap = 0;
+        if (emi_dev_alloc(ctx, bytes, &m.p) != EMI_OK) return false;
+        m.cap = bytes;
+        return true;
+    }
+    // node blocks on the device: upload the terms, emi_kkt_blocks_dev, download what the iteration's host parts read, emi_kkt_factor_dev
+    int factor_terms(const BlockTerms& t, double dc, BlockResult* out) override {
+        using clk = std::chrono::steady_clock;
+        const auto t0 = clk::now();
+        emi_layout_t lay;
+        if (emi_get_layout(ctx, &lay) != EMI_OK) return -1;
+        const size_t M = (size_t)lay.M, nv = (size_t)(lay.ns + lay.nc), nh = (size_t)lay.nhess, np = (size_t)lay.np;
+        if (lay.B != 1 || nv > 16 || lay.real_bytes != 8 || t.row_vars->size() != np) return NOT_OFFERED;
+        if (!rows_valid || rows_sent != *t.row_vars) {
+            std::vector<int> ptr(1, 0), var, ent;
+            for (const auto& row : *t.row_vars) {
+                for (const auto& pr : row) { var.push_back(pr.first); ent.push_back(pr.second); }
+                ptr.push_back((int)var.size());
+            }
+            if (emi_kkt_blocks_rows(ctx, (int)np, ptr.data(), var.data(), ent.data()) != EMI_OK) return -1;
+            rows_sent = *t.row_vars;
+            rows_valid = true;
+        }
+        const size_t mm = (size_t)out->max_mods;
+        const size_t bytes[NMEM] = {nh * M * 8, (size_t)lay.nvals * M * 8, nv * M * 8, std::max<size_t>(np * M, 1) * 8, nv * M, nh * M * 8, nh * M * 8,
+                                    sizeof(int), std::max<size_t>(mm, 1) * sizeof(int), std::max<size_t>(mm, 1) * 8, std::max<size_t>(mm * nv, 1) * 8, 8};
+        for (int i = 0; i < NMEM; ++i)
+            if (!room(i, bytes[i])) return -1;
+        if (emi_h2d(ctx, mem[MH].p, t.H, bytes[MH]) != EMI_OK || emi_h2d(ctx, mem[MV].p, t.VALS, bytes[MV]) != EMI_OK ||
+            emi_h2d(ctx, mem[MSG].p, t.Sigma, bytes[MSG]) != EMI_OK || (np && emi_h2d(ctx, mem[MST].p, t.sig_t, np * M * 8) != EMI_OK) ||
+            emi_h2d(ctx, mem[MFX].p, t.fixed, bytes[MFX]) != EMI_OK)
+            return -1;
+        if (emi_kkt_blocks_dev(ctx, mem[MH].p, mem[MV].p, mem[MSG].p, np ? mem[MST].p : nullptr, mem[MFX].p, t.dw_shift, mem[MQX].p, mem[MQ].p,
+                               out->max_mods, mem[MCNT].p, mem[MNODE].p, mem[MDELTA].p, mem[MVEC].p, mem[MWORST].p) != EMI_OK)
+            return -1;
+        int count = 0;
+        if (emi_d2h(ctx, out->Qexact, mem[MQX].p, bytes[MQX]) != EMI_OK || emi_d2h(ctx, out->Q, mem[MQ].p, bytes[MQ]) != EMI_OK ||
+            emi_d2h(ctx, &count, mem[MCNT].p, sizeof(int)) != EMI_OK || emi_d2h(ctx, &out->worst, mem[MWORST].p, 8) != EMI_OK)
+            return -1;
+        out->count = count;
+        const size_t n = std::min<size_t>((size_t)std::max(count, 0), mm);
+        out->node->resize(n); out->delta->resize(n); out->vec->resize(n * nv);
+        if (n > 0 && (emi_d2h(ctx, out->node->data(), mem[MNODE].p, n * sizeof(int)) != EMI_OK ||
+                      emi_d2h(ctx, out->delta->data(), mem[MDELTA].p, n * 8) != EMI_OK ||
+                      emi_d2h(ctx, out->vec->data(), mem[MVEC].p, n * nv * 8) != EMI_OK))
+            return -1;
+        const auto t1 = clk::now();
+        int info = -1;
+        const int st = emi_kkt_factor_dev(ctx, mem[MQ].p, mem[MV].p, mem[MFX].p, dc, &info);
+        out->t_blocks = std::chrono::duration<double>(t1 - t0).count();
+        out->t_factor = std::chrono::duration<double>(clk::now() - t1).count();
+        return st == EMI_OK ? info : -1;
     }
     int eval(const double* X, const double* U, double* RES, double* VALS, double* COST, bool jac) override {
         return emi_eval_host(ctx, X, U, RES, VALS, COST, EMI_EVAL_ALL | (jac ? 0u : (unsigned)EMI_EVAL_NOJAC));
@@ -1124,6 +1192,8 @@ void eMI355X::solve() {
     opt.stagnation_iters = _algorithm.stagnation_iters;
     opt.crawl_limit = _algorithm.crawl_limit;
     opt.crawl_frac = _algorithm.crawl_frac;
+    if (_algorithm.node_blocks == "device") opt.device_node_blocks = true;
+    else if (_algorithm.node_blocks != "host") die("Alg::node_blocks must be \"host\" or \"device\"");
 
     // the guess vectors of the problem are working storage of the mesh loop below; the caller's own guess
     // (ePSOPT.cpp:47-56) is put back when solve() returns, so that a second solve() starts from it again
@@ -1164,6 +1234,7 @@ void eMI355X::solve() {
         const auto t_run = std::chrono::steady_clock::now();
         r = mi355x::solve_nlp(nlp, ob, mi355x::initial_guess(P));
         _solution.nlp_iterations_total += r.iterations;
+        _solution.node_blocks = r.n_factor_terms > 0 ? "device" : "host";
         _solution.nlp_runs.push_back({P.nodes, r.iterations, r.ok, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_run).count(),
                                       r.t_eval, r.t_hess, r.t_factor, r.t_solve, r.t_lowrank, r.t_blocks, r.t_jt, r.t_matvec, r.n_factor, r.n_solve});
         if (!r.ok && _algorithm.nlp_iter_budget > 0 && _solution.nlp_iterations_total >= _algorithm.nlp_iter_budget)

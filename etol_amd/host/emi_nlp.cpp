@@ -178,15 +178,35 @@ struct Eval {
     double cost = 0;
 };
 
+}  // namespace
+
+void assemble_node_blocks(const double* H, const double* VALS, const double* Sigma, const double* sig_t, const unsigned char* fixed,
+                          double dw_shift, const std::vector<std::vector<std::pair<int, int>>>& rv, int nv, int M, double* Qblk) {
+    const int nh = nv * (nv + 1) / 2, np = (int)rv.size();
+    std::copy(H, H + (size_t)nh * M, Qblk);
+    for (int v = 0; v < nv; ++v)
+        for (int k = 0; k < M; ++k) {
+            const int qq = v * M + k;
+            Qblk[(size_t)(v * (v + 1) / 2 + v) * M + k] += Sigma[qq] + (fixed[qq] ? 0.0 : dw_shift);
+        }
+    // eliminated path rows: sum_j sig_j (grad c_j)(grad c_j)^T on the variables each row depends on
+    for (int j = 0; j < np; ++j)
+        for (size_t a = 0; a < rv[j].size(); ++a)
+            for (size_t b = 0; b <= a; ++b) {
+                const int va = rv[j][a].first, vb = rv[j][b].first;
+                const int hi = std::max(va, vb), lo = std::min(va, vb);
+                double* q = &Qblk[(size_t)(hi * (hi + 1) / 2 + lo) * M];
+                const double* ga = &VALS[(size_t)rv[j][a].second * M];
+                const double* gb = &VALS[(size_t)rv[j][b].second * M];
+                const double* sg = &sig_t[(size_t)j * M];
+                for (int k = 0; k < M; ++k) q[k] += sg[k] * ga[k] * gb[k];
+            }
+}
+
 // Makes every node block of Q (packed lower triangles, Qblk[nh][M]) positive definite over its free
 // variables: cyclic Jacobi eigen-decomposition of the (at most 16 x 16) block; if an eigenvalue is
 // below eps * max|lambda|, the block is rebuilt from max(|lambda|, floor).  Returns the largest
 // shift applied to an eigenvalue (0: nothing was modified).
-struct BlockMod {          // one modified eigenpair of one node block:  Q~_k = Q_k + delta v v^T
-    int node;
-    double delta;
-    double v[16];
-};
 double convexify_node_blocks(double* Qblk, const unsigned char* fixed, int nv, int M, std::vector<BlockMod>* mods) {
     constexpr int NMAX = 16;
     mods->clear();
@@ -284,6 +304,8 @@ double convexify_node_blocks(double* Qblk, const unsigned char* fixed, int nv, i
     }
     return worst;
 }
+
+namespace {
 
 // Host backend: the same matrix as etol_amd/csrc/emi_kkt.hip assembles, dense LDL^T (Bunch-Kaufman).
 class DenseHostKkt : public KktBackend {
@@ -792,6 +814,9 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     std::vector<unsigned char> fixed_mask(nz);
     for (int q = 0; q < nz; ++q) fixed_mask[q] = fidx[q] < 0 ? 1 : 0;
     std::vector<BlockMod> mods;
+    int n_mods = 0;                     // modified eigenpairs of the last factorisation (the true number, also beyond max_lowrank)
+    bool backend_blocks = opt.device_node_blocks && P.kkt != nullptr;   // until the backend says NOT_OFFERED
+    std::vector<double> Sigma(nz);
     std::vector<double> Qexact, rhs_keep(NN0), resid(NN0), x_prev(NN0);
     bool exact_step = false;
     const int max_lowrank = 4096;        // more modified eigenpairs than this: take the modified step untested
@@ -953,7 +978,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
         R.constr_viol = viol;
         if (opt.print_level >= 5)
             printf("iter %3d  cost %.10e  inf_pr %.2e  kkt %.2e  mu %.1e  dw %.1e  nu %.1e  emax %.1e  rho %.0e  r %d%s\n", iter,
-                   E.cost, viol, err0, mu, dw_used, nu, emax, rho, (int)mods.size(), exact_step ? " exact" : "");
+                   E.cost, viol, err0, mu, dw_used, nu, emax, rho, n_mods, exact_step ? " exact" : "");
         if (err0 <= opt.tol) {
             if (emax <= std::max(opt.tol, 1e-9) * 10.0 || mc == 0) { R.ok = true; R.msg = "converged"; break; }
             // a path row is still relaxed: the penalty was too small for it
@@ -1064,35 +1089,41 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             // the factor of C live with the backend (KktBackend::lowrank): on the device for eMI355X.
             const double* V = E.VALS.data();
             const auto tb0 = now();
-            std::copy(E.H.begin(), E.H.end(), Qblk.begin());
-            for (int v = 0; v < nv; ++v)
-                for (int k = 0; k < M; ++k) {
-                    const int qq = v * M + k;
-                    double sg = 0.0;
-                    if (fidx[qq] >= 0) {
-                        if (hasL(qq)) sg += it.zL[qq] / (it.z[qq] - P.zl[qq]);
-                        if (hasU(qq)) sg += it.zU[qq] / (P.zu[qq] - it.z[qq]);
-                    }
-                    Qblk[(size_t)(v * (v + 1) / 2 + v) * M + k] += sg + (fidx[qq] >= 0 ? dw_shift : 0.0);
+            for (int qq = 0; qq < nz; ++qq) {       // barrier diagonal of every variable (0 where fixed)
+                double sg = 0.0;
+                if (fidx[qq] >= 0) {
+                    if (hasL(qq)) sg += it.zL[qq] / (it.z[qq] - P.zl[qq]);
+                    if (hasU(qq)) sg += it.zU[qq] / (P.zu[qq] - it.z[qq]);
                 }
-            // eliminated path rows: sum_j sig_j (grad c_j)(grad c_j)^T on the variables each row depends on
-            for (int j = 0; j < np; ++j)
-                for (size_t a = 0; a < rv[j].size(); ++a)
-                    for (size_t b = 0; b <= a; ++b) {
-                        const int va = rv[j][a].first, vb = rv[j][b].first;
-                        const int hi = std::max(va, vb), lo = std::min(va, vb);
-                        double* q = &Qblk[(size_t)(hi * (hi + 1) / 2 + lo) * M];
-                        const double* ga = &V[(size_t)rv[j][a].second * M];
-                        const double* gb = &V[(size_t)rv[j][b].second * M];
-                        const double* sg = &sig_t[(size_t)j * M];
-                        for (int k = 0; k < M; ++k) q[k] += sg[k] * ga[k] * gb[k];
-                    }
-            Qexact = Qblk;
-            dw = convexify_node_blocks(Qblk.data(), fixed_mask.data(), nv, M, &mods);
-            R.t_blocks += secs(tb0, now());
-            const auto tf0 = now();
-            const int info = kkt->factor(Qblk.data(), V, fixed_mask.data(), dc);
-            R.t_factor += secs(tf0, now());
+                Sigma[qq] = sg;
+            }
+            int info = KktBackend::NOT_OFFERED;
+            if (backend_blocks) {       // assembly, convexification and factorisation by the backend, from the terms
+                Qexact.resize(Qblk.size());
+                KktBackend::BlockResult br;
+                br.Qexact = Qexact.data(); br.Q = Qblk.data(); br.max_mods = max_lowrank;
+                br.node = &lr_node; br.delta = &lr_delta; br.vec = &lr_vec;
+                info = kkt->factor_terms({E.H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, &rv}, dc, &br);
+                if (info == KktBackend::NOT_OFFERED) {
+                    backend_blocks = false;
+                } else {
+                    n_mods = br.count;
+                    ++R.n_factor_terms;
+                    dw = br.worst;
+                    R.t_blocks += br.t_blocks;
+                    R.t_factor += br.t_factor;
+                }
+            }
+            if (!backend_blocks) {
+                assemble_node_blocks(E.H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, rv, nv, M, Qblk.data());
+                Qexact = Qblk;
+                dw = convexify_node_blocks(Qblk.data(), fixed_mask.data(), nv, M, &mods);
+                n_mods = (int)mods.size();
+                R.t_blocks += secs(tb0, now());
+                const auto tf0 = now();
+                info = kkt->factor(Qblk.data(), V, fixed_mask.data(), dc);
+                R.t_factor += secs(tf0, now());
+            }
             ++R.n_factor;
             if (info < 0) { R.msg = "KKT factorisation failed: " + kkt->last_error(); return R; }
             if (info > 0) {   // exactly singular: the defect Jacobian lost rank; regularise the dual block
@@ -1100,11 +1131,11 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
                 continue;
             }
             // the low-rank correction (kept by the backend, next to its factors) and the inertia verdict
-            r_mod = (int)mods.size() <= max_lowrank ? (int)mods.size() : 0;
+            r_mod = n_mods <= max_lowrank ? n_mods : 0;
             lr_node.resize(r_mod);
             lr_delta.resize(r_mod);
             lr_vec.resize((size_t)r_mod * nv);
-            for (int c = 0; c < r_mod; ++c) {
+            for (int c = 0; c < r_mod && !backend_blocks; ++c) {        // (the backend filled the three itself)
                 lr_node[c] = mods[c].node;
                 lr_delta[c] = mods[c].delta;
                 for (int v = 0; v < nv; ++v) lr_vec[(size_t)c * nv + v] = mods[c].v[v];
@@ -1117,12 +1148,12 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
                 return R;
             }
             R.t_lowrank += secs(tl0, now());
-            exact_step = !force_modified && lr_exact && r_mod == (int)mods.size();
+            exact_step = !force_modified && lr_exact && r_mod == n_mods;
             // Inertia search (IPOPT's delta_w): the unmodified K has the wrong inertia.  The step of the reflected
             // blocks is the cheap answer and usually a good one; where it stagnates (search_on, set below) look for
             // the smallest shift K + delta_w I_z whose inertia is right instead -- the verdict for every trial comes
             // from the same low-rank test, at the price of a factorisation each.
-            if (search_on && !exact_step && !force_modified && !mods.empty() && r_mod == (int)mods.size() &&
+            if (search_on && !exact_step && !force_modified && n_mods > 0 && r_mod == n_mods &&
                 shift_trials < max_shift_trials) {
                 if (dw_shift == 0.0) dw_shift = dw_last_ok == 0.0 ? 1e-4 : std::max(1e-20, dw_last_ok / 3.0);
                 else dw_shift *= (dw_last_ok == 0.0 ? 100.0 : 8.0);
@@ -1432,7 +1463,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             force_modified = false;
             continue;
         }
-        if (!accepted && exact_step && !mods.empty() && !force_modified) {
+        if (!accepted && exact_step && n_mods > 0 && !force_modified) {
             // the exact Newton direction is not a descent direction the merit function accepts at this point:
             // redo the iteration with the step of the convexified matrix (a descent direction by construction)
             force_modified = true;

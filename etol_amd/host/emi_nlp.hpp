@@ -61,6 +61,30 @@ class KktBackend {
     // what the last factor() really factorised: [[Q + dw I_x, J^T], [J, -dc I]] (dw on the free state variables).  A backend
     // that never regularises on its own leaves both untouched (the caller presets them to its nominal dc and 0).
     virtual void applied_regularisation(double* dc, double* dw) { (void)dc; (void)dw; }
+    // factor() from the TERMS of the node blocks instead of the finished blocks (NlpOptions::device_node_blocks): the backend
+    // assembles Q_k = H_k + Sigma_k + dw_shift + sum_j sig_t,j g_j g_j^T, makes every block positive definite as
+    // convexify_node_blocks does, factorises, and hands back what the iteration's host parts read.  Returns factor()'s codes, or
+    // NOT_OFFERED (the caller then runs assemble_node_blocks / convexify_node_blocks itself and calls factor()).
+    struct BlockTerms {
+        const double *H, *VALS, *Sigma, *sig_t;     // [nh][M], [nvals][M], [nv][M] (0 where fixed), [np][M]
+        const unsigned char* fixed;                 // [nv*M]
+        double dw_shift;
+        const std::vector<std::vector<std::pair<int, int>>>* row_vars;     // per path row: (variable, VALS entry) pairs
+    };
+    struct BlockResult {
+        double *Qexact, *Q;                 // [nh][M] each, filled by the backend
+        int max_mods;                       // at most this many modified eigenpairs are returned ...
+        int count = 0;                      // ... of this many recorded
+        std::vector<int>* node;             // [min(count, max_mods)]
+        std::vector<double>*delta, *vec;    // ... and [..][nv]
+        double worst = 0;                   // convexify_node_blocks' return value
+        double t_blocks = 0, t_factor = 0;  // seconds of the two parts
+    };
+    static constexpr int NOT_OFFERED = -1000;
+    virtual int factor_terms(const BlockTerms& terms, double dc, BlockResult* out) {
+        (void)terms; (void)dc; (void)out;
+        return NOT_OFFERED;
+    }
     virtual std::string last_error() const { return std::string(); }
 };
 
@@ -115,6 +139,7 @@ struct NlpOptions {
     int crawl_limit = 3;                // consecutive short steps (alpha < crawl_frac * alpha_max) before the crawl rule acts
     double crawl_frac = 0.3;
     double rho_init = 10.0;             // exact-penalty weight of the elastic path rows (escalated x10 as needed)
+    bool device_node_blocks = false;    // node blocks assembled and convexified by the backend (KktBackend::factor_terms) where it offers that
     double acceptable_factor = 100.0;   // "acceptable": KKT error <= acceptable_factor * tol ...
     int acceptable_iter = 10;           // ... over this many consecutive iterations (as IPOPT's acceptable_*)
 };
@@ -132,6 +157,7 @@ struct NlpResult {
     std::vector<double> lamL;           // multipliers of the coupling rows (NlpProblem::links), links.size() * M
     double t_eval = 0, t_factor = 0, t_solve = 0, t_lowrank = 0, t_total = 0;   // seconds: evaluator, KKT factor, KKT solves, host low-rank algebra
     int n_factor = 0, n_solve = 0;      // factorisations (inertia-search trials included) and solve calls
+    int n_factor_terms = 0;             // ... of which the backend assembled and convexified the node blocks itself (KktBackend::factor_terms)
     double t_jt = 0, t_matvec = 0, t_blocks = 0, t_hess = 0;   // host: J^T lambda, refinement matvecs, node-block assembly + eigen-decompositions; Hessian calls
     double rho = 0;                     // penalty weight the solve ended with (warm start of the next mesh)
     int n_backend_shifted = 0;          // factorisations the backend regularised beyond the nominal matrix (applied_regularisation)
@@ -140,6 +166,20 @@ struct NlpResult {
 };
 
 NlpResult solve_nlp(const NlpProblem& prob, const NlpOptions& opt, const std::vector<double>& z0);
+
+// The node blocks of the Newton step on the host (what solve_nlp runs per factorisation attempt; exposed for the tests).
+// assemble_node_blocks: Qblk[nh][M] = H + (Sigma + dw_shift on free diagonals) + sum over path rows j and pairs (a, b <= a) of
+// row_vars[j]: sig_t[j] VALS[entry_a] VALS[entry_b], in that order.
+void assemble_node_blocks(const double* H, const double* VALS, const double* Sigma, const double* sig_t, const unsigned char* fixed,
+                          double dw_shift, const std::vector<std::vector<std::pair<int, int>>>& row_vars, int nv, int M, double* Qblk);
+// convexify_node_blocks: makes every block positive definite over its free variables; one BlockMod per reflected eigenpair
+// (Q~_k = Q_k + delta v v^T), by node, then by position of the eigenvalue; returns the largest shift (0: nothing modified).
+struct BlockMod {
+    int node;
+    double delta;
+    double v[16];
+};
+double convexify_node_blocks(double* Qblk, const unsigned char* fixed, int nv, int M, std::vector<BlockMod>* mods);
 
 // Dense symmetric-indefinite LDL^T (Bunch-Kaufman partial pivoting), lower
 // triangle of a row-major n*n array, in place.  Exposed for the unit tests.

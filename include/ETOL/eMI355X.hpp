@@ -112,6 +112,9 @@ struct Alg {
     double crawl_frac = 0.3;
     std::string linear_solver = "auto";            // Newton step: "host" (dense LDL^T), "device" (structured
                                                    // factorisation in HBM, emi_kkt_*), "auto" = device above 400 KKT rows
+    std::string node_blocks = "host";              // node blocks of the Newton step (assembly, Cholesky screen, eigen-fix): "host", or
+                                                   // "device" (emi_kkt_blocks_dev + emi_kkt_factor_dev: the blocks stay in HBM for the
+                                                   // factorisation) where the device factorises one problem at a time; else the host loop
     int nlp_iter_max = 200;                        // per NLP solve (one mesh, one start), as ePSOPT.cpp:66
     bool plan_second_start = true;                 // the route planned through the free space of the static keep-outs (clearance-weighted: planned_path_guess) is the
                                                    // second start of a mesh-ladder climb, before the bent lines (false: the last cold-start attempt only).  256-scenario
@@ -141,6 +144,7 @@ struct Sol {
     int evaluations = 0;
     double kkt_error = 0, constraint_violation = 0;
     std::string linear_solver;      // what the last solve used for the Newton step
+    std::string node_blocks;        // ... and where its node blocks were assembled and convexified: "host" or "device" (Alg::node_blocks)
     int mesh_iterations = 0;        // NLP solves performed (1 = no refinement happened)
     struct NlpRun {
         size_t nodes; int iterations; bool converged; double seconds;

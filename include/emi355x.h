@@ -303,6 +303,39 @@ int emi_kkt_solve_refined_batch(int n, const emi_ctx_t* ctxs, double* const* rhs
  * IPOPT's delta_w / delta_c tell its own iteration
  * (reference src/ePSOPT/ePSOPT.cpp:62-66: nlp_method "IPOPT").                */
 int emi_kkt_last_regularisation(emi_ctx_t ctx, double* dc, double* dw);
+/* emi_kkt_factor with Qblk, Jblk and fixed in DEVICE memory (copied on the context's stream: e.g. the dQ of
+ * emi_kkt_blocks_dev and the first ns*nv rows of VALS); everything behind the copies is emi_kkt_factor.       */
+int emi_kkt_factor_dev(emi_ctx_t ctx, const void* dQblk, const void* dJblk, const void* dFixed, double dc, int* info);
+
+/* ---- the node blocks of the Newton step, assembled and made positive definite on the device (f64 contexts, ns+nc <= 16) ----
+ * What an interior-point iteration puts in front of emi_kkt_factor, for the B instances of the context at once:
+ *   Q[v][q] = H[v][q] + (v == q: Sigma[v] + (fixed[v] ? 0 : dw_shift)) + sum over path rows j, pairs a, b <= a of row j with
+ *             {var_a, var_b} = {v, q}:  SigT[j] VALS[entry_a] VALS[entry_b]         (rows ascending, pairs in list order)
+ * H[B][nhess][M], VALS[B][nvals][M], Sigma[B][ns+nc][M] (0 where fixed), SigT[B][np][M] (NULL when np == 0), fixed[B][ns+nc][M]
+ * bytes.  Qexact (may be NULL) and Q receive the sum.  Then per block, on a working copy with identity rows / columns for fixed
+ * variables and the scaling d_v = sqrt(max(|A_vv|, 1e-12 max|A|)): a Cholesky screen (pivot <= 1e-8 fails).  A block that
+ * passes stays in Q as assembled, bit for bit.  A block that fails gets a Jacobi eigen-decomposition of the scaled block (to
+ * off^2 < 1e-32 max(1, dia^2), at most 30 sweeps); with nl = max(|lambda|, 1e-9), Q~ = d o (V diag(nl) V^T) o d replaces the
+ * entries of Q whose two variables are free, and every eigenvalue < -1e-9 is recorded: delta = nl - lambda, vec = d o v, so
+ * that Q~ = Q + sum delta vec vec^T up to the floored (|lambda| <= 1e-9) ones -- the columns emi_kkt_lowrank takes.
+ * The list of an instance is ordered by node, then by eigenvalue (ascending); count[b] is the TRUE number of recorded pairs,
+ * of which the first min(count, max_mods) are written to node[B][max_mods] / delta[B][max_mods] / vec[B][max_mods][ns+nc]
+ * (nothing is written behind them; max_mods 0: the three may be NULL).  worst[b] = max delta d_0^2 over the recorded pairs.
+ * No atomics, every sum in a fixed order: two calls give the same bits.
+ * emi_kkt_blocks_rows gives the (variable, VALS entry) pairs of every path row (CSR: row_ptr[np + 1]); np must be the
+ * context's number of path rows.  Without it, a context whose rows all come from the record table takes (px, ns*nv + 2j),
+ * (py, ns*nv + 2j + 1) as emi_jac_structure lays them out.
+ * EMI_ERR_UNSUPPORTED: f32 context, or ns+nc > 16;  EMI_ERR_STATE: rows traced by the model (emi_set_model_source npath > 0)
+ * and no list, or a list of another length;  EMI_ERR_ARG: a pair out of range.  The _dev form is asynchronous on the
+ * context's stream; the _host form copies in, runs it, copies out and synchronises.  Option "blocks_generic" 1 (emi_set_option,
+ * a test switch): the assembly kernel with the block size as a run-time value also where a compiled size (4, 8, 16) exists.  */
+int emi_kkt_blocks_rows(emi_ctx_t ctx, int np, const int* row_ptr, const int* var, const int* entry);
+int emi_kkt_blocks_dev(emi_ctx_t ctx, const void* dH, const void* dVALS, const void* dSigma, const void* dSigT,
+                       const void* dFixed, double dw_shift, void* dQexact, void* dQ, int max_mods, void* dCount, void* dNode,
+                       void* dDelta, void* dVec, void* dWorst);
+int emi_kkt_blocks_host(emi_ctx_t ctx, const double* H, const double* VALS, const double* Sigma, const double* SigT,
+                        const unsigned char* fixed, double dw_shift, double* Qexact, double* Q, int max_mods, int* count,
+                        int* node, double* delta, double* vec, double* worst);
 /* rhs [nrhs][N] (one right-hand side after the other) in, solutions out;
  * may be called repeatedly after one factor.                               */
 int emi_kkt_solve(emi_ctx_t ctx, double* rhs, int nrhs);
