@@ -45,6 +45,24 @@ _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I = C.POINTER(C.c_int)
 
+
+def _ptr_struct(name, fields):
+    return type(name, (C.Structure,), {"_fields_": [(f, _P) for f in fields], "FIELDS": tuple(fields)})
+
+
+# the argument groups of the emi_ipm_* calls (include/emi355x.h): device pointers in the _dev forms, host arrays in the _host forms
+IpmPoint = _ptr_struct("IpmPoint", ("X", "U", "S", "E1", "E2"))
+IpmDuals = _ptr_struct("IpmDuals", ("LamF", "Y", "ZL", "ZU", "VL", "VU", "W1", "W2"))
+IpmStep = _ptr_struct("IpmStep", ("DZLam", "DS", "DY", "DE1", "DE2", "DZL", "DZU", "DVL", "DVU", "DW1", "DW2"))
+IpmElim = _ptr_struct("IpmElim", ("Sigma", "SigT", "SigS", "RhatS", "Rt"))
+
+
+class IpmBounds(C.Structure):
+    _fields_ = [("zl", _P), ("zu", _P), ("nsets", C.c_int), ("cl", _D), ("cu", _D), ("cscale", _D)]
+
+
+_PT, _DU, _ST, _EL, _BD = (C.POINTER(t) for t in (IpmPoint, IpmDuals, IpmStep, IpmElim, IpmBounds))
+
 # every symbol include/emi355x.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "emi_abi_version": (C.c_int, []),
@@ -71,6 +89,19 @@ SYMBOLS = {
     "emi_kkt_blocks_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "emi_kkt_blocks_host": (C.c_int, [_P, _D, _D, _D, _D, C.POINTER(C.c_ubyte), C.c_double, _D, _D, C.c_int, _I, _I, _D, _D, _D]),
     "emi_kkt_solve": (C.c_int, [_P, _D, C.c_int]),
+    "emi_kkt_solve_dev": (C.c_int, [_P, _P, C.c_int]),
+    "emi_ipm_reduce_dev": (C.c_int, [_P, _PT, _DU, _P, _P, _P, _BD, _P, _P, _P, _EL, _P]),
+    "emi_ipm_expand_dev": (C.c_int, [_P, _PT, _DU, _P, _BD, _P, _EL, _P, _ST, _P]),
+    "emi_ipm_trial_dev": (C.c_int, [_P, _PT, _ST, _P, _PT]),
+    "emi_ipm_merit_dev": (C.c_int, [_P, _PT, _P, _P, _BD, _P, _P, C.c_int, _P]),
+    "emi_ipm_accept_dev": (C.c_int, [_P, _PT, _PT, _DU, _ST, _BD, _P, _P, _P, _P]),
+    "emi_ipm_error_dev": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
+    "emi_ipm_reduce_host": (C.c_int, [_P, _PT, _DU, _P, _P, _P, _BD, _P, _P, _P, _EL, _P]),
+    "emi_ipm_expand_host": (C.c_int, [_P, _PT, _DU, _P, _BD, _P, _EL, _P, _ST, _P]),
+    "emi_ipm_trial_host": (C.c_int, [_P, _PT, _ST, _P, _PT]),
+    "emi_ipm_merit_host": (C.c_int, [_P, _PT, _P, _P, _BD, _P, _P, C.c_int, _P]),
+    "emi_ipm_accept_host": (C.c_int, [_P, _PT, _PT, _DU, _ST, _BD, _P, _P, _P, _P]),
+    "emi_ipm_error_host": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

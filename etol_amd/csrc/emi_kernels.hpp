@@ -115,6 +115,28 @@ struct BlocksArgs {
 };
 hipError_t launch_kkt_blocks(const BlocksArgs& a, hipStream_t s);
 
+// the array arithmetic of an interior-point iteration over [instance][node] (emi_ipm.hip).  One argument block for the six calls;
+// each kernel reads and writes the members its call names (include/emi355x.h), the rest stay null.
+struct IpmArgs {
+    int B, M, ns, nc, np, nvals, nsets, reset;
+    double *X, *U, *S, *E1, *E2;                            // point [B][ns][M], [B][nc][M], [B][np][M] x 3
+    double *tX, *tU, *tS, *tE1, *tE2;                       // trial point
+    double *LF, *Y, *ZL, *ZU, *VL, *VU, *W1, *W2;           // multipliers
+    double *DZ, *DS, *DY, *DE1, *DE2, *DZL, *DZU, *DVL, *DVU, *DW1, *DW2;   // step; DZ [B][nv+ns][M] in the KKT unknown order
+    double *Sigma, *SigT, *SigS, *RhatS, *Rt, *Rhs;         // what the reduction leaves
+    const double *RES, *VALS, *G, *COST, *DefRes, *RowRes, *rs;
+    const double *zl, *zu;                                  // [nsets][nv][M]
+    const double* crow;                                     // [5][np]: cl, cu as given; cscale cl, cscale cu; cscale
+    const double *par, *apr, *adu;                          // [B][4] = {mu, rho, tau, nu}; step lengths [B]
+    const unsigned char* mask;                              // [B] or null
+    const int *vptr, *vrow, *vent;                          // per variable: the path rows it enters and the VALS entries, in row order
+    const int *rptr, *rvar, *rent;                          // per path row: (variable, VALS entry)
+    double *part, *out;                                     // [B][chunks][<= 7] partials; the call's per-instance result
+};
+enum { IPM_REDUCE, IPM_EXPAND, IPM_TRIAL, IPM_MERIT, IPM_ACCEPT, IPM_ERROR };
+int ipm_chunks(int M);
+hipError_t launch_ipm(int what, const IpmArgs& a, hipStream_t s);
+
 // model programs compiled at run time (emi_rtc.hip); the int results are EMI_* status codes
 struct RtcModel;
 int rtc_check(bool f32, const char* struct_name, const char* source, int ns, int nc, int npath, int pw, std::string* log);
@@ -137,7 +159,8 @@ struct KktWorkspace;
 int kkt_factor(KktWorkspace** w, hipStream_t stream, const double* dD, int M, int ns, int nv, const double* Qblk,
                const double* Jblk, const unsigned char* fixed, double dc, int method, int* info, std::string* err,
                bool blocks_on_device = false);      // Qblk, Jblk, fixed in device memory (copied on `stream`)
-int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs, std::string* err);
+int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs, std::string* err,
+              bool rhs_on_device = false);          // rhs in device memory: solved in place, no copies, no synchronisation
 bool kkt_set_option(const char* name, int value);   // process-wide diagnostics of the factorisation ("kkt_cholesky", ...)
 int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* node, const double* vec, const double* delta,
                 int* exact, std::string* err);

@@ -1540,26 +1540,31 @@ int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* n
     return EMI_OK;
 }
 
-int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs, std::string* err) {
+int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs, std::string* err, bool rhs_on_device) {
     if (!w || !w->factored) { *err = "emi_kkt_solve: no factorisation (emi_kkt_factor must succeed first)"; return EMI_ERR_STATE; }
     const int N = w->N;
     const size_t elems = (size_t)N * nrhs;
-    KKT_HIP(w->rhs.reserve(elems));
-    KKT_HIP(hipMemcpyAsync(w->rhs.p, rhs, elems * sizeof(double), hipMemcpyHostToDevice, stream));
-    int st = solve_dev(w, stream, nz, w->rhs.p, nrhs, err);
+    double* x = rhs;            // where the right-hand sides are solved in place: the caller's device array, or the workspace's copy
+    if (!rhs_on_device) {
+        KKT_HIP(w->rhs.reserve(elems));
+        KKT_HIP(hipMemcpyAsync(w->rhs.p, rhs, elems * sizeof(double), hipMemcpyHostToDevice, stream));
+        x = w->rhs.p;
+    }
+    int st = solve_dev(w, stream, nz, x, nrhs, err);
     if (st) return st;
     if (w->lr_active) {
         // x <- x + Y C^-1 (U^T x)
         const int r = w->lr_r;
         if (nrhs > 64) { *err = "emi_kkt_solve: at most 64 right-hand sides while a low-rank correction is active"; return EMI_ERR_ARG; }
-        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, nrhs), dim3(64), 0, stream, w->lrT.p, w->rhs.p, w->lr_node.p,
+        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, nrhs), dim3(64), 0, stream, w->lrT.p, x, w->lr_node.p,
                            w->lr_vec.p, r, N, w->M, w->nv);
         KKT_HIP(hipGetLastError());
         KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, nrhs, w->lrC.p, r, w->lrT.p, r));
         const double one = 1.0;
         KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, N, nrhs, r, &one, w->lrY.p, N, w->lrT.p, r,
-                             &one, w->rhs.p, N));
+                             &one, x, N));
     }
+    if (rhs_on_device) return EMI_OK;
     KKT_HIP(hipMemcpyAsync(rhs, w->rhs.p, elems * sizeof(double), hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;

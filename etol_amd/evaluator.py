@@ -374,6 +374,84 @@ class Evaluator:
         self._ck(self.lib.emi_kkt_solve(self.ctx, _dp(rhs), nrhs), "emi_kkt_solve")
         return rhs
 
+    def kkt_solve_dev(self, rhs):
+        """kkt_solve on a device tensor ([N] or [nrhs][N] float64), in place; asynchronous on the context's stream."""
+        nrhs = 1 if rhs.dim() == 1 else rhs.shape[0]
+        self._ck(self.lib.emi_kkt_solve_dev(self.ctx, C.c_void_p(rhs.data_ptr()), nrhs), "emi_kkt_solve_dev")
+
+    # ---- the array arithmetic of an interior-point iteration, batched (emi_ipm_*) ----------------------------------------
+    # Argument groups are dicts keyed as the structs of include/emi355x.h (X U S E1 E2 | LamF Y ZL ZU VL VU W1 W2 | DZLam DS DY DE1
+    # DE2 DZL DZU DVL DVU DW1 DW2 | Sigma SigT SigS RhatS Rt); bounds: dict zl, zu ([nsets][nv][M]) and cl, cu, cscale (host, [np];
+    # cscale optional).  dev=True: torch tensors on this device, asynchronous; dev=False: contiguous float64 numpy arrays (uint8
+    # for the mask), read and written in place, synchronised on return.  A missing key or None is a NULL pointer.
+    @staticmethod
+    def _ipm_addr(a):
+        if a is None:
+            return None
+        return C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else C.c_void_p(a.ctypes.data)
+
+    def _ipm_group(self, cls, d, keep):
+        if d is None:
+            return None
+        g = cls()
+        for f in cls.FIELDS:
+            a = d.get(f)
+            if a is not None and not isinstance(a, torch.Tensor):
+                assert a.dtype == np.float64 and a.flags.c_contiguous, f
+            setattr(g, f, self._ipm_addr(a))
+        keep.append(g)
+        return C.byref(g)
+
+    def _ipm_bounds(self, bd, keep):
+        if bd is None:
+            return None
+        g = L.IpmBounds()
+        g.zl, g.zu, g.nsets = self._ipm_addr(bd.get("zl")), self._ipm_addr(bd.get("zu")), int(bd["zl"].shape[0]) if bd.get("zl") is not None else 0
+        for f in ("cl", "cu", "cscale"):
+            a = bd.get(f)
+            if a is not None and len(a):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                keep.append(a)
+                setattr(g, f, _dp(a))
+        keep.append(g)
+        return C.byref(g)
+
+    def _ipm_call(self, name, dev, build):
+        keep = []
+        fn = getattr(self.lib, f"emi_ipm_{name}_{'dev' if dev else 'host'}")
+        self._ck(fn(self.ctx, *build(keep)), fn.__name__)
+
+    def ipm_reduce(self, point, duals, RES, VALS, G, bounds, par, elim, rhs, DefRes=None, RowRes=None, dev=True):
+        A, pt, du, el = self._ipm_addr, L.IpmPoint, L.IpmDuals, L.IpmElim
+        self._ipm_call("reduce", dev, lambda k: (self._ipm_group(pt, point, k), self._ipm_group(du, duals, k), A(RES), A(VALS), A(G),
+                                                 self._ipm_bounds(bounds, k), A(par), A(DefRes), A(RowRes), self._ipm_group(el, elim, k), A(rhs)))
+
+    def ipm_expand(self, point, duals, VALS, bounds, par, elim, step, scal, rs=None, dev=True):
+        A = self._ipm_addr
+        self._ipm_call("expand", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k), A(VALS),
+                                                 self._ipm_bounds(bounds, k), A(par), self._ipm_group(L.IpmElim, elim, k), A(rs),
+                                                 self._ipm_group(L.IpmStep, step, k), A(scal)))
+
+    def ipm_trial(self, point, step, alpha, trial, dev=True):
+        self._ipm_call("trial", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmStep, step, k), self._ipm_addr(alpha),
+                                                self._ipm_group(L.IpmPoint, trial, k)))
+
+    def ipm_merit(self, point, RES, COST, bounds, par, out, rs=None, reset=False, dev=True):
+        A = self._ipm_addr
+        self._ipm_call("merit", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), A(RES), A(COST), self._ipm_bounds(bounds, k), A(par), A(rs),
+                                                int(bool(reset)), A(out)))
+
+    def ipm_accept(self, point, trial, duals, step, bounds, par, a_pr, a_du, mask=None, dev=True):
+        A = self._ipm_addr
+        self._ipm_call("accept", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmPoint, trial, k),
+                                                 self._ipm_group(L.IpmDuals, duals, k), self._ipm_group(L.IpmStep, step, k),
+                                                 self._ipm_bounds(bounds, k), A(par), A(a_pr), A(a_du), A(mask)))
+
+    def ipm_error(self, point, duals, RES, G, bounds, par, out, dev=True):
+        A = self._ipm_addr
+        self._ipm_call("error", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k), A(RES), A(G),
+                                                self._ipm_bounds(bounds, k), A(par), A(out)))
+
     # ---- measurement -----------------------------------------------------------
     def timer_start(self):
         self._ck(self.lib.emi_timer_start(self.ctx), "emi_timer_start")

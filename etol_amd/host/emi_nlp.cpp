@@ -518,6 +518,277 @@ class ScaledEvaluator : public NlpEvaluator {
     std::vector<double> z_, lam_;
 };
 
+// ---- the array arithmetic of one iteration (emi_nlp.hpp: IpmDims and what follows it) -----------------------------------------
+namespace {
+
+// the bound tests and scaled row bounds of solve_nlp, on an IpmDims
+struct IpmB {
+    const IpmDims& P;
+    bool free_var(int q) const { return P.zu[q] > P.zl[q]; }
+    bool hasL(int q) const { return P.zl[q] > -INF_BOUND; }
+    bool hasU(int q) const { return P.zu[q] < INF_BOUND; }
+    bool shasL(int r) const { return P.cl[r / P.M] > -INF_BOUND; }
+    bool shasU(int r) const { return P.cu[r / P.M] < INF_BOUND; }
+    double cL(int r) const { return P.cls[r / P.M]; }
+    double cU(int r) const { return P.cus[r / P.M]; }
+    int nz() const { return P.nv * P.M; }
+    int md() const { return P.ns * P.M; }
+    int mc() const { return P.np * P.M; }
+    int me() const { return P.ns * P.M + P.ml; }
+};
+inline double ipm_eqr(const IpmDims& P, const IpmRes& e, int r) { const int md = P.ns * P.M; return r < md ? e.RES[r] : e.LNK[r - md]; }
+inline double ipm_row_res(const IpmDims& P, const IpmRes& e, const double* s, const double* e1, const double* e2, int r) {
+    return e.RES[(size_t)P.ns * P.M + r] - s[r] - e1[r] + e2[r];
+}
+
+}  // namespace
+
+void ipm_eliminate_rows(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const IpmRes& e, double mu, double rho, const IpmElim& out) {
+    const IpmB b{P};
+    const int mc = b.mc();
+    for (int r = 0; r < mc; ++r) {
+        double sg = 0, rh = -d.y[r];
+        if (b.shasL(r)) { const double g = x.s[r] - b.cL(r); sg += d.vL[r] / g; rh -= mu / g; }
+        if (b.shasU(r)) { const double g = b.cU(r) - x.s[r]; sg += d.vU[r] / g; rh += mu / g; }
+        out.sig_s[r] = sg;
+        out.rhat_s[r] = rh;
+        const double a1 = x.e1[r] / d.w1[r], a2 = x.e2[r] / d.w2[r];
+        out.sig_t[r] = 1.0 / (1.0 / sg + a1 + a2);
+        out.r_t[r] = ipm_row_res(P, e, x.s, x.e1, x.e2, r) + rh / sg - a1 * (d.y[r] - rho + mu / x.e1[r]) -
+                     a2 * (d.y[r] + rho - mu / x.e2[r]);
+    }
+}
+
+void ipm_barrier_diagonal(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, double* Sigma) {
+    const IpmB b{P};
+    const int nz = b.nz();
+    for (int qq = 0; qq < nz; ++qq) {
+        double sg = 0.0;
+        if (b.free_var(qq)) {
+            if (b.hasL(qq)) sg += d.zL[qq] / (x.z[qq] - P.zl[qq]);
+            if (b.hasU(qq)) sg += d.zU[qq] / (P.zu[qq] - x.z[qq]);
+        }
+        Sigma[qq] = sg;
+    }
+}
+
+void ipm_fill_rt(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* rowres, double mu, double rho, const IpmElim& el) {
+    const int mc = P.np * P.M;
+    for (int r = 0; r < mc; ++r) {
+        const double a1 = x.e1[r] / d.w1[r], a2 = x.e2[r] / d.w2[r];
+        el.r_t[r] = rowres[r] + el.rhat_s[r] / el.sig_s[r] - a1 * (d.y[r] - rho + mu / x.e1[r]) -
+                    a2 * (d.y[r] + rho - mu / x.e2[r]);
+    }
+}
+
+void ipm_build_rhs(const IpmDims& P, const IpmPoint& x, const double* gradf, const double* jtl, const double* VALS, const IpmElim& el,
+                   const double* eqres, double mu, double* out) {
+    const IpmB b{P};
+    const int nz = b.nz(), me = b.me(), M = P.M, np = P.np;
+    const double* V = VALS;
+    const auto& rv = *P.row_vars;
+    std::fill(out, out + (size_t)nz + me, 0.0);
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        double r = gradf[q] + jtl[q];
+        if (b.hasL(q)) r -= mu / (x.z[q] - P.zl[q]);
+        if (b.hasU(q)) r += mu / (P.zu[q] - x.z[q]);
+        out[q] = -r;
+    }
+    for (int j = 0; j < np; ++j)
+        for (int k = 0; k < M; ++k) {
+            const double t = el.sig_t[j * M + k] * el.r_t[j * M + k];
+            for (const auto& ve : rv[j])
+                if (b.free_var(ve.first * M + k)) out[ve.first * M + k] -= V[(size_t)ve.second * M + k] * t;
+        }
+    for (int r = 0; r < me; ++r) out[nz + r] = -eqres[r];
+}
+
+void ipm_expand_step(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* VALS, const IpmElim& el, double mu, double rho,
+                     const IpmStep& st) {
+    const IpmB b{P};
+    const int nz = b.nz(), M = P.M, np = P.np;
+    const double* V = VALS;
+    const auto& rv = *P.row_vars;
+    for (int j = 0; j < np; ++j)
+        for (int k = 0; k < M; ++k) {
+            const int r = j * M + k;
+            double jcdz = 0.0;
+            for (const auto& ve : rv[j]) jcdz += V[(size_t)ve.second * M + k] * st.dz[ve.first * M + k];
+            st.dy[r] = el.sig_t[r] * (jcdz + el.r_t[r]);
+            st.ds[r] = (st.dy[r] - el.rhat_s[r]) / el.sig_s[r];
+            st.de1[r] = x.e1[r] / d.w1[r] * (st.dy[r] + d.y[r] - rho + mu / x.e1[r]);
+            st.de2[r] = x.e2[r] / d.w2[r] * (-st.dy[r] - d.y[r] - rho + mu / x.e2[r]);
+            st.dvL[r] = st.dvU[r] = 0;
+            if (b.shasL(r)) { const double g = x.s[r] - b.cL(r); st.dvL[r] = mu / g - d.vL[r] - d.vL[r] / g * st.ds[r]; }
+            if (b.shasU(r)) { const double g = b.cU(r) - x.s[r]; st.dvU[r] = mu / g - d.vU[r] + d.vU[r] / g * st.ds[r]; }
+            st.dw1[r] = mu / x.e1[r] - d.w1[r] - d.w1[r] / x.e1[r] * st.de1[r];
+            st.dw2[r] = mu / x.e2[r] - d.w2[r] - d.w2[r] / x.e2[r] * st.de2[r];
+        }
+    for (int q = 0; q < nz; ++q) {
+        st.dzL[q] = st.dzU[q] = 0;
+        if (!b.free_var(q)) continue;
+        if (b.hasL(q)) { const double g = x.z[q] - P.zl[q]; st.dzL[q] = mu / g - d.zL[q] - d.zL[q] / g * st.dz[q]; }
+        if (b.hasU(q)) { const double g = P.zu[q] - x.z[q]; st.dzU[q] = mu / g - d.zU[q] + d.zU[q] / g * st.dz[q]; }
+    }
+}
+
+void ipm_step_lengths(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const IpmStep& st, double tau, double* apr_out, double* adu_out) {
+    const IpmB b{P};
+    const int nz = b.nz(), mc = b.mc();
+    double apr = 1.0, adu = 1.0;
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        if (b.hasL(q) && st.dz[q] < 0) apr = std::min(apr, -tau * (x.z[q] - P.zl[q]) / st.dz[q]);
+        if (b.hasU(q) && st.dz[q] > 0) apr = std::min(apr, tau * (P.zu[q] - x.z[q]) / st.dz[q]);
+        if (st.dzL[q] < 0) adu = std::min(adu, -tau * d.zL[q] / st.dzL[q]);
+        if (st.dzU[q] < 0) adu = std::min(adu, -tau * d.zU[q] / st.dzU[q]);
+    }
+    for (int r = 0; r < mc; ++r) {
+        if (b.shasL(r) && st.ds[r] < 0) apr = std::min(apr, -tau * (x.s[r] - b.cL(r)) / st.ds[r]);
+        if (b.shasU(r) && st.ds[r] > 0) apr = std::min(apr, tau * (b.cU(r) - x.s[r]) / st.ds[r]);
+        if (st.de1[r] < 0) apr = std::min(apr, -tau * x.e1[r] / st.de1[r]);
+        if (st.de2[r] < 0) apr = std::min(apr, -tau * x.e2[r] / st.de2[r]);
+        if (st.dvL[r] < 0) adu = std::min(adu, -tau * d.vL[r] / st.dvL[r]);
+        if (st.dvU[r] < 0) adu = std::min(adu, -tau * d.vU[r] / st.dvU[r]);
+        if (st.dw1[r] < 0) adu = std::min(adu, -tau * d.w1[r] / st.dw1[r]);
+        if (st.dw2[r] < 0) adu = std::min(adu, -tau * d.w2[r] / st.dw2[r]);
+    }
+    *apr_out = apr;
+    *adu_out = adu;
+}
+
+void ipm_dphi_mmax(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* gradf, const IpmStep& st, const double* rs,
+                   double mu, double rho, double* dphi_out, double* mmax_out) {
+    const IpmB b{P};
+    const int nz = b.nz(), mc = b.mc(), me = b.me();
+    double dphi = 0;
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        double g = gradf[q];
+        if (b.hasL(q)) g -= mu / (x.z[q] - P.zl[q]);
+        if (b.hasU(q)) g += mu / (P.zu[q] - x.z[q]);
+        dphi += g * st.dz[q];
+    }
+    for (int r = 0; r < mc; ++r) {
+        double g = 0;
+        if (b.shasL(r)) g -= mu / (x.s[r] - b.cL(r));
+        if (b.shasU(r)) g += mu / (b.cU(r) - x.s[r]);
+        dphi += g * st.ds[r] + (rho - mu / x.e1[r]) * st.de1[r] + (rho - mu / x.e2[r]) * st.de2[r];
+    }
+    double mmax = 0;
+    for (int r = 0; r < me; ++r) mmax = std::max(mmax, std::fabs(d.lam[r] + st.dlam[r]) / rs[r]);
+    for (int r = 0; r < mc; ++r) mmax = std::max(mmax, std::fabs(d.y[r] + st.dy[r]));
+    *dphi_out = dphi;
+    *mmax_out = mmax;
+}
+
+double ipm_barrier_merit(const IpmDims& P, const IpmPoint& x, const IpmRes& e, double cost, const double* rs, double mu_t, double nu_t,
+                         double rho, double* infeas) {
+    const IpmB b{P};
+    const int nz = b.nz(), mc = b.mc(), me = b.me();
+    double phi = cost, viol = 0;
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        if (b.hasL(q)) phi -= mu_t * std::log(x.z[q] - P.zl[q]);
+        if (b.hasU(q)) phi -= mu_t * std::log(P.zu[q] - x.z[q]);
+    }
+    for (int r = 0; r < mc; ++r) {
+        if (b.shasL(r)) phi -= mu_t * std::log(x.s[r] - b.cL(r));
+        if (b.shasU(r)) phi -= mu_t * std::log(b.cU(r) - x.s[r]);
+        phi += rho * (x.e1[r] + x.e2[r]) - mu_t * (std::log(x.e1[r]) + std::log(x.e2[r]));
+        viol += std::fabs(ipm_row_res(P, e, x.s, x.e1, x.e2, r));
+    }
+    for (int r = 0; r < me; ++r) viol += rs[r] * std::fabs(ipm_eqr(P, e, r));
+    if (infeas) *infeas = viol;
+    return phi + nu_t * viol;
+}
+
+void ipm_slack_reset(const IpmDims& P, const double* c, const double* e1, const double* e2, double mu, double nu, double* s) {
+    const IpmB b{P};
+    const int mc = b.mc();
+    for (int r = 0; r < mc; ++r) {
+        const double target = c[r] - e1[r] + e2[r];
+        const double lo = b.shasL(r) ? b.cL(r) : -INF_BOUND, hi = b.shasU(r) ? b.cU(r) : INF_BOUND;
+        if (!(target > lo) || !(target < hi)) continue;
+        double keep = nu * std::fabs(target - s[r]), take = 0.0;
+        if (b.shasL(r)) { keep -= mu * std::log(s[r] - lo); take -= mu * std::log(target - lo); }
+        if (b.shasU(r)) { keep -= mu * std::log(hi - s[r]); take -= mu * std::log(hi - target); }
+        if (take < keep) s[r] = target;
+    }
+}
+
+void ipm_update_duals(const IpmDims& P, const IpmPoint& x, const IpmDualsRW& d, const IpmStep& st, double a_pr, double a_du, double mu) {
+    const IpmB b{P};
+    const int nz = b.nz(), mc = b.mc(), me = b.me();
+    const double kappa_sigma = 1e10;
+    auto clampm = [&](double m, double g) { return std::max(std::min(m, kappa_sigma * mu / g), mu / (kappa_sigma * g)); };
+    for (int r = 0; r < me; ++r) d.lam[r] += a_pr * st.dlam[r];
+    for (int r = 0; r < mc; ++r) {
+        d.y[r] += a_pr * st.dy[r];
+        d.vL[r] += a_du * st.dvL[r];
+        d.vU[r] += a_du * st.dvU[r];
+        d.w1[r] += a_du * st.dw1[r];
+        d.w2[r] += a_du * st.dw2[r];
+        if (b.shasL(r)) d.vL[r] = clampm(d.vL[r], x.s[r] - b.cL(r));
+        if (b.shasU(r)) d.vU[r] = clampm(d.vU[r], b.cU(r) - x.s[r]);
+        d.w1[r] = clampm(d.w1[r], x.e1[r]);
+        d.w2[r] = clampm(d.w2[r], x.e2[r]);
+    }
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        d.zL[q] += a_du * st.dzL[q];
+        d.zU[q] += a_du * st.dzU[q];
+        if (b.hasL(q)) d.zL[q] = clampm(d.zL[q], x.z[q] - P.zl[q]);
+        if (b.hasU(q)) d.zU[q] = clampm(d.zU[q], P.zu[q] - x.z[q]);
+    }
+}
+
+double ipm_kkt_error(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* gradf, const double* jtl, const IpmRes& e,
+                     double mu_t, double rho, double* viol_out, double* emax_out) {
+    const IpmB b{P};
+    const int nz = b.nz(), mc = b.mc(), me = b.me();
+    double sumz = 0, summ = 0;
+    int cntz = 0;
+    for (int q = 0; q < nz; ++q) { sumz += d.zL[q] + d.zU[q]; cntz += (d.zL[q] > 0) + (d.zU[q] > 0); }
+    for (int r = 0; r < mc; ++r) {
+        sumz += d.vL[r] + d.vU[r] + d.w1[r] + d.w2[r];
+        cntz += (d.vL[r] > 0) + (d.vU[r] > 0) + 2;
+        summ += std::fabs(d.y[r]);
+    }
+    for (int r = 0; r < me; ++r) summ += std::fabs(d.lam[r]);
+    const double smax = 100.0;
+    const double sd = std::max(smax, (summ + sumz) / std::max(1, me + mc + cntz)) / smax;
+    const double sc = std::max(smax, sumz / std::max(1, cntz)) / smax;
+    double ed = 0, ep = 0, ec = 0, emax = 0;
+    for (int q = 0; q < nz; ++q)
+        if (b.free_var(q)) ed = std::max(ed, std::fabs(gradf[q] + jtl[q] - d.zL[q] + d.zU[q]));
+    for (int r = 0; r < mc; ++r) {
+        ed = std::max(ed, std::fabs(-d.y[r] - d.vL[r] + d.vU[r]));
+        ed = std::max(ed, std::fabs(rho - d.y[r] - d.w1[r]));
+        ed = std::max(ed, std::fabs(rho + d.y[r] - d.w2[r]));
+    }
+    for (int r = 0; r < me; ++r) ep = std::max(ep, std::fabs(ipm_eqr(P, e, r)));
+    for (int r = 0; r < mc; ++r) {
+        ep = std::max(ep, std::fabs(ipm_row_res(P, e, x.s, x.e1, x.e2, r)));
+        emax = std::max(emax, std::max(x.e1[r], x.e2[r]));
+    }
+    for (int q = 0; q < nz; ++q) {
+        if (!b.free_var(q)) continue;
+        if (b.hasL(q)) ec = std::max(ec, std::fabs((x.z[q] - P.zl[q]) * d.zL[q] - mu_t));
+        if (b.hasU(q)) ec = std::max(ec, std::fabs((P.zu[q] - x.z[q]) * d.zU[q] - mu_t));
+    }
+    for (int r = 0; r < mc; ++r) {
+        if (b.shasL(r)) ec = std::max(ec, std::fabs((x.s[r] - b.cL(r)) * d.vL[r] - mu_t));
+        if (b.shasU(r)) ec = std::max(ec, std::fabs((b.cU(r) - x.s[r]) * d.vU[r] - mu_t));
+        ec = std::max(ec, std::fabs(x.e1[r] * d.w1[r] - mu_t));
+        ec = std::max(ec, std::fabs(x.e2[r] * d.w2[r] - mu_t));
+    }
+    if (viol_out) *viol_out = ep;
+    if (emax_out) *emax_out = emax;
+    return std::max(std::max(ed / sd, ep), ec / sc);
+}
+
 NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vector<double>& z0) {
     NlpResult R;
     const int ns = P.ns, nc = P.nc, np = P.np, M = P.M, nv = ns + nc;
@@ -604,6 +875,20 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     auto shasU = [&](int r) { return P.cu[r / M] < INF_BOUND; };
     auto cL = [&](int r) { return shasL(r) ? sig[r / M] * P.cl[r / M] : P.cl[r / M]; };
     auto cU = [&](int r) { return shasU(r) ? sig[r / M] * P.cu[r / M] : P.cu[r / M]; };
+    // the same problem as the free functions of the iteration's array arithmetic take it (ipm_*)
+    IpmDims PD;
+    PD.nv = nv; PD.ns = ns; PD.np = np; PD.M = M; PD.ml = ml;
+    std::vector<double> cls(np), cus(np);       // the row bounds the iteration works with: sig_j * bound where there is one
+    for (int j = 0; j < np; ++j) { cls[j] = cL(j * M); cus[j] = cU(j * M); }
+    PD.zl = P.zl.data(); PD.zu = P.zu.data(); PD.cl = P.cl.data(); PD.cu = P.cu.data(); PD.cls = cls.data(); PD.cus = cus.data();
+    PD.row_vars = &rv;
+    auto point_of = [](const std::vector<double>& z, const std::vector<double>& s, const std::vector<double>& e1, const std::vector<double>& e2) {
+        return IpmPoint{z.data(), s.data(), e1.data(), e2.data()};
+    };
+    auto duals_of = [](const Iterate& I) {
+        return IpmDuals{I.lam.data(), I.y.data(), I.zL.data(), I.zU.data(), I.vL.data(), I.vU.data(), I.w1.data(), I.w2.data()};
+    };
+    auto res_of = [](const Eval& e) { return IpmRes{e.RES.data(), e.LNK.data()}; };
 
     Iterate it;
     it.z = z0;
@@ -706,7 +991,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     double mu = opt.mu_init, nu = 1.0;
     double dw_used = 0.0;   // delta_w of the last exact step, or the largest reflected eigenvalue shift (log only)
     double dw_last_ok = 0.0;   // last nonzero delta_w that gave the right inertia
-    const double tau_min = 0.99, kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5, kappa_sigma = 1e10;
+    const double tau_min = 0.99, kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5;     // (kappa_sigma: ipm_update_duals)
     std::vector<double> y_unscaled(mc);
 
     // --- pieces of the KKT residual at the current point --------------------------------------
@@ -747,63 +1032,11 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     auto row_res = [&](const Eval& e, const std::vector<double>& s, const std::vector<double>& e1,
                        const std::vector<double>& e2, int r) { return e.RES[(size_t)md + r] - s[r] - e1[r] + e2[r]; };
     auto kkt_error = [&](const Iterate& I, double mu_t, double* viol_out, double* emax_out) {
-        double sumz = 0, summ = 0;
-        int cntz = 0;
-        for (int q = 0; q < nz; ++q) { sumz += I.zL[q] + I.zU[q]; cntz += (I.zL[q] > 0) + (I.zU[q] > 0); }
-        for (int r = 0; r < mc; ++r) {
-            sumz += I.vL[r] + I.vU[r] + I.w1[r] + I.w2[r];
-            cntz += (I.vL[r] > 0) + (I.vU[r] > 0) + 2;
-            summ += std::fabs(I.y[r]);
-        }
-        for (int r = 0; r < me; ++r) summ += std::fabs(I.lam[r]);
-        const double smax = 100.0;
-        const double sd = std::max(smax, (summ + sumz) / std::max(1, me + mc + cntz)) / smax;
-        const double sc = std::max(smax, sumz / std::max(1, cntz)) / smax;
-        double ed = 0, ep = 0, ec = 0, emax = 0;
-        for (int q = 0; q < nz; ++q)
-            if (fidx[q] >= 0) ed = std::max(ed, std::fabs(gradf[q] + jtl[q] - I.zL[q] + I.zU[q]));
-        for (int r = 0; r < mc; ++r) {
-            ed = std::max(ed, std::fabs(-I.y[r] - I.vL[r] + I.vU[r]));
-            ed = std::max(ed, std::fabs(rho - I.y[r] - I.w1[r]));
-            ed = std::max(ed, std::fabs(rho + I.y[r] - I.w2[r]));
-        }
-        for (int r = 0; r < me; ++r) ep = std::max(ep, std::fabs(eqr(E, r)));
-        for (int r = 0; r < mc; ++r) {
-            ep = std::max(ep, std::fabs(row_res(E, I.s, I.e1, I.e2, r)));
-            emax = std::max(emax, std::max(I.e1[r], I.e2[r]));
-        }
-        for (int q = 0; q < nz; ++q) {
-            if (fidx[q] < 0) continue;
-            if (hasL(q)) ec = std::max(ec, std::fabs((I.z[q] - P.zl[q]) * I.zL[q] - mu_t));
-            if (hasU(q)) ec = std::max(ec, std::fabs((P.zu[q] - I.z[q]) * I.zU[q] - mu_t));
-        }
-        for (int r = 0; r < mc; ++r) {
-            if (shasL(r)) ec = std::max(ec, std::fabs((I.s[r] - cL(r)) * I.vL[r] - mu_t));
-            if (shasU(r)) ec = std::max(ec, std::fabs((cU(r) - I.s[r]) * I.vU[r] - mu_t));
-            ec = std::max(ec, std::fabs(I.e1[r] * I.w1[r] - mu_t));
-            ec = std::max(ec, std::fabs(I.e2[r] * I.w2[r] - mu_t));
-        }
-        if (viol_out) *viol_out = ep;
-        if (emax_out) *emax_out = emax;
-        return std::max(std::max(ed / sd, ep), ec / sc);
+        return ipm_kkt_error(PD, point_of(I.z, I.s, I.e1, I.e2), duals_of(I), gradf.data(), jtl.data(), res_of(E), mu_t, rho, viol_out, emax_out);
     };
     auto barrier_merit = [&](const std::vector<double>& z, const std::vector<double>& s, const std::vector<double>& e1,
                              const std::vector<double>& e2, const Eval& e, double mu_t, double nu_t, double* infeas) {
-        double phi = e.cost, viol = 0;
-        for (int q = 0; q < nz; ++q) {
-            if (fidx[q] < 0) continue;
-            if (hasL(q)) phi -= mu_t * std::log(z[q] - P.zl[q]);
-            if (hasU(q)) phi -= mu_t * std::log(P.zu[q] - z[q]);
-        }
-        for (int r = 0; r < mc; ++r) {
-            if (shasL(r)) phi -= mu_t * std::log(s[r] - cL(r));
-            if (shasU(r)) phi -= mu_t * std::log(cU(r) - s[r]);
-            phi += rho * (e1[r] + e2[r]) - mu_t * (std::log(e1[r]) + std::log(e2[r]));
-            viol += std::fabs(row_res(e, s, e1, e2, r));
-        }
-        for (int r = 0; r < me; ++r) viol += rs[r] * std::fabs(eqr(e, r));
-        if (infeas) *infeas = viol;
-        return phi + nu_t * viol;
+        return ipm_barrier_merit(PD, point_of(z, s, e1, e2), res_of(e), e.cost, rs.data(), mu_t, nu_t, rho, infeas);
     };
 
     // Newton-step linear algebra: the caller's backend (eMI355X: the device) or the dense host one
@@ -832,31 +1065,15 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     const size_t NN = (size_t)nz + me;
     int r_mod = 0;
     // r_t of the eliminated path rows for given row residuals  c - s - e1 + e2
+    const IpmElim elim{sig_s.data(), rhat_s.data(), sig_t.data(), r_t.data()};
+    const IpmStep step{dz.data(), dlam.data(), ds.data(), dy.data(), de1.data(), de2.data(), dzL.data(), dzU.data(), dvL.data(), dvU.data(),
+                       dw1.data(), dw2.data()};
     auto fill_rt = [&](const std::vector<double>& rowres) {
-        for (int r = 0; r < mc; ++r) {
-            const double a1 = it.e1[r] / it.w1[r], a2 = it.e2[r] / it.w2[r];
-            r_t[r] = rowres[r] + rhat_s[r] / sig_s[r] - a1 * (it.y[r] - rho + mu / it.e1[r]) -
-                     a2 * (it.y[r] + rho - mu / it.e2[r]);
-        }
+        ipm_fill_rt(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), rowres.data(), mu, rho, elim);
     };
     // right-hand side of the reduced KKT system in full indexing (fixed variables: 0), for defect residuals defres
     auto build_rhs = [&](double* out, const double* defres) {
-        const double* V = E.VALS.data();
-        std::fill(out, out + NN, 0.0);
-        for (int q = 0; q < nz; ++q) {
-            if (fidx[q] < 0) continue;
-            double r = gradf[q] + jtl[q];
-            if (hasL(q)) r -= mu / (it.z[q] - P.zl[q]);
-            if (hasU(q)) r += mu / (P.zu[q] - it.z[q]);
-            out[q] = -r;
-        }
-        for (int j = 0; j < np; ++j)
-            for (int k = 0; k < M; ++k) {
-                const double t = sig_t[j * M + k] * r_t[j * M + k];
-                for (const auto& ve : rv[j])
-                    if (fidx[ve.first * M + k] >= 0) out[ve.first * M + k] -= V[(size_t)ve.second * M + k] * t;
-            }
-        for (int r = 0; r < me; ++r) out[nz + r] = -defres[r];
+        ipm_build_rhs(PD, point_of(it.z, it.s, it.e1, it.e2), gradf.data(), jtl.data(), E.VALS.data(), elim, defres, mu, out);
     };
     std::vector<double> soc_def(me), soc_row(mc), soc_rhs(NN), lr_vec, lr_delta;
     std::vector<int> lr_node;
@@ -924,28 +1141,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
     };
     // everything that was eliminated from the system, from dz (uses r_t)
     auto expand_step = [&]() {
-        const double* V = E.VALS.data();
-        for (int j = 0; j < np; ++j)
-            for (int k = 0; k < M; ++k) {
-                const int r = j * M + k;
-                double jcdz = 0.0;
-                for (const auto& ve : rv[j]) jcdz += V[(size_t)ve.second * M + k] * dz[ve.first * M + k];
-                dy[r] = sig_t[r] * (jcdz + r_t[r]);
-                ds[r] = (dy[r] - rhat_s[r]) / sig_s[r];
-                de1[r] = it.e1[r] / it.w1[r] * (dy[r] + it.y[r] - rho + mu / it.e1[r]);
-                de2[r] = it.e2[r] / it.w2[r] * (-dy[r] - it.y[r] - rho + mu / it.e2[r]);
-                dvL[r] = dvU[r] = 0;
-                if (shasL(r)) { const double g = it.s[r] - cL(r); dvL[r] = mu / g - it.vL[r] - it.vL[r] / g * ds[r]; }
-                if (shasU(r)) { const double g = cU(r) - it.s[r]; dvU[r] = mu / g - it.vU[r] + it.vU[r] / g * ds[r]; }
-                dw1[r] = mu / it.e1[r] - it.w1[r] - it.w1[r] / it.e1[r] * de1[r];
-                dw2[r] = mu / it.e2[r] - it.w2[r] - it.w2[r] / it.e2[r] * de2[r];
-            }
-        for (int q = 0; q < nz; ++q) {
-            dzL[q] = dzU[q] = 0;
-            if (fidx[q] < 0) continue;
-            if (hasL(q)) { const double g = it.z[q] - P.zl[q]; dzL[q] = mu / g - it.zL[q] - it.zL[q] / g * dz[q]; }
-            if (hasU(q)) { const double g = P.zu[q] - it.z[q]; dzU[q] = mu / g - it.zU[q] + it.zU[q] / g * dz[q]; }
-        }
+        ipm_expand_step(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), E.VALS.data(), elim, mu, rho, step);
     };
 
     { const auto tj = now(); grad_and_jt(it); R.t_jt += secs(tj, now()); }
@@ -1058,17 +1254,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             break;
         }
         // eliminate (s, e+, e-) of every path row:  dy = sig_t (J_c dz + r_t)
-        for (int r = 0; r < mc; ++r) {
-            double sg = 0, rh = -it.y[r];
-            if (shasL(r)) { const double g = it.s[r] - cL(r); sg += it.vL[r] / g; rh -= mu / g; }
-            if (shasU(r)) { const double g = cU(r) - it.s[r]; sg += it.vU[r] / g; rh += mu / g; }
-            sig_s[r] = sg;
-            rhat_s[r] = rh;
-            const double a1 = it.e1[r] / it.w1[r], a2 = it.e2[r] / it.w2[r];
-            sig_t[r] = 1.0 / (1.0 / sg + a1 + a2);
-            r_t[r] = row_res(E, it.s, it.e1, it.e2, r) + rh / sg - a1 * (it.y[r] - rho + mu / it.e1[r]) -
-                     a2 * (it.y[r] + rho - mu / it.e2[r]);
-        }
+        ipm_eliminate_rows(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), res_of(E), mu, rho, elim);
         // factor with inertia correction
         bool factored = false;
         double dw = 0.0, dc = 0.0;
@@ -1089,14 +1275,7 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             // the factor of C live with the backend (KktBackend::lowrank): on the device for eMI355X.
             const double* V = E.VALS.data();
             const auto tb0 = now();
-            for (int qq = 0; qq < nz; ++qq) {       // barrier diagonal of every variable (0 where fixed)
-                double sg = 0.0;
-                if (fidx[qq] >= 0) {
-                    if (hasL(qq)) sg += it.zL[qq] / (it.z[qq] - P.zl[qq]);
-                    if (hasU(qq)) sg += it.zU[qq] / (P.zu[qq] - it.z[qq]);
-                }
-                Sigma[qq] = sg;
-            }
+            ipm_barrier_diagonal(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), Sigma.data());     // (0 where fixed)
             int info = KktBackend::NOT_OFFERED;
             if (backend_blocks) {       // assembly, convexification and factorisation by the backend, from the terms
                 Qexact.resize(Qblk.size());
@@ -1256,69 +1435,26 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
         // fraction to the boundary
         double apr = 1.0, adu = 1.0;
         auto step_lengths = [&]() {
-            apr = 1.0;
-            adu = 1.0;
-            for (int q = 0; q < nz; ++q) {
-                if (fidx[q] < 0) continue;
-                if (hasL(q) && dz[q] < 0) apr = std::min(apr, -tau * (it.z[q] - P.zl[q]) / dz[q]);
-                if (hasU(q) && dz[q] > 0) apr = std::min(apr, tau * (P.zu[q] - it.z[q]) / dz[q]);
-                if (dzL[q] < 0) adu = std::min(adu, -tau * it.zL[q] / dzL[q]);
-                if (dzU[q] < 0) adu = std::min(adu, -tau * it.zU[q] / dzU[q]);
-            }
-            for (int r = 0; r < mc; ++r) {
-                if (shasL(r) && ds[r] < 0) apr = std::min(apr, -tau * (it.s[r] - cL(r)) / ds[r]);
-                if (shasU(r) && ds[r] > 0) apr = std::min(apr, tau * (cU(r) - it.s[r]) / ds[r]);
-                if (de1[r] < 0) apr = std::min(apr, -tau * it.e1[r] / de1[r]);
-                if (de2[r] < 0) apr = std::min(apr, -tau * it.e2[r] / de2[r]);
-                if (dvL[r] < 0) adu = std::min(adu, -tau * it.vL[r] / dvL[r]);
-                if (dvU[r] < 0) adu = std::min(adu, -tau * it.vU[r] / dvU[r]);
-                if (dw1[r] < 0) adu = std::min(adu, -tau * it.w1[r] / dw1[r]);
-                if (dw2[r] < 0) adu = std::min(adu, -tau * it.w2[r] / dw2[r]);
-            }
+            ipm_step_lengths(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), step, tau, &apr, &adu);
         };
         step_lengths();
         // l1 merit: directional derivative of the barrier function and the penalty weight
-        double dphi = 0, infeas0 = 0;
-        for (int q = 0; q < nz; ++q) {
-            if (fidx[q] < 0) continue;
-            double g = gradf[q];
-            if (hasL(q)) g -= mu / (it.z[q] - P.zl[q]);
-            if (hasU(q)) g += mu / (P.zu[q] - it.z[q]);
-            dphi += g * dz[q];
-        }
-        for (int r = 0; r < mc; ++r) {
-            double g = 0;
-            if (shasL(r)) g -= mu / (it.s[r] - cL(r));
-            if (shasU(r)) g += mu / (cU(r) - it.s[r]);
-            dphi += g * ds[r] + (rho - mu / it.e1[r]) * de1[r] + (rho - mu / it.e2[r]) * de2[r];
-        }
+        double dphi = 0, infeas0 = 0, mmax = 0;
+        ipm_dphi_mmax(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), gradf.data(), step, rs.data(), mu, rho, &dphi, &mmax);
         const double phi0_base = barrier_merit(it.z, it.s, it.e1, it.e2, E, mu, 0.0, &infeas0);
         // penalty weight of the l1 merit function: what the current multipliers and the descent condition
         // ask for.  It may come down again (at most halving per iteration): the multipliers of the first,
         // far-from-feasible iterations are orders of magnitude above those near the solution, and a weight
         // frozen at that level rejects every step whose constraint curvature shows at all.
-        double mmax = 0;
-        for (int r = 0; r < me; ++r) mmax = std::max(mmax, std::fabs(it.lam[r] + dlam[r]) / rs[r]);
-        for (int r = 0; r < mc; ++r) mmax = std::max(mmax, std::fabs(it.y[r] + dy[r]));
         double nu_want = std::max(1.0, std::min(1.1 * mmax, 1e8));
         if (infeas0 > 0) nu_want = std::max(nu_want, dphi / (0.9 * infeas0) + 1.0);
         nu = std::max(nu_want, 0.5 * nu);
         const double phi0 = phi0_base + nu * infeas0;
         const double slope = dphi - nu * infeas0;
-        auto slack_reset = [&]() {
-            // slack reset: a row's slack may jump to the value that closes its residual whenever
-            // that lowers the merit function (the keep-out rows are strongly curved, and a step
-            // along a keep-out boundary otherwise shows up as an equality residual c - s)
-            for (int r = 0; r < mc; ++r) {
-                const double target = Et.RES[(size_t)md + r] - e1t[r] + e2t[r];
-                const double lo = shasL(r) ? cL(r) : -INF_BOUND, hi = shasU(r) ? cU(r) : INF_BOUND;
-                if (!(target > lo) || !(target < hi)) continue;
-                double keep = nu * std::fabs(target - st[r]), take = 0.0;
-                if (shasL(r)) { keep -= mu * std::log(st[r] - lo); take -= mu * std::log(target - lo); }
-                if (shasU(r)) { keep -= mu * std::log(hi - st[r]); take -= mu * std::log(hi - target); }
-                if (take < keep) st[r] = target;
-            }
-        };
+        // slack reset: a row's slack may jump to the value that closes its residual whenever
+        // that lowers the merit function (the keep-out rows are strongly curved, and a step
+        // along a keep-out boundary otherwise shows up as an equality residual c - s)
+        auto slack_reset = [&]() { ipm_slack_reset(PD, Et.RES.data() + md, e1t.data(), e2t.data(), mu, nu, st.data()); };
         // the iterate after a step of length a_pr (primal: zt, st, e1t, e2t hold the trial point) / a_du (bound
         // multipliers), re-evaluated with derivatives
         auto take_step = [&](double a_pr, double a_du) -> bool {
@@ -1326,26 +1462,9 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             it.s = st;
             it.e1 = e1t;
             it.e2 = e2t;
-            auto clampm = [&](double m, double g) { return std::max(std::min(m, kappa_sigma * mu / g), mu / (kappa_sigma * g)); };
-            for (int r = 0; r < me; ++r) it.lam[r] += a_pr * dlam[r];
-            for (int r = 0; r < mc; ++r) {
-                it.y[r] += a_pr * dy[r];
-                it.vL[r] += a_du * dvL[r];
-                it.vU[r] += a_du * dvU[r];
-                it.w1[r] += a_du * dw1[r];
-                it.w2[r] += a_du * dw2[r];
-                if (shasL(r)) it.vL[r] = clampm(it.vL[r], it.s[r] - cL(r));
-                if (shasU(r)) it.vU[r] = clampm(it.vU[r], cU(r) - it.s[r]);
-                it.w1[r] = clampm(it.w1[r], it.e1[r]);
-                it.w2[r] = clampm(it.w2[r], it.e2[r]);
-            }
-            for (int q = 0; q < nz; ++q) {
-                if (fidx[q] < 0) continue;
-                it.zL[q] += a_du * dzL[q];
-                it.zU[q] += a_du * dzU[q];
-                if (hasL(q)) it.zL[q] = clampm(it.zL[q], it.z[q] - P.zl[q]);
-                if (hasU(q)) it.zU[q] = clampm(it.zU[q], P.zu[q] - it.z[q]);
-            }
+            ipm_update_duals(PD, point_of(it.z, it.s, it.e1, it.e2),
+                             IpmDualsRW{it.lam.data(), it.y.data(), it.zL.data(), it.zU.data(), it.vL.data(), it.vU.data(), it.w1.data(), it.w2.data()},
+                             step, a_pr, a_du, mu);
             if (!evaluate(it.z, E, true)) return false;
             { const auto tj = now(); grad_and_jt(it); R.t_jt += secs(tj, now()); }
             return true;

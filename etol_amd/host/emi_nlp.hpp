@@ -181,6 +181,54 @@ struct BlockMod {
 };
 double convexify_node_blocks(double* Qblk, const unsigned char* fixed, int nv, int M, std::vector<BlockMod>* mods);
 
+// The array arithmetic of one interior-point iteration between two evaluator calls, on plain arrays of one instance (what
+// solve_nlp runs; exposed for the tests and as the host definition of the batched kernels of csrc/emi_ipm.hip).  Index
+// conventions of solve_nlp: variables q = v*M + k, path rows r = j*M + k, equality rows r < ns*M the defects, then `ml`
+// coupling rows.  A variable is fixed where !(zu > zl); a bound is absent at |bound| >= 1e19; path values and row bounds are scaled by sig[j].
+struct IpmDims {
+    int nv = 0, ns = 0, np = 0, M = 0;
+    int ml = 0;                             // equality rows behind the defects (NlpProblem::links: M per coupling row)
+    const double *zl = nullptr, *zu = nullptr;      // [nv*M]
+    const double *cl = nullptr, *cu = nullptr;      // [np] as the caller gave them (what says whether a side is bounded) ...
+    const double *cls = nullptr, *cus = nullptr;    // ... and as the iteration works with them: sig[j] * bound where there is one
+    std::vector<std::vector<std::pair<int, int>>> const* row_vars = nullptr;    // per path row: (variable, VALS entry)
+};
+struct IpmPoint { const double *z, *s, *e1, *e2; };                             // [nv*M], [np*M] x 3
+struct IpmDuals { const double *lam, *y, *zL, *zU, *vL, *vU, *w1, *w2; };       // [ns*M + ml], [np*M], [nv*M] x 2, [np*M] x 4
+struct IpmStep { double *dz, *dlam, *ds, *dy, *de1, *de2, *dzL, *dzU, *dvL, *dvU, *dw1, *dw2; };
+struct IpmElim { double *sig_s, *rhat_s, *sig_t, *r_t; };                       // [np*M] each
+// residuals of the equality rows: RES[ns*M] defects then [np*M] path values, LNK[ml] coupling rows (may be null)
+struct IpmRes { const double *RES, *LNK; };
+// (s, e+, e-) of every path row eliminated:  dy = sig_t (J_c dz + r_t), with the row residual c - s - e1 + e2
+void ipm_eliminate_rows(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const IpmRes& e, double mu, double rho, const IpmElim& out);
+// barrier diagonal of every variable (0 where fixed)
+void ipm_barrier_diagonal(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, double* Sigma);
+// r_t for given row residuals (second-order correction); reads sig_s, rhat_s
+void ipm_fill_rt(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* rowres, double mu, double rho, const IpmElim& el);
+// right-hand side of the reduced system [nv*M + ns*M + ml] (fixed variables: 0) for equality residuals eqres; gradf + jtl is
+// the Lagrangian gradient without the bound multipliers
+void ipm_build_rhs(const IpmDims& P, const IpmPoint& x, const double* gradf, const double* jtl, const double* VALS, const IpmElim& el,
+                   const double* eqres, double mu, double* out);
+// every eliminated step component from st.dz (uses r_t)
+void ipm_expand_step(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* VALS, const IpmElim& el, double mu, double rho,
+                     const IpmStep& st);
+// fraction to the boundary
+void ipm_step_lengths(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const IpmStep& st, double tau, double* apr, double* adu);
+// directional derivative of the barrier function along the step, and the largest multiplier after a full step (rs: row weights)
+void ipm_dphi_mmax(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* gradf, const IpmStep& st, const double* rs,
+                   double mu, double rho, double* dphi, double* mmax);
+// barrier function + nu_t * weighted l1 infeasibility at a point; *infeas (may be null) = the infeasibility
+double ipm_barrier_merit(const IpmDims& P, const IpmPoint& x, const IpmRes& e, double cost, const double* rs, double mu_t, double nu_t,
+                         double rho, double* infeas);
+// a row's slack jumps to the value that closes its residual where that lowers the merit function; s in place
+void ipm_slack_reset(const IpmDims& P, const double* c, const double* e1, const double* e2, double mu, double nu, double* s);
+// multipliers after a step of lengths a_pr / a_du, clamped around mu / gap (kappa_sigma = 1e10); x is the NEW primal point
+struct IpmDualsRW { double *lam, *y, *zL, *zU, *vL, *vU, *w1, *w2; };
+void ipm_update_duals(const IpmDims& P, const IpmPoint& x, const IpmDualsRW& d, const IpmStep& st, double a_pr, double a_du, double mu);
+// scaled KKT error of the barrier problem mu_t; *viol, *emax may be null
+double ipm_kkt_error(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, const double* gradf, const double* jtl, const IpmRes& e,
+                     double mu_t, double rho, double* viol_out, double* emax_out);
+
 // Dense symmetric-indefinite LDL^T (Bunch-Kaufman partial pivoting), lower
 // triangle of a row-major n*n array, in place.  Exposed for the unit tests.
 struct LdltFactor {

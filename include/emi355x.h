@@ -339,6 +339,91 @@ int emi_kkt_blocks_host(emi_ctx_t ctx, const double* H, const double* VALS, cons
 /* rhs [nrhs][N] (one right-hand side after the other) in, solutions out;
  * may be called repeatedly after one factor.                               */
 int emi_kkt_solve(emi_ctx_t ctx, double* rhs, int nrhs);
+/* The same with the right-hand sides in DEVICE memory, solved in place: no copies and no synchronisation, asynchronous on the
+ * context's stream (a Woodbury correction from emi_kkt_lowrank is applied as in emi_kkt_solve).  Same statuses.               */
+int emi_kkt_solve_dev(emi_ctx_t ctx, void* dRhs, int nrhs);
+
+/* ---- the array arithmetic of an interior-point iteration, batched (f64 contexts without delays, ns+nc <= 16) ----------------
+ * What ETOL::eMI355X::solve() runs on the host between two evaluations (host/emi_nlp.cpp, the ipm_* functions), over
+ * [instance][node], device memory in and out.  The NLP of one instance: minimise COST s.t. defects RES[i][k] = 0, path rows
+ * cl_j <= c_j <= cu_j written  c - s - e1 + e2 = 0  with a slack s in [cl, cu] and elastics e1, e2 > 0 weighted rho, and variable
+ * bounds zl <= z <= zu.  All arrays node index fastest, B = the context's batch, nv = ns + nc:
+ *   point        X[B][ns][M], U[B][nc][M], S, E1, E2 [B][np][M]
+ *   multipliers  LamF[B][ns][M] (defects), Y[B][np][M] (rows), ZL, ZU [B][nv][M], VL, VU (slack bounds), W1, W2 (elastics) [B][np][M]
+ *   step         DZLam[B][nv+ns][M] in the unknown order of emi_kkt_factor (variables, then defect multipliers): the right-hand
+ *                side going into emi_kkt_solve_dev and the solution coming out; DS, DY, DE1, DE2, DVL, DVU, DW1, DW2 [B][np][M],
+ *                DZL, DZU [B][nv][M]
+ *   bounds       zl, zu [nsets][nv][M], nsets 1 or B (zl == zu fixes a variable, |bound| >= 1e19: absent: the certificate's
+ *                convention); cl, cu, cscale: [np] HOST arrays in both forms, cscale NULL = 1.  The kernels read path values and
+ *                their partials as cscale[j] RES and cscale[j] VALS and the row bounds as cscale[j] cl, cscale[j] cu; the caller
+ *                forms G with LamC = cscale Y.
+ *   par[B][4]    = {mu, rho, tau, nu} per instance (device)
+ *   path-row partials: the (variable, VALS entry) list of emi_kkt_blocks_rows, without one the record table's default.
+ * With g- = z - zl, g+ = zu - z (a term is absent with its bound), c = cscale RES[ns+j], lo = cscale cl, hi = cscale cu:
+ * emi_ipm_reduce   sig_s = VL/(s-lo) + VU/(hi-s);  rhat_s = -Y - mu/(s-lo) + mu/(hi-s);  a1 = E1/W1, a2 = E2/W2;
+ *                  SigT = 1/(1/sig_s + a1 + a2);   Rt = rowres + rhat_s/sig_s - a1 (Y - rho + mu/E1) - a2 (Y + rho - mu/E2)
+ *                  with rowres = RowRes, or c - s - e1 + e2 when RowRes is NULL;   Sigma = ZL/g- + ZU/g+ (0 where fixed);
+ *                  Rhs[v] = -(G - mu/g- + mu/g+) - sum over the partials of v: cscale VALS[e] SigT Rt (0 where fixed);
+ *                  Rhs[nv+i] = -DefRes[i], or -RES[i] when DefRes is NULL.  Sigma and SigT are what emi_kkt_blocks_dev takes.
+ * emi_ipm_expand   dz of fixed variables set to 0 in place;  DY = SigT (sum cscale VALS[e] dz[var] + Rt);  DS = (DY - rhat_s)/sig_s;
+ *                  DE1 = a1 (DY + Y - rho + mu/E1);  DE2 = a2 (-DY - Y - rho + mu/E2);  DVL = mu/(s-lo) - VL - VL/(s-lo) DS;
+ *                  DVU = mu/(hi-s) - VU + VU/(hi-s) DS;  DW1 = mu/E1 - W1 - W1/E1 DE1 (DW2 alike);  DZL = mu/g- - ZL - ZL/g- dz;
+ *                  DZU = mu/g+ - ZU + ZU/g+ dz;   scal[B][4] = {apr, adu, dphi, mmax}: the fraction-to-the-boundary lengths for
+ *                  tau (primal: z, s, e1, e2; dual: every bound multiplier; both <= 1), dphi = sum (costgrad - mu/g- + mu/g+) dz
+ *                  + (-mu/(s-lo) + mu/(hi-s)) DS + (rho - mu/E1) DE1 + (rho - mu/E2) DE2,  mmax = max(|LamF + dlam| / rs, |Y + DY|);
+ *                  rs[B][ns][M]: row weights of the merit function, NULL = 1.
+ * emi_ipm_trial    trial = point + alpha[b] step  (alpha[B] device)
+ * emi_ipm_merit    reset != 0 first: S[r] <- t = c - e1 + e2 where lo < t < hi and the barrier terms of t are below those of S[r]
+ *                  plus nu |t - S[r]| (S in place).  out[B][2] = {phi, infeas}:  phi = COST - mu sum log(g-, g+, s-lo, hi-s, e1, e2)
+ *                  + rho sum (e1 + e2),  infeas = sum |c - s - e1 + e2| + sum rs |RES[i]|.  A point outside a bound gives a
+ *                  non-finite phi for THAT instance (the line search rejects it); no other instance is touched.
+ * emi_ipm_accept   point <- trial;  LamF += a_pr dlam, Y += a_pr DY;  ZL, ZU, VL, VU, W1, W2 += a_du (their steps), each then
+ *                  clamped to [mu / (1e10 gap), 1e10 mu / gap] with the gap at the new point.  a_pr, a_du [B] device; mask[B] bytes
+ *                  (NULL: all): instances with mask 0 keep every bit.  Fixed variables keep ZL, ZU.
+ * emi_ipm_error    out[B][3] = {kkt_error, viol, emax} of the barrier problem mu = par.mu:  ed = max |G - ZL + ZU|, |-Y - VL + VU|,
+ *                  |rho - Y - W1|, |rho + Y - W2|;  ep = viol = max |RES[i]|, |c - s - e1 + e2|;  ec = max |gap multiplier - mu|;
+ *                  sd = max(100, (sum |LamF| + sum |Y| + sumz) / (ns M + np M + cnt)) / 100,  sc = max(100, sumz / cnt) / 100 with
+ *                  sumz the sum and cnt the number of positive bound multipliers (W1, W2 always counted);
+ *                  kkt_error = max(ed / sd, ep, ec / sc);  emax = max(E1, E2).
+ * Sums are added per thread, across the wave, across the workgroup and then over the workgroups of an instance in a fixed order:
+ * two calls give the same bits.  The _dev forms are asynchronous on the context's stream; the _host forms take the same structs
+ * holding HOST arrays of doubles, copy in, run the _dev form, copy out what it writes, and synchronise.
+ * EMI_ERR_UNSUPPORTED: f32 context, delays set (emi_set_delays), ns+nc > 16;  EMI_ERR_ARG: a NULL argument that is not optional. */
+typedef struct emi_ipm_point { void *X, *U, *S, *E1, *E2; } emi_ipm_point_t;
+typedef struct emi_ipm_duals { void *LamF, *Y, *ZL, *ZU, *VL, *VU, *W1, *W2; } emi_ipm_duals_t;
+typedef struct emi_ipm_step { void *DZLam, *DS, *DY, *DE1, *DE2, *DZL, *DZU, *DVL, *DVU, *DW1, *DW2; } emi_ipm_step_t;
+typedef struct emi_ipm_elim { void *Sigma, *SigT, *SigS, *RhatS, *Rt; } emi_ipm_elim_t;    /* [B][nv][M], then [B][np][M] x 4 */
+typedef struct emi_ipm_bounds { const void *zl, *zu; int nsets; const double *cl, *cu, *cscale; } emi_ipm_bounds_t;
+int emi_ipm_reduce_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES, const void* dVALS,
+                       const void* dG, const emi_ipm_bounds_t* bd, const void* dPar, const void* dDefRes, const void* dRowRes,
+                       const emi_ipm_elim_t* out, void* dRhs);
+int emi_ipm_expand_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dVALS,
+                       const emi_ipm_bounds_t* bd, const void* dPar, const emi_ipm_elim_t* el, const void* dRs,
+                       const emi_ipm_step_t* st, void* dScal);
+int emi_ipm_trial_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_step_t* st, const void* dAlpha,
+                      const emi_ipm_point_t* trial);
+int emi_ipm_merit_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const void* dRES, const void* dCOST, const emi_ipm_bounds_t* bd,
+                      const void* dPar, const void* dRs, int reset, void* dOut);
+int emi_ipm_accept_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_point_t* trial, const emi_ipm_duals_t* du,
+                       const emi_ipm_step_t* st, const emi_ipm_bounds_t* bd, const void* dPar, const void* dApr, const void* dAdu,
+                       const void* dMask);
+int emi_ipm_error_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES, const void* dG,
+                      const emi_ipm_bounds_t* bd, const void* dPar, void* dOut);
+int emi_ipm_reduce_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* VALS,
+                        const double* G, const emi_ipm_bounds_t* bd, const double* par, const double* DefRes, const double* RowRes,
+                        const emi_ipm_elim_t* out, double* Rhs);
+int emi_ipm_expand_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* VALS,
+                        const emi_ipm_bounds_t* bd, const double* par, const emi_ipm_elim_t* el, const double* rs,
+                        const emi_ipm_step_t* st, double* scal);
+int emi_ipm_trial_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_step_t* st, const double* alpha,
+                       const emi_ipm_point_t* trial);
+int emi_ipm_merit_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const double* RES, const double* COST, const emi_ipm_bounds_t* bd,
+                       const double* par, const double* rs, int reset, double* out);
+int emi_ipm_accept_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_point_t* trial, const emi_ipm_duals_t* du,
+                        const emi_ipm_step_t* st, const emi_ipm_bounds_t* bd, const double* par, const double* a_pr,
+                        const double* a_du, const unsigned char* mask);
+int emi_ipm_error_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* G,
+                       const emi_ipm_bounds_t* bd, const double* par, double* out);
 
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,
