@@ -47,6 +47,11 @@ EMI_DEV float emi_log(float a) { return logf(a); }
 EMI_DEV float emi_sqrt(float a) { return sqrtf(a); }
 EMI_DEV float emi_pow(float a, float c) { return powf(a, c); }
 
+// The cost integrands below are compiled with contraction OFF (#pragma clang fp contract(off): every product and sum rounded by
+// itself): left to the compiler, which products of L are fused depends on what else the kernel computes -- grad() shares w * u with cost() in the full node kernel and not
+// in the values-only one -- and COST of EVAL_ALL | EVAL_NOJAC came out an fp32 ulp or two off COST of EVAL_ALL.
+// (The built-in models only: the cost of a traced model is generated text and keeps the compiler's choice.)
+
 // ---------------------------------------------------------------------------
 // 2-state single integrator: reference etol_psopt_example1.cpp
 //   dxdt :116-126 (xdot = u0), dydt :128-138 (ydot = u1),
@@ -65,6 +70,7 @@ template <typename T> struct PointMass2D {
         J[1][3] = T(1);
     }
     EMI_DEV static T cost(const ModelParams<T>&, const T* z, T) {
+#pragma clang fp contract(off)
         return z[2] * z[2] + z[3] * z[3];
     }
     EMI_DEV static void grad(const ModelParams<T>&, const T* z, T, T* g) {
@@ -117,6 +123,7 @@ template <typename T> struct Quadrotor2D {
         J[5][7] = T(1) / P.p[1];
     }
     EMI_DEV static T cost(const ModelParams<T>& P, const T* z, T) {
+#pragma clang fp contract(off)
         return P.p[3] * z[6] * z[6] + P.p[4] * z[7] * z[7];
     }
     EMI_DEV static void grad(const ModelParams<T>& P, const T* z, T, T* g) {
@@ -257,6 +264,7 @@ template <typename T> struct FixedWing12 {
         J[11][15] = qS * P.p[12] / Izz;
     }
     EMI_DEV static T cost(const ModelParams<T>& P, const T* z, T) {
+#pragma clang fp contract(off)
         return P.p[15] * (z[12] * z[12] + z[13] * z[13] + z[14] * z[14] + z[15] * z[15]);
     }
     EMI_DEV static void grad(const ModelParams<T>& P, const T* z, T, T* g) {

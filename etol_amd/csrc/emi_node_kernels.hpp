@@ -87,6 +87,18 @@ template <class Model> EMI_DEV constexpr int emi_traced_partials() {
     else return 0;
 }
 
+// a * b + c in ONE rounding, spelled out.  The path rows use it for every sum of products: left to the compiler, which products of
+// `dx * dx + dy * dy` are fused depends on the code around them (the two nodes of one thread came out differently -- one packed
+// multiply and an add, one fma -- and the values-only kernel differently from the full one), so the same row differed by an ulp
+// between EVAL_ALL and EVAL_ALL | EVAL_NOJAC.  Written this way the table rows (disc, ellipse, track) and the sum w_k L_k round alike in
+// every instantiation.  NOT covered: Model::f / jac / grad and `-h * fe` are still contracted as the compiler sees fit (their bits agree
+// between the instantiations today, which tests/test_gpu_f32.py checks for the quadrotor and the fixed wing only), and so are the
+// path rows and the cost of traced models, whose text is generated (host/emi_trace.cpp).
+template <typename T> EMI_DEV T fma1(T a, T b, T c) {
+    if constexpr (sizeof(T) == 4) return __builtin_fmaf(a, b, c);
+    else return __builtin_fma(a, b, c);
+}
+
 // wave64 sum (all lanes end with lane 0 holding the total)
 template <typename T> EMI_DEV T wave_sum(T v) {
 #pragma unroll
@@ -156,7 +168,7 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
 #pragma unroll
                     for (int i = 0; i < NS; ++i) fo[i][e] = -h * fe[i];
                 }
-                lsum += wk[e] * Model::cost(a.P, ze, tk[e]);
+                lsum = fma1(wk[e], Model::cost(a.P, ze, tk[e]), lsum);
             }
             if constexpr (DEFROWS && DEFATOMIC) {
 #pragma unroll
@@ -228,7 +240,7 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const T dx = px[e] - xc, dy = py[e] - yc;
-                        c[e] = (dx * dx + dy * dy) * T(-1) + rsq;
+                        c[e] = rsq - fma1(dx, dx, dy * dy);
                         cx[e] = T(-2) * dx;
                         cy[e] = T(-2) * dy;
                     }
@@ -238,11 +250,11 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const T dx = px[e] - xc, dy = py[e] - yc;
-                        const T delx = ct * dx - st * dy;
-                        const T dely = st * dx + ct * dy;
-                        c[e] = asq * bsq - (bsq * (delx * delx) + asq * (dely * dely));
-                        cx[e] = T(-2) * (bsq * delx * ct + asq * dely * st);
-                        cy[e] = T(-2) * (-bsq * delx * st + asq * dely * ct);
+                        const T delx = fma1(ct, dx, -(st * dy));
+                        const T dely = fma1(st, dx, ct * dy);
+                        c[e] = fma1(asq, bsq, -fma1(bsq, delx * delx, asq * (dely * dely)));
+                        cx[e] = T(-2) * fma1(bsq * delx, ct, asq * dely * st);
+                        cy[e] = T(-2) * fma1(asq * dely, ct, -(bsq * delx * st));
                     }
                 } else {  // EMI_PATH_TRACK: centre tabulated at the node times
                     const int trk = (int)r[1];
@@ -255,7 +267,7 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const T dx = px[e] - xc[e], dy = py[e] - yc[e];
-                        c[e] = (dx * dx + dy * dy) * T(-1) + rsq;
+                        c[e] = rsq - fma1(dx, dx, dy * dy);
                         cx[e] = T(-2) * dx;
                         cy[e] = T(-2) * dy;
                     }
