@@ -109,6 +109,10 @@ SYMBOLS = {
     "emi_kkt_solve_refined": (C.c_int, [_P, _D, C.c_double, C.c_int, _D, _I, _I, _I]),
     "emi_kkt_solve_refined_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), _D, C.c_int, _D, _I, _I, _I]),
     "emi_kkt_lowrank": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _D, _D, C.POINTER(C.c_int)]),
+    "emi_kkt_factor_shard_dev": (C.c_int, [_P, _P, _P, _P, _D, C.POINTER(C.c_ubyte), _I]),
+    "emi_kkt_lowrank_shard_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_ubyte), _I]),
+    "emi_kkt_solve_shard_dev": (C.c_int, [_P, _P, C.POINTER(C.c_ubyte)]),
+    "emi_kkt_solve_refined_shard_dev": (C.c_int, [_P, _P, C.POINTER(C.c_ubyte), _D, C.c_int, _D, _I, _I, _I]),
     "emi_set_batch": (C.c_int, [_P, C.c_int]),
     "emi_set_path": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.c_int]),
     "emi_set_tracks": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),

@@ -66,6 +66,7 @@ struct emi_ctx_s {
     int model = -1, ns = 0, nc = 0, maximize = 0;
     double params[EMI_MAX_PARAMS] = {0};
     emi::KktWorkspace* kkt = nullptr;   // Newton-step workspace (emi_kkt_factor)
+    std::vector<emi::KktWorkspace*> kkt_shard;  // one more per instance of the batch (emi_kkt_*_shard_dev), created on demand; apart from `kkt`
     int kkt_method = 1;                 // 1: Schur complement + Cholesky (falls back to 0 if not quasi-definite); 0: LU of K
     emi::RtcModel* rtc = nullptr;   // model == EMI_MODEL_SOURCE: code object compiled at emi_set_model_source
     // batch / path
@@ -159,6 +160,7 @@ struct emi_ctx_s {
         if (own_stream && stream) (void)hipStreamDestroy(stream);
         emi::rtc_destroy(rtc);
         emi::kkt_destroy(kkt);
+        for (emi::KktWorkspace* w : kkt_shard) emi::kkt_destroy(w);
     }
 };
 
@@ -1069,6 +1071,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     c->delay_dirty = true;      // W(delay) is built for one mesh: [nd][M][M] on these nodes and this horizon
     c->adjw_dirty = true;
     emi::kkt_mesh_changed(c->kkt);
+    for (emi::KktWorkspace* w : c->kkt_shard) emi::kkt_mesh_changed(w);
     // tables sized by M are stale now
     c->ntracks = 0;
     c->track_sets = 0;
@@ -2344,6 +2347,161 @@ static int kkt_solve_from(emi_ctx_t c, void* rhs, int nrhs, bool on_device) {
 int emi_kkt_solve(emi_ctx_t c, double* rhs, int nrhs) { return kkt_solve_from(c, rhs, nrhs, false); }
 
 int emi_kkt_solve_dev(emi_ctx_t c, void* dRhs, int nrhs) { return kkt_solve_from(c, dRhs, nrhs, true); }
+
+// ---- the Newton steps of a context's whole batch, device arrays in and out (the workspaces of c->kkt_shard) ------------------
+namespace {
+
+int shard_check(emi_ctx_t c, const char* what) {
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: f64 contexts only", what);
+    if (c->M <= 0 || c->model < 0 || c->B <= 0) return fail(c, EMI_ERR_STATE, "%s: mesh, model and batch must be set", what);
+    if (c->points_only) return fail(c, EMI_ERR_STATE, "%s: the mesh has no differentiation matrix", what);
+    if (c->nch > 0) return fail(c, EMI_ERR_UNSUPPORTED, "%s: contexts without delays only", what);
+    if (c->ns + c->nc > 16) return fail(c, EMI_ERR_UNSUPPORTED, "%s: node blocks of up to 16 variables (this model has %d)", what, c->ns + c->nc);
+    if (c->kkt_method != 1)
+        return fail(c, EMI_ERR_UNSUPPORTED, "%s: the context is set to the LU method (\"kkt_method\" 0): emi_kkt_factor_dev per instance", what);
+    return EMI_OK;
+}
+
+// the unmasked instances of the batch; need > 0: every one of them must hold a factorisation for the context's mesh and model
+// (1: any, 2: of the Schur path)
+int shard_members(emi_ctx_t c, const char* what, const unsigned char* mask, int need, std::vector<int>& inst) {
+    const int nv = c->ns + c->nc;
+    for (int b = 0; b < c->B; ++b) {
+        if (mask && !mask[b]) continue;
+        if (need) {
+            const int held = b < (int)c->kkt_shard.size() ? emi::kkt_holds(c->kkt_shard[b], c->M, c->ns, nv) : 0;
+            if (held == 0)
+                return fail(c, EMI_ERR_STATE, "%s: instance %d holds no factorisation for this mesh and model (emi_kkt_factor_shard_dev)", what, b);
+            if (need == 2 && held != 1)
+                return fail(c, EMI_ERR_UNSUPPORTED, "%s: instance %d holds no factorisation of the Schur path (the LU fallback is refined by "
+                                                    "the caller: emi_kkt_solve_shard_dev)", what, b);
+        }
+        inst.push_back(b);
+    }
+    return EMI_OK;
+}
+
+}  // namespace
+
+int emi_kkt_factor_shard_dev(emi_ctx_t c, const void* dQ, const void* dVALS, const void* dFixed, const double* dc, const unsigned char* mask,
+                             int* info) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(shard_check(c, "emi_kkt_factor_shard_dev"));
+    if (!dQ || !dVALS || !dFixed || !dc || !info) return fail(c, EMI_ERR_ARG, "emi_kkt_factor_shard_dev: null argument");
+    std::vector<int> inst;
+    EMI_TRY(shard_members(c, "emi_kkt_factor_shard_dev", mask, 0, inst));
+    for (int b : inst)
+        if (!(dc[b] >= 0.0)) return fail(c, EMI_ERR_ARG, "emi_kkt_factor_shard_dev: dc[%d] = %g", b, dc[b]);
+    if (inst.empty()) return EMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((int)c->kkt_shard.size() < c->B) c->kkt_shard.resize((size_t)c->B, nullptr);
+    const int n = (int)inst.size(), M = c->M, ns = c->ns, nv = c->ns + c->nc, nh = nv * (nv + 1) / 2;
+    const size_t vals_stride = (size_t)nvals_of(c) * M;
+    std::vector<emi::KktWorkspace**> pws(n);
+    std::vector<const double*> dD(n, (const double*)c->d_D.p);
+    std::vector<double> dcs(n);
+    std::vector<int> inf(n, -1);
+    for (int a = 0; a < n; ++a) { pws[a] = &c->kkt_shard[inst[a]]; dcs[a] = dc[inst[a]]; }
+    const emi::KktShardSrc src{(const double*)dQ, (const double*)dVALS, (const unsigned char*)dFixed, vals_stride, inst.data()};
+    std::string err;
+    int st = emi::kkt_factor_batch(n, pws.data(), c->stream, dD.data(), M, ns, nv, nullptr, nullptr, nullptr, dcs.data(), inf.data(), &err, &src);
+    if (st) { c->err = err; return st; }
+    // instances the batch could not take (a node block not positive definite, the ladder exhausted): the single path with its LU,
+    // on the instance's own workspace and slices
+    for (int a = 0; a < n; ++a) {
+        const int b = inst[a];
+        if (inf[a] < 0) {
+            st = emi::kkt_factor(&c->kkt_shard[b], c->stream, (const double*)c->d_D.p, M, ns, nv, (const double*)dQ + (size_t)b * nh * M,
+                                 (const double*)dVALS + (size_t)b * vals_stride, (const unsigned char*)dFixed + (size_t)b * nv * M, dc[b], 1,
+                                 &inf[a], &err, true);
+            if (st) { c->err = err; return st; }
+        }
+        info[b] = inf[a];
+    }
+    return EMI_OK;
+}
+
+int emi_kkt_lowrank_shard_dev(emi_ctx_t c, int max_mods, const void* dCount, const void* dNode, const void* dDelta, const void* dVec,
+                              const unsigned char* mask, int* exact) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(shard_check(c, "emi_kkt_lowrank_shard_dev"));
+    if (max_mods < 0 || !exact || (max_mods > 0 && (!dCount || !dNode || !dDelta || !dVec)))
+        return fail(c, EMI_ERR_ARG, "emi_kkt_lowrank_shard_dev: bad argument");
+    std::vector<int> inst;
+    EMI_TRY(shard_members(c, "emi_kkt_lowrank_shard_dev", mask, 1, inst));
+    if (inst.empty()) return EMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int n = (int)inst.size();
+    std::vector<int> all((size_t)c->B, 0), cnt(n, 0), ex(n, 0);
+    if (max_mods > 0) {             // the counts: the one download of this call
+        HIP_TRY(c, hipMemcpyAsync(all.data(), dCount, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<emi::KktWorkspace*> ws(n);
+    for (int a = 0; a < n; ++a) {
+        ws[a] = c->kkt_shard[inst[a]];
+        // max_mods == 0 clears: no list is read, every instance is taken as unmodified (exact, no correction), as emi_kkt_lowrank with r = 0
+        cnt[a] = max_mods > 0 ? std::max(all[inst[a]], 0) : 0;
+    }
+    std::string err;
+    const int st = emi::kkt_lowrank_shard(n, ws.data(), c->stream, max_mods, inst.data(), cnt.data(), (const int*)dNode, (const double*)dDelta,
+                                          (const double*)dVec, ex.data(), &err);
+    if (st) { c->err = err; return st; }
+    for (int a = 0; a < n; ++a) exact[inst[a]] = ex[a];
+    return EMI_OK;
+}
+
+int emi_kkt_solve_shard_dev(emi_ctx_t c, void* dRhs, const unsigned char* mask) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(shard_check(c, "emi_kkt_solve_shard_dev"));
+    if (!dRhs) return fail(c, EMI_ERR_ARG, "emi_kkt_solve_shard_dev: null argument");
+    std::vector<int> inst;
+    EMI_TRY(shard_members(c, "emi_kkt_solve_shard_dev", mask, 1, inst));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int nv = c->ns + c->nc, nz = nv * c->M;
+    const size_t N = (size_t)(nv + c->ns) * c->M;
+    // instances that hold the LU fallback go through the single solve; the rest as one batch
+    std::vector<emi::KktWorkspace*> ws;
+    std::vector<double*> rb;
+    std::string err;
+    for (int b : inst) {
+        emi::KktWorkspace* w = c->kkt_shard[b];
+        double* x = (double*)dRhs + (size_t)b * N;
+        if (emi::kkt_is_schur(w)) { ws.push_back(w); rb.push_back(x); }
+        else if (int st = emi::kkt_solve(w, c->stream, nz, x, 1, &err, true)) { c->err = err; return st; }
+    }
+    if (ws.empty()) return EMI_OK;
+    const int st = emi::kkt_solve_batch((int)ws.size(), ws.data(), c->stream, nz, rb.data(), &err, true);
+    if (st) c->err = err;
+    return st;
+}
+
+int emi_kkt_solve_refined_shard_dev(emi_ctx_t c, void* dRhs, const unsigned char* mask, const double* dc_nominal, int max_steps, double* rel,
+                                    int* nsolve, int* reverted, int* status) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(shard_check(c, "emi_kkt_solve_refined_shard_dev"));
+    if (!dRhs || !dc_nominal || !rel || !nsolve || !reverted || !status || max_steps < 0)
+        return fail(c, EMI_ERR_ARG, "emi_kkt_solve_refined_shard_dev: bad argument");
+    std::vector<int> inst;
+    EMI_TRY(shard_members(c, "emi_kkt_solve_refined_shard_dev", mask, 2, inst));
+    for (int b : inst)
+        if (!(dc_nominal[b] >= 0.0)) return fail(c, EMI_ERR_ARG, "emi_kkt_solve_refined_shard_dev: dc_nominal[%d] = %g", b, dc_nominal[b]);
+    if (inst.empty()) return EMI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int n = (int)inst.size();
+    const size_t N = (size_t)(2 * c->ns + c->nc) * c->M;
+    std::vector<emi::KktWorkspace*> ws(n);
+    std::vector<double*> rb(n);
+    std::vector<double> dcn(n), r(n);
+    std::vector<int> nsv(n), rev(n), sta(n);
+    for (int a = 0; a < n; ++a) { ws[a] = c->kkt_shard[inst[a]]; rb[a] = (double*)dRhs + (size_t)inst[a] * N; dcn[a] = dc_nominal[inst[a]]; }
+    std::string err;
+    const int st = emi::kkt_solve_refined_batch(n, ws.data(), c->stream, rb.data(), dcn.data(), max_steps, r.data(), nsv.data(), rev.data(),
+                                                sta.data(), &err, true);
+    if (st) { c->err = err; return st; }
+    for (int a = 0; a < n; ++a) { rel[inst[a]] = r[a]; nsolve[inst[a]] = nsv[a]; reverted[inst[a]] = rev[a]; status[inst[a]] = sta[a]; }
+    return EMI_OK;
+}
 
 int emi_timer_start(emi_ctx_t c) {
     if (!c) return EMI_ERR_ARG;

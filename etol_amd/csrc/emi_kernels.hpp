@@ -169,11 +169,25 @@ void kkt_last_regularisation(const KktWorkspace* w, double* dc, double* dw);
 void kkt_mesh_changed(KktWorkspace* w);
 bool kkt_is_schur(const KktWorkspace* w);            // holds a factorisation of the Schur path (what the batched solve takes)
 // the Newton steps of n scenarios on one mesh at once (emi_kkt.hip, "Batched entry points")
+// src != nullptr: the blocks of scenario b are instance src->inst[b] of one context's device arrays (Qblk / Jblk / fixed unused)
+struct KktShardSrc {
+    const double* Q;            // [B][nh][M]
+    const double* VALS;         // [B][nvals][M]: the first ns nv rows of an instance are its Jacobian node entries
+    const unsigned char* fixed; // [B][nv][M]
+    size_t vals_stride;         // nvals M
+    const int* inst;            // [n]
+};
 int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const double* const* dD, int M, int ns, int nv,
                      const double* const* Qblk, const double* const* Jblk, const unsigned char* const* fixed, const double* dc, int* info,
-                     std::string* err);
-int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, double* const* rhs, std::string* err);
+                     std::string* err, const KktShardSrc* src = nullptr);
+// rhs_on_device: rhs[b] are device arrays, solved in place (kkt_solve_batch then does not synchronise)
+int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, double* const* rhs, std::string* err,
+                    bool rhs_on_device = false);
 int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, double* const* rhs, const double* dc_nominal, int max_steps,
-                            double* rel, int* nsolve, int* reverted, int* status, std::string* err);
+                            double* rel, int* nsolve, int* reverted, int* status, std::string* err, bool rhs_on_device = false);
+// the instances of one context (emi_kkt_*_shard_dev)
+int kkt_holds(const KktWorkspace* w, int M, int ns, int nv);      // 0 nothing for this shape, 1 Schur factorisation, 2 LU
+int kkt_lowrank_shard(int n, KktWorkspace* const* ws, hipStream_t stream, int max_mods, const int* inst, const int* count, const int* dNode,
+                      const double* dDelta, const double* dVec, int* exact, std::string* err);
 
 }  // namespace emi

@@ -137,6 +137,7 @@ struct KktWorkspace {
     // low-rank correction (kkt_lowrank)
     bool lr_active = false;
     int lr_r = 0, lr_cap = 0;           // columns in use, columns allocated
+    int lr_ld = 0;                      // leading dimension of lrC (lr_r, or the shard's common padded order: kkt_lowrank_shard)
     DeviceArray<double> lrY;            // [N][r]  K~^-1 U
     DeviceArray<double> lrC;            // [r][r]  Cholesky factor of Delta^-1 - U^T Y
     DeviceArray<double> lrT;            // [r][<=64] work
@@ -153,6 +154,13 @@ struct KktWorkspace {
     DeviceArray<double*> b_ptrs;        // device: pointer arrays of the batched rocBLAS calls
     DeviceArray<unsigned char> b_stat;  // device: [2 n] info words, then block flags (factorisation); [4 n] doubles (refined solves)
     PinnedArray<char> b_pin;            // pinned host staging of all three
+    // a call that does not end with a synchronisation (kkt_solve_batch on device arrays) leaves its upload from b_pin in flight:
+    // the next user of the staging waits for this event first (batch_scratch)
+    hipEvent_t b_up_ev = nullptr;
+    bool b_up_pending = false;
+    // device-array forms of the batched solves: where this scenario's right-hand side lives for the duration of ONE call (the
+    // caller's array instead of rhs / ref_b; set and cleared by that call)
+    double *ext_rhs = nullptr, *ext_bb = nullptr;
 };
 
 namespace {
@@ -478,6 +486,49 @@ __global__ void emi_kkt_lr_utx_kernel(double* __restrict__ T, const double* __re
     const double* x = X + (size_t)c * N + node[a];
     for (int v = 0; v < nv; ++v) dot += vec[(size_t)a * nv + v] * x[(size_t)v * M];
     T[(size_t)c * r + a] = dot;
+}
+
+// The same three for a whole shard (kkt_lowrank_shard): blockIdx.y (.z for C) is the entry of a table, every entry with its own
+// column count r.  The lists come straight from emi_kkt_blocks_dev ([B][max_mods] node and delta, [B][max_mods][nv] vec, ordered
+// by node); the scatter kernel also keeps the workspace's own copy of them, since the caller's arrays are rewritten by the next
+// emi_kkt_blocks_dev while the correction lives on.  One writer per entry, no atomics.
+struct KktLrDev {
+    double *Y, *C;              // [N][r] and [ld][ld] of the workspace
+    int* node;                  // the workspace's copies of the lists ...
+    double *vec, *delta;
+    const int* src_node;        // ... and the caller's, at this instance
+    const double *src_vec, *src_delta;
+    int r;
+};
+__global__ __launch_bounds__(64) void emi_kkt_lr_scatter_b_kernel(const KktLrDev* __restrict__ tab, int N, int M, int nv) {
+    const KktLrDev t = tab[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= t.r) return;
+    const int k = t.src_node[c];
+    const bool ok = k >= 0 && k < M;        // (a column that names no node of the mesh becomes a zero column with delta = 1: C gets a 1 on its diagonal)
+    t.node[c] = ok ? k : 0;
+    t.delta[c] = ok ? t.src_delta[c] : 1.0;
+    for (int v = 0; v < nv; ++v) {
+        const double u = ok ? t.src_vec[(size_t)c * nv + v] : 0.0;
+        t.vec[(size_t)c * nv + v] = u;
+        if (ok) t.Y[(size_t)c * N + (size_t)v * M + k] = u;
+    }
+}
+// C padded to the common order ld of the shard: the identity on the diagonal behind r, zero elsewhere (C_pad is positive definite
+// iff C is, and its Cholesky factor holds the factor of C in its leading r x r block)
+__global__ void emi_kkt_lr_c_b_kernel(const KktLrDev* __restrict__ tab, int ld, int N, int M, int nv) {
+    const KktLrDev t = tab[blockIdx.z];
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y * blockDim.y + threadIdx.y;
+    if (a >= ld || c >= ld) return;
+    double val = a == c ? 1.0 : 0.0;
+    if (a < t.r && c < t.r) {
+        double dot = 0;
+        const double* y = t.Y + (size_t)c * N + t.node[a];
+        for (int v = 0; v < nv; ++v) dot += t.vec[(size_t)a * nv + v] * y[(size_t)v * M];
+        val = (a == c ? 1.0 / t.delta[a] : 0.0) - dot;
+    }
+    t.C[(size_t)c * ld + a] = val;
 }
 
 // ---- blocked Cholesky (lower, column-major, in place) ---------------------------------------------------
@@ -851,6 +902,8 @@ struct KktDev {                 // device pointers of one workspace, as the batc
     const int* lr_node;         // low-rank correction of the scenario (lr_r = 0: none active)
     const double *lr_vec, *lr_delta;
     int lr_r;
+    double* lrT;                // ... and where its U^T x goes (emi_kkt_lr_utx_b_kernel)
+    int inst;                   // shard forms: the instance of the caller's [B][.][M] arrays this entry stands for
     const double* Doff;
     unsigned char* fixed;
     int *flag, *info;
@@ -971,6 +1024,32 @@ __global__ __launch_bounds__(256) void emi_trsv_update_kernel(const double* __re
 __global__ __launch_bounds__(256) void emi_trsv_update_b_kernel(const KktDev* __restrict__ tab, int lda, int j0, int bs, int rest) {
     const KktDev t = tab[blockIdx.y];
     emi_trsv_update_kernel_body(t.S + (size_t)j0 * lda + j0 + bs, lda, rest, bs, t.y + j0, t.Cb + j0 + bs);
+}
+// T = U^T x of every scenario of the table that holds a low-rank correction (emi_kkt_lr_utx_kernel with blockIdx.y = scenario)
+__global__ __launch_bounds__(64) void emi_kkt_lr_utx_b_kernel(const KktDev* __restrict__ tab, int M, int nv) {
+    const KktDev t = tab[blockIdx.y];
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= t.lr_r) return;
+    double dot = 0;
+    const double* x = t.rhs + t.lr_node[a];
+    for (int v = 0; v < nv; ++v) dot += t.lr_vec[(size_t)a * nv + v] * x[(size_t)v * M];
+    t.lrT[a] = dot;
+}
+// the node blocks of a shard into the workspaces of its instances (kkt_factor_batch on device arrays): blockIdx.y = table entry,
+// one thread per node walks the rows of the packed triangle, of the Jacobian and of the fixed bytes -- every access of a wave is a
+// run of consecutive elements along the node axis
+__global__ __launch_bounds__(256) void emi_kkt_gather_blocks_b_kernel(const KktDev* __restrict__ tab, const double* __restrict__ Q,
+                                                                     const double* __restrict__ VALS, const unsigned char* __restrict__ fixed,
+                                                                     int M, int nh, int nj, int nv, size_t vals_stride) {
+    const KktDev t = tab[blockIdx.y];
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= M) return;
+    const double* q = Q + (size_t)t.inst * nh * M;
+    const double* j = VALS + (size_t)t.inst * vals_stride;
+    const unsigned char* f = fixed + (size_t)t.inst * nv * M;
+    for (int r = 0; r < nh; ++r) t.Q[(size_t)r * M + k] = q[(size_t)r * M + k];
+    for (int r = 0; r < nj; ++r) t.J[(size_t)r * M + k] = j[(size_t)r * M + k];
+    for (int r = 0; r < nv; ++r) t.fixed[(size_t)r * M + k] = f[(size_t)r * M + k];
 }
 // status words of a batch gathered in one place (one copy to the host instead of two per scenario)
 __global__ void emi_kkt_zero_status_b_kernel(const KktDev* __restrict__ tab, int n) {
@@ -1307,6 +1386,7 @@ void dump_failing_pivot(const KktWorkspace* w, int pivot) {
 void kkt_destroy(KktWorkspace* w) {
     if (!w) return;
     if (w->handle) (void)rocblas_destroy_handle(w->handle);
+    if (w->b_up_ev) (void)hipEventDestroy(w->b_up_ev);
     delete w;       // (every buffer is a DeviceArray member)
 }
 
@@ -1535,6 +1615,7 @@ int kkt_lowrank(KktWorkspace* w, hipStream_t stream, int nz, int r, const int* n
     if (hinfo == 0) {
         w->lr_active = true;
         w->lr_r = r;
+        w->lr_ld = r;
         *exact = 1;
     }
     return EMI_OK;
@@ -1559,7 +1640,7 @@ int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs
         hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, nrhs), dim3(64), 0, stream, w->lrT.p, x, w->lr_node.p,
                            w->lr_vec.p, r, N, w->M, w->nv);
         KKT_HIP(hipGetLastError());
-        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, nrhs, w->lrC.p, r, w->lrT.p, r));
+        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, nrhs, w->lrC.p, w->lr_ld, w->lrT.p, r));
         const double one = 1.0;
         KKT_RB(rocblas_dgemm(w->handle, rocblas_operation_none, rocblas_operation_none, N, nrhs, r, &one, w->lrY.p, N, w->lrT.p, r,
                              &one, x, N));
@@ -1589,6 +1670,10 @@ int kkt_solve(KktWorkspace* w, hipStream_t stream, int nz, double* rhs, int nrhs
 namespace {
 
 int batch_scratch(KktWorkspace* L, size_t tab_bytes, size_t ptr_bytes, size_t stat_bytes, std::string* err) {
+    if (L->b_up_pending) {              // the staging's last upload, queued by a call that did not synchronise
+        KKT_HIP(hipEventSynchronize(L->b_up_ev));
+        L->b_up_pending = false;
+    }
     KKT_HIP(L->b_tab.reserve(tab_bytes));
     KKT_HIP(L->b_ptrs.reserve(ptr_bytes / sizeof(double*)));
     KKT_HIP(L->b_stat.reserve(stat_bytes));
@@ -1669,7 +1754,7 @@ int chol_batched(KktWorkspace* L, hipStream_t stream, const KktDev* d_tab, int n
 // than KKT_NV_MAX variables per node: the LU).
 int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const double* const* dD, int M, int ns, int nv,
                      const double* const* Qblk, const double* const* Jblk, const unsigned char* const* fixed, const double* dc, int* info,
-                     std::string* err) {
+                     std::string* err, const KktShardSrc* src) {
     if (n < 1) { *err = "emi_kkt_factor_batch: bad batch"; return EMI_ERR_ARG; }
     if (nv > KKT_NV_MAX) {              // node blocks beyond the node kernels' arrays: every scenario to the single path (its LU)
         for (int b = 0; b < n; ++b) info[b] = -1;
@@ -1681,7 +1766,8 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
         if (!*pws[b]) *pws[b] = new KktWorkspace();
         KktWorkspace* w = W[b] = *pws[b];
         if (int st = ws_prepare(w, stream, dD[b], M, ns, nv, dc[b], true, 1, err)) return st;
-        if (int st = upload_blocks(w, stream, Qblk[b], Jblk[b], fixed[b], err)) return st;
+        if (!src)
+            if (int st = upload_blocks(w, stream, Qblk[b], Jblk[b], fixed[b], err)) return st;
         info[b] = -1;
     }
     KktWorkspace* L = W[0];
@@ -1722,6 +1808,7 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
             t.flag = d_stat + na + a;
             t.dw = ladder.dw(level[act[a]]);
             t.dc = ladder.dc(level[act[a]], dc[act[a]]);
+            t.inst = src ? src->inst[act[a]] : 0;
             h_tab[a] = t;
             Sptr[a] = w->S.p;
         }
@@ -1736,6 +1823,9 @@ int kkt_factor_batch(int n, KktWorkspace** const* pws, hipStream_t stream, const
         KKT_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)na * sizeof(KktDev), hipMemcpyHostToDevice, stream));
         KKT_HIP(hipMemcpyAsync(L->b_ptrs.p, h_ptr, q * sizeof(double*), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(emi_kkt_zero_status_b_kernel, dim3((na + 63) / 64), dim3(64), 0, stream, (const KktDev*)d_tab, na);
+        if (src && round == 0)      // the blocks of a shard: one launch from the caller's device arrays (every scenario is in the first round)
+            hipLaunchKernelGGL(emi_kkt_gather_blocks_b_kernel, dim3((M + 255) / 256, na), dim3(256), 0, stream, (const KktDev*)d_tab, src->Q, src->VALS,
+                               src->fixed, M, nv * (nv + 1) / 2, ns * nv, nv, src->vals_stride);
         launch_node_inverse(stream, M, ns, nv, nullptr, 0.0, d_tab, na);
         KKT_HIP(hipGetLastError());
         for (int i = 0, p = 0; i < ns; ++i)
@@ -1895,7 +1985,7 @@ __global__ __launch_bounds__(256) void emi_kkt_absmax_b_kernel(const KktDev* __r
     }
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
-// dst <- src (+ add) over N entries: sel 0: rhs <- bb; 1: xx <- rhs; 2: xp <- xx; 3: xx <- xp; 4: xx += rhs
+// dst <- src (+ add) over N entries: sel 0: rhs <- bb; 1: xx <- rhs; 2: xp <- xx; 3: xx <- xp; 4: xx += rhs; 5: bb <- xx
 __global__ void emi_kkt_vecop_b_kernel(const KktDev* __restrict__ tab, int N, int sel) {
     const KktDev t = tab[blockIdx.y];
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1904,14 +1994,17 @@ __global__ void emi_kkt_vecop_b_kernel(const KktDev* __restrict__ tab, int N, in
     else if (sel == 1) t.xx[q] = t.rhs[q];
     else if (sel == 2) t.xp[q] = t.xx[q];
     else if (sel == 3) t.xx[q] = t.xp[q];
+    else if (sel == 5) t.bb[q] = t.xx[q];
     else t.xx[q] += t.rhs[q];
 }
 
 struct SolveShape { int M, ns, nv, N, nz, md, nblk; bool blk; };
 
 void fill_solve_entry(KktDev& t, KktWorkspace* w) {
-    t.Q = w->Q.p; t.J = w->J.p; t.Pinv = w->Pinv.p; t.S = w->S.p; t.Linv = w->Linv.p; t.LinvT = w->LinvT.p; t.T = w->T.p; t.Cb = w->Cb.p; t.rhs = w->rhs.p;
-    t.y = w->trsv_y.p; t.bb = w->ref_b.p; t.xx = w->ref_x.p; t.xp = w->ref_p.p;
+    t.Q = w->Q.p; t.J = w->J.p; t.Pinv = w->Pinv.p; t.S = w->S.p; t.Linv = w->Linv.p; t.LinvT = w->LinvT.p; t.T = w->T.p; t.Cb = w->Cb.p;
+    t.rhs = w->ext_rhs ? w->ext_rhs : w->rhs.p;
+    t.y = w->trsv_y.p; t.bb = w->ext_bb ? w->ext_bb : w->ref_b.p; t.xx = w->ref_x.p; t.xp = w->ref_p.p;
+    t.lrT = w->lrT.p;
     t.fixed = w->fixed.p;
     t.Doff = w->Doff.p;
     t.lr_r = w->lr_active ? w->lr_r : 0;
@@ -1943,7 +2036,7 @@ int solve_arrays(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int 
     A->at_D = arr([](KktWorkspace* w) { return w->Doff.p; });
     A->at_T = arr([](KktWorkspace* w) { return w->T.p; });
     A->at_Cb = arr([](KktWorkspace* w) { return w->Cb.p; });
-    A->at_X = arr([](KktWorkspace* w) { return w->rhs.p; });
+    A->at_X = arr([](KktWorkspace* w) { return w->ext_rhs ? w->ext_rhs : w->rhs.p; });
     A->at_S = arr([](KktWorkspace* w) { return w->S.p; });
     A->at_Y = arr([](KktWorkspace* w) { return w->trsv_y.p; });
     A->at_XX = arr([](KktWorkspace* w) { return w->ref_x.p; });
@@ -2005,15 +2098,22 @@ int solve_core(KktWorkspace* L, hipStream_t stream, const SolveShape& sh, int n,
     hipLaunchKernelGGL(emi_kkt_apply_p_b_kernel, gk, bk, 0, stream, d_tab, M, nv, 1);           // ... x = P y
     hipLaunchKernelGGL(emi_kkt_finish_solve_b_kernel, dim3((N + 255) / 256, n), dim3(256), 0, stream, d_tab, nz, md);
     KKT_HIP(hipGetLastError());
+    // x <- x + Y C^-1 (U^T x) where a low-rank correction is active: U^T x of all of them in one launch (the table has their lists),
+    // then per scenario the small triangular solves and the product with Y, with the scenario's own handle on this stream
+    int r_most = 0;
+    for (int b = 0; b < n; ++b)
+        if (ws[b]->lr_active) r_most = std::max(r_most, ws[b]->lr_r);
+    if (r_most == 0) return EMI_OK;
+    hipLaunchKernelGGL(emi_kkt_lr_utx_b_kernel, dim3((r_most + 63) / 64, n), dim3(64), 0, stream, d_tab, M, nv);
+    KKT_HIP(hipGetLastError());
     for (int b = 0; b < n; ++b) {
         KktWorkspace* w = ws[b];
-        if (!w->lr_active) continue;    // x <- x + Y C^-1 (U^T x), with the scenario's own handle on this stream
+        if (!w->lr_active) continue;
         const int r = w->lr_r;
+        double* x = w->ext_rhs ? w->ext_rhs : w->rhs.p;
         KKT_RB(rocblas_set_stream(w->handle, stream));
-        hipLaunchKernelGGL(emi_kkt_lr_utx_kernel, dim3((r + 63) / 64, 1), dim3(64), 0, stream, w->lrT.p, w->rhs.p, w->lr_node.p, w->lr_vec.p, r, N, M, nv);
-        KKT_HIP(hipGetLastError());
-        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, 1, w->lrC.p, r, w->lrT.p, r));
-        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_none, N, r, &one, w->lrY.p, N, w->lrT.p, 1, &one, w->rhs.p, 1));
+        KKT_RB(rocsolver_dpotrs(w->handle, rocblas_fill_lower, r, 1, w->lrC.p, w->lr_ld, w->lrT.p, r));
+        KKT_RB(rocblas_dgemv(w->handle, rocblas_operation_none, N, r, &one, w->lrY.p, N, w->lrT.p, 1, &one, x, 1));
     }
     return EMI_OK;
 }
@@ -2050,6 +2150,18 @@ int solve_buffers(KktWorkspace* w, int N, int nz, int md, bool refine, std::stri
     return EMI_OK;
 }
 
+// the device-array forms aim the tables at the caller's arrays through KktWorkspace::ext_rhs / ext_bb; whatever way the call ends,
+// the workspaces forget those pointers again
+struct ExternalVectors {
+    int n;
+    KktWorkspace* const* ws;
+    ExternalVectors(int n_, KktWorkspace* const* ws_) : n(n_), ws(ws_) {}
+    ~ExternalVectors() {
+        for (int b = 0; b < n; ++b)
+            if (ws[b]) ws[b]->ext_rhs = ws[b]->ext_bb = nullptr;
+    }
+};
+
 int solve_shape(int n, KktWorkspace* const* ws, SolveShape* sh, std::string* err) {
     KktWorkspace* L = ws[0];
     sh->M = L->M; sh->ns = L->ns; sh->nv = L->nv; sh->N = L->N; sh->nz = L->nv * L->M; sh->md = L->ns * L->M;
@@ -2070,20 +2182,28 @@ int solve_shape(int n, KktWorkspace* const* ws, SolveShape* sh, std::string* err
 
 // One right-hand side per scenario, all factorised on the same mesh (Schur path): rhs[b] [N] host, in place.  Scenarios with an active
 // low-rank correction get their Woodbury term after the common part.
-int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, double* const* rhs, std::string* err) {
+int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, double* const* rhs, std::string* err, bool rhs_on_device) {
     if (n < 1) { *err = "emi_kkt_solve_batch: empty batch"; return EMI_ERR_ARG; }
     (void)nz;
     SolveShape sh;
     if (int st = solve_shape(n, ws, &sh, err)) return st;
     KktWorkspace* L = ws[0];
+    ExternalVectors ext(n, ws);
     for (int b = 0; b < n; ++b) {
         if (int st = solve_buffers(ws[b], sh.N, sh.nz, sh.md, false, err)) return st;
-        KKT_HIP(hipMemcpyAsync(ws[b]->rhs.p, rhs[b], (size_t)sh.N * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (rhs_on_device) ws[b]->ext_rhs = rhs[b];     // solved in place in the caller's array: the table points there
+        else KKT_HIP(hipMemcpyAsync(ws[b]->rhs.p, rhs[b], (size_t)sh.N * sizeof(double), hipMemcpyHostToDevice, stream));
     }
     KKT_RB(rocblas_set_stream(L->handle, stream));
     SolveArrays A;
     if (int st = solve_arrays(L, stream, sh, n, ws, &A, err)) return st;
+    if (rhs_on_device) {            // no synchronisation at the end of this form: whoever takes the staging next waits for this upload
+        if (!L->b_up_ev) KKT_HIP(hipEventCreateWithFlags(&L->b_up_ev, hipEventDisableTiming));
+        KKT_HIP(hipEventRecord(L->b_up_ev, stream));
+        L->b_up_pending = true;
+    }
     if (int st = solve_core(L, stream, sh, n, ws, A, err)) return st;
+    if (rhs_on_device) return EMI_OK;
     for (int b = 0; b < n; ++b) KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->rhs.p, (size_t)sh.N * sizeof(double), hipMemcpyDeviceToHost, stream));
     KKT_HIP(hipStreamSynchronize(stream));
     return EMI_OK;
@@ -2096,16 +2216,20 @@ int kkt_solve_batch(int n, KktWorkspace* const* ws, hipStream_t stream, int nz, 
 // cross to the host (n doubles per round).  Out per scenario: rel[b] = final max |r| / max(1, max |b|), nsolve[b] = solves used,
 // reverted[b] = 1 if the last correction was taken back, status[b] = 0 ok, 2 the first solution is not finite (the caller regularises).
 int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, double* const* rhs, const double* dc_nominal, int max_steps,
-                            double* rel, int* nsolve, int* reverted, int* status, std::string* err) {
+                            double* rel, int* nsolve, int* reverted, int* status, std::string* err, bool rhs_on_device) {
     if (n < 1) { *err = "emi_kkt_solve_refined_batch: empty batch"; return EMI_ERR_ARG; }
     SolveShape sh;
     if (int st = solve_shape(n, ws, &sh, err)) return st;
     KktWorkspace* L = ws[0];
     const int N = sh.N;
     const double refine_rel = std::pow(10.0, -(double)g_tune.refine_exp.load());
+    ExternalVectors ext(n, ws);
     for (int b = 0; b < n; ++b) {
         if (int st = solve_buffers(ws[b], sh.N, sh.nz, sh.md, true, err)) return st;
-        KKT_HIP(hipMemcpyAsync(ws[b]->ref_b.p, rhs[b], (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
+        // the right-hand side b: a copy in the workspace, or -- device form -- the caller's array itself, read where it lies through
+        // the refinement and overwritten with the solution by one launch at the end
+        if (rhs_on_device) ws[b]->ext_bb = rhs[b];
+        else KKT_HIP(hipMemcpyAsync(ws[b]->ref_b.p, rhs[b], (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
         rel[b] = 0.0; nsolve[b] = 0; reverted[b] = 0; status[b] = 0;
     }
     KKT_RB(rocblas_set_stream(L->handle, stream));
@@ -2188,11 +2312,117 @@ int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, 
         KKT_HIP(hipGetLastError());
         for (int a = 0; a < nc; ++a) { ++nsolve[idx[a]]; have_prev[idx[a]] = 1; }
     }
-    for (int b = 0; b < n; ++b) {
-        rel[b] = rlast[b] / std::max(1.0, bmax[b]);
-        KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->ref_x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    for (int b = 0; b < n; ++b) rel[b] = rlast[b] / std::max(1.0, bmax[b]);
+    if (rhs_on_device) {                                                // the solutions into the caller's arrays: bb <- xx of every scenario
+        KKT_HIP(hipStreamSynchronize(stream));                          // (the pinned table may still be read by the last round's upload)
+        if (int st = solve_arrays(L, stream, sh, n, ws, &A, err)) return st;
+        hipLaunchKernelGGL(emi_kkt_vecop_b_kernel, gN, dim3(256), 0, stream, (const KktDev*)A.d_tab, N, 5);
+        KKT_HIP(hipGetLastError());
+    } else {
+        for (int b = 0; b < n; ++b) KKT_HIP(hipMemcpyAsync(rhs[b], ws[b]->ref_x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream));
     }
     KKT_HIP(hipStreamSynchronize(stream));
+    return EMI_OK;
+}
+
+// ---- a shard: the B instances of one context, device arrays in and out ----------------------------------------------------------
+// what a workspace holds for an (M, ns, nv) problem: 0 nothing usable, 1 a factorisation of the Schur path, 2 the LU
+int kkt_holds(const KktWorkspace* w, int M, int ns, int nv) {
+    if (!w || !w->factored || w->M != M || w->ns != ns || w->nv != nv) return 0;
+    return w->method_used == 1 ? 1 : 2;
+}
+
+// Inertia verdict and Woodbury set-up (kkt_lowrank) for n workspaces at once, from the lists emi_kkt_blocks_dev left on the device:
+// entry b reads the lists of instance inst[b] ([.][max_mods] node and delta, [.][max_mods][nv] vec) and takes count[b] columns
+// (host: the one download is the caller's).  The lists are ordered by node already -- no sort, no upload.  count 0: exact, no
+// correction; count > max_mods or > 4096 (solve_nlp's cap): not exact, no correction.  The others: U scattered by one table launch,
+// Y = K~^-1 U per workspace with solve_dev (the r columns of one instance are a batch of their own: ns large GEMMs), C by one table
+// launch padded to the largest count r_max with the identity, ONE chol_batched over all of them; its status words are the verdicts.
+int kkt_lowrank_shard(int n, KktWorkspace* const* ws, hipStream_t stream, int max_mods, const int* inst, const int* count, const int* dNode,
+                      const double* dDelta, const double* dVec, int* exact, std::string* err) {
+    std::vector<int> cand;
+    int r_max = 0;
+    for (int b = 0; b < n; ++b) {
+        KktWorkspace* w = ws[b];
+        if (!w || !w->factored) { *err = "emi_kkt_lowrank_shard_dev: no factorisation"; return EMI_ERR_STATE; }
+        w->lr_active = false;
+        w->lr_r = 0;
+        exact[b] = count[b] == 0 ? 1 : 0;
+        if (count[b] <= 0 || count[b] > max_mods || count[b] > 4096) continue;
+        cand.push_back(b);
+        r_max = std::max(r_max, count[b]);
+    }
+    const int nc = (int)cand.size();
+    if (nc == 0) return EMI_OK;
+    KktWorkspace* L = ws[cand[0]];
+    const int N = L->N, nv = L->nv, M = L->M, nz = nv * M;
+    for (int a = 0; a < nc; ++a) {
+        KktWorkspace* w = ws[cand[a]];
+        if (w->lr_cap < r_max) {
+            KKT_HIP(w->lrY.release());
+            KKT_HIP(w->lr_vec.release());
+            w->lr_cap = r_max + r_max / 4 + 16;
+        }
+        const size_t cap = (size_t)w->lr_cap;
+        KKT_HIP(w->lrY.reserve((size_t)N * cap));
+        KKT_HIP(w->lrC.reserve(cap * cap));
+        KKT_HIP(w->lr_node.reserve(cap));
+        KKT_HIP(w->lr_vec.reserve(cap * nv));
+        KKT_HIP(w->lr_delta.reserve(cap));
+        KKT_HIP(w->lrT.reserve(cap * 64));
+        KKT_HIP(w->info.reserve(1));
+        KKT_HIP(w->chol_blk.reserve(CHOL_NB * CHOL_NB + CHOL_NB));
+    }
+    const int nsteps = (r_max + CHOL_NB - 1) / CHOL_NB;
+    const size_t dev_bytes = (size_t)nc * sizeof(KktDev), lr_bytes = (size_t)nc * sizeof(KktLrDev);
+    const size_t ptr_bytes = (size_t)nc * 2 * (nsteps + nsteps / 2 + 4) * sizeof(double*), stat_bytes = (size_t)2 * nc * sizeof(int);
+    if (int st = batch_scratch(L, dev_bytes + lr_bytes, ptr_bytes, stat_bytes, err)) return st;
+    KktDev* h_tab = reinterpret_cast<KktDev*>(L->b_pin.p);
+    KktLrDev* h_lr = reinterpret_cast<KktLrDev*>(L->b_pin.p + dev_bytes);
+    double** h_ptr = reinterpret_cast<double**>(L->b_pin.p + dev_bytes + lr_bytes);
+    int* h_stat = reinterpret_cast<int*>(L->b_pin.p + dev_bytes + lr_bytes + ptr_bytes);
+    KktDev* d_tab = reinterpret_cast<KktDev*>(L->b_tab.p);
+    KktLrDev* d_lr = reinterpret_cast<KktLrDev*>(L->b_tab.p + dev_bytes);
+    int* d_stat = reinterpret_cast<int*>(L->b_stat.p);
+    std::vector<double*> Cptr(nc);
+    for (int a = 0; a < nc; ++a) {
+        KktWorkspace* w = ws[cand[a]];
+        const size_t at = (size_t)inst[cand[a]] * max_mods;
+        KktLrDev t{};
+        t.Y = w->lrY.p; t.C = w->lrC.p; t.node = w->lr_node.p; t.vec = w->lr_vec.p; t.delta = w->lr_delta.p;
+        t.src_node = dNode + at; t.src_delta = dDelta + at; t.src_vec = dVec + at * nv;
+        t.r = count[cand[a]];
+        h_lr[a] = t;
+        KktDev c{};                     // what chol_batched reads of an entry: the matrix, its status word, its diagonal-block scratch
+        c.S = w->lrC.p; c.chol_blk = w->chol_blk.p; c.info = d_stat + a; c.flag = d_stat + nc + a;
+        h_tab[a] = c;
+        Cptr[a] = w->lrC.p;
+        KKT_HIP(hipMemsetAsync(w->lrY.p, 0, (size_t)N * t.r * sizeof(double), stream));
+    }
+    KKT_HIP(hipMemcpyAsync(L->b_tab.p, L->b_pin.p, dev_bytes + lr_bytes, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(emi_kkt_zero_status_b_kernel, dim3((nc + 63) / 64), dim3(64), 0, stream, (const KktDev*)d_tab, nc);
+    hipLaunchKernelGGL(emi_kkt_lr_scatter_b_kernel, dim3((r_max + 63) / 64, nc), dim3(64), 0, stream, (const KktLrDev*)d_lr, N, M, nv);
+    KKT_HIP(hipGetLastError());
+    for (int a = 0; a < nc; ++a) {
+        KktWorkspace* w = ws[cand[a]];
+        if (int st = solve_dev(w, stream, nz, w->lrY.p, count[cand[a]], err)) return st;
+    }
+    hipLaunchKernelGGL(emi_kkt_lr_c_b_kernel, dim3((r_max + 15) / 16, (r_max + 15) / 16, nc), dim3(16, 16), 0, stream, (const KktLrDev*)d_lr, r_max, N,
+                       M, nv);
+    KKT_HIP(hipGetLastError());
+    KKT_RB(rocblas_set_stream(L->handle, stream));
+    size_t used = 0;
+    if (int st = chol_batched(L, stream, d_tab, nc, Cptr.data(), r_max, h_ptr, L->b_ptrs.p, &used, err)) return st;
+    KKT_HIP(hipMemcpyAsync(h_stat, d_stat, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, stream));
+    KKT_HIP(hipStreamSynchronize(stream));
+    for (int a = 0; a < nc; ++a) {
+        if (h_stat[a] != 0) continue;
+        KktWorkspace* w = ws[cand[a]];
+        w->lr_active = true;
+        w->lr_r = count[cand[a]];
+        w->lr_ld = r_max;
+        exact[cand[a]] = 1;
+    }
     return EMI_OK;
 }
 

@@ -379,6 +379,57 @@ class Evaluator:
         nrhs = 1 if rhs.dim() == 1 else rhs.shape[0]
         self._ck(self.lib.emi_kkt_solve_dev(self.ctx, C.c_void_p(rhs.data_ptr()), nrhs), "emi_kkt_solve_dev")
 
+    # ---- the Newton steps of the whole batch, device tensors in and out (emi_kkt_*_shard_dev) -----------------------------
+    # Tensors in the layouts of include/emi355x.h; mask: None (every instance) or B flags; the per-instance scalars come back as
+    # numpy arrays of length B (entries of masked instances are -1 / nan: the library does not write them).
+    def _shard_mask(self, mask):
+        if mask is None:
+            return None, None
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert m.shape == (self.layout.B,)
+        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+    def kkt_factor_shard_dev(self, Q, VALS, fixed, dc, mask=None):
+        """Factorise the Newton systems of the batch (Q [B][nhess][M], VALS [B][nvals][M] float64, fixed [B][nv][M] uint8, dc a
+        scalar or B values); returns info [B]: 0 factorised, > 0 singular."""
+        B = self.layout.B
+        dc = np.ascontiguousarray(np.broadcast_to(np.asarray(dc, dtype=np.float64), (B,)))
+        info = np.full(B, -1, dtype=np.int32)
+        m, mp = self._shard_mask(mask)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self.lib.emi_kkt_factor_shard_dev(self.ctx, ptr(Q), ptr(VALS), ptr(fixed), _dp(dc), mp,
+                                                   info.ctypes.data_as(C.POINTER(C.c_int))), "emi_kkt_factor_shard_dev")
+        return info
+
+    def kkt_lowrank_shard_dev(self, max_mods, count=None, node=None, delta=None, vec=None, mask=None):
+        """Inertia verdict and Woodbury set-up per instance from the lists of kkt_blocks_dev (device tensors); max_mods 0 clears.
+        Returns exact [B] (1: solves of that instance answer for the unmodified matrix)."""
+        exact = np.full(self.layout.B, -1, dtype=np.int32)
+        m, mp = self._shard_mask(mask)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self.lib.emi_kkt_lowrank_shard_dev(self.ctx, int(max_mods), ptr(count), ptr(node), ptr(delta), ptr(vec), mp,
+                                                    exact.ctypes.data_as(C.POINTER(C.c_int))), "emi_kkt_lowrank_shard_dev")
+        return exact
+
+    def kkt_solve_shard_dev(self, rhs, mask=None):
+        """rhs [B][2 ns + nc][M] float64 device tensor, solved in place; asynchronous on the context's stream."""
+        m, mp = self._shard_mask(mask)
+        self._ck(self.lib.emi_kkt_solve_shard_dev(self.ctx, C.c_void_p(rhs.data_ptr()) if rhs is not None else None, mp),
+                 "emi_kkt_solve_shard_dev")
+
+    def kkt_solve_refined_shard_dev(self, rhs, dc_nominal, max_steps=10, mask=None):
+        """The solve with its iterative refinement on the device, in place on rhs; returns dict rel, nsolve, reverted, status [B]."""
+        B = self.layout.B
+        dcn = np.ascontiguousarray(np.broadcast_to(np.asarray(dc_nominal, dtype=np.float64), (B,)))
+        out = dict(rel=np.full(B, np.nan), nsolve=np.full(B, -1, dtype=np.int32), reverted=np.full(B, -1, dtype=np.int32),
+                   status=np.full(B, -1, dtype=np.int32))
+        m, mp = self._shard_mask(mask)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._ck(self.lib.emi_kkt_solve_refined_shard_dev(self.ctx, C.c_void_p(rhs.data_ptr()) if rhs is not None else None, mp, _dp(dcn),
+                                                          int(max_steps), _dp(out["rel"]), ip(out["nsolve"]), ip(out["reverted"]),
+                                                          ip(out["status"])), "emi_kkt_solve_refined_shard_dev")
+        return out
+
     # ---- the array arithmetic of an interior-point iteration, batched (emi_ipm_*) ----------------------------------------
     # Argument groups are dicts keyed as the structs of include/emi355x.h (X U S E1 E2 | LamF Y ZL ZU VL VU W1 W2 | DZLam DS DY DE1
     # DE2 DZL DZU DVL DVU DW1 DW2 | Sigma SigT SigS RhatS Rt); bounds: dict zl, zu ([nsets][nv][M]) and cl, cu, cscale (host, [np];

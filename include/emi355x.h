@@ -425,6 +425,52 @@ int emi_ipm_accept_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_
 int emi_ipm_error_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* G,
                        const emi_ipm_bounds_t* bd, const double* par, double* out);
 
+/* ---- The Newton steps of a context's whole batch (a "shard"), device arrays in and out ------------------------------------
+ *
+ * The joint between the batched kernels above (emi_eval_dev ... emi_kkt_blocks_dev, emi_ipm_*_dev: [B][.][M] arrays of ONE
+ * context) and the batched Newton-step machinery (emi_kkt_factor_batch ...: n contexts, host arrays).  The context owns one
+ * Newton-step workspace per instance of its batch, created at the first call that needs it, freed with the context, told of
+ * every emi_set_mesh, and apart from the workspace of emi_kkt_factor / _solve / _lowrank, whose results these calls never touch.
+ * f64 contexts without delays, Schur method ("kkt_method" 1), ns + nc <= 16; otherwise EMI_ERR_UNSUPPORTED.
+ * Memory: every instance holds its own Schur complement S, (ns M)^2 doubles -- 0.3 GB per instance at 1024 nodes of a 6-state
+ * model, before the factor's block inverses; a failed allocation returns EMI_ERR_HIP with the message of the single call.
+ *
+ * Layouts are those of the neighbouring calls:
+ *   dQ      [B][nhess][M]    the Q of emi_kkt_blocks_dev
+ *   dVALS   [B][nvals][M]    emi_eval_dev's; the first ns (ns + nc) rows of an instance are its Jacobian node entries
+ *   dFixed  [B][ns+nc][M]    bytes
+ *   dRhs    [B][2 ns+nc][M]  the DZLam of emi_ipm_reduce_dev / emi_ipm_expand_dev, solved in place
+ *   dCount [B], dNode / dDelta [B][max_mods], dVec [B][max_mods][ns+nc]   as emi_kkt_blocks_dev writes them
+ *   mask    [B] host bytes, NULL = every instance.  An instance with mask 0 is not touched: its factors, its low-rank state and
+ *           its slice of dRhs keep every bit.
+ *   dc, info, exact, dc_nominal, rel, nsolve, reverted, status   [B] HOST arrays, read and written at unmasked instances only:
+ *           these per-instance scalars are all that crosses.
+ *
+ * emi_kkt_factor_shard_dev          emi_kkt_factor_batch over the shard's workspaces: the same regularisation ladder round by round,
+ *                                   the same kernels and rocBLAS calls, one synchronisation per round.  info[b] = 0 factorised,
+ *                                   > 0 singular (raise dc[b], call again with a mask on those).  An instance the batch cannot take (a
+ *                                   node block not positive definite, the ladder exhausted) goes through the single path and its LU
+ *                                   inside the call.  The blocks reach the workspaces by one launch, not by copies per instance.
+ * emi_kkt_lowrank_shard_dev         emi_kkt_lowrank per instance from the device lists (already ordered by node: no sort, no upload;
+ *                                   the B counts are the one download).  count 0: exact[b] = 1, no correction.  count > max_mods or
+ *                                   > 4096: exact[b] = 0, no correction (the modified step, untested).  Otherwise exact[b] = 1 and the
+ *                                   Woodbury correction is active iff Delta^-1 - U^T K~^-1 U is positive definite.  max_mods == 0 reads
+ *                                   no list and clears the correction of every unmasked instance (exact[b] = 1).
+ * emi_kkt_solve_shard_dev           dRhs[b] <- K~_b^-1 dRhs[b] (K_b^-1 while the instance's correction is active).  Returns nothing per
+ *                                   instance and does not synchronise: asynchronous on the context's stream, like emi_kkt_solve_dev.
+ *                                   Instances that hold the LU go through the single solve.
+ * emi_kkt_solve_refined_shard_dev   emi_kkt_solve_refined_batch, rule for rule, in place on dRhs; outputs as there.  Every unmasked
+ *                                   instance must hold a factorisation of the Schur path (else EMI_ERR_UNSUPPORTED).
+ * EMI_ERR_STATE: mesh, model or batch not set; solve or low-rank with an unmasked instance that holds no factorisation for the
+ * context's present mesh.  EMI_ERR_ARG: NULL where not optional, negative dc.                                                     */
+int emi_kkt_factor_shard_dev(emi_ctx_t ctx, const void* dQ, const void* dVALS, const void* dFixed, const double* dc,
+                             const unsigned char* mask, int* info);
+int emi_kkt_lowrank_shard_dev(emi_ctx_t ctx, int max_mods, const void* dCount, const void* dNode, const void* dDelta,
+                              const void* dVec, const unsigned char* mask, int* exact);
+int emi_kkt_solve_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned char* mask);
+int emi_kkt_solve_refined_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned char* mask, const double* dc_nominal, int max_steps,
+                                    double* rel, int* nsolve, int* reverted, int* status);
+
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,
  * for reports, tools and tests (csrc/emi_api.hip: plan_pass, plan_piece).           */
