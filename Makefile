@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean
+.PHONY: all lib host oracle clean check-keep-record
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -88,6 +88,12 @@ tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(H
 
 oracle:
 	$(MAKE) -C oracle
+
+# the bookkeeping behind EMI_EVAL_KEEP_INVARIANT (emi_keep_record.hpp, host-only) as a stand-alone program under the host sanitizers
+KEEP_CHECK_OUT ?= $(LIBDIR)/keep_record_check
+check-keep-record: tests/harness/keep_record_main.cpp $(CSRC)/emi_keep_record.hpp | $(LIBDIR)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -I$(CSRC) -o $(KEEP_CHECK_OUT) $<
+	$(KEEP_CHECK_OUT)
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

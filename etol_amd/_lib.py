@@ -22,6 +22,7 @@ MODEL_SOURCE = 100   # installed by emi_set_model_source
 PATH_ELLIPSE, PATH_DISC, PATH_TRACK = 0, 1, 2
 PATH_REC = 8
 EVAL_NODES, EVAL_DEFECT, EVAL_ALL, EVAL_NOJAC = 1, 2, 3, 4
+EVAL_KEEP_INVARIANT = 8   # the model-invariant VALS rows are in place: see emi_eval_dev in include/emi355x.h
 
 
 class EmiError(RuntimeError):
@@ -118,6 +119,7 @@ SYMBOLS = {
     "emi_set_tracks": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
     "emi_get_layout": (C.c_int, [_P, C.POINTER(Layout)]),
     "emi_jac_structure": (C.c_int, [_P, _I, _I]),
+    "emi_invariant_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_ubyte), _I]),
     "emi_dev_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "emi_dev_free": (C.c_int, [_P, _P]),
     "emi_h2d": (C.c_int, [_P, _P, _P, C.c_size_t]),

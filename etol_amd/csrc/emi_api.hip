@@ -16,6 +16,7 @@
 
 #include "emi355x.h"
 #include "emi_device_array.hpp"
+#include "emi_keep_record.hpp"
 #include "emi_kernels.hpp"
 
 namespace {
@@ -110,6 +111,7 @@ struct emi_ctx_s {
     int pass_order = -1;        // "pass_order" option: one-launch pass, MFMA workgroups of an XCD first (1), interleaved with the node
                                 // workgroups (0), or by batch size (-1: first for small batches)
     int sym_combine = 1;        // "sym_combine" option: 1 slices combined in-kernel by ticket, 0 by emi_symdefect_combine_kernel
+    emi::KeepRecord keep;       // which VALS buffer holds this problem's model-invariant rows (EMI_EVAL_KEEP_INVARIANT)
     // host-form staging
     DevBuf s_X, s_U, s_RES, s_VALS, s_COST, s_LF, s_LC, s_H;
     // adjoint pass (emi_lagr_grad_* / emi_kkt_certificate_*): workspace grown on demand
@@ -250,6 +252,13 @@ int np_total(emi_ctx_t c) { return c->np + c->np_model; }     // rows of the rec
 int nvals_of(emi_ctx_t c) { return c->ns * (c->ns + c->nc) + 2 * c->np + c->np_model * (int)c->pvars.size() + (c->ns + c->nc); }
 int nres_of(emi_ctx_t c) { return c->ns + np_total(c); }
 int nhess_of(emi_ctx_t c) { const int nv = c->ns + c->nc; return nv * (nv + 1) / 2; }
+
+// the staging buffer of VALS (host forms): a buffer that has to grow is a new, unwritten one -- also where the allocator hands
+// back the old address, so the record is told before the old one goes
+int ensure_vals_staging(emi_ctx_t c, size_t bytes) {
+    if (c->s_VALS.bytes() < bytes) c->keep.written(c->s_VALS.p);
+    return ensure(c, c->s_VALS, bytes);
+}
 
 int ready(emi_ctx_t c) {
     if (!c) return EMI_ERR_ARG;
@@ -424,7 +433,7 @@ int plan_piece(emi_ctx_t c, int B) {
 
 // One launch of the evaluation pass: instances [first, first + B) of the context's batch.  The whole batch as a rule; pieces of it
 // where plan_piece says so.  The context is not written to on the way: the batch of a launch is this argument.
-struct Launch { int first, B; };
+struct Launch { int first, B; bool keep = false; };      // keep: the model-invariant VALS rows are in place already (emi_eval_dev decides)
 // ... and its arrays (device memory, in the context's real type), already at the launch's first instance
 struct PassIO { const void *X, *U; void *RES, *VALS, *COST; };
 
@@ -460,6 +469,7 @@ void fill_node_args(emi_ctx_t c, Launch L, emi::NodeArgs<T>& a, const PassIO& io
     a.px = c->px;
     a.py = c->py;
     a.store_mode = store_mode_for(c, L.B);
+    a.keep = L.keep ? 1 : 0;
     a.h = (T)((c->tf - c->t0) / 2.0);
     a.sgn = c->maximize ? T(-1) : T(1);
     for (int i = 0; i < EMI_MAX_PARAMS; ++i) a.P.p[i] = (T)c->params[i];
@@ -1047,6 +1057,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
                  double tf) {
     if (!c || M < 2 || !tau || !w) return fail(c, EMI_ERR_ARG, "emi_set_mesh: bad argument");
     if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_set_mesh: tf must exceed t0");
+    c->keep.bump();             // h, D_kk and the weights enter the invariant rows of VALS
     HIP_TRY(c, hipSetDevice(c->device));
     // D == NULL is a points-only mesh: the node functions are evaluated at arbitrary abscissae (the ODE-error estimate between
     // the collocation nodes); there is no differentiation matrix, so EMI_EVAL_DEFECT and the KKT entry points refuse
@@ -1085,6 +1096,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
 // (px, py) that this model may not have.
 static void model_in_force(emi_ctx_t c, int model, int ns, int nc, int npath, const int* path_vars, int n_path_vars,
                            const double* params, int nparams, int maximize) {
+    c->keep.bump();             // the model, its parameters and the cost sign
     c->model = model;
     c->ns = ns;
     c->nc = nc;
@@ -1153,6 +1165,7 @@ int emi_check_model_source(const char* struct_name, const char* source, int ns, 
 int emi_set_batch(emi_ctx_t c, int B) {
     if (!c || B < 1) return fail(c, EMI_ERR_ARG, "emi_set_batch: B must be >= 1");
     if (c->M <= 0) return fail(c, EMI_ERR_STATE, "emi_set_mesh must precede emi_set_batch");
+    c->keep.bump();
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t rb = c->f32 ? 4 : 8;
     int st = ensure(c, c->d_cost_part, (size_t)B * emi::node_chunks(c->M) * rb);
@@ -1164,6 +1177,7 @@ int emi_set_batch(emi_ctx_t c, int B) {
 int emi_set_delays(emi_ctx_t c, int x_horizon, int u_horizon, double dt) {
     if (!c || x_horizon < 0 || u_horizon < 0) return fail(c, EMI_ERR_ARG, "emi_set_delays: horizons must be >= 0");
     if (c->model < 0) return fail(c, EMI_ERR_STATE, "emi_set_model / emi_set_model_source must precede emi_set_delays");
+    c->keep.bump();
     const int nxd = std::max(x_horizon - 1, 0) * c->ns;
     // nc_free + nxd + uh * nc_free = nc  (the model's control count includes the delayed values)
     const int rest = c->nc - nxd;
@@ -1199,6 +1213,7 @@ int emi_delay_matrix(int M, const double* tau, const double* w, double t0, doubl
 int emi_set_path(emi_ctx_t c, int np, int nsets, const double* recs, int px_state, int py_state) {
     if (!c || np < 0) return fail(c, EMI_ERR_ARG, "emi_set_path: bad argument");
     if (c->model < 0) return fail(c, EMI_ERR_STATE, "emi_set_model must precede emi_set_path");
+    c->keep.bump();             // the row layout of VALS
     if (np > 0 && (!recs || nsets < 1)) return fail(c, EMI_ERR_ARG, "emi_set_path: null table");
     if (px_state < 0 || px_state >= c->ns || py_state < 0 || py_state >= c->ns || px_state == py_state)
         return fail(c, EMI_ERR_ARG, "emi_set_path: state indices (%d,%d) out of range", px_state, py_state);
@@ -1220,6 +1235,7 @@ int emi_set_path(emi_ctx_t c, int np, int nsets, const double* recs, int px_stat
 int emi_set_tracks(emi_ctx_t c, int ntracks, int nsets, const double* xc, const double* yc) {
     if (!c || ntracks < 0) return fail(c, EMI_ERR_ARG, "emi_set_tracks: bad argument");
     if (c->M <= 0) return fail(c, EMI_ERR_STATE, "emi_set_mesh must precede emi_set_tracks");
+    c->keep.bump();
     if (ntracks > 0 && (!xc || !yc || nsets < 1)) return fail(c, EMI_ERR_ARG, "emi_set_tracks: null table");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)ntracks * nsets * c->M;
@@ -1279,6 +1295,14 @@ int emi_jac_structure(emi_ctx_t c, int* rows, int* cols) {
     return EMI_OK;
 }
 
+int emi_invariant_rows(int model, int np, unsigned char* mask, int* nvals) {
+    int ns, nc;
+    if (np < 0 || emi_model_dims(model, &ns, &nc, nullptr)) return EMI_ERR_ARG;
+    if (nvals) *nvals = ns * (ns + nc) + 2 * np + (ns + nc);
+    if (mask && !emi::invariant_rows(model, np, mask)) return EMI_ERR_ARG;
+    return EMI_OK;
+}
+
 int emi_dev_alloc(emi_ctx_t c, size_t bytes, void** dptr) {
     if (!c || !dptr) return EMI_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1314,9 +1338,16 @@ int emi_eval_dev(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* 
         (dVALS || (flags & EMI_EVAL_NOJAC)))
         piece = plan_piece(c, c->B);
     const PassIO io{dX, dU, dRES, dVALS, dCOST};
-    if (piece <= 0) return eval_launch(c, Launch{0, c->B}, io, flags);
-    for (int first = 0; first < c->B && st == EMI_OK; first += piece)
-        st = eval_launch(c, Launch{first, std::min(piece, c->B - first)}, io_at(c, io, first), flags);
+    // EMI_EVAL_KEEP_INVARIANT: honoured where this pass writes the Jacobian into the buffer the record names, under the generation
+    // it was made in; any other Jacobian pass writes everything and renews the record -- once ALL its pieces are out.  Passes that
+    // write no Jacobian (line searches interleave them) leave the record alone.
+    const emi::KeepRecord::Pass kp = c->keep.begin_pass((flags & EMI_EVAL_NODES) && !(flags & EMI_EVAL_NOJAC),
+                                                        flags & EMI_EVAL_KEEP_INVARIANT, dVALS);
+    flags &= ~(unsigned)EMI_EVAL_KEEP_INVARIANT;
+    if (piece <= 0) st = eval_launch(c, Launch{0, c->B, kp.keep}, io, flags);
+    for (int first = 0; piece > 0 && first < c->B && st == EMI_OK; first += piece)
+        st = eval_launch(c, Launch{first, std::min(piece, c->B - first), kp.keep}, io_at(c, io, first), flags);
+    c->keep.end_pass(kp, dVALS, st == EMI_OK);
     return st;
 }
 
@@ -1331,14 +1362,15 @@ int emi_eval_host(emi_ctx_t c, const double* X, const double* U, double* RES, do
     if ((st = upload_real(c, c->s_X, X, nX))) return st;
     if ((st = upload_real(c, c->s_U, U, nU))) return st;
     if ((st = ensure(c, c->s_RES, nR * rb))) return st;
-    if ((st = ensure(c, c->s_VALS, nV * rb))) return st;
+    if ((st = ensure_vals_staging(c, nV * rb))) return st;
     if ((st = ensure(c, c->s_COST, (size_t)c->B * rb))) return st;
     if (!(flags & EMI_EVAL_NODES)) {
         // accumulate-only form: the caller's RES is the starting value
         if (!RES) return fail(c, EMI_ERR_ARG, "emi_eval_host: defect-only needs RES in/out");
         if ((st = upload_real(c, c->s_RES, RES, nR))) return st;
     }
-    if ((st = emi_eval_dev(c, c->s_X.p, c->s_U.p, c->s_RES.p, c->s_VALS.p, c->s_COST.p, flags))) return st;
+    // (the staging buffer is the context's own: the record knows whether it still holds the invariant rows)
+    if ((st = emi_eval_dev(c, c->s_X.p, c->s_U.p, c->s_RES.p, c->s_VALS.p, c->s_COST.p, flags | EMI_EVAL_KEEP_INVARIANT))) return st;
     if ((st = download_real(c, RES, c->s_RES.p, nR))) return st;
     if (!(flags & EMI_EVAL_NOJAC) && (flags & EMI_EVAL_NODES))
         if ((st = download_real(c, VALS, c->s_VALS.p, nV))) return st;
@@ -1521,7 +1553,9 @@ static int lagr_grad_host(emi_ctx_t c, bool total, const double* VALS, const dou
     if (!VALS || !LamF || !G || (np_total(c) > 0 && !LamC)) return fail(c, EMI_ERR_ARG, "%s: null pointer", who);
     const size_t M = c->M, B = c->B, nf = c->ns + c->nc - c->nch;
     const size_t nV = B * nvals_of(c) * M, nF = B * c->ns * M, nC = B * np_total(c) * M, nG = B * nf * M, nGd = B * c->nch * M;
+    c->keep.written(c->s_VALS.p);           // the caller's VALS replace what an evaluation left in the staging buffer
     if ((st = upload_real(c, c->s_VALS, VALS, nV))) return st;
+    c->keep.written(c->s_VALS.p);
     if ((st = upload_real(c, c->s_LF, LamF, nF))) return st;
     if (nC && (st = upload_real(c, c->s_LC, LamC, nC))) return st;
     if ((st = ensure(c, c->s_G, nG * 8))) return st;
@@ -1612,7 +1646,7 @@ static int kkt_certificate_host(emi_ctx_t c, bool total, const double* X, const 
     if ((st = upload_real(c, c->s_zl, zl, (size_t)nsets * nv * M))) return st;
     if ((st = upload_real(c, c->s_zu, zu, (size_t)nsets * nv * M))) return st;
     if ((st = ensure(c, c->s_RES, nR * 8))) return st;
-    if ((st = ensure(c, c->s_VALS, nV * 8))) return st;
+    if ((st = ensure_vals_staging(c, nV * 8))) return st;
     if ((st = ensure(c, c->s_COST, B * 8))) return st;
     if ((st = ensure(c, c->s_G, nG * 8))) return st;
     if ((st = ensure(c, c->s_cert, B * 6 * 8))) return st;

@@ -67,6 +67,7 @@ template <typename T> struct NodeArgs {
     int path_sets, track_sets, ntracks;
     int px, py;
     int store_mode;     // launcher only: cache policy of the result stores (0 plain, 1 write-through sc1, 2 non-temporal)
+    int keep;           // launcher only: 1 = VALS holds the model-invariant rows already, take the KEEP instantiation where there is one
     T h, sgn;
     ModelParams<T> P;
 };

@@ -171,7 +171,7 @@ struct PassArgsF32 {
     NodeArgs<float> n;
     int nm8, nn8, nbx, order;
 };
-template <class Model>
+template <class Model, bool KEEP = false>     // KEEP: the node role leaves the model-invariant VALS rows alone (emi_nodes_body)
 __global__ __launch_bounds__(256, 3) void emi_pass_f32_kernel(PassArgsF32 a) {      // 3 workgroups per CU (50.7 KB of LDS each): <= 168 registers
     const int g = blockIdx.x, xcd = g & 7, j = g >> 3;
     const PassRole role = pass_role_of(j, a.nm8, a.nn8, a.order);
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256, 3) void emi_pass_f32_kernel(PassArgsF32 a) {  
         emi_defect_f32_body<true>(a.d, xcd * a.nm8 + role.index, 8 * a.nm8);
     } else {
         const int nid = xcd * a.nn8 + role.index;
-        emi_nodes_body<float, Model, 2, true, true, 0, true>(a.n, nid % a.nbx, nid / a.nbx, a.nbx);
+        emi_nodes_body<float, Model, 2, true, true, 0, true, KEEP>(a.n, nid % a.nbx, nid / a.nbx, a.nbx);
     }
 }
 
@@ -202,7 +202,8 @@ hipError_t launch_pass_f32(int model, const DefectArgsF32& d, const NodeArgs<flo
     a.nm8 = nm / 8;
     a.nn8 = nn / 8;
     a.order = order;
-    hipLaunchKernelGGL((emi_pass_f32_kernel<FixedWing12<float>>), dim3(nm + nn), dim3(256), 0, s, a);
+    if (n.keep) hipLaunchKernelGGL((emi_pass_f32_kernel<FixedWing12<float>, true>), dim3(nm + nn), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((emi_pass_f32_kernel<FixedWing12<float>>), dim3(nm + nn), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -294,17 +294,23 @@ static hipError_t launch_nodes_model(const NodeArgs<T>& a, bool jac, hipStream_t
     const bool vec2 = (M % 2 == 0);
     const int per_block = EMI_NODE_THREADS * (vec2 ? 2 : 1);
     dim3 grid((M + per_block - 1) / per_block, a.B), block(EMI_NODE_THREADS);
+    // (a.keep: the instantiations that leave the model-invariant VALS rows alone; a values-only launch has none to leave)
+    const bool keep = jac && a.keep;
     if constexpr (sizeof(T) == 8 && !DEFROWS) {
         // the kernel that runs beside the MFMA defect kernel: its stores may bypass L2 retention
+        if (vec2 && keep && a.store_mode == 1) { hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS, 1, true>), grid, block, 0, s, a); return hipGetLastError(); }
+        if (vec2 && keep && a.store_mode == 2) { hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS, 2, true>), grid, block, 0, s, a); return hipGetLastError(); }
         if (vec2 && jac && a.store_mode == 1) { hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS, 1>), grid, block, 0, s, a); return hipGetLastError(); }
         if (vec2 && jac && a.store_mode == 2) { hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS, 2>), grid, block, 0, s, a); return hipGetLastError(); }
     }
     if (vec2) {
-        if (jac) hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS>), grid, block, 0, s, a);
-        else     hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, false, DEFROWS>), grid, block, 0, s, a);
+        if (keep)     hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS, 0, true>), grid, block, 0, s, a);
+        else if (jac) hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, true, DEFROWS>), grid, block, 0, s, a);
+        else          hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 2, false, DEFROWS>), grid, block, 0, s, a);
     } else {
-        if (jac) hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 1, true, DEFROWS>), grid, block, 0, s, a);
-        else     hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 1, false, DEFROWS>), grid, block, 0, s, a);
+        if (keep)     hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 1, true, DEFROWS, 0, true>), grid, block, 0, s, a);
+        else if (jac) hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 1, true, DEFROWS>), grid, block, 0, s, a);
+        else          hipLaunchKernelGGL((emi_nodes_kernel<T, Model, 1, false, DEFROWS>), grid, block, 0, s, a);
     }
     return hipGetLastError();
 }
@@ -317,6 +323,24 @@ hipError_t launch_cost_finish(const T* part, T* cost, int B, int nchunks, T scal
 }
 template hipError_t launch_cost_finish<double>(const double*, double*, int, int, double, hipStream_t);
 template hipError_t launch_cost_finish<float>(const float*, float*, int, int, float, hipStream_t);
+
+// one byte per VALS row of `model` with np table rows: 1 = the row does not depend on (X, U) (what the KEEP instantiations skip)
+template <class Model>
+static void invariant_rows_model(int np, unsigned char* mask) {
+    constexpr int NS = Model::NS, NV = Model::NV;
+    for (int i = 0; i < NS; ++i)
+        for (int v = 0; v < NV; ++v) mask[i * NV + v] = emi_jac_varies<Model>(i, v, 0) ? 0 : 1;
+    for (int j = 0; j < 2 * np; ++j) mask[NS * NV + j] = 0;
+    for (int v = 0; v < NV; ++v) mask[NS * NV + 2 * np + v] = emi_grad_varies<Model>(v, 0) ? 0 : 1;
+}
+bool invariant_rows(int model, int np, unsigned char* mask) {
+    switch (model) {
+        case 0: invariant_rows_model<PointMass2D<double>>(np, mask); return true;
+        case 1: invariant_rows_model<Quadrotor2D<double>>(np, mask); return true;
+        case 2: invariant_rows_model<FixedWing12<double>>(np, mask); return true;
+    }
+    return false;
+}
 
 int node_chunks(int M) {
     const int per_block = EMI_NODE_THREADS * ((M % 2 == 0) ? 2 : 1);

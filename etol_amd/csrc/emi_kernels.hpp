@@ -16,6 +16,7 @@ static_assert(EMI_PATH_ELLIPSE == 0 && EMI_PATH_DISC == 1 && EMI_PATH_TRACK == 2
 namespace emi {
 
 int node_chunks(int M);
+bool invariant_rows(int model, int np, unsigned char* mask);    // [ns nv + 2 np + nv] bytes, 1 = row invariant; false: not a built-in model
 template <typename T>
 hipError_t launch_nodes(int model, const NodeArgs<T>& a, bool jac, bool defect_rows, hipStream_t s);
 template <typename T> hipError_t launch_hess(int model, const HessArgs<T>& a, hipStream_t s);

@@ -12,6 +12,10 @@
 //   L(z)   integrand cost               g[v]    = dL/dz_v
 //   hess() adds  cL*L_zz + sum_i cf[i]*f_i,zz  into the packed lower triangle
 //          H[v*(v+1)/2 + q], q<=v
+//   jac_varies(i, v) / grad_varies(v)   true where J[i][v] / g[v] depends on z or t; false where it is a function of the
+//          parameters alone (a structural zero included).  The node kernel may then leave the VALS row of that entry as an
+//          earlier pass wrote it (EMI_EVAL_KEEP_INVARIANT).  A model that declares neither means "everything varies".
+//          (Plain constexpr functions: the compiler takes those on the host and on the device alike.)
 //   NPATH  path rows the model computes itself (0 for the hand-written models, whose keep-outs come from the
 //          record table; generated models carry the user's traced constraint callbacks):
 //          path(P, z, t, c, cx, cy)      values and partials w.r.t. the two path states
@@ -59,6 +63,8 @@ EMI_DEV float emi_pow(float a, float c) { return powf(a, c); }
 // ---------------------------------------------------------------------------
 template <typename T> struct PointMass2D {
     static constexpr int NS = 2, NC = 2, NV = 4, NPARAM = 0, NPATH = 0;
+    static constexpr bool jac_varies(int, int) { return false; }
+    static constexpr bool grad_varies(int v) { return v >= 2; }
     EMI_DEV static void f(const ModelParams<T>&, const T* z, T, T* fo) {
         fo[0] = z[2];
         fo[1] = z[3];
@@ -95,6 +101,8 @@ template <typename T> struct PointMass2D {
 // ---------------------------------------------------------------------------
 template <typename T> struct Quadrotor2D {
     static constexpr int NS = 6, NC = 2, NV = 8, NPARAM = 5, NPATH = 0;
+    static constexpr bool jac_varies(int i, int v) { return (i == 3 || i == 4) && (v == 2 || v == 6); }
+    static constexpr bool grad_varies(int v) { return v >= 6; }
     EMI_DEV static void f(const ModelParams<T>& P, const T* z, T, T* fo) {
         T s, c;
         emi_sincos(z[2], &s, &c);
@@ -157,6 +165,25 @@ template <typename T> struct Quadrotor2D {
 // ---------------------------------------------------------------------------
 template <typename T> struct FixedWing12 {
     static constexpr int NS = 12, NC = 4, NV = 16, NPARAM = 16, NPATH = 0;
+    // bit v of row i: J[i][v] of jac() below is written from z (the other entries are 0, 1 or quotients of parameters)
+    static constexpr bool jac_varies(int i, int v) {
+        constexpr unsigned rows[NS] = {
+            0x01F8,     // f0: phi theta psi ub vb wb
+            0x01F8,     // f1
+            0x01D8,     // f2: phi theta ub vb wb
+            0x0C18,     // f3: phi theta qr rr (pr: 1)
+            0x0C08,     // f4: phi qr rr
+            0x0C18,     // f5: phi theta qr rr
+            0x0D90,     // f6: theta vb wb qr rr (thrust: 1 / m)
+            0x0B58,     // f7: phi theta ub wb pr rr (vb: -damp / m)
+            0x06D8,     // f8: phi theta ub vb pr qr (wb: -qS CLa / (V m))
+            0x0C00,     // f9: qr rr (pr: -damp / Ixx, aileron: constant)
+            0x0A00,     // f10: pr rr
+            0x0600,     // f11: pr qr
+        };
+        return (rows[i] >> v) & 1u;
+    }
+    static constexpr bool grad_varies(int v) { return v >= 12; }
     struct Pre {
         T sph, cph, sth, cth, sps, cps, tth, icth;
     };

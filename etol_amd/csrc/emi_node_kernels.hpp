@@ -87,6 +87,14 @@ template <class Model> EMI_DEV constexpr int emi_traced_partials() {
     else return 0;
 }
 
+// Whether entry (i, v) of the dynamics Jacobian / entry v of the cost gradient depends on (z, t), by the model's own declaration
+// (Model::jac_varies / grad_varies, emi_models.hpp).  A model that declares nothing -- every traced and run-time compiled one --
+// means "everything varies".
+template <class Model> constexpr auto emi_jac_varies(int i, int v, int) -> decltype(Model::jac_varies(i, v)) { return Model::jac_varies(i, v); }
+template <class Model> constexpr bool emi_jac_varies(int, int, long) { return true; }
+template <class Model> constexpr auto emi_grad_varies(int v, int) -> decltype(Model::grad_varies(v)) { return Model::grad_varies(v); }
+template <class Model> constexpr bool emi_grad_varies(int, long) { return true; }
+
 // a * b + c in ONE rounding, spelled out.  The path rows use it for every sum of products: left to the compiler, which products of
 // `dx * dx + dy * dy` are fused depends on the code around them (the two nodes of one thread came out differently -- one packed
 // multiply and an add, one fma -- and the values-only kernel differently from the full one), so the same row differed by an ulp
@@ -126,7 +134,11 @@ template <typename T> EMI_DEV T wave_sum(T v) {
 // DEFATOMIC (with DEFROWS): -h f is ADDED to the defect rows with no-return float atomics instead of stored -- the one-launch fp32 pass
 // (emi_defect_f32.hip), where the MFMA role adds D.X to the same, zeroed, rows in no particular order: two contributions per element,
 // and 0 + a + b = 0 + b + a exactly, so the result does not depend on which role comes first.
-template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST, bool DEFATOMIC = false>
+// KEEP (with JAC): the rows of the dynamics block and of the cost gradient that the model declares invariant are NOT stored -- they
+// are functions of the mesh, the parameters and the cost sign alone (0, -h, D_kk, -h / p ...; 50 of the quadrotor's 96 VALS rows)
+// and VALS still holds them from an earlier full pass of the same context (EMI_EVAL_KEEP_INVARIANT; emi_api.hip keeps the record
+// that says so).  Whole rows are skipped; what fed only those stores goes with them.  Path partials, RES and COST always vary.
+template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST, bool DEFATOMIC = false, bool KEEP = false>
 EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, const int nbx) {
     constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV;
     const int M = a.M;
@@ -204,11 +216,12 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
             for (int i = 0; i < NS; ++i)
 #pragma unroll
                 for (int v = 0; v < NV; ++v)
-                    stV((size_t)(i * NV + v) * M + k0, Jv[i][v]);
+                    if (!KEEP || emi_jac_varies<Model>(i, v, 0)) stV((size_t)(i * NV + v) * M + k0, Jv[i][v]);
             // cost gradient: behind the dynamics block, two partials per table row and PW per traced row
             const size_t goff = (size_t)(NS * NV + 2 * (a.np - Model::NPATH) + emi_traced_partials<Model>()) * M;
 #pragma unroll
-            for (int v = 0; v < NV; ++v) stV(goff + (size_t)v * M + k0, gv[v]);
+            for (int v = 0; v < NV; ++v)
+                if (!KEEP || emi_grad_varies<Model>(v, 0)) stV(goff + (size_t)v * M + k0, gv[v]);
         }
         // ---- K2 path constraints (records are wave-uniform: scalar loads) --
         const int np = a.np - Model::NPATH;      // rows of the record table; the model's own rows follow them
@@ -333,9 +346,9 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
     }
 }
 
-template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST = 0>
+template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST = 0, bool KEEP = false>
 __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_nodes_kernel(NodeArgs<T> a) {
-    emi_nodes_body<T, Model, VEC, JAC, DEFROWS, ST>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
+    emi_nodes_body<T, Model, VEC, JAC, DEFROWS, ST, false, KEEP>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
 }
 
 template <typename T>

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "emi_kernels.hpp"
 #include "emi_models.hpp"
@@ -179,15 +180,26 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     a.nm8 = (nm + 7) / 8;
     a.nn8 = ((nn + HS - 1) / HS + 7) / 8;          // node-role WORKGROUPS per XCD: one takes HS chunks
     const size_t lds = (size_t)HS * NST * ((2 * SW * FUSED_TI + 2 * 64 * CT + 63) / 64 * 64) * BK * sizeof(double);
-    static bool attr_done[4] = {false, false, false, false};
     const int st = (na.store_mode >= 0 && na.store_mode <= 3) ? na.store_mode : 0;   // result stores: plain / sc1 (write-through) / non-temporal / nt sc1
-    auto kern = st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS>
-              : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS>
-                         : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS>));
-    if (!attr_done[st]) {
+    // The KEEP instantiations (na.keep: the node role leaves the model-invariant VALS rows alone) exist for the forms the default
+    // dispatch chooses: three ring stages, undivided K range.  The forms only an option reaches write everything, which is always right.
+    constexpr bool HAS_KEEP = NST == 3 && HS == 1;
+    const bool keep = HAS_KEEP && na.keep;
+    auto pick = [&](auto keep_c) {
+        constexpr bool K = decltype(keep_c)::value;
+        return st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS, K>
+             : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS, K>
+                        : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS, K> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS, K>));
+    };
+    auto kern = pick(std::false_type{});
+    if constexpr (HAS_KEEP) {
+        if (keep) kern = pick(std::true_type{});
+    }
+    static bool attr_done[2][4] = {};
+    if (!attr_done[keep][st]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        attr_done[st] = true;
+        attr_done[keep][st] = true;
     }
     hipLaunchKernelGGL(kern, dim3(8 * (a.nm8 + a.nn8)), dim3(256 * HS), lds, s, a);
     return hipGetLastError();

@@ -949,7 +949,8 @@ __global__ __launch_bounds__(256) void emi_symdefect_combine_kernel(SymDefectArg
 // (The all-states form, SW > 3, holds 96 accumulator registers and has always run one workgroup per CU.)
 #define EMI_PASS_OCC __attribute__((amdgpu_waves_per_eu(SW > 3 ? 1 : 2, 2)))
 #endif
-template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1>
+// KEEP: the node role leaves the model-invariant VALS rows as an earlier full pass wrote them (emi_nodes_body); the MFMA role is the same.
+template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool KEEP = false>
 __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(PassArgs a) {
 #ifdef EMI_ENTRY_PAD_NOPS      // build-time experiment (tools/ab_build.sh): shift the whole instruction stream by 4-byte steps
     asm volatile(".rept " EMI_STR(EMI_ENTRY_PAD_NOPS) "\n\ts_nop 0\n\t.endr" ::: "memory");
@@ -969,7 +970,7 @@ __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(Pas
         // barriers only count the waves still running)
         const int nid = (xcd * a.nn8 + role.index) * HS + (HS > 1 ? (int)(threadIdx.x >> 8) : 0);
         if (nid >= a.nn) return;
-        emi_nodes_body<double, Model, VEC, true, false, ST>(a.n, nid % a.nbx, nid / a.nbx, a.nbx);
+        emi_nodes_body<double, Model, VEC, true, false, ST, false, KEEP>(a.n, nid % a.nbx, nid / a.nbx, a.nbx);
     }
 }
 

@@ -49,6 +49,17 @@ def track_centres(t, x, y, node_t):
     return xc, yc
 
 
+def invariant_rows(model, np_rows=0):
+    """Which VALS rows of a built-in model with np_rows table rows do not depend on (X, U): bool array [nvals]
+    (host, emi_invariant_rows)."""
+    lib = L.load()
+    n = C.c_int()
+    L.check(lib.emi_invariant_rows(int(model), int(np_rows), None, C.byref(n)), what="emi_invariant_rows")
+    mask = np.zeros(n.value, dtype=np.uint8)
+    L.check(lib.emi_invariant_rows(int(model), int(np_rows), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), None), what="emi_invariant_rows")
+    return mask.astype(bool)
+
+
 class Evaluator:
     """One libemi355x context: mesh + model + batch, evaluated on one GPU."""
 
@@ -63,12 +74,15 @@ class Evaluator:
         self._keep = []
         self._lay = None        # cached emi_get_layout / emi_get_delays answers: eval_dev is the timed call of bench.py and of any
         self._nd = None         # batched user, and two ctypes round trips per pass show at 14 - 20 us passes; reset by every set_*
+        self._kept = None       # the VALS tensor eval_dev last ran a full Jacobian pass into (held: its address cannot be recycled) ...
+        self._kept_version = -1  # ... and its torch version counter then: any torch write to it since shows as another value
 
     def _changed(self):
         self._lay = None
         self._nd = None
 
     def close(self):
+        self._kept = None
         if self.ctx:
             self.lib.emi_destroy(self.ctx)
             self.ctx = C.c_void_p()
@@ -170,7 +184,12 @@ class Evaluator:
         return res, vals, cost
 
     def eval_dev(self, X, U, RES, VALS, COST, flags=L.EVAL_ALL):
-        """X,U,RES,VALS,COST: contiguous torch tensors on this evaluator's device."""
+        """X,U,RES,VALS,COST: contiguous torch tensors on this evaluator's device.
+
+        A Jacobian pass into the very VALS tensor of this evaluator's previous one, untouched by torch in between, adds
+        EVAL_KEEP_INVARIANT by itself: the rows that depend on the mesh and the model alone are not stored again (the library
+        checks for its part that mesh, model, batch and tables are still the same).  Code that writes into VALS past torch (a raw
+        pointer, another library) must overwrite it through torch once -- VALS.add_(0) will do -- or the rows it destroyed stay destroyed."""
         lay = self.layout
         for t, shape in ((X, (lay.B, lay.ns, lay.M)), (U, (lay.B, lay.nc - self.n_delayed, lay.M)),
                          (RES, (lay.B, lay.nres, lay.M)), (VALS, (lay.B, lay.nvals, lay.M)), (COST, (lay.B,))):
@@ -179,7 +198,12 @@ class Evaluator:
             if tuple(t.shape) != shape or t.dtype != self.dtype or not t.is_contiguous() or t.device != self.device:
                 raise ValueError(f"tensor {tuple(t.shape)} {t.dtype} {t.device} does not match layout {shape} {self.dtype}")
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        jac = VALS is not None and (flags & L.EVAL_NODES) and not (flags & L.EVAL_NOJAC)
+        if jac and VALS is self._kept and VALS._version == self._kept_version:
+            flags |= L.EVAL_KEEP_INVARIANT
         self._ck(self.lib.emi_eval_dev(self.ctx, ptr(X), ptr(U), ptr(RES), ptr(VALS), ptr(COST), flags), "emi_eval_dev")
+        if jac:
+            self._kept, self._kept_version = VALS, VALS._version
 
     def hess_dev(self, X, U, lamF, lamC, sigma, H):
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None

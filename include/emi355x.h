@@ -128,7 +128,8 @@ enum {
     EMI_EVAL_NODES = 1u,   /* K1+K2+K3+K5: node functions, Jacobian values   */
     EMI_EVAL_DEFECT = 2u,  /* K4: accumulate D.X into the defect rows        */
     EMI_EVAL_ALL = 3u,
-    EMI_EVAL_NOJAC = 4u    /* values only (line-search evaluations)          */
+    EMI_EVAL_NOJAC = 4u,   /* values only (line-search evaluations)          */
+    EMI_EVAL_KEEP_INVARIANT = 8u  /* leave the model-invariant VALS rows as they are: see emi_eval_dev */
 };
 
 typedef struct {
@@ -495,6 +496,11 @@ int emi_plan_pass(emi_ctx_t ctx, int B, emi_pass_plan_t* out);
  * rows/cols have nvals*M entries ordered like VALS; cost-gradient entries
  * carry row = -1.                                                          */
 int emi_jac_structure(emi_ctx_t ctx, int* rows, int* cols);
+/* No device and no context needed: which rows of VALS do not depend on (X, U) for a built-in model with np table rows
+ * -- entries of the dynamics block and of the cost gradient that are 0, -h, D_kk or a quotient of parameters times h
+ * (Quadrotor2D: 50 of its 56 + 2 np rows).  mask[r] = 1 for such a row, 0 otherwise (mask may be NULL); *nvals = the
+ * number of rows.  These are the rows a pass with EMI_EVAL_KEEP_INVARIANT does not store.  EMI_ERR_ARG: not a built-in model. */
+int emi_invariant_rows(int model, int np, unsigned char* mask, int* nvals);
 
 /* ---- device memory helpers (for callers without their own allocator) ---- */
 int emi_dev_alloc(emi_ctx_t ctx, size_t bytes, void** dptr);
@@ -504,11 +510,23 @@ int emi_d2h(emi_ctx_t ctx, void* dst, const void* src, size_t bytes);
 
 /* ---- the hot path -------------------------------------------------------- */
 /* Device-pointer form: every pointer is device memory of the layout above,
- * in the context's real type.  Asynchronous on the context's stream.        */
+ * in the context's real type.  Asynchronous on the context's stream.
+ *
+ * EMI_EVAL_KEEP_INVARIANT (with a pass that writes the Jacobian): the caller asserts that dVALS is the buffer THIS context
+ * last filled with a full Jacobian pass and that nobody else has written its invariant rows (emi_invariant_rows) since.
+ * The pass then does not store those rows again -- they depend on the mesh, the model parameters and the cost sign only
+ * (400 of the 976 bytes a quadrotor node-eval writes) -- and every other output is bit for bit what a full pass gives.
+ * The context keeps its own record (buffer address, whole batch written, a generation bumped by emi_set_mesh, emi_set_model,
+ * emi_set_model_source, emi_set_batch, emi_set_path, emi_set_tracks, emi_set_delays) and honours the flag only where address
+ * and generation match; otherwise, and for run-time compiled models and launch forms without such a kernel, the pass
+ * writes everything, which renews the record.  EMI_EVAL_NOJAC passes leave the record alone.  What the record cannot see
+ * is the caller's side of the assertion: a buffer freed and allocated again at the same address, or overwritten by other
+ * code, must not be passed with the flag.                                                                            */
 int emi_eval_dev(emi_ctx_t ctx, const void* dX, const void* dU, void* dRES,
                  void* dVALS, void* dCOST, unsigned flags);
 /* Host-buffer form (double in/out whatever the arithmetic type): copies in,
- * evaluates, copies out, synchronises.  Output pointers may be NULL.        */
+ * evaluates, copies out, synchronises.  Output pointers may be NULL.  (VALS is staged in a buffer of the context's own,
+ * so this form keeps the invariant rows by itself from its second Jacobian pass on.)                                  */
 int emi_eval_host(emi_ctx_t ctx, const double* X, const double* U, double* RES,
                   double* VALS, double* COST, unsigned flags);
 

@@ -231,7 +231,7 @@ def main():
             for f in forms:
                 ms = 1e3 * float(np.median(times[f]))
                 rec = dict(B=B, M=M, form=f, rotate=a.rotate, touch=a.touch, ms_per_pass=round(ms, 5), node_evals_per_s=float("%.4g" % (B * M / (ms * 1e-3))),
-                           kernel=names[f], rounds=a.rounds)
+                           kernel=names[f], rounds=a.rounds, ms_min=round(1e3 * min(times[f]), 5), ms_max=round(1e3 * max(times[f]), 5))
                 fo.write(json.dumps(rec) + "\n")
                 print(f"B={B:6d} {f:16s} {ms:9.4f} ms  {rec['node_evals_per_s']:.3e}/s  {names[f][:60]}", flush=True)
         ev.close()
