@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record
+.PHONY: all lib host oracle clean check-keep-record check-nlp
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -94,6 +94,16 @@ KEEP_CHECK_OUT ?= $(LIBDIR)/keep_record_check
 check-keep-record: tests/harness/keep_record_main.cpp $(CSRC)/emi_keep_record.hpp | $(LIBDIR)
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -I$(CSRC) -o $(KEEP_CHECK_OUT) $<
 	$(KEEP_CHECK_OUT)
+
+# the NLP iteration (emi_nlp.cpp: its state object, the steps and iterates it copies and takes back) as a stand-alone program under
+# the host sanitizers, on the CPU oracle: no Python, no device
+SANITIZE      := -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer
+NLP_CHECK_OUT ?= $(LIBDIR)/nlp_sanitize_check
+check-nlp: tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_nlp.hpp $(CSRC)/emi_host.cpp oracle/emi_oracle.c | $(LIBDIR)
+	$(CC) $(SANITIZE) -std=c99 -c oracle/emi_oracle.c -o $(NLP_CHECK_OUT)_oracle.o
+	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -I$(HOST) -o $(NLP_CHECK_OUT) tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(CSRC)/emi_host.cpp \
+		$(NLP_CHECK_OUT)_oracle.o -lm
+	$(NLP_CHECK_OUT)
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

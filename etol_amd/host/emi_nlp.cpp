@@ -165,19 +165,6 @@ void ldlt_solve(const LdltFactor& F, double* b) {
 namespace {
 
 constexpr double INF_BOUND = 1e19;
-
-struct Iterate {
-    std::vector<double> z, s, e1, e2;             // primal: variables, row slacks, elastics
-    std::vector<double> lam, y;                   // equality multipliers (defects, path rows)
-    std::vector<double> zL, zU, vL, vU, w1, w2;   // bound multipliers (0 where the bound is infinite)
-};
-
-struct Eval {
-    std::vector<double> RES, VALS, H;
-    std::vector<double> LNK;          // residuals of the coupling rows (NlpProblem::links), [link][M]
-    double cost = 0;
-};
-
 }  // namespace
 
 void assemble_node_blocks(const double* H, const double* VALS, const double* Sigma, const double* sig_t, const unsigned char* fixed,
@@ -789,133 +776,364 @@ double ipm_kkt_error(const IpmDims& P, const IpmPoint& x, const IpmDuals& d, con
     return std::max(std::max(ed / sd, ep), ec / sc);
 }
 
-NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vector<double>& z0) {
-    NlpResult R;
-    const int ns = P.ns, nc = P.nc, np = P.np, M = P.M, nv = ns + nc;
-    const int nz = nv * M, md = ns * M, mc = np * M, nh = nv * (nv + 1) / 2;
-    const int nl = (int)P.links.size(), ml = nl * M, me = md + ml;      // coupling rows behind the defects: me equality multipliers
-    for (const NlpLink& L : P.links)
-        if (L.dst < 0 || L.dst >= nv || L.src < 0 || L.src >= nv || L.dst == L.src || (int)L.W.size() != M * M) {
-            R.msg = "solve_nlp: a coupling row names variables outside the problem or has no M x M operator";
-            return R;
-        }
-    if (nl > 0 && P.kkt) { R.msg = "solve_nlp: coupling rows (delayed values) are solved with the dense host backend only"; return R; }
-    // (variable, VALS entry) pairs of every path row
-    std::vector<std::vector<std::pair<int, int>>> rv = P.row_vars;
-    if (rv.empty())
-        for (int j = 0; j < np; ++j) rv.push_back({{P.px, ns * nv + 2 * j}, {P.py, ns * nv + 2 * j + 1}});
-    if ((int)rv.size() != np) { R.msg = "solve_nlp: row_vars has the wrong length"; return R; }
-    int npart = 0;
-    for (const auto& r : rv) npart += (int)r.size();
-    const int nvals = ns * nv + npart + nv;
-    if (!P.vscale.empty()) {            // iterate on the scaled variables (ScaledEvaluator above), answer in the caller's
-        if ((int)P.vscale.size() != nv || (int)z0.size() != nz || (int)P.zl.size() != nz || (int)P.zu.size() != nz || !P.ev) {
-            R.msg = "solve_nlp: inconsistent problem sizes (vscale)";
-            return R;
-        }
-        for (double sv : P.vscale)
-            if (!(sv > 0) || !std::isfinite(sv)) { R.msg = "solve_nlp: vscale must be positive"; return R; }
-        for (const NlpLink& L : P.links)        // (d - W z) / s keeps W only if both ends carry the same scale
-            if (P.vscale[L.dst] != P.vscale[L.src]) { R.msg = "solve_nlp: a coupled variable must be scaled like its source"; return R; }
-        NlpProblem Q = P;
-        Q.vscale.clear();
-        Q.row_vars = rv;
-        ScaledEvaluator sev(P, rv, npart);
-        Q.ev = &sev;
-        std::vector<double> zs(z0);
-        for (int v = 0; v < nv; ++v)
-            for (int k = 0; k < M; ++k) {
-                const size_t q = (size_t)v * M + k;
-                const double inv = 1.0 / P.vscale[v];
-                zs[q] *= inv;
-                if (Q.zl[q] > -INF_BOUND) Q.zl[q] *= inv;
-                if (Q.zu[q] < INF_BOUND) Q.zu[q] *= inv;
-                if (P.zl[q] == P.zu[q]) Q.zu[q] = Q.zl[q];
-            }
-        if ((int)Q.lamF0.size() == md)
-            for (int i = 0; i < ns; ++i)
-                for (int k = 0; k < M; ++k) Q.lamF0[(size_t)i * M + k] *= P.vscale[i];
-        NlpResult S = solve_nlp(Q, opt, zs);
-        for (int v = 0; v < nv && (int)S.z.size() == nz; ++v)
-            for (int k = 0; k < M; ++k) S.z[(size_t)v * M + k] *= P.vscale[v];
-        for (int i = 0; i < ns && (int)S.lamF.size() == md; ++i)
-            for (int k = 0; k < M; ++k) S.lamF[(size_t)i * M + k] /= P.vscale[i];
-        for (size_t l = 0; l < P.links.size() && S.lamL.size() == P.links.size() * M; ++l)      // row (d - W z) / s: multiplier / s
-            for (int k = 0; k < M; ++k) S.lamL[l * M + k] /= P.vscale[P.links[l].dst];
-        return S;
-    }
-    if (!P.ev || (int)P.zl.size() != nz || (int)P.zu.size() != nz || (int)P.D.size() != M * M ||
-        (int)P.cl.size() != np || (int)P.cu.size() != np || (int)z0.size() != nz) {
-        R.msg = "solve_nlp: inconsistent problem sizes";
-        return R;
-    }
-    const auto tstart = std::chrono::steady_clock::now();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
-    };
+// ---- the iteration: its state as an object, its phases as members ("Phases of the iteration") -------------
+namespace {
 
-    // free-variable map
-    std::vector<int> fidx(nz, -1);
-    int nf = 0;
-    for (int q = 0; q < nz; ++q)
-        if (P.zu[q] > P.zl[q]) fidx[q] = nf++;
-    auto hasL = [&](int q) { return P.zl[q] > -INF_BOUND; };
-    auto hasU = [&](int q) { return P.zu[q] < INF_BOUND; };
-    // path rows are iterated on in scaled form  sigma_j * c_j  (same KKT points, better
-    // balanced against the defects: a keep-out value is O(a^2 b^2) ~ 1e-3 unscaled)
-    std::vector<double> sig(np, 1.0);
-    if (!P.cscale.empty()) {
-        if ((int)P.cscale.size() != np) { R.msg = "solve_nlp: cscale has the wrong length"; return R; }
-        for (int j = 0; j < np; ++j) sig[j] = P.cscale[j] > 0 ? P.cscale[j] : 1.0;
-    }
-    for (int j = 0; j < np; ++j)
-        if (!(P.cl[j] > -INF_BOUND) && !(P.cu[j] < INF_BOUND)) { R.msg = "solve_nlp: path row without any bound"; return R; }
-    auto shasL = [&](int r) { return P.cl[r / M] > -INF_BOUND; };
-    auto shasU = [&](int r) { return P.cu[r / M] < INF_BOUND; };
-    auto cL = [&](int r) { return shasL(r) ? sig[r / M] * P.cl[r / M] : P.cl[r / M]; };
-    auto cU = [&](int r) { return shasU(r) ? sig[r / M] * P.cu[r / M] : P.cu[r / M]; };
-    // the same problem as the free functions of the iteration's array arithmetic take it (ipm_*)
-    IpmDims PD;
-    PD.nv = nv; PD.ns = ns; PD.np = np; PD.M = M; PD.ml = ml;
-    std::vector<double> cls(np), cus(np);       // the row bounds the iteration works with: sig_j * bound where there is one
-    for (int j = 0; j < np; ++j) { cls[j] = cL(j * M); cus[j] = cU(j * M); }
-    PD.zl = P.zl.data(); PD.zu = P.zu.data(); PD.cl = P.cl.data(); PD.cu = P.cu.data(); PD.cls = cls.data(); PD.cus = cus.data();
-    PD.row_vars = &rv;
-    auto point_of = [](const std::vector<double>& z, const std::vector<double>& s, const std::vector<double>& e1, const std::vector<double>& e2) {
-        return IpmPoint{z.data(), s.data(), e1.data(), e2.data()};
-    };
-    auto duals_of = [](const Iterate& I) {
-        return IpmDuals{I.lam.data(), I.y.data(), I.zL.data(), I.zU.data(), I.vL.data(), I.vU.data(), I.w1.data(), I.w2.data()};
-    };
-    auto res_of = [](const Eval& e) { return IpmRes{e.RES.data(), e.LNK.data()}; };
+using Clock = std::chrono::steady_clock;
+using RowVars = std::vector<std::vector<std::pair<int, int>>>;
+inline double secs_since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+// v pushed into the interior of [l, u] (a side that is not there: hasL / hasU false)
+inline double pushed_inside(double v, double l, double u, bool hasL, bool hasU, const NlpOptions& opt) {
+    double pl = hasL ? opt.bound_push * std::max(1.0, std::fabs(l)) : 0, pu = hasU ? opt.bound_push * std::max(1.0, std::fabs(u)) : 0;
+    if (hasL && hasU) { pl = std::min(pl, opt.bound_frac * (u - l)); pu = std::min(pu, opt.bound_frac * (u - l)); }
+    if (hasL) v = std::max(v, l + pl);
+    if (hasU) v = std::min(v, u - pu);
+    return v;
+}
+inline bool all_finite(const double* v, size_t n) {
+    bool fin = true;
+    for (size_t r = 0; r < n && fin; ++r) fin = std::isfinite(v[r]);
+    return fin;
+}
 
-    Iterate it;
-    it.z = z0;
-    // push the start into the interior of the bounds
-    for (int q = 0; q < nz; ++q) {
-        const double l = P.zl[q], u = P.zu[q];
-        if (fidx[q] < 0) { it.z[q] = l; continue; }
-        double pl = 0, pu = 0;
-        if (hasL(q)) pl = opt.bound_push * std::max(1.0, std::fabs(l));
-        if (hasU(q)) pu = opt.bound_push * std::max(1.0, std::fabs(u));
-        if (hasL(q) && hasU(q)) {
-            pl = std::min(pl, opt.bound_frac * (u - l));
-            pu = std::min(pu, opt.bound_frac * (u - l));
-        }
-        if (hasL(q)) it.z[q] = std::max(it.z[q], l + pl);
-        if (hasU(q)) it.z[q] = std::min(it.z[q], u - pu);
-    }
-
+struct Iterate {
+    std::vector<double> z, s, e1, e2;             // primal: variables, row slacks, elastics
+    std::vector<double> lam, y;                   // equality multipliers (defects then coupling rows, path rows)
+    std::vector<double> zL, zU, vL, vU, w1, w2;   // bound multipliers (0 where the bound is infinite)
+};
+struct Eval {
+    std::vector<double> RES, VALS;
+    std::vector<double> LNK;          // residuals of the coupling rows (NlpProblem::links), [link][M]
+    double cost = 0;
+};
+// an iterate with everything evaluated at it: what the residual-based acceptance keeps and takes back as a whole
+struct Point : Iterate {
     Eval E;
-    E.RES.resize((size_t)(ns + np) * M);
-    E.VALS.resize((size_t)nvals * M);
-    E.H.resize((size_t)nh * M);
-    auto evaluate = [&](const std::vector<double>& z, Eval& e, bool jac) -> bool {
+    std::vector<double> gradf, jtl;   // cost gradient and J^T (lam, y)
+};
+// a Newton step with the r_t of the eliminated rows it was expanded from and its fraction-to-the-boundary lengths: what the
+// second-order correction keeps and takes back as a whole
+struct Step {
+    std::vector<double> dz, dlam, ds, dy, de1, de2, dzL, dzU, dvL, dvU, dw1, dw2, r_t;
+    double apr = 1.0, adu = 1.0;
+};
+
+// One solve.  The driver (solve_nlp) calls start(), then per iteration test_and_update_barrier(), newton_system() and
+// line_search() for as long as each says `go`, then finish().  Every Ipm* view of a member array is built where it is used
+// (here(), duals(), elim(), ...): none is kept across an assignment to the array it points into.
+class IpmSolve {
+ public:
+    enum class Next { go, finish, abort };    // next phase / leave the loop and finish() / return result() as it stands
+
+    IpmSolve(const NlpProblem& prob, const NlpOptions& options, RowVars row_vars, int n_partials)
+        : P(prob), opt(options), rv(std::move(row_vars)), ns(P.ns), np(P.np), M(P.M), nv(P.ns + P.nc), nz(nv * M), md(ns * M),
+          mc(np * M), nl((int)P.links.size()), ml(nl * M), me(md + ml), npart(n_partials), NN((size_t)nz + me), host_kkt(P),
+          kkt(P.kkt ? P.kkt : &host_kkt), backend_blocks(opt.device_node_blocks && P.kkt != nullptr) {
+        const size_t nh = (size_t)nv * (nv + 1) / 2, nvals = (size_t)ns * nv + npart + nv;
+        // path rows are iterated on in scaled form  sigma_j * c_j  (same KKT points, better balanced against the defects)
+        sig.assign(np, 1.0);
+        if ((int)P.cscale.size() == np)
+            for (int j = 0; j < np; ++j) sig[j] = P.cscale[j] > 0 ? P.cscale[j] : 1.0;
+        for (int j = 0; j < np; ++j) {      // the row bounds the iteration works with: sig_j * bound where there is one
+            cls.push_back(P.cl[j] > -INF_BOUND ? sig[j] * P.cl[j] : P.cl[j]);
+            cus.push_back(P.cu[j] < INF_BOUND ? sig[j] * P.cu[j] : P.cu[j]);
+        }
+        PD.nv = nv; PD.ns = ns; PD.np = np; PD.M = M; PD.ml = ml; PD.row_vars = &rv;
+        PD.zl = P.zl.data(); PD.zu = P.zu.data(); PD.cl = P.cl.data(); PD.cu = P.cu.data(); PD.cls = cls.data(); PD.cus = cus.data();
+        fixed_mask.resize(nz);
+        for (int q = 0; q < nz; ++q) fixed_mask[q] = B.free_var(q) ? 0 : 1;
+        rs.assign(me, 1.0);
+        it.E.RES.resize((size_t)(ns + np) * M);
+        it.E.VALS.resize(nvals * M);
+        Et.RES.resize(it.E.RES.size());
+        H.resize(nh * M);
+        Qblk.resize(nh * M);
+        for (auto* v : {&it.gradf, &it.jtl, &zt, &Sigma, &step.dz, &step.dzL, &step.dzU}) v->resize(nz);
+        for (auto* v : {&st, &e1t, &e2t, &y_unscaled, &sig_t, &sig_s, &rhat_s, &step.ds, &step.dy, &step.de1, &step.de2, &step.dvL, &step.dvU,
+                        &step.dw1, &step.dw2, &step.r_t, &soc_row})
+            v->resize(mc);
+        for (auto* v : {&step.dlam, &eqres, &soc_def}) v->resize(me);
+        for (auto* v : {&rhs_full, &rhs_keep, &resid, &x_prev, &soc_rhs}) v->resize(NN);
+    }
+    IpmSolve(const IpmSolve&) = delete;
+    IpmSolve& operator=(const IpmSolve&) = delete;
+
+    const NlpResult& result() const { return R; }
+
+    // interior push of z0, first evaluation, slacks and elastics, multipliers, merit row weights, first J^T lambda
+    bool start(const std::vector<double>& z0) {
+        it.z = z0;
+        for (int q = 0; q < nz; ++q)        // push the start into the interior of the bounds
+            it.z[q] = fixed_mask[q] ? P.zl[q] : pushed_inside(it.z[q], P.zl[q], P.zu[q], B.hasL(q), B.hasU(q), opt);
+        if (!evaluate(it.z, it.E, true)) return evaluator_failed(), false;
+        rho = opt.rho_init > 0 ? opt.rho_init : 10.0;
+        for (auto* v : {&it.s, &it.e1, &it.e2, &it.y, &it.vL, &it.vU}) v->assign(mc, 0.0);
+        for (int r = 0; r < mc; ++r) {
+            const double c0 = it.E.RES[(size_t)md + r];
+            it.s[r] = pushed_inside(c0, B.cL(r), B.cU(r), B.shasL(r), B.shasU(r), opt);
+            const double gap = c0 - it.s[r], ee = opt.bound_push * std::max(1.0, std::fabs(gap));
+            it.e1[r] = std::max(gap, 0.0) + ee;     // residual c - s - e1 + e2 starts at exactly 0
+            it.e2[r] = std::max(-gap, 0.0) + ee;
+        }
+        it.lam.assign(me, 0.0);
+        if ((int)P.lamF0.size() == md) std::copy(P.lamF0.begin(), P.lamF0.end(), it.lam.begin());
+        // row weights of the merit function (jacobian_defect_scaling): 1 / max(1, inf-norm of the defect row of the Jacobian at the start)
+        if (P.jacobian_defect_scaling) {
+            const double* V0 = it.E.VALS.data();
+            for (int k = 0; k < M; ++k) {
+                double dmax = 0;
+                for (int j = 0; j < M; ++j)
+                    if (j != k) dmax = std::max(dmax, std::fabs(P.D[(size_t)k * M + j]));
+                for (int i = 0; i < ns; ++i) {
+                    double nrm = dmax;
+                    for (int v = 0; v < nv; ++v) nrm = std::max(nrm, std::fabs(V0[(size_t)(i * nv + v) * M + k]));
+                    rs[i * M + k] = 1.0 / std::max(1.0, nrm);
+                }
+            }
+        }
+        if ((int)P.lamC0.size() == mc)      // iterated on in scaled form; inside the penalty box
+            for (int r = 0; r < mc; ++r) it.y[r] = std::min(std::max(P.lamC0[r] / sig[r / M], -0.9 * rho), 0.9 * rho);
+        it.zL.assign(nz, 0.0); it.zU.assign(nz, 0.0);
+        it.w1.assign(mc, rho); it.w2.assign(mc, rho);
+        reset_elastic_duals();
+        for (int q = 0; q < nz; ++q) if (!fixed_mask[q]) { if (B.hasL(q)) it.zL[q] = 1.0; if (B.hasU(q)) it.zU[q] = 1.0; }
+        for (int r = 0; r < mc; ++r) { if (B.shasL(r)) it.vL[r] = 1.0; if (B.shasU(r)) it.vU[r] = 1.0; }
+        mu = opt.mu_init, nu = 1.0;
+        grad_and_jt();
+        return true;
+    }
+
+    // convergence, acceptable-level, locally-infeasible, iteration and time tests; stagnation rule; barrier loop with penalty escalation
+    Next test_and_update_barrier(int iter) {
+        R.iterations = iter;
+        double viol = 0;
+        err0 = kkt_error(0.0, &viol, &emax);
+        R.kkt_error = err0;
+        R.constr_viol = viol;
+        if (opt.print_level >= 5)
+            printf("iter %3d  cost %.10e  inf_pr %.2e  kkt %.2e  mu %.1e  dw %.1e  nu %.1e  emax %.1e  rho %.0e  r %d%s\n", iter,
+                   it.E.cost, viol, err0, mu, dw_used, nu, emax, rho, n_mods, exact_step ? " exact" : "");
+        if (err0 <= opt.tol) {
+            if (emax <= std::max(opt.tol, 1e-9) * 10.0 || mc == 0) { R.ok = true; R.msg = "converged"; return Next::finish; }
+            // a path row is still relaxed: the penalty was too small for it
+            if (rho >= 1e12 || futile_escalation(emax)) { R.msg = "converged to a point that violates the path rows (locally infeasible)"; return Next::finish; }
+            escalate_penalty();
+        }
+        // stagnation at round-off above the tolerance (large meshes): accept like IPOPT's acceptable level
+        if (acceptable()) {
+            if (++n_acceptable >= opt.acceptable_iter) { R.ok = true; R.msg = "converged to acceptable level"; return Next::finish; }
+        } else {
+            n_acceptable = 0;
+        }
+        // reflected steps that have not reduced the KKT residual of the barrier problem by 10 % over `stagnation_iters` iterations: switch the inertia search
+        // on (measured, profiles/r01_notes.md: 4 costs the keep-out Monte-Carlo sets half their throughput in trial factorisations, 12 keeps it and still rescues the fixed wing)
+        const double err_mu_now = kkt_error(mu, nullptr, nullptr);
+        if (last_step_reflected && err_mu_now > 0.9 * stagn_ref) {
+            if (++stagn >= opt.stagnation_iters) {
+                search_on = true;
+                if (opt.mu_restart > 1.0 && !mu_restarted && mu < 1e-4) {
+                    mu_restarted = true;
+                    mu = std::min(1e-3, mu * opt.mu_restart);
+                    nu = 1.0;
+                    stagn = 0;
+                    stagn_ref = 1e300;
+                    if (opt.print_level >= 5) printf("stagnation at a small barrier parameter: raised to %.1e\n", mu);
+                }
+            }
+        } else {
+            stagn = 0;
+            stagn_ref = err_mu_now;
+        }
+        if (iter >= opt.max_iter) { R.msg = "maximum number of iterations exceeded"; return Next::finish; }
+        if (secs_since(tstart) > opt.max_cpu_time) { R.msg = "time limit exceeded"; return Next::finish; }
+        // barrier update (may fire several times in a row)
+        const double kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5;     // (kappa_sigma: ipm_update_duals)
+        while (mu > opt.tol / 10.0 && kkt_error(mu, nullptr, nullptr) <= kappa_eps * mu) {
+            // this barrier problem is solved.  A row multiplier at the penalty weight (or, equivalently, an elastic still far above mu / rho)
+            // means the weight is too small for that row: raise it now instead of converging to a relaxed point first
+            double ymax = 0;
+            for (int r = 0; r < mc; ++r) ymax = std::max(ymax, std::fabs(it.y[r]));
+            if (mc > 0 && (emax > std::max(1e-6, 100.0 * mu) || ymax > 0.9 * rho) && rho < 1e12) {
+                if (futile_escalation(emax)) { R.msg = "the path rows stay violated while the penalty weight grows (locally infeasible)"; return Next::finish; }
+                escalate_penalty();
+                nu = 1.0;
+                break;
+            }
+            mu = std::max(opt.tol / 10.0, std::min(kappa_mu * mu, std::pow(mu, theta_mu)));
+            nu = 1.0;    // a new barrier problem: the penalty weight is rebuilt from its multipliers, not inherited
+        }
+        tau = std::max(0.99, 1.0 - mu);
+        return Next::go;
+    }
+
+    // Hessian, row elimination, attempt loop (node blocks, factorisation, low-rank verdict, inertia search), refined solve -> rhs_full
+    Next newton_system() {
+        // exact Lagrangian Hessian blocks from the device
+        for (int r = 0; r < mc; ++r) y_unscaled[r] = sig[r / M] * it.y[r];
+        const auto th0 = Clock::now();
+        const int hess_rc = P.ev->hess(it.z.data(), it.z.data() + (size_t)ns * M, it.lam.data(), np ? y_unscaled.data() : nullptr, 1.0, H.data());
+        R.t_hess += secs_since(th0);
+        if (hess_rc != 0) { R.msg = "Hessian evaluation failed: " + P.ev->last_error(); return Next::finish; }
+        // eliminate (s, e+, e-) of every path row:  dy = sig_t (J_c dz + r_t)
+        ipm_eliminate_rows(PD, here(), duals(), res_of(it.E), mu, rho, elim());
+        // factor with inertia correction
+        bool factored = false;
+        double dw = 0.0, dc = 0.0;
+        double dw_shift = 0.0;      // primal regularisation delta_w I of the inertia search (below)
+        int shift_trials = 0;
+        for (int attempt = 0; attempt < 24; ++attempt) {
+            const int info = factor_node_blocks(dc, dw_shift, &dw);
+            if (info < 0) { R.msg = "KKT factorisation failed: " + kkt->last_error(); return Next::abort; }
+            if (info > 0) { raise_dc(dc); continue; }   // exactly singular: the defect Jacobian lost rank; regularise the dual block
+            if (!lowrank_verdict()) return Next::abort;
+            // Inertia search (IPOPT's delta_w): the unmodified K has the wrong inertia.  The step of the reflected blocks is the cheap answer and
+            // usually a good one; where it stagnates (search_on, set by the stagnation rule) look for the smallest shift K + delta_w I_z whose inertia
+            // is right instead -- the verdict for every trial comes from the same low-rank test, at the price of a factorisation each
+            // (experiments, profiles/r01_notes.md: max_shift_trials = 0 switches the search off).
+            if (search_on && !exact_step && !force_modified && n_mods > 0 && r_mod == n_mods && shift_trials < opt.max_shift_trials) {
+                if (dw_shift == 0.0) dw_shift = dw_last_ok == 0.0 ? 1e-4 : std::max(1e-20, dw_last_ok / 3.0);
+                else dw_shift *= (dw_last_ok == 0.0 ? 100.0 : 8.0);
+                ++shift_trials;
+                continue;
+            }
+            if (exact_step && dw_shift > 0.0) dw_last_ok = dw_shift;
+            for (int r = 0; r < me; ++r) eqres[r] = ipm_eqr(PD, res_of(it.E), r);
+            build_rhs(rhs_full.data(), eqres.data());
+            std::copy(rhs_full.begin(), rhs_full.begin() + NN, rhs_keep.begin());
+            const auto ts0 = Clock::now();
+            // a backend that refines on its own (the device: residuals and corrections never leave HBM) ...
+            double rel_dev = 0.0;
+            int ns_dev = 0, rev_dev = 0;
+            const int rr = kkt->solve_refined(rhs_full.data(), dc, 8, &rel_dev, &ns_dev, &rev_dev);
+            if (rr == 0 || rr == 2) {
+                R.t_solve += secs_since(ts0);
+                R.n_solve += ns_dev;
+                if (rr == 2 || !all_finite(rhs_full.data(), NN)) { raise_dc(dc); continue; }
+                const BackendShift sh = backend_shift(dc);
+                R.n_refine_reverted += rev_dev;
+                step_used_with(sh, rel_dev);
+            } else {
+                if (rr < 0) { R.msg = "KKT solve failed: " + kkt->last_error(); return Next::abort; }
+                // ... otherwise: solve, then refine against the host's own matrix-vector product
+                const int sst = kkt->solve(rhs_full.data(), 1);
+                R.t_solve += secs_since(ts0);
+                ++R.n_solve;
+                if (sst != 0) { R.msg = "KKT solve failed: " + kkt->last_error(); return Next::abort; }
+                if (!all_finite(rhs_full.data(), NN)) { raise_dc(dc); continue; }
+                refine_on_host(dc);
+            }
+            if (exact_step) dw = dw_shift;     // the log shows delta_w of an exact step, else the largest reflected shift
+            factored = true;
+            break;
+        }
+        if (!factored) { R.msg = "KKT matrix could not be factorised (still singular after dual regularisation)"; return Next::finish; }
+        dw_used = dw;
+        last_step_reflected = !exact_step;
+        if (exact_step && dw_shift == 0.0) search_on = false;      // the plain Newton matrix is fine again
+        return Next::go;
+    }
+
+    // step expansion and lengths, merit slope and penalty weight, backtracking with the two rescues of its first trial, take_step
+    Next line_search() {
+        // the step in the eliminated quantities
+        set_step_from(rhs_full);
+        // l1 merit: directional derivative of the barrier function and the penalty weight
+        double dphi = 0, mmax = 0;
+        MeritRef ref;
+        ipm_dphi_mmax(PD, here(), duals(), it.gradf.data(), step_view(), rs.data(), mu, rho, &dphi, &mmax);
+        const double phi0_base = barrier_merit(here(), it.E, 0.0, &ref.infeas0);
+        // penalty weight of the l1 merit function: what the current multipliers and the descent condition ask for.  It may come down again
+        // (at most halving per iteration): the multipliers of the first, far-from-feasible iterations are orders of magnitude above those near
+        // the solution, and a weight frozen at that level rejects every step whose constraint curvature shows at all.
+        double nu_want = std::max(1.0, std::min(1.1 * mmax, 1e8));
+        if (ref.infeas0 > 0) nu_want = std::max(nu_want, dphi / (0.9 * ref.infeas0) + 1.0);
+        nu = std::max(nu_want, 0.5 * nu);
+        ref.phi0 = phi0_base + nu * ref.infeas0;
+        ref.slope = dphi - nu * ref.infeas0;
+        // backtracking
+        double alpha = step.apr;
+        bool accepted = false, newton_accepted = false;
+        for (int ls = 0; ls < 40; ++ls) {
+            if (!evaluate_trial(alpha)) return Next::abort;
+            if (armijo(barrier_merit(trial(), Et, nu, nullptr), alpha, ref)) { accepted = true; break; }
+            if (ls == 0) {
+                const Tried soc = second_order_correction(ref, &alpha);
+                if (soc == Tried::failed) return Next::abort;
+                if (soc == Tried::taken) { accepted = true; break; }
+                // Close to a solution the merit function stops resolving progress: the full Newton step changes it by less than constraint
+                // curvature and round-off move it, and the backtracking then crawls with steps of 1e-6 for a hundred iterations.  There -- and
+                // wherever the line search has just cut three steps in a row below 30 % of the longest admissible step (`crawl`: the same effect
+                // further out, with a penalty weight the far-from-feasible start left behind; crawl_limit = 1000 switches the rule off) -- the
+                // KKT residual itself is the better judge.
+                if (err0 <= 1e-2 || crawl >= opt.crawl_limit) {
+                    const Tried full = residual_based_acceptance();
+                    if (full == Tried::failed) return Next::abort;
+                    if (full == Tried::taken) { newton_accepted = true; break; }
+                }
+            }
+            alpha *= 0.5;
+        }
+        if (opt.print_level >= 6)
+            printf("          apr %.3e  alpha %.3e  adu %.3e  dphi %.3e  infeas1 %.3e  slope %.3e\n", step.apr, alpha, step.adu, dphi, ref.infeas0, ref.slope);
+        if (newton_accepted) { crawl = 0; force_modified = false; return Next::go; }       // the iterate is already updated and re-evaluated
+        if (!accepted && exact_step && n_mods > 0 && !force_modified) {
+            // the exact Newton direction is not a descent direction the merit function accepts at this point:
+            // redo the iteration with the step of the convexified matrix (a descent direction by construction)
+            force_modified = true;
+            return Next::go;
+        }
+        force_modified = false;
+        if (!accepted) {
+            R.msg = "line search failed";
+            // IPOPT's rule for a search that can go no further: the point is a solution only if it meets the acceptable level (the same
+            // acceptable_factor as the iteration-count rule); otherwise the failure is reported, with kkt_error / constr_viol for the caller to judge
+            if (acceptable()) { R.ok = true; R.msg = "converged to acceptable level (line search at round-off)"; }
+            return Next::finish;
+        }
+        // accept
+        crawl = alpha < opt.crawl_frac * step.apr ? crawl + 1 : 0;
+        if (!take_step(alpha, step.adu)) return Next::abort;
+        return Next::go;
+    }
+
+    NlpResult finish() {
+        R.cost = it.E.cost;
+        R.rho = rho;
+        R.t_total = secs_since(tstart);
+        if (opt.print_level >= 5)
+            printf("time: total %.2f s = evaluator %.2f + KKT factor %.2f (%d factorisations) + KKT solves %.2f (%d calls) + low-rank/refinement (host) %.2f + rest"
+                   " (of the host part: J^T lambda %.2f, refinement matvecs %.2f, node blocks %.2f; Hessian calls %.2f)\n",
+                   R.t_total, R.t_eval, R.t_factor, R.n_factor, R.t_solve, R.n_solve, R.t_lowrank, R.t_jt, R.t_matvec, R.t_blocks, R.t_hess);
+        R.z = it.z;
+        R.lamF.assign(it.lam.begin(), it.lam.begin() + md);
+        R.lamL.assign(it.lam.begin() + md, it.lam.end());
+        R.lamC.resize(mc);
+        for (int r = 0; r < mc; ++r) R.lamC[r] = sig[r / M] * it.y[r];
+        return std::move(R);
+    }
+
+ private:
+    enum class Tried { rejected, taken, failed };       // of a trial the line search makes: failed = the evaluator did (R.msg set)
+    struct MeritRef { double phi0 = 0, slope = 0, infeas0 = 0; };    // merit, its slope and the infeasibility at the current point
+    struct BackendShift { bool shifted; double dc, dw; };           // what the backend factorised beyond the nominal matrix
+
+    // ---- views, built where they are used -----------------------------------------------------------------------------------
+    IpmPoint here() const { return IpmPoint{it.z.data(), it.s.data(), it.e1.data(), it.e2.data()}; }
+    IpmPoint trial() const { return IpmPoint{zt.data(), st.data(), e1t.data(), e2t.data()}; }
+    IpmDuals duals() const { return IpmDuals{it.lam.data(), it.y.data(), it.zL.data(), it.zU.data(), it.vL.data(), it.vU.data(), it.w1.data(), it.w2.data()}; }
+    static IpmRes res_of(const Eval& e) { return IpmRes{e.RES.data(), e.LNK.data()}; }
+    IpmElim elim() { return IpmElim{sig_s.data(), rhat_s.data(), sig_t.data(), step.r_t.data()}; }
+    IpmStep step_view() {
+        return IpmStep{step.dz.data(), step.dlam.data(), step.ds.data(), step.dy.data(), step.de1.data(), step.de2.data(), step.dzL.data(),
+                       step.dzU.data(), step.dvL.data(), step.dvU.data(), step.dw1.data(), step.dw2.data()};
+    }
+
+    void evaluator_failed() { R.msg = "evaluator failed: " + P.ev->last_error(); }
+    bool evaluate(const std::vector<double>& z, Eval& e, bool jac) {
         ++R.evaluations;
-        const auto te = now();
+        const auto te = Clock::now();
         const int est = P.ev->eval(z.data(), z.data() + (size_t)ns * M, e.RES.data(), jac ? e.VALS.data() : nullptr, &e.cost, jac);
-        R.t_eval += secs(te, now());
+        R.t_eval += secs_since(te);
         if (est != 0) return false;
         e.LNK.resize(ml);
         for (int l = 0; l < nl; ++l) {
@@ -939,72 +1157,19 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             }
         }
         return true;
-    };
-    if (!evaluate(it.z, E, true)) { R.msg = "evaluator failed: " + P.ev->last_error(); return R; }
-
-    double rho = opt.rho_init > 0 ? opt.rho_init : 10.0;
-    it.s.assign(mc, 0.0);
-    it.e1.assign(mc, 0.0);
-    it.e2.assign(mc, 0.0);
-    for (int r = 0; r < mc; ++r) {
-        const double c0 = E.RES[(size_t)md + r];
-        double v = c0;
-        const double l = cL(r), u = cU(r);
-        double pl = shasL(r) ? opt.bound_push * std::max(1.0, std::fabs(l)) : 0;
-        double pu = shasU(r) ? opt.bound_push * std::max(1.0, std::fabs(u)) : 0;
-        if (shasL(r) && shasU(r)) { pl = std::min(pl, opt.bound_frac * (u - l)); pu = std::min(pu, opt.bound_frac * (u - l)); }
-        if (shasL(r)) v = std::max(v, l + pl);
-        if (shasU(r)) v = std::min(v, u - pu);
-        it.s[r] = v;
-        const double gap = c0 - v, ee = opt.bound_push * std::max(1.0, std::fabs(gap));
-        it.e1[r] = std::max(gap, 0.0) + ee;     // residual c - s - e1 + e2 starts at exactly 0
-        it.e2[r] = std::max(-gap, 0.0) + ee;
     }
-    it.lam.assign(me, 0.0);
-    it.y.assign(mc, 0.0);
-    if ((int)P.lamF0.size() == md) std::copy(P.lamF0.begin(), P.lamF0.end(), it.lam.begin());
-    auto eqr = [&](const Eval& e, int r) { return r < md ? e.RES[r] : e.LNK[r - md]; };      // residual of equality row r
-    // row weights of the merit function (jacobian_defect_scaling): 1 / max(1, inf-norm of the defect row of the Jacobian at the start)
-    std::vector<double> rs(me, 1.0);
-    if (P.jacobian_defect_scaling) {
-        const double* V0 = E.VALS.data();
-        for (int k = 0; k < M; ++k) {
-            double dmax = 0;
-            for (int j = 0; j < M; ++j)
-                if (j != k) dmax = std::max(dmax, std::fabs(P.D[(size_t)k * M + j]));
-            for (int i = 0; i < ns; ++i) {
-                double nrm = dmax;
-                for (int v = 0; v < nv; ++v) nrm = std::max(nrm, std::fabs(V0[(size_t)(i * nv + v) * M + k]));
-                rs[i * M + k] = 1.0 / std::max(1.0, nrm);
-            }
-        }
-    }
-    if ((int)P.lamC0.size() == mc)      // iterated on in scaled form; inside the penalty box
-        for (int r = 0; r < mc; ++r) it.y[r] = std::min(std::max(P.lamC0[r] / sig[r / M], -0.9 * rho), 0.9 * rho);
-    it.zL.assign(nz, 0.0); it.zU.assign(nz, 0.0);
-    it.vL.assign(mc, 0.0); it.vU.assign(mc, 0.0);
-    it.w1.assign(mc, rho); it.w2.assign(mc, rho);
-    for (int r = 0; r < mc; ++r) { it.w1[r] = std::max(1e-8, rho - it.y[r]); it.w2[r] = std::max(1e-8, rho + it.y[r]); }
-    for (int q = 0; q < nz; ++q) if (fidx[q] >= 0) { if (hasL(q)) it.zL[q] = 1.0; if (hasU(q)) it.zU[q] = 1.0; }
-    for (int r = 0; r < mc; ++r) { if (shasL(r)) it.vL[r] = 1.0; if (shasU(r)) it.vU[r] = 1.0; }
-
-    double mu = opt.mu_init, nu = 1.0;
-    double dw_used = 0.0;   // delta_w of the last exact step, or the largest reflected eigenvalue shift (log only)
-    double dw_last_ok = 0.0;   // last nonzero delta_w that gave the right inertia
-    const double tau_min = 0.99, kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5;     // (kappa_sigma: ipm_update_duals)
-    std::vector<double> y_unscaled(mc);
-
-    // --- pieces of the KKT residual at the current point --------------------------------------
-    std::vector<double> gradf(nz), jtl(nz);
-    auto grad_and_jt = [&](const Iterate& I) {
-        const double* V = E.VALS.data();
+    // cost gradient and J^T (lam, y) at the iterate
+    void grad_and_jt() {
+        const auto tj = Clock::now();
+        const double* V = it.E.VALS.data();
+        std::vector<double>&gradf = it.gradf, &jtl = it.jtl;
         for (int v = 0; v < nv; ++v)
             for (int k = 0; k < M; ++k) gradf[v * M + k] = V[(size_t)(ns * nv + npart + v) * M + k];
         std::fill(jtl.begin(), jtl.end(), 0.0);
         // J_d^T lam: off-diagonal D part, then the node blocks (which hold D_kk)
         for (int i = 0; i < ns; ++i)
             for (int k = 0; k < M; ++k) {
-                const double l = I.lam[i * M + k];
+                const double l = it.lam[i * M + k];
                 if (l == 0.0) continue;
                 const double* Dk = &P.D[(size_t)k * M];
                 double* col = &jtl[(size_t)i * M];
@@ -1014,80 +1179,141 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
             }
         for (int j = 0; j < np; ++j)
             for (int k = 0; k < M; ++k) {
-                const double yy = I.y[j * M + k];
+                const double yy = it.y[j * M + k];
                 for (const auto& ve : rv[j]) jtl[ve.first * M + k] += V[(size_t)ve.second * M + k] * yy;
             }
         for (int l = 0; l < nl; ++l) {          // coupling rows: + nu on the coupled variable, - W^T nu on its source
             const NlpLink& L = P.links[l];
             double* col = &jtl[(size_t)L.src * M];
             for (int k = 0; k < M; ++k) {
-                const double nu_k = I.lam[md + l * M + k];
+                const double nu_k = it.lam[md + l * M + k];
                 if (nu_k == 0.0) continue;
                 jtl[(size_t)L.dst * M + k] += nu_k;
                 const double* Wk = &L.W[(size_t)k * M];
                 for (int j = 0; j < M; ++j) col[j] -= Wk[j] * nu_k;
             }
         }
-    };
-    auto row_res = [&](const Eval& e, const std::vector<double>& s, const std::vector<double>& e1,
-                       const std::vector<double>& e2, int r) { return e.RES[(size_t)md + r] - s[r] - e1[r] + e2[r]; };
-    auto kkt_error = [&](const Iterate& I, double mu_t, double* viol_out, double* emax_out) {
-        return ipm_kkt_error(PD, point_of(I.z, I.s, I.e1, I.e2), duals_of(I), gradf.data(), jtl.data(), res_of(E), mu_t, rho, viol_out, emax_out);
-    };
-    auto barrier_merit = [&](const std::vector<double>& z, const std::vector<double>& s, const std::vector<double>& e1,
-                             const std::vector<double>& e2, const Eval& e, double mu_t, double nu_t, double* infeas) {
-        return ipm_barrier_merit(PD, point_of(z, s, e1, e2), res_of(e), e.cost, rs.data(), mu_t, nu_t, rho, infeas);
-    };
+        R.t_jt += secs_since(tj);
+    }
+    double kkt_error(double mu_t, double* viol_out, double* emax_out) const {
+        return ipm_kkt_error(PD, here(), duals(), it.gradf.data(), it.jtl.data(), res_of(it.E), mu_t, rho, viol_out, emax_out);
+    }
+    double barrier_merit(const IpmPoint& x, const Eval& e, double nu_t, double* infeas) const {
+        return ipm_barrier_merit(PD, x, res_of(e), e.cost, rs.data(), mu, nu_t, rho, infeas);
+    }
+    bool acceptable() const { return err0 <= opt.acceptable_factor * opt.tol && (mc == 0 || emax <= 1e-6); }
 
-    // Newton-step linear algebra: the caller's backend (eMI355X: the device) or the dense host one
-    const size_t NN0 = (size_t)nz + me;
-    DenseHostKkt host_kkt(P);
-    KktBackend* kkt = P.kkt ? P.kkt : &host_kkt;
-    std::vector<double> Qblk((size_t)nh * M), rhs_full((size_t)nz + me), eqres(me);
-    std::vector<unsigned char> fixed_mask(nz);
-    for (int q = 0; q < nz; ++q) fixed_mask[q] = fidx[q] < 0 ? 1 : 0;
-    std::vector<BlockMod> mods;
-    int n_mods = 0;                     // modified eigenpairs of the last factorisation (the true number, also beyond max_lowrank)
-    bool backend_blocks = opt.device_node_blocks && P.kkt != nullptr;   // until the backend says NOT_OFFERED
-    std::vector<double> Sigma(nz);
-    std::vector<double> Qexact, rhs_keep(NN0), resid(NN0), x_prev(NN0);
-    bool exact_step = false;
-    const int max_lowrank = 4096;        // more modified eigenpairs than this: take the modified step untested
-    std::vector<double> dz(nz), ds(mc), de1(mc), de2(mc), dlam(me), dy(mc), dzL(nz), dzU(nz), dvL(mc), dvU(mc),
-        dw1(mc), dw2(mc);
-    std::vector<double> sig_t(mc), r_t(mc), sig_s(mc), rhat_s(mc);
-    Eval Et, Ekeep;
-    Et.RES.resize(E.RES.size());
-    Et.VALS.resize(E.VALS.size());
-    std::vector<double> zt(nz), st(mc), e1t(mc), e2t(mc);
+    void reset_elastic_duals() {
+        for (int r = 0; r < mc; ++r) { it.w1[r] = std::max(1e-8, rho - it.y[r]); it.w2[r] = std::max(1e-8, rho + it.y[r]); }
+    }
+    void escalate_penalty() { rho *= 10.0; mu = std::max(mu, 1e-2); reset_elastic_duals(); }
+    // Raising the penalty weight is the answer to a relaxed path row only while it helps: beyond 1e5, `max_futile_escalations` tenfold raises in
+    // a row that have not halved the largest elastic variable end the solve (a keep-out that cannot be cleared from this side)
+    bool futile_escalation(double emax_now) {
+        if (rho < 1e5) return false;         // weights a multiplier of a scaled row can plausibly need: keep raising
+        if (emax_now < 0.5 * emax_ref) { emax_ref = emax_now; futile = 0; return false; }
+        return ++futile >= opt.max_futile_escalations;
+    }
 
-    // ---- pieces of one Newton step, shared by the regular step and the second-order correction ----
-    const size_t NN = (size_t)nz + me;
-    int r_mod = 0;
+    // ---- pieces of the Newton system -----------------------------------------------------------------------------------------
+    void raise_dc(double& dc) const { dc = dc == 0.0 ? 1e-8 * std::pow(mu, 0.25) : dc * 100.0; }
     // r_t of the eliminated path rows for given row residuals  c - s - e1 + e2
-    const IpmElim elim{sig_s.data(), rhat_s.data(), sig_t.data(), r_t.data()};
-    const IpmStep step{dz.data(), dlam.data(), ds.data(), dy.data(), de1.data(), de2.data(), dzL.data(), dzU.data(), dvL.data(), dvU.data(),
-                       dw1.data(), dw2.data()};
-    auto fill_rt = [&](const std::vector<double>& rowres) {
-        ipm_fill_rt(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), rowres.data(), mu, rho, elim);
-    };
-    // right-hand side of the reduced KKT system in full indexing (fixed variables: 0), for defect residuals defres
-    auto build_rhs = [&](double* out, const double* defres) {
-        ipm_build_rhs(PD, point_of(it.z, it.s, it.e1, it.e2), gradf.data(), jtl.data(), E.VALS.data(), elim, defres, mu, out);
-    };
-    std::vector<double> soc_def(me), soc_row(mc), soc_rhs(NN), lr_vec, lr_delta;
-    std::vector<int> lr_node;
+    void fill_rt(const std::vector<double>& rowres) { ipm_fill_rt(PD, here(), duals(), rowres.data(), mu, rho, elim()); }
+    // right-hand side of the reduced KKT system in full indexing (fixed variables: 0), for equality residuals eqr
+    void build_rhs(double* out, const double* eqr) {
+        ipm_build_rhs(PD, here(), it.gradf.data(), it.jtl.data(), it.E.VALS.data(), elim(), eqr, mu, out);
+    }
+    // One factorisation attempt.  The backend's factorisation (the device: Cholesky of a Schur complement) reports no inertia,
+    // so the matrix handed to it has its inertia by construction: every node block  Q_k = H_k + Sigma_k + sum_j sig_t g_j g_j^T
+    // is made positive definite (negative eigenvalues reflected, Q~_k = Q_k + sum delta v v^T), which makes K~ quasi-definite:
+    // exactly nz positive and md negative eigenvalues.  With U = [v; 0] (r columns, one per modified eigenpair) the true matrix is
+    // K = K~ - U Delta U^T and  inertia(K) = (nz - r, md, 0) + inertia(C),  C = Delta^-1 - U^T K~^-1 U  (r x r; both Schur
+    // complements of [[K~, U], [U^T, Delta^-1]]).  So r extra solves with the same factors decide EXACTLY whether the unmodified
+    // K has the right inertia (lowrank_verdict); if it has, the Woodbury identity turns the solve with K~ into the exact Newton
+    // step (quadratic convergence is kept); if not, the step of K~ is the inertia-corrected one.  Y = K~^-1 U and the factor of
+    // C live with the backend (KktBackend::lowrank): on the device for eMI355X.
+    // Returns KktBackend::factor's codes; *dw = the largest reflected eigenvalue shift.
+    int factor_node_blocks(double dc, double dw_shift, double* dw) {
+        const double* V = it.E.VALS.data();
+        const auto tb0 = Clock::now();
+        ipm_barrier_diagonal(PD, here(), duals(), Sigma.data());     // (0 where fixed)
+        int info = KktBackend::NOT_OFFERED;
+        if (backend_blocks) {       // assembly, convexification and factorisation by the backend, from the terms
+            Qexact.resize(Qblk.size());
+            KktBackend::BlockResult br;
+            br.Qexact = Qexact.data(); br.Q = Qblk.data(); br.max_mods = max_lowrank;
+            br.node = &lr_node; br.delta = &lr_delta; br.vec = &lr_vec;
+            info = kkt->factor_terms({H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, &rv}, dc, &br);
+            if (info == KktBackend::NOT_OFFERED) {
+                backend_blocks = false;
+            } else {
+                n_mods = br.count;
+                ++R.n_factor_terms;
+                *dw = br.worst;
+                R.t_blocks += br.t_blocks;
+                R.t_factor += br.t_factor;
+            }
+        }
+        if (!backend_blocks) {
+            assemble_node_blocks(H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, rv, nv, M, Qblk.data());
+            Qexact = Qblk;
+            *dw = convexify_node_blocks(Qblk.data(), fixed_mask.data(), nv, M, &mods);
+            n_mods = (int)mods.size();
+            R.t_blocks += secs_since(tb0);
+            const auto tf0 = Clock::now();
+            info = kkt->factor(Qblk.data(), V, fixed_mask.data(), dc);
+            R.t_factor += secs_since(tf0);
+        }
+        ++R.n_factor;
+        return info;
+    }
+    // the low-rank correction (kept by the backend, next to its factors) and the inertia verdict: sets exact_step
+    bool lowrank_verdict() {
+        r_mod = n_mods <= max_lowrank ? n_mods : 0;
+        lr_node.resize(r_mod);
+        lr_delta.resize(r_mod);
+        lr_vec.resize((size_t)r_mod * nv);
+        for (int c = 0; c < r_mod && !backend_blocks; ++c) {        // (the backend filled the three itself)
+            lr_node[c] = mods[c].node;
+            lr_delta[c] = mods[c].delta;
+            for (int v = 0; v < nv; ++v) lr_vec[(size_t)c * nv + v] = mods[c].v[v];
+        }
+        const auto tl0 = Clock::now();
+        bool lr_exact = false;
+        if (force_modified) r_mod = 0;      // the exact step failed the line search here: take the convexified one
+        if (kkt->lowrank(r_mod, lr_node.data(), lr_vec.data(), lr_delta.data(), &lr_exact) != 0) {
+            R.msg = "KKT low-rank correction failed: " + kkt->last_error();
+            return false;
+        }
+        R.t_lowrank += secs_since(tl0);
+        exact_step = !force_modified && lr_exact && r_mod == n_mods;
+        return true;
+    }
+    // The backend may have factorised a MORE regularised matrix than it was given (applied_regularisation: the Schur path's ladder):
+    // counted, and reported with the residual the step is finally used with (an inexact Newton step: the line search still decides)
+    BackendShift backend_shift(double dc) {
+        BackendShift sh{false, dc, 0.0};
+        kkt->applied_regularisation(&sh.dc, &sh.dw);
+        sh.shifted = sh.dw > 0.0 || sh.dc > std::max(dc, 1e-9) * 1.0001;
+        if (sh.shifted) ++R.n_backend_shifted;
+        return sh;
+    }
+    void step_used_with(const BackendShift& sh, double rel) {
+        R.worst_step_residual = std::max(R.worst_step_residual, rel);
+        if (opt.print_level >= 5 && sh.shifted && rel > 1e-6)
+            printf("          backend factorised with dc %.1e dw %.1e; step used with relative residual %.2e\n", sh.dc, sh.dw, rel);
+    }
     // y = [[Q, J^T], [J, -dc I]] x  with the node blocks Qb (fixed variables: identity rows/columns)
-    std::vector<double> xfree;
-    auto kkt_matvec = [&](const double* Qb, const double* x, double* y, double dcv) {
-        const double* V = E.VALS.data();
+    void kkt_matvec(const double* Qb, const double* x, double* y, double dcv) {
+        const double* V = it.E.VALS.data();
+        const unsigned char* fixed = fixed_mask.data();
         std::fill(y, y + NN, 0.0);
         for (int k = 0; k < M; ++k)
             for (int v = 0; v < nv; ++v) {
-                if (fixed_mask[v * M + k]) continue;
+                if (fixed[v * M + k]) continue;
                 double acc = 0;
                 for (int q = 0; q < nv; ++q) {
-                    if (fixed_mask[q * M + k]) continue;
+                    if (fixed[q * M + k]) continue;
                     const int hi = std::max(v, q), lo = std::min(v, q);
                     acc += Qb[(size_t)(hi * (hi + 1) / 2 + lo) * M + k] * x[q * M + k];
                 }
@@ -1097,14 +1323,14 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
         // and the node-diagonal term (which lives in the node blocks V) taken out again
         xfree.assign(x, x + nz);
         for (int q = 0; q < nz; ++q)
-            if (fixed_mask[q]) xfree[q] = 0.0;
+            if (fixed[q]) xfree[q] = 0.0;
         for (int i = 0; i < ns; ++i) {
             const double* xi = &xfree[(size_t)i * M];
             double* yi = &y[(size_t)i * M];
             for (int k = 0; k < M; ++k) {
-                const int R = nz + i * M + k;
+                const int Rr = nz + i * M + k;
                 const double* Dk = &P.D[(size_t)k * M];
-                const double xr = x[R];
+                const double xr = x[Rr];
                 double acc = 0;
 #pragma omp simd reduction(+ : acc)
                 for (int j = 0; j < M; ++j) acc += Dk[j] * xi[j];
@@ -1113,12 +1339,12 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
                 acc -= Dk[k] * xi[k];
                 yi[k] -= Dk[k] * xr;
                 for (int v = 0; v < nv; ++v) {
-                    if (fixed_mask[v * M + k]) continue;
+                    if (fixed[v * M + k]) continue;
                     const double jv = V[(size_t)(i * nv + v) * M + k];
                     acc += jv * x[v * M + k];
                     y[v * M + k] += jv * xr;
                 }
-                y[R] = acc - dcv * xr;
+                y[Rr] = acc - dcv * xr;
             }
         }
         for (int l = 0; l < nl; ++l) {          // coupling rows
@@ -1130,494 +1356,268 @@ NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vecto
                 const double* Wk = &L.W[(size_t)k * M];
                 const double xr = x[Rr];
                 double acc = xfree[(size_t)L.dst * M + k];
-                for (int j = 0; j < M; ++j) acc -= Wk[j] * xs[j];
+                // (the fused operation, spelt out: vectorised in order, the compiler would round the product first)
+                for (int j = 0; j < M; ++j) acc = std::fma(-Wk[j], xs[j], acc);
                 for (int j = 0; j < M; ++j) ys[j] -= Wk[j] * xr;
                 y[(size_t)L.dst * M + k] += xr;
                 y[Rr] = acc - dcv * xr;
             }
         }
         for (int q = 0; q < nz; ++q)
-            if (fixed_mask[q]) y[q] = x[q];
-    };
-    // everything that was eliminated from the system, from dz (uses r_t)
-    auto expand_step = [&]() {
-        ipm_expand_step(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), E.VALS.data(), elim, mu, rho, step);
-    };
-
-    { const auto tj = now(); grad_and_jt(it); R.t_jt += secs(tj, now()); }
-    int n_acceptable = 0;
-    bool force_modified = false;
-    bool search_on = false, last_step_reflected = false;
-    // Raising the penalty weight is the answer to a relaxed path row only while it helps: beyond 1e5,
-    // `max_futile_escalations` tenfold raises in a row that have not halved the largest elastic variable end the solve (a keep-out that cannot be
-    // cleared from this side: the Monte-Carlo scenario of this kind used to burn 950 iterations up to rho = 1e11).
-    bool locally_infeasible = false;
-    int futile = 0;
-    double emax_ref = 1e300;
-    auto futile_escalation = [&](double emax_now) {
-        if (rho < 1e5) return false;         // weights a multiplier of a scaled row can plausibly need: keep raising
-        if (emax_now < 0.5 * emax_ref) { emax_ref = emax_now; futile = 0; return false; }
-        return ++futile >= opt.max_futile_escalations;
-    };
-    int stagn = 0, crawl = 0;
-    bool mu_restarted = false;
-    // (experiments, profiles/r01_notes.md) max_shift_trials = 0 switches the inertia search off, crawl_limit = 1000 the crawl rule
-    const int max_shift_trials = opt.max_shift_trials;
-    const int stagn_limit = opt.stagnation_iters;
-    const int crawl_limit = opt.crawl_limit;
-    double stagn_ref = 1e300;
-    for (int iter = 0;; ++iter) {
-        R.iterations = iter;
-        double viol = 0, emax = 0;
-        const double err0 = kkt_error(it, 0.0, &viol, &emax);
-        R.kkt_error = err0;
-        R.constr_viol = viol;
-        if (opt.print_level >= 5)
-            printf("iter %3d  cost %.10e  inf_pr %.2e  kkt %.2e  mu %.1e  dw %.1e  nu %.1e  emax %.1e  rho %.0e  r %d%s\n", iter,
-                   E.cost, viol, err0, mu, dw_used, nu, emax, rho, n_mods, exact_step ? " exact" : "");
-        if (err0 <= opt.tol) {
-            if (emax <= std::max(opt.tol, 1e-9) * 10.0 || mc == 0) { R.ok = true; R.msg = "converged"; break; }
-            // a path row is still relaxed: the penalty was too small for it
-            if (rho >= 1e12 || futile_escalation(emax)) {
-                R.msg = "converged to a point that violates the path rows (locally infeasible)";
-                break;
-            }
-            rho *= 10.0;
-            mu = std::max(mu, 1e-2);
-            for (int r = 0; r < mc; ++r) { it.w1[r] = std::max(1e-8, rho - it.y[r]); it.w2[r] = std::max(1e-8, rho + it.y[r]); }
-        }
-        // stagnation at round-off above the tolerance (large meshes): accept like IPOPT's acceptable level
-        if (err0 <= opt.acceptable_factor * opt.tol && (mc == 0 || emax <= 1e-6)) {
-            if (++n_acceptable >= opt.acceptable_iter) { R.ok = true; R.msg = "converged to acceptable level"; break; }
-        } else {
-            n_acceptable = 0;
-        }
-        // reflected steps that have not reduced the KKT residual of the barrier problem by 10 % over `stagn_limit` iterations:
-        // switch the inertia search on (measured, profiles/r01_notes.md: 4 costs the keep-out Monte-Carlo sets half their
-        // throughput in trial factorisations, 12 keeps it and still rescues the fixed-wing problems)
-        {
-            const double err_mu_now = kkt_error(it, mu, nullptr, nullptr);
-            if (last_step_reflected && err_mu_now > 0.9 * stagn_ref) {
-                if (++stagn >= stagn_limit) {
-                    search_on = true;
-                    if (opt.mu_restart > 1.0 && !mu_restarted && mu < 1e-4) {
-                        mu_restarted = true;
-                        mu = std::min(1e-3, mu * opt.mu_restart);
-                        nu = 1.0;
-                        stagn = 0;
-                        stagn_ref = 1e300;
-                        if (opt.print_level >= 5) printf("stagnation at a small barrier parameter: raised to %.1e\n", mu);
-                    }
-                }
-            } else {
-                stagn = 0;
-                stagn_ref = err_mu_now;
-            }
-        }
-        if (iter >= opt.max_iter) { R.msg = "maximum number of iterations exceeded"; break; }
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count() > opt.max_cpu_time) {
-            R.msg = "time limit exceeded";
-            break;
-        }
-        // barrier update (may fire several times in a row)
-        while (mu > opt.tol / 10.0 && kkt_error(it, mu, nullptr, nullptr) <= kappa_eps * mu) {
-            // this barrier problem is solved.  A row multiplier at the penalty weight (or, equivalently, an
-            // elastic still far above mu / rho) means the weight is too small for that row: raise it now
-            // instead of converging to a relaxed point first
-            double ymax = 0;
-            for (int r = 0; r < mc; ++r) ymax = std::max(ymax, std::fabs(it.y[r]));
-            if (mc > 0 && (emax > std::max(1e-6, 100.0 * mu) || ymax > 0.9 * rho) && rho < 1e12) {
-                if (futile_escalation(emax)) { locally_infeasible = true; break; }
-                rho *= 10.0;
-                mu = std::max(mu, 1e-2);
-                for (int r = 0; r < mc; ++r) { it.w1[r] = std::max(1e-8, rho - it.y[r]); it.w2[r] = std::max(1e-8, rho + it.y[r]); }
-                nu = 1.0;
-                break;
-            }
-            mu = std::max(opt.tol / 10.0, std::min(kappa_mu * mu, std::pow(mu, theta_mu)));
-            nu = 1.0;    // a new barrier problem: the penalty weight is rebuilt from its multipliers, not inherited
-        }
-        if (locally_infeasible) {
-            R.msg = "the path rows stay violated while the penalty weight grows (locally infeasible)";
-            break;
-        }
-        const double tau = std::max(tau_min, 1.0 - mu);
-
-        // exact Lagrangian Hessian blocks from the device
-        for (int r = 0; r < mc; ++r) y_unscaled[r] = sig[r / M] * it.y[r];
-        const auto th0 = now();
-        const int hess_rc = P.ev->hess(it.z.data(), it.z.data() + (size_t)ns * M, it.lam.data(), np ? y_unscaled.data() : nullptr, 1.0,
-                                       E.H.data());
-        R.t_hess += secs(th0, now());
-        if (hess_rc != 0) {
-            R.msg = "Hessian evaluation failed: " + P.ev->last_error();
-            break;
-        }
-        // eliminate (s, e+, e-) of every path row:  dy = sig_t (J_c dz + r_t)
-        ipm_eliminate_rows(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), res_of(E), mu, rho, elim);
-        // factor with inertia correction
-        bool factored = false;
-        double dw = 0.0, dc = 0.0;
-        double dw_shift = 0.0;      // primal regularisation delta_w I of the inertia search (below)
-        int shift_trials = 0;
-        for (int attempt = 0; attempt < 24; ++attempt) {
-            // The device factorisation is an LU and reports no inertia, so the matrix handed to the
-            // backend has its inertia by construction: every node block
-            //     Q_k = H_k + Sigma_k + sum_j sig_t g_j g_j^T
-            // is made positive definite (negative eigenvalues reflected, Q~_k = Q_k + sum delta v v^T),
-            // which makes K~ quasi-definite: exactly nz positive and md negative eigenvalues.  With
-            // U = [v; 0] (r columns, one per modified eigenpair) the true matrix is K = K~ - U Delta U^T and
-            //     inertia(K) = (nz - r, md, 0) + inertia(C),   C = Delta^-1 - U^T K~^-1 U   (r x r)
-            // (both Schur complements of [[K~, U], [U^T, Delta^-1]]).  So r extra solves with the same
-            // factors decide EXACTLY whether the unmodified K has the right inertia; if it has, the
-            // Woodbury identity turns the solve with K~ into the exact Newton step (quadratic
-            // convergence is kept); if not, the step of K~ is the inertia-corrected one.  Y = K~^-1 U and
-            // the factor of C live with the backend (KktBackend::lowrank): on the device for eMI355X.
-            const double* V = E.VALS.data();
-            const auto tb0 = now();
-            ipm_barrier_diagonal(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), Sigma.data());     // (0 where fixed)
-            int info = KktBackend::NOT_OFFERED;
-            if (backend_blocks) {       // assembly, convexification and factorisation by the backend, from the terms
-                Qexact.resize(Qblk.size());
-                KktBackend::BlockResult br;
-                br.Qexact = Qexact.data(); br.Q = Qblk.data(); br.max_mods = max_lowrank;
-                br.node = &lr_node; br.delta = &lr_delta; br.vec = &lr_vec;
-                info = kkt->factor_terms({E.H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, &rv}, dc, &br);
-                if (info == KktBackend::NOT_OFFERED) {
-                    backend_blocks = false;
-                } else {
-                    n_mods = br.count;
-                    ++R.n_factor_terms;
-                    dw = br.worst;
-                    R.t_blocks += br.t_blocks;
-                    R.t_factor += br.t_factor;
-                }
-            }
-            if (!backend_blocks) {
-                assemble_node_blocks(E.H.data(), V, Sigma.data(), sig_t.data(), fixed_mask.data(), dw_shift, rv, nv, M, Qblk.data());
-                Qexact = Qblk;
-                dw = convexify_node_blocks(Qblk.data(), fixed_mask.data(), nv, M, &mods);
-                n_mods = (int)mods.size();
-                R.t_blocks += secs(tb0, now());
-                const auto tf0 = now();
-                info = kkt->factor(Qblk.data(), V, fixed_mask.data(), dc);
-                R.t_factor += secs(tf0, now());
-            }
-            ++R.n_factor;
-            if (info < 0) { R.msg = "KKT factorisation failed: " + kkt->last_error(); return R; }
-            if (info > 0) {   // exactly singular: the defect Jacobian lost rank; regularise the dual block
-                dc = dc == 0.0 ? 1e-8 * std::pow(mu, 0.25) : dc * 100.0;
-                continue;
-            }
-            // the low-rank correction (kept by the backend, next to its factors) and the inertia verdict
-            r_mod = n_mods <= max_lowrank ? n_mods : 0;
-            lr_node.resize(r_mod);
-            lr_delta.resize(r_mod);
-            lr_vec.resize((size_t)r_mod * nv);
-            for (int c = 0; c < r_mod && !backend_blocks; ++c) {        // (the backend filled the three itself)
-                lr_node[c] = mods[c].node;
-                lr_delta[c] = mods[c].delta;
-                for (int v = 0; v < nv; ++v) lr_vec[(size_t)c * nv + v] = mods[c].v[v];
-            }
-            const auto tl0 = now();
-            bool lr_exact = false;
-            if (force_modified) r_mod = 0;      // the exact step failed the line search here: take the convexified one
-            if (kkt->lowrank(r_mod, lr_node.data(), lr_vec.data(), lr_delta.data(), &lr_exact) != 0) {
-                R.msg = "KKT low-rank correction failed: " + kkt->last_error();
-                return R;
-            }
-            R.t_lowrank += secs(tl0, now());
-            exact_step = !force_modified && lr_exact && r_mod == n_mods;
-            // Inertia search (IPOPT's delta_w): the unmodified K has the wrong inertia.  The step of the reflected
-            // blocks is the cheap answer and usually a good one; where it stagnates (search_on, set below) look for
-            // the smallest shift K + delta_w I_z whose inertia is right instead -- the verdict for every trial comes
-            // from the same low-rank test, at the price of a factorisation each.
-            if (search_on && !exact_step && !force_modified && n_mods > 0 && r_mod == n_mods &&
-                shift_trials < max_shift_trials) {
-                if (dw_shift == 0.0) dw_shift = dw_last_ok == 0.0 ? 1e-4 : std::max(1e-20, dw_last_ok / 3.0);
-                else dw_shift *= (dw_last_ok == 0.0 ? 100.0 : 8.0);
-                ++shift_trials;
-                continue;
-            }
-            if (exact_step && dw_shift > 0.0) dw_last_ok = dw_shift;
-            for (int r = 0; r < me; ++r) eqres[r] = eqr(E, r);
-            build_rhs(rhs_full.data(), eqres.data());
-            std::copy(rhs_full.begin(), rhs_full.begin() + NN, rhs_keep.begin());
-            const auto ts0 = now();
-            // a backend that refines on its own (the device: residuals and corrections never leave HBM) ...
-            double rel_dev = 0.0;
-            int ns_dev = 0, rev_dev = 0;
-            const int rr = kkt->solve_refined(rhs_full.data(), dc, 8, &rel_dev, &ns_dev, &rev_dev);
-            if (rr == 0 || rr == 2) {
-                R.t_solve += secs(ts0, now());
-                R.n_solve += ns_dev;
-                if (rr == 2) { dc = dc == 0.0 ? 1e-8 * std::pow(mu, 0.25) : dc * 100.0; continue; }
-                bool fin = true;
-                for (size_t r = 0; r < NN && fin; ++r) fin = std::isfinite(rhs_full[r]);
-                if (!fin) { dc = dc == 0.0 ? 1e-8 * std::pow(mu, 0.25) : dc * 100.0; continue; }
-                double dc_applied = dc, dw_applied = 0.0;
-                kkt->applied_regularisation(&dc_applied, &dw_applied);
-                const bool shifted = dw_applied > 0.0 || dc_applied > std::max(dc, 1e-9) * 1.0001;
-                if (shifted) ++R.n_backend_shifted;
-                R.n_refine_reverted += rev_dev;
-                R.worst_step_residual = std::max(R.worst_step_residual, rel_dev);
-                if (opt.print_level >= 5 && shifted && rel_dev > 1e-6)
-                    printf("          backend factorised with dc %.1e dw %.1e; step used with relative residual %.2e\n", dc_applied, dw_applied, rel_dev);
-                if (exact_step) dw = dw_shift;
-                factored = true;
-                break;
-            }
-            if (rr < 0) { R.msg = "KKT solve failed: " + kkt->last_error(); return R; }
-            // ... otherwise: solve, then refine against the host's own matrix-vector product
-            const int sst = kkt->solve(rhs_full.data(), 1);
-            R.t_solve += secs(ts0, now());
-            ++R.n_solve;
-            if (sst != 0) { R.msg = "KKT solve failed: " + kkt->last_error(); return R; }
-            bool finite = true;
-            for (size_t r = 0; r < NN && finite; ++r) finite = std::isfinite(rhs_full[r]);
-            if (!finite) { dc = dc == 0.0 ? 1e-8 * std::pow(mu, 0.25) : dc * 100.0; continue; }
-            // iterative refinement against the matrix the step belongs to (K if exact, K~ otherwise): the
-            // factorisation of a 1000-node KKT matrix leaves residuals that would stall the Newton
-            // iteration some orders above the requested tolerance.  The backend may have factorised a MORE regularised
-            // matrix than it was given (applied_regularisation: the Schur path's ladder); the refinement then is a
-            // stationary iteration with (K + E)^-1 that need not contract, so a correction that makes the residual worse
-            // is taken back, and the residual the step is finally used with is recorded (an inexact Newton step: the
-            // line search below still decides; R.worst_step_residual lets a caller see how inexact).
-            {
-                const std::vector<double>& Qm = exact_step ? Qexact : Qblk;
-                double dc_applied = dc, dw_applied = 0.0;
-                kkt->applied_regularisation(&dc_applied, &dw_applied);
-                const bool shifted = dw_applied > 0.0 || dc_applied > std::max(dc, 1e-9) * 1.0001;
-                if (shifted) ++R.n_backend_shifted;
-                double bmax = 0;
-                for (size_t r = 0; r < NN; ++r) bmax = std::max(bmax, std::fabs(rhs_keep[r]));
-                double prev = 1e300, rlast = 0.0;
-                bool have_prev = false;
-                for (int ir = 0; ir < 8; ++ir) {      // (8 since the backend may have regularised the factorised matrix: linear convergence)
-                    { const auto tm = now(); kkt_matvec(Qm.data(), rhs_full.data(), resid.data(), dc); R.t_matvec += secs(tm, now()); }
-                    double rmax = 0;
-                    for (size_t r = 0; r < NN; ++r) { resid[r] = rhs_keep[r] - resid[r]; rmax = std::max(rmax, std::fabs(resid[r])); }
-                    if (have_prev && !(rmax < prev)) {          // the last correction did harm: undo it and stop
-                        for (size_t r = 0; r < NN; ++r) rhs_full[r] = x_prev[r];
-                        ++R.n_refine_reverted;
-                        rlast = prev;
-                        break;
-                    }
-                    rlast = rmax;
-                    if (!(rmax > 1e-14 * std::max(1.0, bmax)) || !(rmax < 0.5 * prev)) break;
-                    prev = rmax;
-                    { const auto ts = now(); const int rs = kkt->solve(resid.data(), 1); R.t_solve += secs(ts, now()); ++R.n_solve; if (rs != 0) break; }
-                    bool fin = true;
-                    for (size_t r = 0; r < NN && fin; ++r) fin = std::isfinite(resid[r]);
-                    if (!fin) break;
-                    x_prev.assign(rhs_full.begin(), rhs_full.begin() + NN);
-                    have_prev = true;
-                    for (size_t r = 0; r < NN; ++r) rhs_full[r] += resid[r];
-                }
-                const double rel = rlast / std::max(1.0, bmax);
-                R.worst_step_residual = std::max(R.worst_step_residual, rel);
-                if (opt.print_level >= 5 && shifted && rel > 1e-6)
-                    printf("          backend factorised with dc %.1e dw %.1e; step used with relative residual %.2e\n", dc_applied, dw_applied, rel);
-            }
-            if (exact_step) dw = dw_shift;     // the log shows delta_w of an exact step, else the largest reflected shift
-            factored = true;
-            break;
-        }
-        if (!factored) { R.msg = "KKT matrix could not be factorised (still singular after dual regularisation)"; break; }
-        dw_used = dw;
-        last_step_reflected = !exact_step;
-        if (exact_step && dw_shift == 0.0) search_on = false;      // the plain Newton matrix is fine again
-
-        // the step in the eliminated quantities
-        for (int q = 0; q < nz; ++q) dz[q] = fidx[q] >= 0 ? rhs_full[q] : 0.0;
-        for (int r = 0; r < me; ++r) dlam[r] = rhs_full[nz + r];
-        expand_step();
-        // fraction to the boundary
-        double apr = 1.0, adu = 1.0;
-        auto step_lengths = [&]() {
-            ipm_step_lengths(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), step, tau, &apr, &adu);
-        };
-        step_lengths();
-        // l1 merit: directional derivative of the barrier function and the penalty weight
-        double dphi = 0, infeas0 = 0, mmax = 0;
-        ipm_dphi_mmax(PD, point_of(it.z, it.s, it.e1, it.e2), duals_of(it), gradf.data(), step, rs.data(), mu, rho, &dphi, &mmax);
-        const double phi0_base = barrier_merit(it.z, it.s, it.e1, it.e2, E, mu, 0.0, &infeas0);
-        // penalty weight of the l1 merit function: what the current multipliers and the descent condition
-        // ask for.  It may come down again (at most halving per iteration): the multipliers of the first,
-        // far-from-feasible iterations are orders of magnitude above those near the solution, and a weight
-        // frozen at that level rejects every step whose constraint curvature shows at all.
-        double nu_want = std::max(1.0, std::min(1.1 * mmax, 1e8));
-        if (infeas0 > 0) nu_want = std::max(nu_want, dphi / (0.9 * infeas0) + 1.0);
-        nu = std::max(nu_want, 0.5 * nu);
-        const double phi0 = phi0_base + nu * infeas0;
-        const double slope = dphi - nu * infeas0;
-        // slack reset: a row's slack may jump to the value that closes its residual whenever
-        // that lowers the merit function (the keep-out rows are strongly curved, and a step
-        // along a keep-out boundary otherwise shows up as an equality residual c - s)
-        auto slack_reset = [&]() { ipm_slack_reset(PD, Et.RES.data() + md, e1t.data(), e2t.data(), mu, nu, st.data()); };
-        // the iterate after a step of length a_pr (primal: zt, st, e1t, e2t hold the trial point) / a_du (bound
-        // multipliers), re-evaluated with derivatives
-        auto take_step = [&](double a_pr, double a_du) -> bool {
-            it.z = zt;
-            it.s = st;
-            it.e1 = e1t;
-            it.e2 = e2t;
-            ipm_update_duals(PD, point_of(it.z, it.s, it.e1, it.e2),
-                             IpmDualsRW{it.lam.data(), it.y.data(), it.zL.data(), it.zU.data(), it.vL.data(), it.vU.data(), it.w1.data(), it.w2.data()},
-                             step, a_pr, a_du, mu);
-            if (!evaluate(it.z, E, true)) return false;
-            { const auto tj = now(); grad_and_jt(it); R.t_jt += secs(tj, now()); }
-            return true;
-        };
-        // backtracking
-        double alpha = apr;
-        bool accepted = false;
-        bool newton_accepted = false;
-        for (int ls = 0; ls < 40; ++ls) {
-            for (int q = 0; q < nz; ++q) zt[q] = it.z[q] + alpha * dz[q];
-            for (int r = 0; r < mc; ++r) {
-                st[r] = it.s[r] + alpha * ds[r];
-                e1t[r] = it.e1[r] + alpha * de1[r];
-                e2t[r] = it.e2[r] + alpha * de2[r];
-            }
-            if (!evaluate(zt, Et, false)) { R.msg = "evaluator failed: " + P.ev->last_error(); return R; }
-            slack_reset();
-            const double phit = barrier_merit(zt, st, e1t, e2t, Et, mu, nu, nullptr);
-            if (std::isfinite(phit) && phit <= phi0 + 1e-4 * alpha * std::min(slope, 0.0) + 1e-13 * std::fabs(phi0)) {
-                accepted = true;
-                break;
-            }
-            // Second-order correction (as in IPOPT's line search): the first trial point was rejected
-            // and is less feasible than the current one -- the curvature of the constraints, not the
-            // direction, is to blame (Maratos effect; without this the l1 merit function lets the
-            // iteration crawl along the strongly curved defect / keep-out rows with steps of 2^-8).
-            // Re-solve with the SAME factorisation for the constraint values seen at the trial point.
-            if (ls == 0) {
-                double infeas_t = 0;
-                barrier_merit(zt, st, e1t, e2t, Et, mu, 0.0, &infeas_t);
-                if (std::isfinite(infeas_t) && infeas_t >= infeas0) {
-                    const std::vector<double> b_dz = dz, b_ds = ds, b_de1 = de1, b_de2 = de2, b_dlam = dlam, b_dy = dy,
-                                              b_dzL = dzL, b_dzU = dzU, b_dvL = dvL, b_dvU = dvU, b_dw1 = dw1, b_dw2 = dw2,
-                                              b_rt = r_t;
-                    const double b_apr = apr, b_adu = adu;
-                    for (int r = 0; r < me; ++r) soc_def[r] = alpha * eqr(E, r) + eqr(Et, r);
-                    for (int r = 0; r < mc; ++r)
-                        soc_row[r] = alpha * row_res(E, it.s, it.e1, it.e2, r) + row_res(Et, st, e1t, e2t, r);
-                    double infeas_old = infeas_t;
-                    for (int pc = 0; pc < 4 && !accepted; ++pc) {
-                        fill_rt(soc_row);
-                        build_rhs(soc_rhs.data(), soc_def.data());
-                        if (kkt->solve(soc_rhs.data(), 1) != 0) break;
-                        bool fin = true;
-                        for (size_t r = 0; r < NN && fin; ++r) fin = std::isfinite(soc_rhs[r]);
-                        if (!fin) break;
-                        for (int q = 0; q < nz; ++q) dz[q] = fidx[q] >= 0 ? soc_rhs[q] : 0.0;
-                        for (int r = 0; r < me; ++r) dlam[r] = soc_rhs[nz + r];
-                        expand_step();
-                        step_lengths();
-                        const double asoc = apr;
-                        for (int q = 0; q < nz; ++q) zt[q] = it.z[q] + asoc * dz[q];
-                        for (int r = 0; r < mc; ++r) {
-                            st[r] = it.s[r] + asoc * ds[r];
-                            e1t[r] = it.e1[r] + asoc * de1[r];
-                            e2t[r] = it.e2[r] + asoc * de2[r];
-                        }
-                        if (!evaluate(zt, Et, false)) { R.msg = "evaluator failed: " + P.ev->last_error(); return R; }
-                        slack_reset();
-                        double infeas_s = 0;
-                        const double phis = barrier_merit(zt, st, e1t, e2t, Et, mu, nu, &infeas_s);
-                        if (std::isfinite(phis) && phis <= phi0 + 1e-4 * asoc * std::min(slope, 0.0) + 1e-13 * std::fabs(phi0)) {
-                            accepted = true;
-                            alpha = asoc;
-                            ++R.soc_steps;
-                            break;
-                        }
-                        if (!std::isfinite(infeas_s) || infeas_s > 0.99 * infeas_old) break;
-                        infeas_old = infeas_s;
-                        for (int r = 0; r < me; ++r) soc_def[r] = asoc * soc_def[r] + eqr(Et, r);
-                        for (int r = 0; r < mc; ++r) soc_row[r] = asoc * soc_row[r] + row_res(Et, st, e1t, e2t, r);
-                    }
-                    if (accepted) break;
-                    dz = b_dz; ds = b_ds; de1 = b_de1; de2 = b_de2; dlam = b_dlam; dy = b_dy; dzL = b_dzL; dzU = b_dzU;
-                    dvL = b_dvL; dvU = b_dvU; dw1 = b_dw1; dw2 = b_dw2; r_t = b_rt;
-                    apr = b_apr; adu = b_adu;
-                }
-            }
-            // Close to a solution the merit function stops resolving progress: the full Newton step changes it
-            // by less than constraint curvature and round-off move it, and the backtracking then crawls with steps
-            // of 1e-6 for a hundred iterations.  There -- and wherever the line search has just cut three steps in a
-            // row below 30 % of the longest admissible step (`crawl`: the same effect further out, with a penalty
-            // weight the far-from-feasible start left behind) -- the KKT residual itself is the better judge: take
-            // the full step if it reduces the residual of the current barrier problem (else undo and backtrack).
-            if (ls == 0 && (err0 <= 1e-2 || crawl >= crawl_limit)) {
-                const double err_mu = kkt_error(it, mu, nullptr, nullptr);
-                const Iterate it_keep = it;
-                const std::vector<double> gradf_keep = gradf, jtl_keep = jtl;
-                Ekeep.RES = E.RES; Ekeep.VALS = E.VALS; Ekeep.LNK = E.LNK; Ekeep.cost = E.cost;
-                for (int q = 0; q < nz; ++q) zt[q] = it.z[q] + apr * dz[q];
-                for (int r = 0; r < mc; ++r) {
-                    st[r] = it.s[r] + apr * ds[r];
-                    e1t[r] = it.e1[r] + apr * de1[r];
-                    e2t[r] = it.e2[r] + apr * de2[r];
-                }
-                if (!take_step(apr, adu)) { R.msg = "evaluator failed: " + P.ev->last_error(); return R; }
-                const double err_tr = kkt_error(it, mu, nullptr, nullptr);
-                if (std::isfinite(err_tr) && err_tr <= 0.9 * err_mu) {
-                    newton_accepted = true;
-                    ++R.newton_steps;
-                    break;
-                }
-                it = it_keep;
-                gradf = gradf_keep;
-                jtl = jtl_keep;
-                E.RES = Ekeep.RES; E.VALS = Ekeep.VALS; E.LNK = Ekeep.LNK; E.cost = Ekeep.cost;
-            }
-            alpha *= 0.5;
-        }
-        if (opt.print_level >= 6)
-            printf("          apr %.3e  alpha %.3e  adu %.3e  dphi %.3e  infeas1 %.3e  slope %.3e\n", apr, alpha, adu, dphi,
-                   infeas0, slope);
-        if (newton_accepted) {       // the iterate is already updated and re-evaluated
-            crawl = 0;
-            force_modified = false;
-            continue;
-        }
-        if (!accepted && exact_step && n_mods > 0 && !force_modified) {
-            // the exact Newton direction is not a descent direction the merit function accepts at this point:
-            // redo the iteration with the step of the convexified matrix (a descent direction by construction)
-            force_modified = true;
-            continue;
-        }
-        force_modified = false;
-        if (!accepted) {
-            R.msg = "line search failed";
-            // IPOPT's rule for a search that can go no further: the point is a solution only if it meets the
-            // acceptable level (the same acceptable_factor as the iteration-count rule above); otherwise the
-            // failure is reported, with kkt_error / constr_viol for the caller to judge
-            if (err0 <= opt.acceptable_factor * opt.tol && (mc == 0 || emax <= 1e-6)) {
-                R.ok = true;
-                R.msg = "converged to acceptable level (line search at round-off)";
-            }
-            break;
-        }
-        // accept
-        const double crawl_frac = opt.crawl_frac;
-        crawl = alpha < crawl_frac * apr ? crawl + 1 : 0;
-        if (!take_step(alpha, adu)) { R.msg = "evaluator failed: " + P.ev->last_error(); return R; }
+            if (fixed[q]) y[q] = x[q];
     }
-    R.cost = E.cost;
-    R.rho = rho;
-    R.t_total = secs(tstart, now());
-    if (opt.print_level >= 5)
-        printf("time: total %.2f s = evaluator %.2f + KKT factor %.2f (%d factorisations) + KKT solves %.2f (%d calls) + low-rank/refinement (host) %.2f + rest"
-               " (of the host part: J^T lambda %.2f, refinement matvecs %.2f, node blocks %.2f; Hessian calls %.2f)\n",
-               R.t_total, R.t_eval, R.t_factor, R.n_factor, R.t_solve, R.n_solve, R.t_lowrank, R.t_jt, R.t_matvec, R.t_blocks, R.t_hess);
-    R.z = it.z;
-    R.lamF.assign(it.lam.begin(), it.lam.begin() + md);
-    R.lamL.assign(it.lam.begin() + md, it.lam.end());
-    R.lamC.resize(mc);
-    for (int r = 0; r < mc; ++r) R.lamC[r] = sig[r / M] * it.y[r];
-    return R;
+    // The host twin of KktBackend::solve_refined, around solve(): iterative refinement of rhs_full against the matrix the step
+    // belongs to (K if exact, K~ otherwise): the factorisation of a 1000-node KKT matrix leaves residuals that would stall the Newton
+    // iteration some orders above the requested tolerance.  Where the backend regularised beyond the nominal matrix this is a
+    // stationary iteration with (K + E)^-1 that need not contract, so a correction that makes the residual worse is taken back.
+    void refine_on_host(double dc) {
+        const std::vector<double>& Qm = exact_step ? Qexact : Qblk;
+        const BackendShift sh = backend_shift(dc);
+        double bmax = 0;
+        for (size_t r = 0; r < NN; ++r) bmax = std::max(bmax, std::fabs(rhs_keep[r]));
+        double prev = 1e300, rlast = 0.0;
+        bool have_prev = false;
+        for (int ir = 0; ir < 8; ++ir) {      // (8 since the backend may have regularised the factorised matrix: linear convergence)
+            { const auto tm = Clock::now(); kkt_matvec(Qm.data(), rhs_full.data(), resid.data(), dc); R.t_matvec += secs_since(tm); }
+            double rmax = 0;
+            for (size_t r = 0; r < NN; ++r) { resid[r] = rhs_keep[r] - resid[r]; rmax = std::max(rmax, std::fabs(resid[r])); }
+            if (have_prev && !(rmax < prev)) {          // the last correction did harm: undo it and stop
+                for (size_t r = 0; r < NN; ++r) rhs_full[r] = x_prev[r];
+                ++R.n_refine_reverted;
+                rlast = prev;
+                break;
+            }
+            rlast = rmax;
+            if (!(rmax > 1e-14 * std::max(1.0, bmax)) || !(rmax < 0.5 * prev)) break;
+            prev = rmax;
+            { const auto ts = Clock::now(); const int rc = kkt->solve(resid.data(), 1); R.t_solve += secs_since(ts); ++R.n_solve; if (rc != 0) break; }
+            if (!all_finite(resid.data(), NN)) break;
+            x_prev.assign(rhs_full.begin(), rhs_full.begin() + NN);
+            have_prev = true;
+            for (size_t r = 0; r < NN; ++r) rhs_full[r] += resid[r];
+        }
+        step_used_with(sh, rlast / std::max(1.0, bmax));
+    }
+
+    // ---- pieces of the line search -------------------------------------------------------------------------------------------
+    // the whole step from a solution of the reduced system: everything that was eliminated (uses r_t), and its lengths
+    void set_step_from(const std::vector<double>& sol) {
+        for (int q = 0; q < nz; ++q) step.dz[q] = fixed_mask[q] ? 0.0 : sol[q];
+        for (int r = 0; r < me; ++r) step.dlam[r] = sol[nz + r];
+        ipm_expand_step(PD, here(), duals(), it.E.VALS.data(), elim(), mu, rho, step_view());
+        ipm_step_lengths(PD, here(), duals(), step_view(), tau, &step.apr, &step.adu);      // fraction to the boundary
+    }
+    // the primal trial point for step length a
+    void form_trial(double a) {
+        for (int q = 0; q < nz; ++q) zt[q] = it.z[q] + a * step.dz[q];
+        for (int r = 0; r < mc; ++r) {
+            st[r] = it.s[r] + a * step.ds[r];
+            e1t[r] = it.e1[r] + a * step.de1[r];
+            e2t[r] = it.e2[r] + a * step.de2[r];
+        }
+    }
+    // ... evaluated without derivatives, and with the slack reset: a row's slack may jump to the value that closes its residual whenever
+    // that lowers the merit function (the keep-out rows are strongly curved: a step along one otherwise shows as a residual c - s)
+    bool evaluate_trial(double a) {
+        form_trial(a);
+        if (!evaluate(zt, Et, false)) return evaluator_failed(), false;
+        ipm_slack_reset(PD, Et.RES.data() + md, e1t.data(), e2t.data(), mu, nu, st.data());
+        return true;
+    }
+    static bool armijo(double phi, double a, const MeritRef& m) {
+        return std::isfinite(phi) && phi <= m.phi0 + 1e-4 * a * std::min(m.slope, 0.0) + 1e-13 * std::fabs(m.phi0);
+    }
+    // the iterate after a step of length a_pr (primal: zt, st, e1t, e2t hold the trial point) / a_du (bound
+    // multipliers), re-evaluated with derivatives
+    bool take_step(double a_pr, double a_du) {
+        it.z = zt;
+        it.s = st;
+        it.e1 = e1t;
+        it.e2 = e2t;
+        ipm_update_duals(PD, here(),
+                         IpmDualsRW{it.lam.data(), it.y.data(), it.zL.data(), it.zU.data(), it.vL.data(), it.vU.data(), it.w1.data(), it.w2.data()},
+                         step_view(), a_pr, a_du, mu);
+        if (!evaluate(it.z, it.E, true)) return evaluator_failed(), false;
+        grad_and_jt();
+        return true;
+    }
+    // Second-order correction (as in IPOPT's line search): the first trial point (length *alpha, in zt .. Et) was rejected and is less
+    // feasible than the current one -- the curvature of the constraints, not the direction, is to blame (Maratos effect; without this
+    // the l1 merit function lets the iteration crawl along the strongly curved defect / keep-out rows with steps of 2^-8).  Re-solve
+    // with the SAME factorisation for the constraint values seen at the trial point.  Taken: the corrected step is in `step`, its
+    // trial point in zt .. Et and its length in *alpha; rejected: `step` is what it was.
+    Tried second_order_correction(const MeritRef& ref, double* alpha) {
+        double infeas_t = 0;
+        barrier_merit(trial(), Et, 0.0, &infeas_t);
+        if (!(std::isfinite(infeas_t) && infeas_t >= ref.infeas0)) return Tried::rejected;
+        const Step keep = step;
+        // the residuals to correct for: a * (those of the step before) + those at its trial point, from the current point's on
+        for (int r = 0; r < me; ++r) soc_def[r] = ipm_eqr(PD, res_of(it.E), r);
+        for (int r = 0; r < mc; ++r) soc_row[r] = ipm_row_res(PD, res_of(it.E), it.s.data(), it.e1.data(), it.e2.data(), r);
+        double a = *alpha, infeas_old = infeas_t;
+        for (int pc = 0; pc < 4; ++pc) {
+            for (int r = 0; r < me; ++r) soc_def[r] *= a;       // (scaled, then added to: the product is rounded, not fused into the sum)
+            for (int r = 0; r < me; ++r) soc_def[r] += ipm_eqr(PD, res_of(Et), r);
+            for (int r = 0; r < mc; ++r) soc_row[r] = a * soc_row[r] + ipm_row_res(PD, res_of(Et), st.data(), e1t.data(), e2t.data(), r);
+            fill_rt(soc_row);
+            build_rhs(soc_rhs.data(), soc_def.data());
+            if (kkt->solve(soc_rhs.data(), 1) != 0) break;
+            if (!all_finite(soc_rhs.data(), NN)) break;
+            set_step_from(soc_rhs);
+            const double asoc = step.apr;
+            if (!evaluate_trial(asoc)) return Tried::failed;
+            double infeas_s = 0;
+            if (armijo(barrier_merit(trial(), Et, nu, &infeas_s), asoc, ref)) {
+                *alpha = asoc;
+                ++R.soc_steps;
+                return Tried::taken;
+            }
+            if (!std::isfinite(infeas_s) || infeas_s > 0.99 * infeas_old) break;
+            infeas_old = infeas_s;
+            a = asoc;
+        }
+        step = keep;
+        return Tried::rejected;
+    }
+    // Residual-based acceptance: take the full step if it reduces the KKT residual of the current barrier problem, else take
+    // the iterate back as it was (and backtrack)
+    Tried residual_based_acceptance() {
+        const double err_mu = kkt_error(mu, nullptr, nullptr);
+        it_keep = it;
+        form_trial(step.apr);
+        if (!take_step(step.apr, step.adu)) return Tried::failed;
+        const double err_tr = kkt_error(mu, nullptr, nullptr);
+        if (std::isfinite(err_tr) && err_tr <= 0.9 * err_mu) {
+            ++R.newton_steps;
+            return Tried::taken;
+        }
+        it = it_keep;
+        ++R.restored_steps;
+        return Tried::rejected;
+    }
+
+    // ---- the problem ---------------------------------------------------------------------------------------------------------
+    const NlpProblem& P;
+    const NlpOptions& opt;
+    const RowVars rv;                   // (variable, VALS entry) pairs of every path row
+    const int ns, np, M, nv, nz, md, mc;
+    const int nl, ml, me;               // coupling rows behind the defects: me equality multipliers
+    const int npart;
+    const size_t NN;                    // unknowns of the reduced system
+    const Clock::time_point tstart = Clock::now();
+    std::vector<double> sig, cls, cus;  // row scales; scaled row bounds
+    IpmDims PD;                         // the same problem as the ipm_* functions take it
+    const IpmB B{PD};
+    std::vector<unsigned char> fixed_mask;
+    std::vector<double> rs;             // row weights of the merit function
+    // ---- the iterate and the scalars of the barrier / penalty / inertia-search / stagnation / crawl rules -----------------------
+    Point it, it_keep;
+    Eval Et;                            // trial point: values ...
+    std::vector<double> zt, st, e1t, e2t;   // ... and primal variables
+    double mu = 0, nu = 1.0, rho = 0;
+    double err0 = 0, emax = 0, tau = 0;     // of this iteration: KKT error at mu = 0, largest elastic, fraction to the boundary
+    double dw_used = 0.0;               // delta_w of the last exact step, or the largest reflected eigenvalue shift (log only)
+    double dw_last_ok = 0.0;            // last nonzero delta_w that gave the right inertia
+    int n_acceptable = 0, futile = 0, stagn = 0, crawl = 0;
+    bool force_modified = false, search_on = false, last_step_reflected = false, mu_restarted = false;
+    double emax_ref = 1e300, stagn_ref = 1e300;
+    // ---- Newton-step linear algebra: the caller's backend (eMI355X: the device) or the dense host one -----------------------------
+    DenseHostKkt host_kkt;
+    KktBackend* const kkt;
+    bool backend_blocks;                // until the backend says NOT_OFFERED
+    static constexpr int max_lowrank = 4096;        // more modified eigenpairs than this: take the modified step untested
+    std::vector<double> H, Qblk, Qexact, Sigma, y_unscaled;
+    std::vector<double> sig_t, sig_s, rhat_s;       // row elimination (r_t: with the step)
+    std::vector<BlockMod> mods;
+    int n_mods = 0;                     // modified eigenpairs of the last factorisation (the true number, also beyond max_lowrank)
+    int r_mod = 0;                      // ... of which the low-rank correction holds
+    bool exact_step = false;
+    std::vector<int> lr_node;
+    std::vector<double> lr_vec, lr_delta;
+    std::vector<double> rhs_full, rhs_keep, eqres, resid, x_prev, xfree;
+    // ---- the step, and the right-hand sides of its second-order correction -------------------------------------------------------
+    Step step;
+    std::vector<double> soc_def, soc_row, soc_rhs;
+    NlpResult R;
+};
+
+// Iterate on the scaled variables (ScaledEvaluator above), answer in the caller's
+NlpResult solve_scaled(const NlpProblem& P, const NlpOptions& opt, const std::vector<double>& z0, const RowVars& rv, int npart) {
+    NlpResult R;
+    const int ns = P.ns, M = P.M, nv = ns + P.nc, nz = nv * M, md = ns * M;
+    if ((int)P.vscale.size() != nv || (int)z0.size() != nz || (int)P.zl.size() != nz || (int)P.zu.size() != nz || !P.ev) {
+        R.msg = "solve_nlp: inconsistent problem sizes (vscale)";
+        return R;
+    }
+    for (double sv : P.vscale)
+        if (!(sv > 0) || !std::isfinite(sv)) { R.msg = "solve_nlp: vscale must be positive"; return R; }
+    for (const NlpLink& L : P.links)        // (d - W z) / s keeps W only if both ends carry the same scale
+        if (P.vscale[L.dst] != P.vscale[L.src]) { R.msg = "solve_nlp: a coupled variable must be scaled like its source"; return R; }
+    NlpProblem Q = P;
+    Q.vscale.clear();
+    Q.row_vars = rv;
+    ScaledEvaluator sev(P, rv, npart);
+    Q.ev = &sev;
+    std::vector<double> zs(z0);
+    for (int v = 0; v < nv; ++v)
+        for (int k = 0; k < M; ++k) {
+            const size_t q = (size_t)v * M + k;
+            const double inv = 1.0 / P.vscale[v];
+            zs[q] *= inv;
+            if (Q.zl[q] > -INF_BOUND) Q.zl[q] *= inv;
+            if (Q.zu[q] < INF_BOUND) Q.zu[q] *= inv;
+            if (P.zl[q] == P.zu[q]) Q.zu[q] = Q.zl[q];
+        }
+    if ((int)Q.lamF0.size() == md)
+        for (int i = 0; i < ns; ++i)
+            for (int k = 0; k < M; ++k) Q.lamF0[(size_t)i * M + k] *= P.vscale[i];
+    NlpResult S = solve_nlp(Q, opt, zs);
+    for (int v = 0; v < nv && (int)S.z.size() == nz; ++v)
+        for (int k = 0; k < M; ++k) S.z[(size_t)v * M + k] *= P.vscale[v];
+    for (int i = 0; i < ns && (int)S.lamF.size() == md; ++i)
+        for (int k = 0; k < M; ++k) S.lamF[(size_t)i * M + k] /= P.vscale[i];
+    for (size_t l = 0; l < P.links.size() && S.lamL.size() == P.links.size() * M; ++l)      // row (d - W z) / s: multiplier / s
+        for (int k = 0; k < M; ++k) S.lamL[l * M + k] /= P.vscale[P.links[l].dst];
+    return S;
+}
+
+}  // namespace
+
+NlpResult solve_nlp(const NlpProblem& P, const NlpOptions& opt, const std::vector<double>& z0) {
+    NlpResult R;
+    const int ns = P.ns, np = P.np, M = P.M, nv = ns + P.nc, nz = nv * M;
+    for (const NlpLink& L : P.links)
+        if (L.dst < 0 || L.dst >= nv || L.src < 0 || L.src >= nv || L.dst == L.src || (int)L.W.size() != M * M) {
+            R.msg = "solve_nlp: a coupling row names variables outside the problem or has no M x M operator";
+            return R;
+        }
+    if (!P.links.empty() && P.kkt) { R.msg = "solve_nlp: coupling rows (delayed values) are solved with the dense host backend only"; return R; }
+    // (variable, VALS entry) pairs of every path row
+    RowVars rv = P.row_vars;
+    if (rv.empty())
+        for (int j = 0; j < np; ++j) rv.push_back({{P.px, ns * nv + 2 * j}, {P.py, ns * nv + 2 * j + 1}});
+    if ((int)rv.size() != np) { R.msg = "solve_nlp: row_vars has the wrong length"; return R; }
+    int npart = 0;
+    for (const auto& r : rv) npart += (int)r.size();
+    if (!P.vscale.empty()) return solve_scaled(P, opt, z0, rv, npart);
+    if (!P.ev || (int)P.zl.size() != nz || (int)P.zu.size() != nz || (int)P.D.size() != M * M ||
+        (int)P.cl.size() != np || (int)P.cu.size() != np || (int)z0.size() != nz) {
+        R.msg = "solve_nlp: inconsistent problem sizes";
+        return R;
+    }
+    if (!P.cscale.empty() && (int)P.cscale.size() != np) { R.msg = "solve_nlp: cscale has the wrong length"; return R; }
+    for (int j = 0; j < np; ++j)
+        if (!(P.cl[j] > -INF_BOUND) && !(P.cu[j] < INF_BOUND)) { R.msg = "solve_nlp: path row without any bound"; return R; }
+    IpmSolve S(P, opt, std::move(rv), npart);
+    if (!S.start(z0)) return S.result();
+    for (int iter = 0;; ++iter) {
+        IpmSolve::Next next = S.test_and_update_barrier(iter);
+        if (next == IpmSolve::Next::go) next = S.newton_system();
+        if (next == IpmSolve::Next::go) next = S.line_search();
+        if (next == IpmSolve::Next::abort) return S.result();
+        if (next == IpmSolve::Next::finish) break;
+    }
+    return S.finish();
 }
 
 }  // namespace mi355x

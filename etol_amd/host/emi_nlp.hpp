@@ -9,11 +9,12 @@
 // value comes from the device through an NlpEvaluator; the linear algebra of
 // the step is either a dense symmetric-indefinite LDL^T on the host (small
 // problems such as the shipped resource/configs ones: exact inertia) or a
-// KktBackend -- the device assembly + LU of etol_amd/csrc/emi_kkt.hip (SURVEY.md
-// section 8f rank 1).  An LU reports no inertia, so that branch factorises a
-// quasi-definite matrix (node blocks of Q made positive definite: inertia known
-// by construction) and recovers the exact Newton step, together with an exact
-// inertia test of the unmodified matrix, from a low-rank Woodbury correction.
+// KktBackend -- the device assembly + Cholesky of a Schur complement of
+// etol_amd/csrc/emi_kkt.hip.  That factorisation
+// reports no inertia, so that branch factorises a quasi-definite matrix (node
+// blocks of Q made positive definite: inertia known by construction) and
+// recovers the exact Newton step, together with an exact inertia test of the
+// unmodified matrix, from a low-rank Woodbury correction.
 #ifndef ETOL_MI355X_EMI_NLP_HPP_
 #define ETOL_MI355X_EMI_NLP_HPP_
 
@@ -121,7 +122,7 @@ struct NlpProblem {
     std::vector<double> lamF0, lamC0;   // optional warm start of the defect / path-row multipliers (ns*M, np*M)
     std::vector<NlpLink> links;         // linear coupling rows (delayed values); the dense host backend only (kkt must be null)
     NlpEvaluator* ev = nullptr;
-    KktBackend* kkt = nullptr;          // null: dense LDL^T on the host (with inertia); else e.g. the device LU
+    KktBackend* kkt = nullptr;          // null: dense LDL^T on the host (with inertia); else e.g. the device factorisation
 };
 
 struct NlpOptions {
@@ -151,6 +152,7 @@ struct NlpResult {
     int evaluations = 0;
     int newton_steps = 0;               // iterations accepted on the KKT residual alone (near the solution)
     int soc_steps = 0;                  // iterations accepted through a second-order correction
+    int restored_steps = 0;             // full steps tried on the KKT residual and taken back (the iterate restored as it was)
     double cost = 0, kkt_error = 0, constr_viol = 0;
     std::vector<double> z;              // (ns+nc)*M solution
     std::vector<double> lamF, lamC;     // multipliers of the defect and path rows

@@ -19,6 +19,17 @@ namespace {
 
 std::string g_out, g_out2;
 std::string g_linear_solver = "auto";   // mx::Alg::linear_solver for the harness solves
+std::string g_node_blocks;              // mx::Alg::node_blocks for the harness solves ("": the setup() default)
+std::vector<double> g_runs;             // Sol::nlp_runs of the last eMI355X solve of the harness (harness_last_nlp_runs)
+void before_solve(ETOL::eMI355X& solver) {
+    if (!g_node_blocks.empty()) solver.getAlgorithm()->node_blocks = g_node_blocks;
+}
+void after_solve(ETOL::eMI355X& solver) {
+    g_runs.clear();
+    for (const auto& r : solver.getSolution()->nlp_runs)
+        g_runs.insert(g_runs.end(), {(double)r.nodes, (double)r.iterations, r.converged ? 1.0 : 0.0, r.seconds, r.t_eval, r.t_hess, r.t_factor,
+                                     r.t_solve, r.t_lowrank, r.t_blocks, r.t_jt, r.t_matvec});
+}
 
 // a TrajectoryOptimizer that can be instantiated without a GPU (for the loader tests)
 class Plain : public ETOL::TrajectoryOptimizer {
@@ -394,7 +405,9 @@ extern "C" int harness_solve_delay_demo(int nsteps, double dt, int xh, int uh, d
     solver.getAlgorithm()->nlp_tolerance = tol;
     solver.getAlgorithm()->nlp_iter_max = 400;
     solver.getAlgorithm()->print_level = print_level;
+    before_solve(solver);
     t->solve();
+    after_solve(solver);
     g_out = solver.getSolution()->error_msg;
     if (solver.getSolution()->error_flag) { t->close(); return 1; }
     const size_t M = nsteps + 1;
@@ -497,6 +510,14 @@ extern "C" void harness_set_speed_limit(double v) { g_speed_limit = v; }
 int g_refine = -1;              // harness_solve_example1: -1 = the setup() default ("automatic"), 0 = "none", 1 = "automatic"
 extern "C" void harness_set_refine(int mode) { g_refine = mode; }
 extern "C" void harness_set_linear_solver(const char* name) { g_linear_solver = name; }
+extern "C" void harness_set_node_blocks(const char* name) { g_node_blocks = name; }
+// Sol::nlp_runs of the last eMI355X solve, 12 values per run: nodes, iterations, converged, seconds, then the seconds of the evaluator,
+// Hessian, factor, solve, low-rank, node-block, J^T lambda and matvec parts; returns the number of values (copied when cap suffices)
+extern "C" int harness_last_nlp_runs(double* out, int cap) {
+    const int n = (int)g_runs.size();
+    if (out && cap >= n && n > 0) std::memcpy(out, g_runs.data(), (size_t)n * sizeof(double));
+    return n;
+}
 extern "C" const char* harness_last_linear_solver(void) { return g_out2.c_str(); }
 
 // ETOL::eMI355X::odeError (the PSOPT-style relative local error) of a given trajectory of the quadrotor problem
@@ -530,7 +551,9 @@ extern "C" int harness_solve_quadrotor(int nsteps, double dt, int ndiscs, double
     solver.getAlgorithm()->linear_solver = g_linear_solver;
     solver.getAlgorithm()->scaling = g_scaling < 0 ? solver.getAlgorithm()->scaling : (g_scaling ? "automatic" : "none");
     if (g_defect_scaling) solver.getAlgorithm()->defect_scaling = "jacobian-based";
+    before_solve(solver);
     solver.solve();
+    after_solve(solver);
     g_out2 = solver.getSolution()->linear_solver;
     const mx::Sol* s = solver.getSolution();
     *iters = s->nlp_iterations;
@@ -731,7 +754,9 @@ extern "C" int harness_solve_fixedwing(int nsteps, double tf, double lateral, do
     solver.getAlgorithm()->linear_solver = g_linear_solver;
     solver.getAlgorithm()->scaling = g_scaling < 0 ? solver.getAlgorithm()->scaling : (g_scaling ? "automatic" : "none");
     if (g_defect_scaling) solver.getAlgorithm()->defect_scaling = "jacobian-based";
+    before_solve(solver);
     solver.solve();
+    after_solve(solver);
     const mx::Sol* s = solver.getSolution();
     *iters = s->nlp_iterations;
     g_out = s->error_msg;
@@ -989,7 +1014,9 @@ int harness_solve_example1(const char* xml, int with_obstacles, double tol, int 
     e.solver.getAlgorithm()->scaling = g_scaling < 0 ? e.solver.getAlgorithm()->scaling : (g_scaling ? "automatic" : "none");
     if (g_defect_scaling) e.solver.getAlgorithm()->defect_scaling = "jacobian-based";
     if (g_refine >= 0) e.solver.getAlgorithm()->mesh_refinement = g_refine ? "automatic" : "none";
+    before_solve(e.solver);
     t->solve();
+    after_solve(e.solver);
     g_out2 = e.solver.getSolution()->linear_solver;
     const mx::Sol* s = e.solver.getSolution();
     *iters = s->nlp_iterations;
