@@ -62,6 +62,20 @@ class IpmBounds(C.Structure):
     _fields_ = [("zl", _P), ("zu", _P), ("nsets", C.c_int), ("cl", _D), ("cu", _D), ("cscale", _D)]
 
 
+class IpmOptions(C.Structure):
+    """emi_ipm_options_t: fields left at zero take solve_nlp's defaults"""
+    _fields_ = [(n, C.c_double) for n in ("tol", "mu_init", "bound_push", "bound_frac", "rho_init", "acceptable_factor")] + \
+               [(n, C.c_int) for n in ("max_iter", "acceptable_iter", "max_futile_escalations")]
+
+
+class IpmResult(C.Structure):
+    """emi_ipm_result_t: how one instance of emi_ipm_solve_shard_* ended"""
+    _fields_ = [(n, C.c_int) for n in ("status", "iterations", "evaluations", "factorisations", "reflected_steps")] + \
+               [(n, C.c_double) for n in ("cost", "kkt_error", "constr_viol", "emax", "mu", "rho")]
+
+
+IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
+
 _PT, _DU, _ST, _EL, _BD = (C.POINTER(t) for t in (IpmPoint, IpmDuals, IpmStep, IpmElim, IpmBounds))
 
 # every symbol include/emi355x.h declares: name -> (restype, argtypes)
@@ -103,6 +117,11 @@ SYMBOLS = {
     "emi_ipm_merit_host": (C.c_int, [_P, _PT, _P, _P, _BD, _P, _P, C.c_int, _P]),
     "emi_ipm_accept_host": (C.c_int, [_P, _PT, _PT, _DU, _ST, _BD, _P, _P, _P, _P]),
     "emi_ipm_error_host": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
+    "emi_ipm_start_dev": (C.c_int, [_P, C.c_int, _PT, _DU, _P, _BD, _P, C.c_double, C.c_double, _P, _P]),
+    "emi_ipm_error_parts_dev": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
+    "emi_ipm_error_parts_host": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
+    "emi_ipm_solve_shard_dev": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
+    "emi_ipm_solve_shard_host": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

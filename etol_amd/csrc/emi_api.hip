@@ -140,6 +140,7 @@ struct emi_ctx_s {
     std::vector<double> ipm_crow_h;     // [5][np]: cl, cu, cscale cl, cscale cu, cscale (what ipm_crow holds)
     emi::DeviceArray<double> ipm_crow, ipm_part;
     std::vector<DevBuf> ipm_stage;
+    emi::IpmSolveWs* ipm_solve = nullptr;   // device arrays of the lock-step driver (emi_ipm_solve_shard_*), created at its first call
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;
     int profile = 0;          // emi_profile_enable level (0 off)
@@ -163,6 +164,7 @@ struct emi_ctx_s {
         emi::rtc_destroy(rtc);
         emi::kkt_destroy(kkt);
         for (emi::KktWorkspace* w : kkt_shard) emi::kkt_destroy(w);
+        emi::ipm_solve_destroy(ipm_solve);
     }
 };
 
@@ -1954,7 +1956,7 @@ int ipm_common(emi_ctx_t c, const char* what, const emi_ipm_bounds_t* bd, const 
 }
 
 int ipm_partials(emi_ctx_t c, emi::IpmArgs& a) {
-    HIP_TRY(c, c->ipm_part.reserve((size_t)c->B * emi::ipm_chunks(c->M) * 7));
+    HIP_TRY(c, c->ipm_part.reserve((size_t)c->B * emi::ipm_chunks(c->M) * emi::IPM_MAX_PARTIALS));
     a.part = c->ipm_part.p;
     return EMI_OK;
 }
@@ -2079,6 +2081,42 @@ int emi_ipm_error_dev(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_dual
     ipm_set_point(a, pt); ipm_set_duals(a, du);
     a.RES = (const double*)dRES; a.G = (const double*)dG; a.out = (double*)dOut;
     HIP_TRY(c, emi::launch_ipm(emi::IPM_ERROR, a, c->stream));
+    return EMI_OK;
+}
+
+int emi_ipm_start_dev(emi_ctx_t c, int phase, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES, const emi_ipm_bounds_t* bd,
+                      const void* dPar, double bound_push, double bound_frac, void* dFixed, const void* dMask) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ipm_check(c, "emi_ipm_start_dev"));
+    const int np = np_total(c);
+    bool ok = pt && du && bd && phase >= 0 && phase <= 2;
+    if (ok && phase == 0) ok = pt->X && (c->nc == 0 || pt->U) && du->LamF && dFixed && bound_push > 0 && bound_frac > 0;
+    if (ok && phase == 1) ok = ipm_has_point(pt, c->nc, np) && ipm_has_duals(du, np) && dRES && dPar && bound_push > 0 && bound_frac > 0;
+    if (ok && phase == 2) ok = dPar && (np == 0 || (du->Y && du->W1 && du->W2));
+    if (!ok) return fail(c, EMI_ERR_ARG, "emi_ipm_start_dev: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    emi::IpmArgs a{};
+    EMI_TRY(ipm_common(c, "emi_ipm_start_dev", bd, dPar, a));
+    ipm_set_point(a, pt); ipm_set_duals(a, du);
+    a.RES = (const double*)dRES; a.fixedb = (unsigned char*)dFixed; a.mask = (const unsigned char*)dMask; a.push = bound_push; a.frac = bound_frac;
+    HIP_TRY(c, emi::launch_ipm(phase == 0 ? emi::IPM_START_PUSH : phase == 1 ? emi::IPM_START_ROWS : emi::IPM_RESET_W, a, c->stream));
+    return EMI_OK;
+}
+
+int emi_ipm_error_parts_dev(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES, const void* dG,
+                            const emi_ipm_bounds_t* bd, const void* dPar, void* dOut) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ipm_check(c, "emi_ipm_error_parts_dev"));
+    const int np = np_total(c);
+    if (!ipm_has_point(pt, c->nc, np) || !ipm_has_duals(du, np) || !dRES || !dG || !bd || !dPar || !dOut)
+        return fail(c, EMI_ERR_ARG, "emi_ipm_error_parts_dev: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    emi::IpmArgs a{};
+    EMI_TRY(ipm_common(c, "emi_ipm_error_parts_dev", bd, dPar, a));
+    EMI_TRY(ipm_partials(c, a));
+    ipm_set_point(a, pt); ipm_set_duals(a, du);
+    a.RES = (const double*)dRES; a.G = (const double*)dG; a.out = (double*)dOut;
+    HIP_TRY(c, emi::launch_ipm(emi::IPM_ERROR_PARTS, a, c->stream));
     return EMI_OK;
 }
 
@@ -2246,6 +2284,17 @@ int emi_ipm_error_host(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_dua
     const void *dR = s.place(RES, z.res, true, false), *dG = s.place(G, z.var, true, false), *dP = s.place(par, z.inst * 4, true, false);
     void* dO = s.place(out, z.inst * 3, false, true);
     IPM_HOST_END(emi_ipm_error_dev(c, pt ? &dp : nullptr, du ? &dd : nullptr, dR, dG, bd ? &db : nullptr, dP, dO));
+}
+
+int emi_ipm_error_parts_host(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* G,
+                             const emi_ipm_bounds_t* bd, const double* par, double* out) {
+    IPM_HOST_BEGIN("emi_ipm_error_parts_host", bd ? bd->nsets : 0);
+    const emi_ipm_point_t dp = stage_point(s, z, pt, true, false);
+    const emi_ipm_duals_t dd = stage_duals(s, z, du, true, false);
+    const emi_ipm_bounds_t db = stage_bounds(s, z, bd);
+    const void *dR = s.place(RES, z.res, true, false), *dG = s.place(G, z.var, true, false), *dP = s.place(par, z.inst * 4, true, false);
+    void* dO = s.place(out, z.inst * 8, false, true);
+    IPM_HOST_END(emi_ipm_error_parts_dev(c, pt ? &dp : nullptr, du ? &dd : nullptr, dR, dG, bd ? &db : nullptr, dP, dO));
 }
 
 int emi_kkt_lowrank(emi_ctx_t c, int r, const int* node, const double* vec, const double* delta, int* exact) {
@@ -2535,6 +2584,53 @@ int emi_kkt_solve_refined_shard_dev(emi_ctx_t c, void* dRhs, const unsigned char
     if (st) { c->err = err; return st; }
     for (int a = 0; a < n; ++a) { rel[inst[a]] = r[a]; nsolve[inst[a]] = nsv[a]; reverted[inst[a]] = rev[a]; status[inst[a]] = sta[a]; }
     return EMI_OK;
+}
+
+// ---- lock-step interior-point solve of the whole batch (the driver: emi_ipm_solve.hip) -------------------------------------------
+extern "C++" {
+namespace emi {
+
+int ctx_shard_holds(emi_ctx_t c, int b) {
+    return b < (int)c->kkt_shard.size() ? kkt_holds(c->kkt_shard[b], c->M, c->ns, c->ns + c->nc) : 0;
+}
+
+void ctx_shard_forget_ladders(emi_ctx_t c) {
+    for (KktWorkspace* w : c->kkt_shard) kkt_forget_ladder(w);
+}
+
+int ctx_ipm_launch(emi_ctx_t c, int what, const emi_ipm_bounds_t* bd, const void* dPar, IpmArgs& a) {
+    EMI_TRY(ipm_common(c, "emi_ipm_solve_shard_dev", bd, dPar, a));
+    HIP_TRY(c, launch_ipm(what, a, c->stream));
+    return EMI_OK;
+}
+
+}  // namespace emi
+}  // extern "C++"
+
+int emi_ipm_solve_shard_dev(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt, void* dLamF,
+                            void* dLamC, emi_ipm_result_t* results) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ipm_check(c, "emi_ipm_solve_shard_dev"));
+    EMI_TRY(shard_check(c, "emi_ipm_solve_shard_dev"));
+    EMI_TRY(ready(c));
+    const int np = np_total(c);
+    if (!dX || (c->nc > 0 && !dU) || !bd || !opt || !dLamF || (np > 0 && !dLamC) || !results)
+        return fail(c, EMI_ERR_ARG, "emi_ipm_solve_shard_dev: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const emi::IpmSolveDims d{c->device, c->B, c->M, c->ns, c->nc, np, nvals_of(c), nhess_of(c), c->stream};
+    std::string err;
+    const int st = emi::ipm_solve_shard(c, &c->ipm_solve, d, dX, dU, bd, *opt, dLamF, dLamC, results, &err);
+    if (st && !err.empty()) c->err = err;
+    return st;
+}
+
+int emi_ipm_solve_shard_host(emi_ctx_t c, double* X, double* U, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt, double* LamF,
+                             double* LamC, emi_ipm_result_t* results) {
+    IPM_HOST_BEGIN("emi_ipm_solve_shard_host", bd ? bd->nsets : 0);
+    void *dX = s.place(X, z.X, true, true), *dU = s.place(U, z.U, true, true);
+    void *dLF = s.place(LamF, z.X, false, true), *dLC = s.place(LamC, z.row, false, true);
+    const emi_ipm_bounds_t db = stage_bounds(s, z, bd);
+    IPM_HOST_END(emi_ipm_solve_shard_dev(c, dX, dU, bd ? &db : nullptr, opt, dLF, dLC, results));
 }
 
 int emi_timer_start(emi_ctx_t c) {

@@ -10,7 +10,12 @@
 //   emi_ipm_merit_kernel    slack reset (optional), barrier function and l1 infeasibility as partials
 //   emi_ipm_accept_kernel   point <- trial point, multipliers += step, clamped around mu / gap; masked instances untouched
 //   emi_ipm_error_kernel    scale sums and the four maxima of the scaled KKT error as partials
-//   emi_ipm_finish_kernel   the partials of the three reducing kernels, added in chunk order, and what is formed from them
+//   emi_ipm_finish_kernel   the partials of the reducing kernels, added in chunk order, and what is formed from them
+// and for the lock-step driver (emi_ipm_solve.hip):
+//   emi_ipm_error_parts_kernel  the components of the KKT error, from which the error of any barrier parameter follows
+//   emi_ipm_start_kernel    start(): interior push and fixed bytes; slacks, elastics and multipliers after the first evaluation; the
+//                           reset of the elastic multipliers after a penalty escalation (masked)
+//   emi_ipm_lamc_kernel     LamC = cscale Y
 //
 // One thread per (instance, node), 256 threads, grid (ceil(M / 256), B).  The loops run over variables and rows, so every access
 // of a wave is a run of consecutive doubles along the node axis.  NOT "all loads of a thread before its stores": the number of
@@ -367,9 +372,132 @@ __global__ __launch_bounds__(IPM_T) void emi_ipm_error_kernel(IpmArgs a) {
     block_partials<7>(v, op, a.part + ((size_t)b * gridDim.x + blockIdx.x) * 7);
 }
 
+// ---- components of the KKT error: what emi_ipm_error_kernel folds into one number for par.mu, kept apart -----------------------------
+// The sums and the maxima ed, ep, emax are those of emi_ipm_error_kernel term for term; instead of ec = max |product - mu| the
+// smallest and the largest product, from which ec follows for any mu (rounding is monotonic: the same bits as the maximum of the
+// rounded differences); and max |Y|, which the barrier update asks for.
+__global__ __launch_bounds__(IPM_T) void emi_ipm_error_parts_kernel(IpmArgs a) {
+    const int k = blockIdx.x * IPM_T + threadIdx.x, b = blockIdx.y;
+    const bool act = k < a.M;
+    const Idx ix(a, b, act ? k : 0);
+    const int ns = a.ns, np = a.np;
+    const double rho = a.par[b * 4 + 1];
+    double sumz = 0, summ = 0, cnt = 0, ed = 0, ep = 0, pmin = 1e300, pmax = -1e300, emax = 0, ymax = 0;
+    if (act) {
+        for (int v = 0; v < ix.nv; ++v) {
+            const double z = *ix.z(a.X, a.U, v), zl = a.zl[ix.bnd(v)], zu = a.zu[ix.bnd(v)];
+            const double zL = a.ZL[ix.var(v)], zU = a.ZU[ix.var(v)], g = a.G[ix.var(v)];
+            sumz += zL + zU;
+            cnt += (zL > 0) + (zU > 0);
+            if (!(zu > zl)) continue;
+            ed = fmax(ed, fabs(g - zL + zU));
+            if (zl > -IPM_INF) { const double p = (z - zl) * zL; pmin = fmin(pmin, p); pmax = fmax(pmax, p); }
+            if (zu < IPM_INF) { const double p = (zu - z) * zU; pmin = fmin(pmin, p); pmax = fmax(pmax, p); }
+        }
+        for (int j = 0; j < np; ++j) {
+            const RowB rb(a, j);
+            const size_t r = ix.row(j);
+            const double s = a.S[r], e1 = a.E1[r], e2 = a.E2[r], y = a.Y[r], vL = a.VL[r], vU = a.VU[r], w1 = a.W1[r], w2 = a.W2[r];
+            const double c = rb.cs * a.RES[ix.res(ns + j)];
+            sumz += vL + vU + w1 + w2;
+            cnt += (vL > 0) + (vU > 0) + 2;
+            summ += fabs(y);
+            ed = fmax(ed, fabs(-y - vL + vU));
+            ed = fmax(ed, fabs(rho - y - w1));
+            ed = fmax(ed, fabs(rho + y - w2));
+            ep = fmax(ep, fabs(c - s - e1 + e2));
+            emax = fmax(emax, fmax(e1, e2));
+            ymax = fmax(ymax, fabs(y));
+            if (rb.hasL) { const double p = (s - rb.lo) * vL; pmin = fmin(pmin, p); pmax = fmax(pmax, p); }
+            if (rb.hasU) { const double p = (rb.hi - s) * vU; pmin = fmin(pmin, p); pmax = fmax(pmax, p); }
+            const double p1 = e1 * w1, p2 = e2 * w2;
+            pmin = fmin(pmin, fmin(p1, p2));
+            pmax = fmax(pmax, fmax(p1, p2));
+        }
+        for (int i = 0; i < ns; ++i) {
+            summ += fabs(a.LF[ix.st(i)]);
+            ep = fmax(ep, fabs(a.RES[ix.res(i)]));
+        }
+    }
+    double v[9] = {sumz, summ, cnt, ed, ep, pmin, pmax, emax, ymax};
+    constexpr int op[9] = {R_SUM, R_SUM, R_SUM, R_MAX, R_MAX, R_MIN, R_MAX, R_MAX, R_MAX};
+    block_partials<9>(v, op, a.part + ((size_t)b * gridDim.x + blockIdx.x) * 9);
+}
+
+// ---- the start of a lock-step solve (solve_nlp's start()) and the small array steps of its rounds -------------------------------------
+// Every operation below is an exact one or a single rounded one with contraction off: the arrays are, bit for bit, what the
+// formulas give in any IEEE arithmetic.
+__device__ __forceinline__ double pushed_inside(double v, double l, double u, bool hasL, bool hasU, double push, double frac) {
+#pragma clang fp contract(off)
+    double pl = hasL ? push * fmax(1.0, fabs(l)) : 0.0, pu = hasU ? push * fmax(1.0, fabs(u)) : 0.0;
+    if (hasL && hasU) { pl = fmin(pl, frac * (u - l)); pu = fmin(pu, frac * (u - l)); }
+    if (hasL) v = fmax(v, l + pl);
+    if (hasU) v = fmin(v, u - pu);
+    return v;
+}
+
+__global__ __launch_bounds__(IPM_T) void emi_ipm_start_kernel(IpmArgs a, int phase) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * IPM_T + threadIdx.x, b = blockIdx.y;
+    if (k >= a.M) return;
+    const Idx ix(a, b, k);
+    const int ns = a.ns, np = a.np;
+    if (phase == IPM_START_PUSH) {
+        for (int v = 0; v < ix.nv; ++v) {
+            const double zl = a.zl[ix.bnd(v)], zu = a.zu[ix.bnd(v)];
+            double* z = ix.z(a.X, a.U, v);
+            const bool fx = !(zu > zl);
+            a.fixedb[ix.var(v)] = fx ? 1 : 0;
+            *z = fx ? zl : pushed_inside(*z, zl, zu, zl > -IPM_INF, zu < IPM_INF, a.push, a.frac);
+        }
+        for (int i = 0; i < ns; ++i) a.LF[ix.st(i)] = 0.0;
+        return;
+    }
+    const double rho = a.par[b * 4 + 1];
+    if (phase == IPM_RESET_W) {
+        if (a.mask && !a.mask[b]) return;
+        for (int j = 0; j < np; ++j) {
+            const size_t r = ix.row(j);
+            const double y = a.Y[r];
+            a.W1[r] = fmax(1e-8, rho - y);
+            a.W2[r] = fmax(1e-8, rho + y);
+        }
+        return;
+    }
+    for (int v = 0; v < ix.nv; ++v) {           // IPM_START_ROWS
+        const double zl = a.zl[ix.bnd(v)], zu = a.zu[ix.bnd(v)];
+        const bool fr = zu > zl;
+        a.ZL[ix.var(v)] = fr && zl > -IPM_INF ? 1.0 : 0.0;
+        a.ZU[ix.var(v)] = fr && zu < IPM_INF ? 1.0 : 0.0;
+    }
+    for (int j = 0; j < np; ++j) {
+        const RowB rb(a, j);
+        const size_t r = ix.row(j);
+        const double c0 = rb.cs * a.RES[ix.res(ns + j)];
+        const double s = pushed_inside(c0, rb.lo, rb.hi, rb.hasL, rb.hasU, a.push, a.frac);
+        const double gap = c0 - s, ee = a.push * fmax(1.0, fabs(gap));
+        a.S[r] = s;
+        a.E1[r] = fmax(gap, 0.0) + ee;          // the residual c - s - e1 + e2 starts at exactly 0
+        a.E2[r] = fmax(-gap, 0.0) + ee;
+        a.Y[r] = 0.0;
+        a.VL[r] = rb.hasL ? 1.0 : 0.0;
+        a.VU[r] = rb.hasU ? 1.0 : 0.0;
+        a.W1[r] = fmax(1e-8, rho);
+        a.W2[r] = fmax(1e-8, rho);
+    }
+}
+
+// path-row multipliers in the caller's units
+__global__ __launch_bounds__(IPM_T) void emi_ipm_lamc_kernel(IpmArgs a) {
+    const int k = blockIdx.x * IPM_T + threadIdx.x, b = blockIdx.y;
+    if (k >= a.M) return;
+    const Idx ix(a, b, k);
+    for (int j = 0; j < a.np; ++j) a.LamC[ix.row(j)] = a.crow[4 * a.np + j] * a.Y[ix.row(j)];
+}
+
 // ---- the partials of an instance in chunk order -------------------------------------------------------------------------------------
 // what: 0 expand -> out[b][4] = {apr, adu, dphi, mmax};  1 merit -> out[b][2] = {COST + phi, infeas};
-//       2 error -> out[b][3] = {kkt_error, viol, emax}
+//       2 error -> out[b][3] = {kkt_error, viol, emax};  3 error parts -> out[b][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}
 __global__ __launch_bounds__(IPM_T) void emi_ipm_finish_kernel(const double* part, const double* cost, double* out, int B, int nchunk, int what,
                                                               int me_mc) {
     const int b = blockIdx.x * IPM_T + threadIdx.x;
@@ -386,6 +514,18 @@ __global__ __launch_bounds__(IPM_T) void emi_ipm_finish_kernel(const double* par
         double phi = cost[b], viol = 0.0;
         for (int c = 0; c < nchunk; ++c) { phi += p[c * 2]; viol += p[c * 2 + 1]; }
         out[b * 2] = phi; out[b * 2 + 1] = viol;
+    } else if (what == 3) {
+        const double* p = part + (size_t)b * nchunk * 9;
+        double sumz = 0, summ = 0, cnt = 0, ed = 0, ep = 0, pmin = 1e300, pmax = -1e300, emax = 0, ymax = 0;
+        for (int c = 0; c < nchunk; ++c) {
+            sumz += p[c * 9]; summ += p[c * 9 + 1]; cnt += p[c * 9 + 2];
+            ed = fmax(ed, p[c * 9 + 3]); ep = fmax(ep, p[c * 9 + 4]); pmin = fmin(pmin, p[c * 9 + 5]); pmax = fmax(pmax, p[c * 9 + 6]);
+            emax = fmax(emax, p[c * 9 + 7]); ymax = fmax(ymax, p[c * 9 + 8]);
+        }
+        const double smax = 100.0;
+        double* o = out + (size_t)b * 8;
+        o[0] = ed; o[1] = fmax(smax, (summ + sumz) / fmax(1.0, (double)me_mc + cnt)) / smax; o[2] = ep;
+        o[3] = fmax(smax, sumz / fmax(1.0, cnt)) / smax; o[4] = pmin; o[5] = pmax; o[6] = emax; o[7] = ymax;
     } else {
         const double* p = part + (size_t)b * nchunk * 7;
         double sumz = 0, summ = 0, cnt = 0, ed = 0, ep = 0, ec = 0, emax = 0;
@@ -423,6 +563,12 @@ hipError_t launch_ipm(int what, const IpmArgs& a, hipStream_t s) {
             hipLaunchKernelGGL(emi_ipm_error_kernel, grid, dim3(IPM_T), 0, s, a);
             hipLaunchKernelGGL(emi_ipm_finish_kernel, fgrid, dim3(IPM_T), 0, s, a.part, nullptr, a.out, a.B, nchunk, 2, (a.ns + a.np) * a.M);
             break;
+        case IPM_ERROR_PARTS:
+            hipLaunchKernelGGL(emi_ipm_error_parts_kernel, grid, dim3(IPM_T), 0, s, a);
+            hipLaunchKernelGGL(emi_ipm_finish_kernel, fgrid, dim3(IPM_T), 0, s, a.part, nullptr, a.out, a.B, nchunk, 3, (a.ns + a.np) * a.M);
+            break;
+        case IPM_START_PUSH: case IPM_START_ROWS: case IPM_RESET_W: hipLaunchKernelGGL(emi_ipm_start_kernel, grid, dim3(IPM_T), 0, s, a, what); break;
+        case IPM_LAMC: hipLaunchKernelGGL(emi_ipm_lamc_kernel, grid, dim3(IPM_T), 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

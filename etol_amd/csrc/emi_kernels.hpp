@@ -132,9 +132,18 @@ struct IpmArgs {
     const unsigned char* mask;                              // [B] or null
     const int *vptr, *vrow, *vent;                          // per variable: the path rows it enters and the VALS entries, in row order
     const int *rptr, *rvar, *rent;                          // per path row: (variable, VALS entry)
-    double *part, *out;                                     // [B][chunks][<= 7] partials; the call's per-instance result
+    double *part, *out;                                     // [B][chunks][<= 9] partials; the call's per-instance result
+    // the lock-step driver's own array kernels (IPM_START_*, IPM_LAMC)
+    unsigned char* fixedb;                                  // [B][nv][M] bytes: 1 where a variable is fixed (written by IPM_START_PUSH)
+    double* LamC;                                           // [B][np][M] = cscale Y
+    double push, frac;                                      // bound_push, bound_frac of the interior push
 };
-enum { IPM_REDUCE, IPM_EXPAND, IPM_TRIAL, IPM_MERIT, IPM_ACCEPT, IPM_ERROR };
+// IPM_START_PUSH: z pushed inside its bounds (fixed variables set to their bound), the fixed bytes, LamF = 0;  IPM_START_ROWS, after
+// the first evaluation: S, E1, E2 from the path values, Y = 0, bound multipliers 1 where a bound exists, W1 / W2 from rho;
+// IPM_RESET_W: W1 / W2 = max(1e-8, rho -+ Y) at the instances of `mask`;  IPM_LAMC: LamC = cscale Y;
+// IPM_ERROR_PARTS: out[B][8], the components of the scaled KKT error (emi_ipm_error_parts_*)
+enum { IPM_REDUCE, IPM_EXPAND, IPM_TRIAL, IPM_MERIT, IPM_ACCEPT, IPM_ERROR, IPM_ERROR_PARTS, IPM_START_PUSH, IPM_START_ROWS, IPM_RESET_W, IPM_LAMC };
+constexpr int IPM_MAX_PARTIALS = 9;
 int ipm_chunks(int M);
 hipError_t launch_ipm(int what, const IpmArgs& a, hipStream_t s);
 
@@ -190,5 +199,21 @@ int kkt_solve_refined_batch(int n, KktWorkspace* const* ws, hipStream_t stream, 
 int kkt_holds(const KktWorkspace* w, int M, int ns, int nv);      // 0 nothing for this shape, 1 Schur factorisation, 2 LU
 int kkt_lowrank_shard(int n, KktWorkspace* const* ws, hipStream_t stream, int max_mods, const int* inst, const int* count, const int* dNode,
                       const double* dDelta, const double* dVec, int* exact, std::string* err);
+void kkt_forget_ladder(KktWorkspace* w);        // the next factorisation starts at the nominal regularisation level again
+
+// the lock-step interior-point driver of one context's batch (emi_ipm_solve.hip); its device arrays live in an IpmSolveWs the
+// context owns
+struct IpmSolveWs;
+void ipm_solve_destroy(IpmSolveWs* w);
+struct IpmSolveDims { int device, B, M, ns, nc, np, nvals, nhess; hipStream_t stream; };
+// dX .. dLamC device arrays; returns an EMI_* status (on EMI_ERR_HIP *err says what failed; the statuses of the emi_*_dev calls
+// it makes come back with the context's own message)
+int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* dX, void* dU, const emi_ipm_bounds_t* bd,
+                    const emi_ipm_options_t& opt, void* dLamF, void* dLamC, emi_ipm_result_t* results, std::string* err);
+// what the driver asks the context directly (emi_api.hip): kkt_holds of instance b's shard workspace; the ladders forgotten; an
+// array kernel of emi_ipm.hip that has no entry point of its own (IPM_LAMC) on the context's row bounds
+int ctx_shard_holds(emi_ctx_t c, int b);
+void ctx_shard_forget_ladders(emi_ctx_t c);
+int ctx_ipm_launch(emi_ctx_t c, int what, const emi_ipm_bounds_t* bd, const void* dPar, IpmArgs& a);
 
 }  // namespace emi

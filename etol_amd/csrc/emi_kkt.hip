@@ -1392,6 +1392,11 @@ void kkt_destroy(KktWorkspace* w) {
 
 bool kkt_is_schur(const KktWorkspace* w) { return w && w->factored && w->method_used == 1; }
 
+// (the lock-step driver calls this at its start: two identical solves then climb the same ladders and give the same bits)
+void kkt_forget_ladder(KktWorkspace* w) {
+    if (w) w->reg_M = 0;
+}
+
 void kkt_mesh_changed(KktWorkspace* w) {
     if (!w) return;
     w->doff_M = 0;

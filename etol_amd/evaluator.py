@@ -527,6 +527,44 @@ class Evaluator:
         self._ipm_call("error", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k), A(RES), A(G),
                                                 self._ipm_bounds(bounds, k), A(par), A(out)))
 
+    def ipm_error_parts(self, point, duals, RES, G, bounds, par, out, dev=True):
+        """out [B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: the components of ipm_error's KKT error (any barrier parameter)"""
+        A = self._ipm_addr
+        self._ipm_call("error_parts", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k), A(RES), A(G),
+                                                      self._ipm_bounds(bounds, k), A(par), A(out)))
+
+    def ipm_start(self, phase, point, duals, bounds, RES=None, par=None, fixed=None, mask=None, bound_push=1e-2, bound_frac=1e-2):
+        """solve_nlp's start() on device tensors: phase 0 interior push of X, U and the fixed bytes; 1 slacks, elastics and multipliers
+        from the first evaluation; 2 the reset of W1, W2 (include/emi355x.h: emi_ipm_start_dev)"""
+        keep = []
+        A = self._ipm_addr
+        self._ck(self.lib.emi_ipm_start_dev(self.ctx, int(phase), self._ipm_group(L.IpmPoint, point, keep), self._ipm_group(L.IpmDuals, duals, keep),
+                                            A(RES), self._ipm_bounds(bounds, keep), A(par), float(bound_push), float(bound_frac), A(fixed), A(mask)),
+                 "emi_ipm_start_dev")
+
+    # ---- lock-step interior-point solve of the whole batch on this mesh (emi_ipm_solve_shard_*) ---------------------------------
+    def ipm_solve_shard(self, X, U, bounds, options=None, dev=True):
+        """X [B][ns][M], U [B][nc][M]: the starts on entry, the final iterates on return (in place); bounds as for the ipm_* calls;
+        options: dict of emi_ipm_options_t fields (missing ones take solve_nlp's defaults).  dev=True: torch tensors on this device,
+        dev=False: contiguous float64 numpy arrays.  Returns (LamF [B][ns][M], LamC [B][np][M], results): the multipliers in the
+        kind of array given, and one dict per instance with the fields of emi_ipm_result_t."""
+        lay = self.layout
+        opt = L.IpmOptions()
+        for k, v in (options or {}).items():
+            setattr(opt, k, v)
+        if dev:
+            kw = dict(dtype=torch.float64, device=X.device)
+            LamF, LamC = torch.zeros((lay.B, lay.ns, lay.M), **kw), torch.zeros((lay.B, lay.np, lay.M), **kw)
+        else:
+            assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in (X, U))
+            LamF, LamC = np.zeros((lay.B, lay.ns, lay.M)), np.zeros((lay.B, lay.np, lay.M))
+        res = (L.IpmResult * lay.B)()
+        keep = []
+        A = self._ipm_addr
+        fn = self.lib.emi_ipm_solve_shard_dev if dev else self.lib.emi_ipm_solve_shard_host
+        self._ck(fn(self.ctx, A(X), A(U), self._ipm_bounds(bounds, keep), C.byref(opt), A(LamF), A(LamC) if lay.np else None, res), fn.__name__)
+        return LamF, LamC, [{n: getattr(r, n) for n, _ in L.IpmResult._fields_} for r in res]
+
     # ---- measurement -----------------------------------------------------------
     def timer_start(self):
         self._ck(self.lib.emi_timer_start(self.ctx), "emi_timer_start")

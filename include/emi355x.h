@@ -472,6 +472,68 @@ int emi_kkt_solve_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned char* mask
 int emi_kkt_solve_refined_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned char* mask, const double* dc_nominal, int max_steps,
                                     double* rel, int* nsolve, int* reverted, int* status);
 
+/* ---- Lock-step interior-point solve of a context's whole batch on ONE mesh ----------------------------------------------------
+ *
+ * B starting trajectories in, B solved ones out: the calls above (emi_eval_dev, emi_lagr_grad_dev, emi_hess_dev, emi_ipm_*_dev,
+ * emi_kkt_blocks_dev, emi_kkt_*_shard_dev) chained inside the library, one round = one iteration of every instance that is
+ * still active, with the per-instance control (convergence test, penalty escalation, barrier update, merit weight, Armijo
+ * backtracking) as kernels of one thread per instance (csrc/emi_ipm_solve.hip, the rules in csrc/emi_ipm_control.hpp).  Per round
+ * a few bytes per instance reach the host: who is active, the factorisation's info / exact / status, who is still searching.
+ * The rules are those of ETOL::mi355x::solve_nlp (host/emi_nlp.cpp) without second-order correction, residual-based acceptance
+ * and crawl rule, inertia search, stagnation rule, variable and Jacobian-based scaling, warm-start multipliers, coupling rows and
+ * time limit.
+ *   dX[B][ns][M], dU[B][nc][M]   the start on entry (pushed into the bounds by the call), the final iterate on return
+ *   dLamF[B][ns][M]              out: defect multipliers
+ *   dLamC[B][np][M]              out: path-row multipliers in the caller's units (cscale Y), the Lagrangian of emi_hess_*: the
+ *                                outputs go straight into emi_kkt_certificate_dev.  May be NULL without path rows.
+ *   bd                           bounds as for emi_ipm_*: zl, zu [nsets][nv][M] (device in the _dev form), cl, cu, cscale host
+ *   opt                          zero-initialised fields take solve_nlp's defaults: tol 1e-8, mu_init 0.1, bound_push and
+ *                                bound_frac 1e-2, rho_init 10, acceptable_factor 100, max_iter 200, acceptable_iter 10,
+ *                                max_futile_escalations 3
+ *   results[B]                   host: status (EMI_IPM_*), iterations, evaluations, factorisations, steps of the convexified
+ *                                matrix, and cost, KKT error at mu = 0, largest residual, largest elastic, mu, rho at the end
+ * Path-row partials: the list of emi_kkt_blocks_rows, or the default.  An instance that has ended is masked out of every call
+ * that takes a mask and keeps every bit of its iterate; the call returns when none is active.  Two identical calls give the
+ * same bits.  The iterate's slacks, multipliers, step, elimination arrays, trial point, H, Q, eigenpair lists, G and the state
+ * records are device arrays of the context, created at the first call, grown when mesh or batch grow, freed with the context.
+ * Returns EMI_OK when the run ended normally whatever the instances' statuses; EMI_ERR_UNSUPPORTED: f32 context, delays set,
+ * ns + nc > 16, LU method;  EMI_ERR_STATE: mesh, model or batch not set;  EMI_ERR_ARG: a NULL argument that is not optional.
+ * The _host form takes host arrays (zl, zu included), copies in, runs the _dev form, copies out and synchronises.            */
+enum { EMI_IPM_CONVERGED = 0, EMI_IPM_ACCEPTABLE = 1, EMI_IPM_MAX_ITER = 2, EMI_IPM_LINE_SEARCH = 3, EMI_IPM_INFEASIBLE = 4,
+       EMI_IPM_FACTOR = 5 /* still singular after the dual ladder, or the instance left the Schur path */, EMI_IPM_NOT_FINITE = 6 };
+typedef struct emi_ipm_options {
+  double tol, mu_init, bound_push, bound_frac, rho_init, acceptable_factor;
+  int max_iter, acceptable_iter, max_futile_escalations;
+} emi_ipm_options_t;
+typedef struct emi_ipm_result {
+  int status, iterations, evaluations, factorisations, reflected_steps;
+  double cost, kkt_error, constr_viol, emax, mu, rho;
+} emi_ipm_result_t;
+int emi_ipm_solve_shard_dev(emi_ctx_t ctx, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt,
+                            void* dLamF, void* dLamC, emi_ipm_result_t* results);
+int emi_ipm_solve_shard_host(emi_ctx_t ctx, double* X, double* U, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt,
+                             double* LamF, double* LamC, emi_ipm_result_t* results);
+/* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
+ * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
+ * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
+ * test at mu = 0 and every firing of the barrier update.  par is read for rho only.  Same reduction order, same statuses.     */
+/* The array part of solve_nlp's start(), as the lock-step solve runs it (device arrays; asynchronous on the context's stream):
+ *   phase 0  X, U pushed inside their bounds by bound_push max(1, |bound|), at most bound_frac of the interval (a fixed variable is
+ *            set to its bound); dFixed[B][nv][M] bytes = 1 where fixed; LamF = 0.          Reads pt (X, U), du (LamF), bd.
+ *   phase 1  after the first evaluation: S = cscale RES[ns+j] pushed inside its row bounds, gap = c - S, E1 = max(gap, 0) + e,
+ *            E2 = max(-gap, 0) + e with e = bound_push max(1, |gap|); Y = 0; ZL, ZU, VL, VU = 1 where the bound exists (0 at
+ *            fixed variables); W1 = W2 = max(1e-8, rho).                                   Reads dRES, bd, dPar.
+ *   phase 2  W1 = max(1e-8, rho - Y), W2 = max(1e-8, rho + Y) at the instances of dMask (bytes, NULL: all): the reset of the
+ *            elastic multipliers after a penalty escalation.
+ * Exact operations or single rounded ones, never fused: the arrays are the formulas' bits.  Statuses as the emi_ipm_* calls.  */
+int emi_ipm_start_dev(emi_ctx_t ctx, int phase, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES,
+                      const emi_ipm_bounds_t* bd, const void* dPar, double bound_push, double bound_frac, void* dFixed,
+                      const void* dMask);
+int emi_ipm_error_parts_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const void* dRES, const void* dG,
+                            const emi_ipm_bounds_t* bd, const void* dPar, void* dOut);
+int emi_ipm_error_parts_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* G,
+                             const emi_ipm_bounds_t* bd, const double* par, double* out);
+
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,
  * for reports, tools and tests (csrc/emi_api.hip: plan_pass, plan_piece).           */
