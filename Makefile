@@ -55,6 +55,8 @@ $(LIBDIR)/emi_ipm.o: $(CSRC)/emi_ipm.hip $(CSRC_HDR) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(LIBDIR)/emi_ipm_solve.o: $(CSRC)/emi_ipm_solve.hip $(CSRC_HDR) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(LIBDIR)/emi_ipm_ladder.o: $(CSRC)/emi_ipm_ladder.hip $(CSRC_HDR) | $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(LIBDIR)/emi_rtc_sources.inc: $(RTC_HDR) tools/embed_src.py | $(LIBDIR)
 	python3 tools/embed_src.py $@ $(RTC_HDR)
 $(LIBDIR)/emi_rtc.o: $(CSRC)/emi_rtc.hip $(LIBDIR)/emi_rtc_sources.inc $(CSRC_HDR) | $(LIBDIR)
@@ -65,7 +67,7 @@ $(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
 $(LIBDIR)/emi_comm.o: $(CSRC)/emi_comm.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
-$(LIBDIR)/libemi355x.so: $(LIBDIR)/emi_kernels.o $(LIBDIR)/emi_symdefect.o $(LIBDIR)/emi_defect_f32.o $(LIBDIR)/emi_api.o $(LIBDIR)/emi_rtc.o $(LIBDIR)/emi_kkt.o $(LIBDIR)/emi_adjoint.o $(LIBDIR)/emi_kkt_blocks.o $(LIBDIR)/emi_ipm.o $(LIBDIR)/emi_ipm_solve.o $(LIBDIR)/emi_host.o $(LIBDIR)/emi_comm.o
+$(LIBDIR)/libemi355x.so: $(LIBDIR)/emi_kernels.o $(LIBDIR)/emi_symdefect.o $(LIBDIR)/emi_defect_f32.o $(LIBDIR)/emi_api.o $(LIBDIR)/emi_rtc.o $(LIBDIR)/emi_kkt.o $(LIBDIR)/emi_adjoint.o $(LIBDIR)/emi_kkt_blocks.o $(LIBDIR)/emi_ipm.o $(LIBDIR)/emi_ipm_solve.o $(LIBDIR)/emi_ipm_ladder.o $(LIBDIR)/emi_host.o $(LIBDIR)/emi_comm.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
 
 HOST_SRC := $(HOST)/TrajectoryOptimizer.cpp $(HOST)/eMI355X.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_trace.cpp
@@ -83,7 +85,7 @@ $(LIBDIR)/etol_mi355x_example1: etol_amd/examples/etol_mi355x_example1.cpp $(LIB
 $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $(LIBDIR)/libetol_mi355x.so
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
-HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp
+HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp
 tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR) $(CSRC)/emi_ipm_control.hpp
 	$(CXX) $(CXXFLAGS) -I$(HOST) -I$(CSRC) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'

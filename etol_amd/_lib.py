@@ -74,6 +74,11 @@ class IpmResult(C.Structure):
                [(n, C.c_double) for n in ("cost", "kkt_error", "constr_viol", "emax", "mu", "rho")]
 
 
+class IpmRung(C.Structure):
+    """emi_ipm_rung_t: one rung of emi_ipm_solve_ladder_*"""
+    _fields_ = [("M", C.c_int), ("bd", IpmBounds), ("recs", _D), ("opt", IpmOptions), ("repair", C.c_int)]
+
+
 IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
 
 _PT, _DU, _ST, _EL, _BD = (C.POINTER(t) for t in (IpmPoint, IpmDuals, IpmStep, IpmElim, IpmBounds))
@@ -122,6 +127,11 @@ SYMBOLS = {
     "emi_ipm_error_parts_host": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
     "emi_ipm_solve_shard_dev": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
     "emi_ipm_solve_shard_host": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
+    "emi_prolong_matrix": (C.c_int, [C.c_int, _D, _D, C.c_int, _D, _D]),
+    "emi_prolong_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    "emi_repair_guess_dev": (C.c_int, [_P, _P]),
+    "emi_ipm_solve_ladder_dev": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.POINTER(IpmResult)]),
+    "emi_ipm_solve_ladder_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.POINTER(IpmResult)]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

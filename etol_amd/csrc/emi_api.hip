@@ -141,6 +141,8 @@ struct emi_ctx_s {
     emi::DeviceArray<double> ipm_crow, ipm_part;
     std::vector<DevBuf> ipm_stage;
     emi::IpmSolveWs* ipm_solve = nullptr;   // device arrays of the lock-step driver (emi_ipm_solve_shard_*), created at its first call
+    emi::IpmLadderWs* ipm_ladder = nullptr; // ... and of the mesh ladder over it (emi_ipm_solve_ladder_*)
+    bool path_has_track = false;            // the record table holds a row of kind EMI_PATH_TRACK
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;
     int profile = 0;          // emi_profile_enable level (0 off)
@@ -165,6 +167,7 @@ struct emi_ctx_s {
         emi::kkt_destroy(kkt);
         for (emi::KktWorkspace* w : kkt_shard) emi::kkt_destroy(w);
         emi::ipm_solve_destroy(ipm_solve);
+        emi::ipm_ladder_destroy(ipm_ladder);
     }
 };
 
@@ -1110,6 +1113,7 @@ static void model_in_force(emi_ctx_t c, int model, int ns, int nc, int npath, co
     for (int i = 0; i < nparams; ++i) c->params[i] = params[i];
     c->np = 0;
     c->path_sets = 0;
+    c->path_has_track = false;
 }
 
 int emi_set_model(emi_ctx_t c, int model, const double* params, int nparams, int maximize) {
@@ -1220,13 +1224,16 @@ int emi_set_path(emi_ctx_t c, int np, int nsets, const double* recs, int px_stat
     if (px_state < 0 || px_state >= c->ns || py_state < 0 || py_state >= c->ns || px_state == py_state)
         return fail(c, EMI_ERR_ARG, "emi_set_path: state indices (%d,%d) out of range", px_state, py_state);
     HIP_TRY(c, hipSetDevice(c->device));
+    bool has_track = false;
     for (size_t i = 0; i < (size_t)np * nsets; ++i) {
         const int kind = (int)recs[i * EMI_PATH_REC];
         if (kind != EMI_PATH_ELLIPSE && kind != EMI_PATH_DISC && kind != EMI_PATH_TRACK)
             return fail(c, EMI_ERR_ARG, "emi_set_path: record %zu has unknown kind %d", i, kind);
+        has_track = has_track || kind == EMI_PATH_TRACK;
     }
     int st = upload_real(c, c->d_path, recs, (size_t)np * nsets * EMI_PATH_REC);
     if (st) return st;
+    c->path_has_track = has_track;
     c->np = np;
     c->path_sets = np > 0 ? nsets : 0;
     c->px = px_state;
@@ -2631,6 +2638,91 @@ int emi_ipm_solve_shard_host(emi_ctx_t c, double* X, double* U, const emi_ipm_bo
     void *dLF = s.place(LamF, z.X, false, true), *dLC = s.place(LamC, z.row, false, true);
     const emi_ipm_bounds_t db = stage_bounds(s, z, bd);
     IPM_HOST_END(emi_ipm_solve_shard_dev(c, dX, dU, bd ? &db : nullptr, opt, dLF, dLC, results));
+}
+
+// ---- the mesh ladder over the lock-step solve (kernels and driver: emi_ipm_ladder.hip) ---------------------------------------------
+int emi_prolong_dev(emi_ctx_t c, int Mc, int Mf, const void* dPT, const void* dVc, int R, void* dVf) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_prolong_dev: f64 contexts only");
+    if (Mc < 2 || Mf < 2 || R < 0 || !dPT || (R > 0 && (!dVc || !dVf))) return fail(c, EMI_ERR_ARG, "emi_prolong_dev: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, emi::launch_prolong((const double*)dPT, (const double*)dVc, (double*)dVf, Mc, Mf, R, c->stream));
+    return EMI_OK;
+}
+
+int emi_repair_guess_dev(emi_ctx_t c, void* dX) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_repair_guess_dev: f64 contexts only");
+    EMI_TRY(ready(c));
+    if (!dX) return fail(c, EMI_ERR_ARG, "emi_repair_guess_dev: null argument");
+    if (c->B > 65535) return fail(c, EMI_ERR_UNSUPPORTED, "emi_repair_guess_dev: up to 65535 instances");
+    if (c->np > 0 && c->path_has_track && c->ntracks <= 0)
+        return fail(c, EMI_ERR_STATE, "emi_repair_guess_dev: the table has rows of kind EMI_PATH_TRACK: emi_set_tracks must follow emi_set_mesh");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const emi::RepairArgs a{(double*)dX, (const double*)c->d_path.p, (const double*)c->d_trkx.p, (const double*)c->d_trky.p, c->B, c->ns, c->M,
+                            c->np, c->path_sets, c->px, c->py, c->ntracks, c->track_sets};
+    HIP_TRY(c, emi::launch_repair_guess(a, c->stream));
+    return EMI_OK;
+}
+
+namespace {
+
+// what the ladder refuses before it touches the context (the mesh need not be set: the call sets it)
+int ladder_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t* rungs) {
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: f64 contexts only", what);
+    if (c->model < 0 || c->B <= 0) return fail(c, EMI_ERR_STATE, "%s: model and batch must be set", what);
+    if (c->nch > 0) return fail(c, EMI_ERR_UNSUPPORTED, "%s: contexts with delays are not taken", what);
+    if (c->ns + c->nc > 16) return fail(c, EMI_ERR_UNSUPPORTED, "%s: up to 16 variables per node (this model has %d)", what, c->ns + c->nc);
+    if (c->kkt_method != 1) return fail(c, EMI_ERR_UNSUPPORTED, "%s: the context is set to the LU method (\"kkt_method\" 0)", what);
+    if (nrungs < 1 || !rungs) return fail(c, EMI_ERR_ARG, "%s: no rungs", what);
+    bool track = c->np > 0 && c->path_has_track;
+    for (int r = 0; r < nrungs; ++r) {
+        if (rungs[r].M < 2) return fail(c, EMI_ERR_ARG, "%s: rung %d has %d nodes", what, r, rungs[r].M);
+        if (!rungs[r].bd.zl || !rungs[r].bd.zu) return fail(c, EMI_ERR_ARG, "%s: rung %d has no bounds", what, r);
+        if (!rungs[r].recs) continue;
+        if (c->np <= 0) return fail(c, EMI_ERR_ARG, "%s: rung %d brings a record table and the context has none", what, r);
+        for (size_t i = 0; i < (size_t)c->np * c->path_sets; ++i) track = track || (int)rungs[r].recs[i * EMI_PATH_REC] == EMI_PATH_TRACK;
+    }
+    if (track)
+        return fail(c, EMI_ERR_UNSUPPORTED, "%s: rows of kind EMI_PATH_TRACK have their centres per mesh, which this call cannot supply", what);
+    return EMI_OK;
+}
+
+}  // namespace
+
+int emi_ipm_solve_ladder_dev(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0,
+                             void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ladder_check(c, "emi_ipm_solve_ladder_dev", nrungs, rungs));
+    const int np = np_total(c);
+    if (!dX0 || !dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np > 0 && !dLamC) || !results)
+        return fail(c, EMI_ERR_ARG, "emi_ipm_solve_ladder_dev: null argument");
+    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_ipm_solve_ladder_dev: tf must exceed t0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const emi::IpmLadderDims d{c->B, c->ns, c->nc, np, c->np, c->path_sets, c->px, c->py, c->stream};
+    std::string err;
+    const int st = emi::ipm_solve_ladder(c, &c->ipm_ladder, d, nrungs, rungs, t0, tf, dX0, dU0, dX, dU, dLamF, dLamC, results, &err);
+    if (st && !err.empty()) c->err = err;
+    return st;
+}
+
+int emi_ipm_solve_ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const double* X0, const double* U0,
+                              double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ladder_check(c, "emi_ipm_solve_ladder_host", nrungs, rungs));
+    HIP_TRY(c, hipSetDevice(c->device));
+    IpmStager s(c);
+    const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, ML = (size_t)rungs[nrungs - 1].M;
+    const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
+    void *dX = s.place(X, B * c->ns * ML * 8, false, true), *dU = s.place(U, B * c->nc * ML * 8, false, true);
+    void *dLF = s.place(LamF, B * c->ns * ML * 8, false, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * ML * 8, false, true);
+    std::vector<emi_ipm_rung_t> dr(rungs, rungs + nrungs);
+    for (emi_ipm_rung_t& g : dr) {
+        const size_t bytes = (size_t)std::max(g.bd.nsets, 0) * nv * (size_t)g.M * 8;
+        g.bd.zl = s.place(g.bd.zl, bytes, true, false);
+        g.bd.zu = s.place(g.bd.zu, bytes, true, false);
+    }
+    IPM_HOST_END(emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
 }
 
 int emi_timer_start(emi_ctx_t c) {

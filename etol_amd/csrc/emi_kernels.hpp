@@ -216,4 +216,21 @@ int ctx_shard_holds(emi_ctx_t c, int b);
 void ctx_shard_forget_ladders(emi_ctx_t c);
 int ctx_ipm_launch(emi_ctx_t c, int what, const emi_ipm_bounds_t* bd, const void* dPar, IpmArgs& a);
 
+// the mesh ladder of one context's batch (emi_ipm_ladder.hip): prolongation Vf[R][Mf] = Vc[R][Mc] P^T from PT[Mc][Mf], the repair
+// of the position states X[B][ns][M] against the record table (recs [path_sets][np][EMI_PATH_REC], tracks [track_sets][ntracks][M]),
+// and the driver over the rungs, whose device arrays live in an IpmLadderWs the context owns
+hipError_t launch_prolong(const double* PT, const double* Vc, double* Vf, int Mc, int Mf, int R, hipStream_t s);
+struct RepairArgs {
+    double* X;
+    const double *recs, *trkx, *trky;
+    int B, ns, M, np, path_sets, px, py, ntracks, track_sets;
+};
+hipError_t launch_repair_guess(const RepairArgs& a, hipStream_t s);
+struct IpmLadderWs;
+void ipm_ladder_destroy(IpmLadderWs* w);
+struct IpmLadderDims { int B, ns, nc, np, np_table, path_sets, px, py; hipStream_t stream; };     // np: table rows and traced rows
+int ipm_solve_ladder(emi_ctx_t c, IpmLadderWs** pw, const IpmLadderDims& d, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf,
+                     const void* dX0, const void* dU0, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results,
+                     std::string* err);
+
 }  // namespace emi

@@ -565,6 +565,78 @@ class Evaluator:
         self._ck(fn(self.ctx, A(X), A(U), self._ipm_bounds(bounds, keep), C.byref(opt), A(LamF), A(LamC) if lay.np else None, res), fn.__name__)
         return LamF, LamC, [{n: getattr(r, n) for n, _ in L.IpmResult._fields_} for r in res]
 
+    # ---- the mesh ladder over the lock-step solve (emi_prolong_*, emi_repair_guess_dev, emi_ipm_solve_ladder_*) -----------------
+    @staticmethod
+    def prolong_matrix(Mc, Mf, coarse=None, fine=None):
+        """P [Mf][Mc]: the Lagrange basis of the coarse LGL nodes at the fine ones (host, emi_prolong_matrix); coarse / fine: (tau, w,
+        ..) of other node sets than lgl(Mc) / lgl(Mf)"""
+        lib = L.load()
+        tc, wc = (np.ascontiguousarray(a, dtype=np.float64) for a in (coarse if coarse is not None else lgl(Mc))[:2])
+        tf_ = np.ascontiguousarray((fine if fine is not None else lgl(Mf))[0], dtype=np.float64)
+        P = np.empty((Mf, Mc))
+        L.check(lib.emi_prolong_matrix(int(Mc), _dp(tc), _dp(wc), int(Mf), _dp(tf_), _dp(P)), what="emi_prolong_matrix")
+        return P
+
+    def prolong(self, PT, Vc, Vf=None):
+        """Vf [.., Mf] = Vc [.., Mc] P^T on the device from PT [Mc][Mf] = P transposed (torch tensors, float64); asynchronous"""
+        Mc, Mf = PT.shape
+        assert Vc.shape[-1] == Mc and PT.is_contiguous() and Vc.is_contiguous()
+        R = Vc.numel() // Mc
+        if Vf is None:
+            Vf = torch.empty(tuple(Vc.shape[:-1]) + (Mf,), dtype=torch.float64, device=Vc.device)
+        assert Vf.is_contiguous() and Vf.numel() == R * Mf
+        self._ck(self.lib.emi_prolong_dev(self.ctx, int(Mc), int(Mf), C.c_void_p(PT.data_ptr()), C.c_void_p(Vc.data_ptr()), int(R),
+                                          C.c_void_p(Vf.data_ptr())), "emi_prolong_dev")
+        return Vf
+
+    def repair_guess(self, X):
+        """interior nodes of X [B][ns][M] (device tensor, in place) inside a keep-out of the record table moved out of it; asynchronous"""
+        self._ck(self.lib.emi_repair_guess_dev(self.ctx, C.c_void_p(X.data_ptr()) if X is not None else None), "emi_repair_guess_dev")
+
+    def ipm_solve_ladder(self, rungs, t0, tf, X0, U0, dev=True):
+        """rungs: list of dict M, bounds (as for the ipm_* calls, at this M), and optionally recs (record table of emi_set_path's
+        shape), options (dict of emi_ipm_options_t fields), repair.  X0 [B][ns][M_0], U0 [B][nc][M_0] are read only.  dev=True: torch
+        tensors on this device; dev=False: contiguous float64 numpy arrays.  Returns (X, U, LamF, LamC, results[rung][b]) on the last
+        rung's mesh, which is the context's mesh afterwards."""
+        lay = self.layout
+        B, ns, nc, npth, Ml = lay.B, lay.ns, lay.nc, lay.np, int(rungs[-1]["M"]) if rungs else 0
+        keep = []
+        arr = (L.IpmRung * max(1, len(rungs)))()
+        for g, r in zip(arr, rungs):
+            g.M = int(r["M"])
+            bd = r["bounds"]
+            g.bd.zl, g.bd.zu, g.bd.nsets = self._ipm_addr(bd.get("zl")), self._ipm_addr(bd.get("zu")), int(bd["zl"].shape[0])
+            for f in ("cl", "cu", "cscale"):
+                a = bd.get(f)
+                if a is not None and len(a):
+                    a = np.ascontiguousarray(a, dtype=np.float64)
+                    keep.append(a)
+                    setattr(g.bd, f, _dp(a))
+            if r.get("recs") is not None:
+                a = np.ascontiguousarray(r["recs"], dtype=np.float64)
+                keep.append(a)
+                g.recs = _dp(a)
+            for k, v in (r.get("options") or {}).items():
+                setattr(g.opt, k, v)
+            g.repair = int(bool(r.get("repair")))
+        if dev:
+            kw = dict(dtype=torch.float64, device=X0.device)
+            new = lambda *s: torch.zeros(s, **kw)
+        else:
+            assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in (X0, U0))
+            new = lambda *s: np.zeros(s)
+        X, U, LamF, LamC = new(B, ns, Ml), new(B, nc, Ml), new(B, ns, Ml), new(B, npth, Ml)
+        res = (L.IpmResult * max(1, len(rungs) * B))()
+        A = self._ipm_addr
+        fn = self.lib.emi_ipm_solve_ladder_dev if dev else self.lib.emi_ipm_solve_ladder_host
+        st = fn(self.ctx, len(rungs), arr, float(t0), float(tf), A(X0), A(U0), A(X), A(U), A(LamF), A(LamC) if npth else None, res)
+        self._changed()
+        self._ck(st, fn.__name__)
+        self.tau, self.w, self.D = lgl(Ml)
+        self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
+        fields = [n for n, _ in L.IpmResult._fields_]
+        return X, U, LamF, LamC, [[{n: getattr(res[r * B + b], n) for n in fields} for b in range(B)] for r in range(len(rungs))]
+
     # ---- measurement -----------------------------------------------------------
     def timer_start(self):
         self._ck(self.lib.emi_timer_start(self.ctx), "emi_timer_start")

@@ -513,6 +513,58 @@ int emi_ipm_solve_shard_dev(emi_ctx_t ctx, void* dX, void* dU, const emi_ipm_bou
                             void* dLamF, void* dLamC, emi_ipm_result_t* results);
 int emi_ipm_solve_shard_host(emi_ctx_t ctx, double* X, double* U, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt,
                              double* LamF, double* LamC, emi_ipm_result_t* results);
+/* ---- Lock-step solve over a MESH LADDER: every instance on the same rung at the same time --------------------------------------
+ *
+ * B coarse starts in, B solved trajectories on the finest mesh and their multipliers out; between the rungs the trajectories are
+ * interpolated by a kernel and never visit the host (csrc/emi_ipm_ladder.hip).
+ *
+ * emi_prolong_matrix (host, no device needed): P[Mf][Mc], row q = the Lagrange basis polynomials of the coarse LGL nodes
+ * (tau_c, w_c) at tau_f[q], in the barycentric second form with the weights (-1)^j sqrt(w_j); where tau_f[q] == tau_c[j] exactly
+ * the row is the unit vector e_j.  Any Mc >= 2, Mf >= 2.
+ * emi_prolong_dev: Vf[r][q] = sum_j P[q][j] Vc[r][j] for R rows, from dPT[Mc][Mf] = P transposed (device).  Asynchronous on the
+ * context's stream; needs no mesh, model or batch.  Fused multiply-adds in ascending j, one writer per output: a unit row of P
+ * copies the coarse value (a -0 arrives as +0), a row's bits do not depend on R or on the other rows, two calls give the same
+ * bits.  f64 contexts only (EMI_ERR_UNSUPPORTED).
+ * emi_repair_guess_dev: ETOL::mi355x::repair_guess on dX[B][ns][M] for the context's record table (shared or per instance) on the
+ * context's mesh: an interior node whose position (px, py) lies inside a keep-out (quadratic form below 1.025) is moved out
+ * radially to 1.05, from a dead centre (form below 1e-12) along the minor axis; up to 50 sweeps over the table rows in row
+ * order, until a sweep moves nothing.  End nodes are never touched; rows of kind EMI_PATH_TRACK take their centres from the
+ * arrays of emi_set_tracks (EMI_ERR_STATE without them); traced rows are skipped.  Single rounded operations, never fused: the
+ * bits are the formulas' bits.  Asynchronous.  EMI_ERR_UNSUPPORTED: f32 context;  EMI_ERR_STATE: mesh, model or batch not set.
+ *
+ * emi_ipm_solve_ladder_dev: per rung r = 0 .. nrungs-1
+ *   1. emi_lgl and emi_set_mesh(M_r, .., t0, tf);
+ *   2. emi_set_path with the rung's recs where given (np, nsets, px, py as the context has them: a caller inflates its
+ *      keep-outs per rung this way); after the call the context holds what the last rung set;
+ *   3. from the second rung on, X and U prolonged from the previous rung's final iterate (emi_prolong_dev);
+ *   4. emi_repair_guess_dev where the rung asks for it;
+ *   5. emi_ipm_solve_shard_dev on this rung with the rung's bounds and options (its start pushes the prolonged point inside the
+ *      bounds).
+ * Multipliers are not carried: LamF = 0 at every start.  Every instance climbs whatever its status on a rung; results[r][b] says
+ * what happened (a non-finite iterate ends EMI_IPM_NOT_FINITE on the next rung).  dX0 [B][ns][M_0] and dU0 [B][nc][M_0] are only
+ * read; dX, dU, dLamF, dLamC are sized for the LAST rung.  The interpolation matrix and the iterates of the rungs below the last
+ * are device arrays of the context (grown as needed, freed with it); per rung pair Mc Mf doubles go up, nothing of a trajectory's
+ * size comes down.  On return the context is on the last rung's mesh.  A ladder of one rung runs the launches of
+ * emi_ipm_solve_shard_dev on a copy of the start.
+ * EMI_ERR_UNSUPPORTED: whatever emi_ipm_solve_shard_dev refuses, and a record table (the context's or a rung's) with a row of
+ * kind EMI_PATH_TRACK: the centres of such rows are per mesh and this call has no way to supply them.  EMI_ERR_ARG: nrungs < 1,
+ * a rung with M < 2, a NULL that is not optional, recs given while the context has no table.  EMI_ERR_STATE: model or batch
+ * not set (whatever mesh the context is on is replaced).  The _host form takes host arrays (every rung's zl, zu included) and
+ * synchronises.                                                                                                                 */
+typedef struct emi_ipm_rung {
+  int M;                       /* LGL nodes of this rung */
+  emi_ipm_bounds_t bd;         /* bounds at this M (zl, zu [nsets][nv][M]) */
+  const double* recs;          /* host, shape of emi_set_path's table; NULL: keep the context's */
+  emi_ipm_options_t opt;       /* zero fields: the defaults of emi_ipm_solve_shard_dev (warm mu_init / bound_push go here) */
+  int repair;                  /* non-zero: emi_repair_guess_dev on the prolonged states before the solve */
+} emi_ipm_rung_t;
+int emi_prolong_matrix(int Mc, const double* tau_c, const double* w_c, int Mf, const double* tau_f, double* P);
+int emi_prolong_dev(emi_ctx_t ctx, int Mc, int Mf, const void* dPT, const void* dVc, int R, void* dVf);
+int emi_repair_guess_dev(emi_ctx_t ctx, void* dX);
+int emi_ipm_solve_ladder_dev(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0,
+                             const void* dU0, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
+int emi_ipm_solve_ladder_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const double* X0,
+                              const double* U0, double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results);
 /* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
  * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
  * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
