@@ -37,25 +37,7 @@ CSRC_HDR  := $(wildcard $(CSRC)/*.hpp) include/emi355x.h
 # headers a model program compiled at run time (hiprtc, emi_rtc.hip) includes: embedded as text
 RTC_HDR   := $(CSRC)/emi_models.hpp $(CSRC)/emi_args.hpp $(CSRC)/emi_node_kernels.hpp $(CSRC)/emi_symdefect_kernels.hpp
 
-$(LIBDIR)/emi_kernels.o: $(CSRC)/emi_kernels.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_symdefect.o: $(CSRC)/emi_symdefect.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_defect_f32.o: $(CSRC)/emi_defect_f32.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_api.o: $(CSRC)/emi_api.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_kkt.o: $(CSRC)/emi_kkt.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_adjoint.o: $(CSRC)/emi_adjoint.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_kkt_blocks.o: $(CSRC)/emi_kkt_blocks.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_ipm.o: $(CSRC)/emi_ipm.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_ipm_solve.o: $(CSRC)/emi_ipm_solve.hip $(CSRC_HDR) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(LIBDIR)/emi_ipm_ladder.o: $(CSRC)/emi_ipm_ladder.hip $(CSRC_HDR) | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC_HDR) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(LIBDIR)/emi_rtc_sources.inc: $(RTC_HDR) tools/embed_src.py | $(LIBDIR)
 	python3 tools/embed_src.py $@ $(RTC_HDR)
@@ -67,7 +49,9 @@ $(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
 $(LIBDIR)/emi_comm.o: $(CSRC)/emi_comm.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
-$(LIBDIR)/libemi355x.so: $(LIBDIR)/emi_kernels.o $(LIBDIR)/emi_symdefect.o $(LIBDIR)/emi_defect_f32.o $(LIBDIR)/emi_api.o $(LIBDIR)/emi_rtc.o $(LIBDIR)/emi_kkt.o $(LIBDIR)/emi_adjoint.o $(LIBDIR)/emi_kkt_blocks.o $(LIBDIR)/emi_ipm.o $(LIBDIR)/emi_ipm_solve.o $(LIBDIR)/emi_ipm_ladder.o $(LIBDIR)/emi_host.o $(LIBDIR)/emi_comm.o
+LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_rtc emi_kkt emi_adjoint \
+           emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_host emi_comm
+$(LIBDIR)/libemi355x.so: $(LIB_OBJ:%=$(LIBDIR)/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
 
 HOST_SRC := $(HOST)/TrajectoryOptimizer.cpp $(HOST)/eMI355X.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_trace.cpp

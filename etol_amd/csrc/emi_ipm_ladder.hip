@@ -14,11 +14,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <string>
 #include <vector>
 
-#include "emi_device_array.hpp"
-#include "emi_kernels.hpp"
+#include "emi_ctx.hpp"
 
 namespace emi {
 namespace {
@@ -117,27 +115,15 @@ struct IpmLadderWs {
 
 void ipm_ladder_destroy(IpmLadderWs* w) { delete w; }
 
-#define L_HIP(call)                                                                          \
-    do {                                                                                     \
-        const hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                              \
-            *err = std::string("emi_ipm_solve_ladder_dev: " #call " failed: ") + hipGetErrorString(e_); \
-            return EMI_ERR_HIP;                                                              \
-        }                                                                                    \
-    } while (0)
-#define L_TRY(call)                \
-    do {                           \
-        const int st_ = (call);    \
-        if (st_) return st_;       \
-    } while (0)
+#define L_HIP(call) HIP_TRY_AS(c, "emi_ipm_solve_ladder_dev", call)
+#define L_TRY EMI_TRY
 
-int ipm_solve_ladder(emi_ctx_t c, IpmLadderWs** pw, const IpmLadderDims& d, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf,
-                     const void* dX0, const void* dU0, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results,
-                     std::string* err) {
-    if (!*pw) *pw = new IpmLadderWs();
-    IpmLadderWs& w = **pw;
-    const size_t B = (size_t)d.B;
-    const hipStream_t s = d.stream;
+int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
+                     void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results) {
+    if (!c->ipm_ladder) c->ipm_ladder = new IpmLadderWs();
+    IpmLadderWs& w = *c->ipm_ladder;
+    const size_t B = (size_t)c->B, ns = (size_t)c->ns, nc = (size_t)c->nc, np = (size_t)emi_api::np_total(c);
+    const hipStream_t s = c->stream;
     std::vector<double> tau, wt, D, tau_c, w_c, P, PT;
     const void *pX = nullptr, *pU = nullptr;        // the previous rung's final iterate
     for (int r = 0; r < nrungs; ++r) {
@@ -147,18 +133,18 @@ int ipm_solve_ladder(emi_ctx_t c, IpmLadderWs** pw, const IpmLadderDims& d, int 
         tau.resize(M); wt.resize(M); D.resize((size_t)M * M);
         L_TRY(emi_lgl(M, tau.data(), wt.data(), D.data()));
         L_TRY(emi_set_mesh(c, M, tau.data(), wt.data(), D.data(), t0, tf));
-        if (g.recs) L_TRY(emi_set_path(c, d.np_table, d.path_sets, g.recs, d.px, d.py));
+        if (g.recs) L_TRY(emi_set_path(c, c->np, c->path_sets, g.recs, c->px, c->py));
         // where this rung's iterate lives: the caller's arrays on the last rung, else one of the two sets (not the previous rung's)
         void *cX = dX, *cU = dU, *cLF = dLamF, *cLC = dLamC;
         if (!last) {
             L_HIP(hipStreamSynchronize(s));             // a launch in flight may still use an array that has to move
-            L_HIP(w.X[r & 1].reserve(B * d.ns * M)); L_HIP(w.U[r & 1].reserve(B * d.nc * M));
-            L_HIP(w.LamF.reserve(B * d.ns * M)); L_HIP(w.LamC.reserve(B * d.np * M));
+            L_HIP(w.X[r & 1].reserve(B * ns * M)); L_HIP(w.U[r & 1].reserve(B * nc * M));
+            L_HIP(w.LamF.reserve(B * ns * M)); L_HIP(w.LamC.reserve(B * np * M));
             cX = w.X[r & 1].p; cU = w.U[r & 1].p; cLF = w.LamF.p; cLC = w.LamC.p;
         }
         if (r == 0) {
-            L_HIP(hipMemcpyAsync(cX, dX0, B * d.ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-            if (d.nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, B * d.nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+            L_HIP(hipMemcpyAsync(cX, dX0, B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+            if (nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, B * nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
         } else {
             P.resize((size_t)M * Mc); PT.resize((size_t)M * Mc);
             L_TRY(emi_prolong_matrix(Mc, tau_c.data(), w_c.data(), M, tau.data(), P.data()));
@@ -168,8 +154,8 @@ int ipm_solve_ladder(emi_ctx_t c, IpmLadderWs** pw, const IpmLadderDims& d, int 
             L_HIP(w.PT.reserve(PT.size()));
             L_HIP(hipMemcpyAsync(w.PT.p, PT.data(), PT.size() * sizeof(double), hipMemcpyHostToDevice, s));
             L_HIP(hipStreamSynchronize(s));             // (PT is rewritten for the next pair)
-            L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pX, d.B * d.ns, cX));
-            if (d.nc > 0) L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pU, d.B * d.nc, cU));
+            L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pX, c->B * c->ns, cX));
+            if (nc > 0) L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pU, c->B * c->nc, cU));
         }
         if (g.repair) L_TRY(emi_repair_guess_dev(c, cX));
         L_TRY(emi_ipm_solve_shard_dev(c, cX, cU, &g.bd, &g.opt, cLF, cLC, results + (size_t)r * B));

@@ -36,12 +36,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
 
-#include "emi_device_array.hpp"
+#include "emi_ctx.hpp"
 #include "emi_ipm_control.hpp"
-#include "emi_kernels.hpp"
 
 namespace emi {
 namespace {
@@ -107,30 +105,19 @@ struct IpmSolveWs {
 
 void ipm_solve_destroy(IpmSolveWs* w) { delete w; }
 
-#define S_HIP(call)                                                                        \
-    do {                                                                                   \
-        const hipError_t e_ = (call);                                                      \
-        if (e_ != hipSuccess) {                                                            \
-            *err = std::string("emi_ipm_solve_shard_dev: " #call " failed: ") + hipGetErrorString(e_); \
-            return EMI_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-#define S_TRY(call)                \
-    do {                           \
-        const int st_ = (call);    \
-        if (st_) return st_;       \
-    } while (0)
+#define S_HIP(call) HIP_TRY_AS(c, "emi_ipm_solve_shard_dev", call)
+#define S_TRY EMI_TRY
 
-int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* dX, void* dU, const emi_ipm_bounds_t* bd,
-                    const emi_ipm_options_t& given, void* dLamF, void* dLamC, emi_ipm_result_t* results, std::string* err) {
-    if (!*pw) *pw = new IpmSolveWs();
-    IpmSolveWs& w = **pw;
-    const int B = d.B, M = d.M, ns = d.ns, nc = d.nc, nv = ns + nc, np = d.np;
+int ipm_solve_shard(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t& given, void* dLamF, void* dLamC,
+                    emi_ipm_result_t* results) {
+    if (!c->ipm_solve) c->ipm_solve = new IpmSolveWs();
+    IpmSolveWs& w = *c->ipm_solve;
+    const int B = c->B, M = c->M, ns = c->ns, nc = c->nc, nv = ns + nc, np = emi_api::np_total(c);
     const size_t nX = (size_t)B * ns * M, nU = (size_t)B * nc * M, nVar = (size_t)B * nv * M, nRow = (size_t)B * np * M;
-    const size_t nKkt = (size_t)B * (nv + ns) * M, nRes = (size_t)B * (ns + np) * M, nVals = (size_t)B * d.nvals * M, nH = (size_t)B * d.nhess * M;
+    const size_t nKkt = (size_t)B * (nv + ns) * M, nRes = (size_t)B * (ns + np) * M, nVals = (size_t)B * emi_api::nvals_of(c) * M, nH = (size_t)B * emi_api::nhess_of(c) * M;
     const size_t N1 = (size_t)(nv + ns) * M;                    // unknowns of one instance
     const int mm = std::min(4096, nv * M);                      // eigenpairs per instance the lists hold (solve_nlp's max_lowrank)
-    const hipStream_t s = d.stream;
+    const hipStream_t s = c->stream;
 
     // zero-initialised options take solve_nlp's defaults (NlpOptions)
     emi_ipm_options_t opt = given;
@@ -173,7 +160,7 @@ int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* d
     const dim3 cgrid((B + CTL_T - 1) / CTL_T), cblock(CTL_T);
 
     // ---- start(): state records, interior push; the rest follows the first evaluation ---------------------------------------------
-    ctx_shard_forget_ladders(c);
+    for (KktWorkspace* k : c->kkt_shard) kkt_forget_ladder(k);
     for (int b = 0; b < B; ++b) {
         ipm_ctl_start(w.h_state.p[b], opt.mu_init, opt.rho_init);
         double* p = w.h_par.p + (size_t)b * 4;
@@ -196,7 +183,7 @@ int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* d
         if (np > 0) {           // path-row multipliers in the caller's units, for the gradient and the Hessian
             IpmArgs a{};
             a.Y = w.Y.p; a.LamC = (double*)dLamC;
-            S_TRY(ctx_ipm_launch(c, IPM_LAMC, bd, w.par.p, a));
+            S_TRY(emi_api::ctx_ipm_launch(c, IPM_LAMC, bd, w.par.p, a));
         }
         S_TRY(emi_lagr_grad_dev(c, w.VALS.p, dLamF, dLamC, 1.0, w.G.p));
         S_TRY(emi_ipm_error_parts_dev(c, &pt, &du, w.RES.p, w.G.p, bd, w.par.p, w.parts.p));
@@ -235,7 +222,7 @@ int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* d
                 if (!todo[b]) continue;
                 ++nfact[b];
                 if (info[b] > 0) dc[b] = ipm_ctl_raise_dc(dc[b], w.h_par.p[(size_t)b * 4]);     // singular: regularise the dual block
-                else if (ctx_shard_holds(c, b) != 1) { failed[b] = 1; todo[b] = 0; }            // the instance left the Schur path
+                else if (kkt_holds(c->kkt_shard[b], M, ns, nv) != 1) { failed[b] = 1; todo[b] = 0; }    // the instance left the Schur path
                 else fresh[b] = 1;
                 m_lists[b] = fresh[b] && !fm[b];
                 m_clear[b] = fresh[b] && fm[b];

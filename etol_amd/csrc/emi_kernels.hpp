@@ -1,5 +1,5 @@
 // emi_kernels.hpp -- launcher prototypes shared by the kernel translation units and the C-ABI
-// implementation (emi_api.hip).  Argument blocks and tile constants: emi_args.hpp.
+// implementation (emi_api*.hip, which share the context through emi_ctx.hpp).  Argument blocks and tile constants: emi_args.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -205,16 +205,9 @@ void kkt_forget_ladder(KktWorkspace* w);        // the next factorisation starts
 // context owns
 struct IpmSolveWs;
 void ipm_solve_destroy(IpmSolveWs* w);
-struct IpmSolveDims { int device, B, M, ns, nc, np, nvals, nhess; hipStream_t stream; };
-// dX .. dLamC device arrays; returns an EMI_* status (on EMI_ERR_HIP *err says what failed; the statuses of the emi_*_dev calls
-// it makes come back with the context's own message)
-int ipm_solve_shard(emi_ctx_t c, IpmSolveWs** pw, const IpmSolveDims& d, void* dX, void* dU, const emi_ipm_bounds_t* bd,
-                    const emi_ipm_options_t& opt, void* dLamF, void* dLamC, emi_ipm_result_t* results, std::string* err);
-// what the driver asks the context directly (emi_api.hip): kkt_holds of instance b's shard workspace; the ladders forgotten; an
-// array kernel of emi_ipm.hip that has no entry point of its own (IPM_LAMC) on the context's row bounds
-int ctx_shard_holds(emi_ctx_t c, int b);
-void ctx_shard_forget_ladders(emi_ctx_t c);
-int ctx_ipm_launch(emi_ctx_t c, int what, const emi_ipm_bounds_t* bd, const void* dPar, IpmArgs& a);
+// dX .. dLamC device arrays; returns an EMI_* status with the context's message set (its own, or that of the emi_*_dev call that failed)
+int ipm_solve_shard(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t& opt, void* dLamF, void* dLamC,
+                    emi_ipm_result_t* results);
 
 // the mesh ladder of one context's batch (emi_ipm_ladder.hip): prolongation Vf[R][Mf] = Vc[R][Mc] P^T from PT[Mc][Mf], the repair
 // of the position states X[B][ns][M] against the record table (recs [path_sets][np][EMI_PATH_REC], tracks [track_sets][ntracks][M]),
@@ -228,9 +221,7 @@ struct RepairArgs {
 hipError_t launch_repair_guess(const RepairArgs& a, hipStream_t s);
 struct IpmLadderWs;
 void ipm_ladder_destroy(IpmLadderWs* w);
-struct IpmLadderDims { int B, ns, nc, np, np_table, path_sets, px, py; hipStream_t stream; };     // np: table rows and traced rows
-int ipm_solve_ladder(emi_ctx_t c, IpmLadderWs** pw, const IpmLadderDims& d, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf,
-                     const void* dX0, const void* dU0, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results,
-                     std::string* err);
+int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
+                     void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
 
 }  // namespace emi

@@ -136,7 +136,7 @@ template <typename T> EMI_DEV T wave_sum(T v) {
 // and 0 + a + b = 0 + b + a exactly, so the result does not depend on which role comes first.
 // KEEP (with JAC): the rows of the dynamics block and of the cost gradient that the model declares invariant are NOT stored -- they
 // are functions of the mesh, the parameters and the cost sign alone (0, -h, D_kk, -h / p ...; 50 of the quadrotor's 96 VALS rows)
-// and VALS still holds them from an earlier full pass of the same context (EMI_EVAL_KEEP_INVARIANT; emi_api.hip keeps the record
+// and VALS still holds them from an earlier full pass of the same context (EMI_EVAL_KEEP_INVARIANT; emi_api_pass.hip keeps the record
 // that says so).  Whole rows are skipped; what fed only those stores goes with them.  Path partials, RES and COST always vary.
 template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST, bool DEFATOMIC = false, bool KEEP = false>
 EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, const int nbx) {

@@ -588,7 +588,7 @@ int emi_ipm_error_parts_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi
 
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,
- * for reports, tools and tests (csrc/emi_api.hip: plan_pass, plan_piece).           */
+ * for reports, tools and tests (csrc/emi_api_pass.hip: plan_pass, plan_piece).      */
 typedef struct emi_pass_plan {
   int one_launch;      /* 1: the pass goes out as ONE launch (emi_pass_f64_kernel: MFMA-role + node-role workgroups) */
   int sw;              /* states per MFMA workgroup */

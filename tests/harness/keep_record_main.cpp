@@ -1,6 +1,6 @@
 // keep_record_main.cpp -- stand-alone check of the record behind EMI_EVAL_KEEP_INVARIANT (etol_amd/csrc/emi_keep_record.hpp), built
 // with the host sanitizers (`make check-keep-record`).  It replays, without a device, the sequences emi_eval_dev / emi_eval_host
-// and the setters of emi_api.hip put the record through; the buffers are host allocations that stand for device addresses.
+// (emi_api_pass.hip) and the setters of emi_api.hip put the record through; the buffers are host allocations that stand for device addresses.
 #include <cstdio>
 #include <cstdlib>
 #include <memory>

@@ -143,6 +143,72 @@ def test_overflow_determinism_and_forms(results, key):
     ev.close()
 
 
+def staging_case(B, want):
+    """[B] instances of a "deficient" case (no eigenpair anywhere), each with ONE node taken over from an "inertia" case: a block
+    the reference gives want[b] negative eigenvalues.  A block is the [b, :, k] column of the five input arrays, so a column moved
+    as a whole brings its verdict along; both cases come from blocks_ref.make_case."""
+    nv, ns, M, npth = 8, 6, 33, 2
+    case = R.make_case("deficient", nv, ns, M, B, npth, 4242, dw=1e-4)
+    donor = R.make_case("inertia", nv, ns, M, B, npth, 4243, dw=1e-4)
+    Qd, _ = R.assemble(donor["H"], donor["VALS"], donor["Sigma"], donor["SigT"], donor["fixed"], donor["dw"], donor["rows"], nv)
+    nneg = np.array([[R.fix_block(Qd[b, :, k], donor["fixed"][b, :, k], nv)["nneg"] for k in range(M)] for b in range(B)])
+    for b in range(B):
+        sb, sk = np.argwhere(nneg == want[b])[b]            # (a different donor block per instance)
+        for name in ("H", "VALS", "Sigma", "SigT", "fixed"):
+            case[name][b, :, 3 + b] = donor[name][sb, :, sk]
+    return case
+
+
+def test_host_forms_share_staging_without_crosstalk(built):
+    """emi_kkt_blocks_host and the interior-point host forms stage through the same slots of the context.  Node blocks at batch 2,
+    then batch 5 (every slot grows), emi_ipm_trial_host, the node blocks at batch 5 and at batch 2 again: the same bits for the same
+    instances every time, nothing written behind an instance's min(count, max_mods) list entries (the wrapper fills node / delta /
+    vec with -1 / nan before each call), and emi_eval_host -- whose VALS staging buffer holds the invariant rows -- unchanged."""
+    from etol_amd import workloads as W
+    nv, ns, M, npth, mm = 8, 6, 33, 2, 2
+    want = [1, 3, 1, 2, 1]                                  # eigenpairs per instance: below, at and above max_mods
+    c5 = staging_case(5, want)
+    c2 = {k: (np.ascontiguousarray(v[:2]) if isinstance(v, np.ndarray) and v.ndim == 3 else v) for k, v in c5.items()}
+    X, U, _ = W.quadrotor_batch(11, 2, M, 0)
+    ev = make_ev(nv, M, 2, npth)
+    blocks = lambda c: ev.kkt_blocks_host(c["H"], c["VALS"], c["Sigma"], c["SigT"], c["fixed"], c["dw"], max_mods=mm)
+
+    def lists_end_at_the_count(out, B):
+        for b in range(B):
+            assert out["count"][b] >= 1
+            n = min(int(out["count"][b]), mm)
+            assert (out["node"][b, :n] == 3 + b).all() and np.isfinite(out["delta"][b, :n]).all() and np.isfinite(out["vec"][b, :n]).all()
+            assert (out["node"][b, n:] == -1).all() and np.isnan(out["delta"][b, n:]).all() and np.isnan(out["vec"][b, n:]).all()
+
+    vals_before = ev.eval_host(X, U)[1]
+    first = blocks(c2)                                      # 1.
+    lists_end_at_the_count(first, 2)
+    assert list(first["count"]) == want[:2]
+    ev.set_batch(5)                                         # 2.
+    rng = np.random.default_rng(5)
+    r = lambda *shape: rng.standard_normal(shape)
+    pt = dict(X=r(5, ns, M), U=r(5, nv - ns, M), S=r(5, npth, M), E1=r(5, npth, M), E2=r(5, npth, M))
+    step = dict(DZLam=r(5, nv + ns, M), DS=r(5, npth, M), DE1=r(5, npth, M), DE2=r(5, npth, M))
+    trial = {k: np.full_like(v, np.nan) for k, v in pt.items()}
+    alpha = rng.uniform(0.1, 1.0, 5)
+    ev.ipm_trial(pt, step, alpha, trial, dev=False)         # 3.
+    al = alpha[:, None, None]
+    for got, x, d in [(np.concatenate([trial["X"], trial["U"]], axis=1), np.concatenate([pt["X"], pt["U"]], axis=1), step["DZLam"][:, :nv]),
+                      (trial["S"], pt["S"], step["DS"]), (trial["E1"], pt["E1"], step["DE1"]), (trial["E2"], pt["E2"], step["DE2"])]:
+        # x + alpha d with one rounding (fma) or two
+        assert (np.abs(got - (x + al * d)) <= 2 * R.EPS * (np.abs(x) + np.abs(al * d))).all()
+    wide = blocks(c5)                                       # 4.
+    lists_end_at_the_count(wide, 5)
+    assert list(wide["count"]) == want
+    assert same_bits(first, {k: v[:2] for k, v in wide.items()})
+    ev.set_batch(2)                                         # 5.
+    again = blocks(c2)
+    lists_end_at_the_count(again, 2)
+    assert same_bits(first, again)
+    assert np.array_equal(ev.eval_host(X, U)[1].view(np.uint8), vals_before.view(np.uint8))
+    ev.close()
+
+
 @pytest.mark.parametrize("ns,nc", [(5, 1), (11, 1), (1, 1)], ids=["nv6", "nv12", "nv2"])
 def test_block_sizes_between_the_compiled_ones(built, ns, nc):
     """nv = 6, 12 and 2 (models that exist only for their dimensions): the run-time-nv assembly kernel at an nv that has no compiled

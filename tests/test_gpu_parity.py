@@ -934,7 +934,7 @@ def test_mfma_defect_kernel_variants_for_the_two_state_model(built, sym_ct):
 
 def _expected_default_form(ev, B):
     """The name emi_eval_dev reports for the LAST launch of a batch of B instances, from the library's own statement of its
-    launch policy (emi_plan_pass: csrc/emi_api.hip plan_pass / plan_piece are the one definition; nothing is restated here)."""
+    launch policy (emi_plan_pass: csrc/emi_api_pass.hip plan_pass / plan_piece are the one definition; nothing is restated here)."""
     p = ev.plan(B)
     last = p["tail"] if p["tail"] else (p["piece"] if p["piece"] else B)
     q = ev.plan(last)

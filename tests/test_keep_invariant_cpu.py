@@ -67,7 +67,7 @@ def test_argument_errors(built):
 
 def test_record_bookkeeping_as_a_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """The record emi_eval_dev consults (etol_amd/csrc/emi_keep_record.hpp) has no device in it: tests/harness/keep_record_main.cpp
-    replays the call sequences of emi_api.hip against it, built with -fsanitize=address,undefined (`make check-keep-record`)."""
+    replays the call sequences of emi_api.hip and emi_api_pass.hip against it, built with -fsanitize=address,undefined (`make check-keep-record`)."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does a change to the host side of the C ABI (csrc/emi_api.hip) leave the library as it was?  Run in two trees -- the parent
+"""Does a change to the host side of the C ABI (csrc/emi_api*.hip) leave the library as it was?  Run in two trees -- the parent
 commit's and the changed one, each with its own built library -- and compare what they write:
 
    python tools/api_identity.py plan    OUT.json   emi_plan_pass (all fields) and emi_last_path over a grid; launches no kernel
