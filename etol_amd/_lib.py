@@ -65,13 +65,15 @@ class IpmBounds(C.Structure):
 class IpmOptions(C.Structure):
     """emi_ipm_options_t: fields left at zero take solve_nlp's defaults"""
     _fields_ = [(n, C.c_double) for n in ("tol", "mu_init", "bound_push", "bound_frac", "rho_init", "acceptable_factor")] + \
-               [(n, C.c_int) for n in ("max_iter", "acceptable_iter", "max_futile_escalations")]
+               [(n, C.c_int) for n in ("max_iter", "acceptable_iter", "max_futile_escalations", "rules", "crawl_limit")] + \
+               [("crawl_frac", C.c_double)]
 
 
 class IpmResult(C.Structure):
     """emi_ipm_result_t: how one instance of emi_ipm_solve_shard_* ended"""
     _fields_ = [(n, C.c_int) for n in ("status", "iterations", "evaluations", "factorisations", "reflected_steps")] + \
-               [(n, C.c_double) for n in ("cost", "kkt_error", "constr_viol", "emax", "mu", "rho")]
+               [(n, C.c_double) for n in ("cost", "kkt_error", "constr_viol", "emax", "mu", "rho")] + \
+               [(n, C.c_int) for n in ("newton_steps", "restored_steps")]
 
 
 class IpmRung(C.Structure):
@@ -79,6 +81,7 @@ class IpmRung(C.Structure):
     _fields_ = [("M", C.c_int), ("bd", IpmBounds), ("recs", _D), ("opt", IpmOptions), ("repair", C.c_int)]
 
 
+IPM_RULE_RESIDUAL = 1   # emi_ipm_options_t.rules: residual-based acceptance of the full step and the crawl rule
 IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
 
 _PT, _DU, _ST, _EL, _BD = (C.POINTER(t) for t in (IpmPoint, IpmDuals, IpmStep, IpmElim, IpmBounds))
@@ -125,6 +128,8 @@ SYMBOLS = {
     "emi_ipm_start_dev": (C.c_int, [_P, C.c_int, _PT, _DU, _P, _BD, _P, C.c_double, C.c_double, _P, _P]),
     "emi_ipm_error_parts_dev": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
     "emi_ipm_error_parts_host": (C.c_int, [_P, _PT, _DU, _P, _P, _BD, _P, _P]),
+    "emi_ipm_keep_dev": (C.c_int, [_P, _PT, _DU, _PT, _DU, _P, C.c_int]),
+    "emi_ipm_keep_host": (C.c_int, [_P, _PT, _DU, _PT, _DU, _P, C.c_int]),
     "emi_ipm_solve_shard_dev": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
     "emi_ipm_solve_shard_host": (C.c_int, [_P, _P, _P, _BD, C.POINTER(IpmOptions), _P, _P, C.POINTER(IpmResult)]),
     "emi_prolong_matrix": (C.c_int, [C.c_int, _D, _D, C.c_int, _D, _D]),

@@ -317,6 +317,28 @@ int emi_ipm_error_parts_dev(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ip
     return EMI_OK;
 }
 
+int emi_ipm_keep_dev(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const emi_ipm_point_t* kpt, const emi_ipm_duals_t* kdu,
+                     const void* dMask, int restore) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(ipm_check(c, "emi_ipm_keep_dev"));
+    const int np = np_total(c);
+    if (!ipm_has_point(pt, c->nc, np) || !ipm_has_duals(du, np) || !ipm_has_point(kpt, c->nc, np) || !ipm_has_duals(kdu, np))
+        return fail(c, EMI_ERR_ARG, "emi_ipm_keep_dev: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    emi::IpmKeepArgs a{};
+    const emi_ipm_point_t* P[2] = {pt, kpt};
+    const emi_ipm_duals_t* D[2] = {du, kdu};
+    for (int side = 0; side < 2; ++side) {
+        void* const v[13] = {P[side]->X, P[side]->U, P[side]->S, P[side]->E1, P[side]->E2, D[side]->LamF, D[side]->Y, D[side]->ZL, D[side]->ZU,
+                             D[side]->VL, D[side]->VU, D[side]->W1, D[side]->W2};
+        for (int i = 0; i < 13; ++i) (side ? a.kept : a.live)[i] = (double*)v[i];
+    }
+    a.mask = (const unsigned char*)dMask;
+    a.B = c->B; a.M = c->M; a.ns = c->ns; a.nc = c->nc; a.np = np; a.restore = restore ? 1 : 0;
+    HIP_TRY(c, emi::launch_ipm_keep(a, c->stream));
+    return EMI_OK;
+}
+
 // ---- the _host forms: every array copied in, the _dev form run, what it writes copied out, synchronised -------------------------------
 int emi_ipm_reduce_host(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* VALS, const double* G,
                         const emi_ipm_bounds_t* bd, const double* par, const double* DefRes, const double* RowRes, const emi_ipm_elim_t* out,
@@ -399,6 +421,16 @@ int emi_ipm_error_parts_host(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_i
     IPM_HOST_END(emi_ipm_error_parts_dev(c, pt ? &dp : nullptr, du ? &dd : nullptr, dR, dG, bd ? &db : nullptr, dP, dO));
 }
 
+int emi_ipm_keep_host(emi_ctx_t c, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const emi_ipm_point_t* kpt, const emi_ipm_duals_t* kdu,
+                      const unsigned char* mask, int restore) {
+    IPM_HOST_BEGIN("emi_ipm_keep_host", 0);
+    // (both sides go in and come out: an instance the mask leaves out keeps its bits on the side that is written)
+    const emi_ipm_point_t dp = stage_point(s, z, pt, true, true), dk = stage_point(s, z, kpt, true, true);
+    const emi_ipm_duals_t dd = stage_duals(s, z, du, true, true), de = stage_duals(s, z, kdu, true, true);
+    const void* dM = s.place(mask, (size_t)c->B, true, false);
+    IPM_HOST_END(emi_ipm_keep_dev(c, pt ? &dp : nullptr, du ? &dd : nullptr, kpt ? &dk : nullptr, kdu ? &de : nullptr, dM, restore));
+}
+
 // ---- lock-step interior-point solve of the whole batch (the driver: emi_ipm_solve.hip) -------------------------------------------
 int emi_ipm_solve_shard_dev(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt, void* dLamF,
                             void* dLamC, emi_ipm_result_t* results) {
@@ -409,6 +441,7 @@ int emi_ipm_solve_shard_dev(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bound
     const int np = np_total(c);
     if (!dX || (c->nc > 0 && !dU) || !bd || !opt || !dLamF || (np > 0 && !dLamC) || !results)
         return fail(c, EMI_ERR_ARG, "emi_ipm_solve_shard_dev: null argument");
+    if (opt->rules & ~EMI_IPM_RULE_RESIDUAL) return fail(c, EMI_ERR_ARG, "emi_ipm_solve_shard_dev: unknown bit in rules (%d)", opt->rules);
     HIP_TRY(c, hipSetDevice(c->device));
     return emi::ipm_solve_shard(c, dX, dU, bd, *opt, dLamF, dLamC, results);
 }
@@ -461,6 +494,7 @@ int ladder_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t
     for (int r = 0; r < nrungs; ++r) {
         if (rungs[r].M < 2) return fail(c, EMI_ERR_ARG, "%s: rung %d has %d nodes", what, r, rungs[r].M);
         if (!rungs[r].bd.zl || !rungs[r].bd.zu) return fail(c, EMI_ERR_ARG, "%s: rung %d has no bounds", what, r);
+        if (rungs[r].opt.rules & ~EMI_IPM_RULE_RESIDUAL) return fail(c, EMI_ERR_ARG, "%s: rung %d has an unknown bit in rules", what, r);
         if (!rungs[r].recs) continue;
         if (c->np <= 0) return fail(c, EMI_ERR_ARG, "%s: rung %d brings a record table and the context has none", what, r);
         for (size_t i = 0; i < (size_t)c->np * c->path_sets; ++i) track = track || (int)rungs[r].recs[i * EMI_PATH_REC] == EMI_PATH_TRACK;

@@ -13,6 +13,10 @@
 //     the error components of the multipliers before the reset.  The update follows in the next round.
 //   * mu^1.5 is mu sqrt(mu) and mu^0.25 is sqrt(sqrt(mu)): correctly rounded on host and device alike, where pow is not.
 //   * an error that is not finite ends the instance (EMI_IPM_NOT_FINITE); solve_nlp has no such exit.
+//   * residual-based acceptance (EMI_IPM_RULE_RESIDUAL) is three steps around array kernels -- select, the full step and its
+//     evaluation, decide -- with its own record per instance (IpmCtlRescue).  A stepped iterate with ANY component of its error
+//     that is not finite is taken back (solve_nlp asks std::isfinite of the maximum, which drops a NaN); the attempt counts as one
+//     evaluation and a kept step is evaluated again at the head of the next round, where solve_nlp goes on with the values it has.
 // Every function is free of fused multiply-adds (contraction off), so the host and the device compute the same bits.
 #pragma once
 
@@ -39,6 +43,10 @@ struct IpmCtlOptions {
     double tol, acceptable_factor;
     int max_iter, acceptable_iter, max_futile_escalations;
     int has_rows;                   // the problem has path rows (np > 0)
+    // residual-based acceptance and the crawl rule (at the end: a record built from the fields above leaves them zero, the rule off)
+    int rules;                      // EMI_IPM_RULE_* bits
+    int crawl_limit;                // consecutive short steps before the crawl rule acts
+    double crawl_frac;              // a step is short below this fraction of the longest admissible one
 };
 
 // the state record of one instance
@@ -197,6 +205,67 @@ EMI_CTL_HD inline void ipm_ctl_search_step(const double* mer, int exact_with_mod
     s.force_modified = 0;
     // a search that can go no further: the point is a solution only if it meets the acceptable level
     s.status = ipm_ctl_acceptable(s, o) ? EMI_IPM_ACCEPTABLE : EMI_IPM_LINE_SEARCH;
+}
+
+// ---- residual-based acceptance of the full step and the crawl rule (solve_nlp: residual_based_acceptance and the lines around
+// its call in line_search) ---------------------------------------------------------------------------------------------------------
+// what the rule keeps per instance, apart from IpmCtlState (whose layout the CPU test's shim fills field by field)
+struct IpmCtlRescue {
+    int crawl;                      // accepted steps in a row that were shorter than crawl_frac apr
+    int candidate;                  // between select and decide: the full step of this instance is being tried
+    int newton_steps, restored_steps;   // full steps kept / taken back
+    double err_mu;                  // KKT error of the present barrier problem at the iterate the step starts from
+};
+
+EMI_CTL_HD inline void ipm_ctl_rescue_start(IpmCtlRescue& r) {
+    r.crawl = r.candidate = r.newton_steps = r.restored_steps = 0;
+    r.err_mu = 0.0;
+}
+
+// the first trial point (length apr) of this instance has just failed the Armijo test, and the rule is for it
+EMI_CTL_HD inline bool ipm_ctl_rescue_applies(const IpmCtlState& s, const IpmCtlRescue& r, const IpmCtlOptions& o) {
+    EMI_CTL_NO_FMA
+    if (!(o.rules & EMI_IPM_RULE_RESIDUAL) || s.status != IPM_RUNNING || !s.searching || s.passes != 1) return false;
+    return s.err0 <= 1e-2 || r.crawl >= o.crawl_limit;
+}
+
+// select, after the first backtracking pass: parts_now are the error components of the iterate with its present multipliers and
+// penalty weight (the round head's predate the reset of the elastic multipliers an escalation brings)
+EMI_CTL_HD inline void ipm_ctl_rescue_select(const double* parts_now, const IpmCtlState& s, IpmCtlRescue& r, const IpmCtlOptions& o) {
+    EMI_CTL_NO_FMA
+    r.candidate = ipm_ctl_rescue_applies(s, r, o) ? 1 : 0;
+    if (r.candidate) r.err_mu = ipm_ctl_kkt(parts_now, s.mu);
+}
+
+// decide, from the error components of the stepped iterate: true = the step stands (the iteration is over, and the accept at the
+// end of the line search must not touch the instance), false = the iterate is to be restored and the search goes on with the
+// alpha the search step has already halved.  An instance that is no candidate is left as it is (false).
+EMI_CTL_HD inline bool ipm_ctl_rescue_decide(const double* parts_tr, IpmCtlState& s, IpmCtlRescue& r) {
+    EMI_CTL_NO_FMA
+    if (!r.candidate) return false;
+    r.candidate = 0;
+    ++s.evaluations;
+    const double err_tr = ipm_ctl_kkt(parts_tr, s.mu);
+    double all = err_tr;                // (a maximum drops a NaN: every component is asked)
+    for (int i = 0; i < IPM_NPARTS; ++i) all += parts_tr[i];
+    if (all - all == 0.0 && err_tr <= 0.9 * r.err_mu) {
+        s.searching = 0;
+        s.accepted = 0;
+        s.force_modified = 0;
+        ++s.iterations;
+        r.crawl = 0;
+        ++r.newton_steps;
+        return true;
+    }
+    ++r.restored_steps;
+    return false;
+}
+
+// crawl update, once after the line-search loop: scal[0] is apr, s.alpha the accepted length
+EMI_CTL_HD inline void ipm_ctl_rescue_crawl(const double* scal, const IpmCtlState& s, IpmCtlRescue& r, const IpmCtlOptions& o) {
+    EMI_CTL_NO_FMA
+    if (!(o.rules & EMI_IPM_RULE_RESIDUAL) || !s.accepted) return;
+    r.crawl = s.alpha < o.crawl_frac * scal[0] ? r.crawl + 1 : 0;
 }
 
 }  // namespace emi

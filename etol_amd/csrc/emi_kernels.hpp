@@ -209,6 +209,16 @@ void ipm_solve_destroy(IpmSolveWs* w);
 int ipm_solve_shard(emi_ctx_t c, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t& opt, void* dLamF, void* dLamC,
                     emi_ipm_result_t* results);
 
+// the iterate of the instances of `mask` copied between the live arrays and a kept set (emi_ipm_solve.hip: emi_ipm_keep_kernel).
+// live / kept in the order X U S E1 E2 LamF Y ZL ZU VL VU W1 W2; mask [B] device bytes or null; restore: kept -> live
+struct IpmKeepArgs {
+    double* live[13];
+    double* kept[13];
+    const unsigned char* mask;
+    int B, M, ns, nc, np, restore;
+};
+hipError_t launch_ipm_keep(const IpmKeepArgs& a, hipStream_t s);
+
 // the mesh ladder of one context's batch (emi_ipm_ladder.hip): prolongation Vf[R][Mf] = Vc[R][Mc] P^T from PT[Mc][Mf], the repair
 // of the position states X[B][ns][M] against the record table (recs [path_sets][np][EMI_PATH_REC], tracks [track_sets][ntracks][M]),
 // and the driver over the rungs, whose device arrays live in an IpmLadderWs the context owns

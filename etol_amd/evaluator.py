@@ -533,6 +533,13 @@ class Evaluator:
         self._ipm_call("error_parts", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k), A(RES), A(G),
                                                       self._ipm_bounds(bounds, k), A(par), A(out)))
 
+    def ipm_keep(self, point, duals, kept_point, kept_duals, mask=None, restore=False, dev=True):
+        """the iterate (X U S E1 E2 | LamF Y ZL ZU VL VU W1 W2) of the instances of mask ([B] uint8, None: all) copied live -> kept, or
+        kept -> live with restore; an instance the mask leaves out keeps every bit (include/emi355x.h: emi_ipm_keep_dev)"""
+        self._ipm_call("keep", dev, lambda k: (self._ipm_group(L.IpmPoint, point, k), self._ipm_group(L.IpmDuals, duals, k),
+                                               self._ipm_group(L.IpmPoint, kept_point, k), self._ipm_group(L.IpmDuals, kept_duals, k),
+                                               self._ipm_addr(mask), int(bool(restore))))
+
     def ipm_start(self, phase, point, duals, bounds, RES=None, par=None, fixed=None, mask=None, bound_push=1e-2, bound_frac=1e-2):
         """solve_nlp's start() on device tensors: phase 0 interior push of X, U and the fixed bytes; 1 slacks, elastics and multipliers
         from the first evaluation; 2 the reset of W1, W2 (include/emi355x.h: emi_ipm_start_dev)"""

@@ -1057,9 +1057,11 @@ class IpmSolve {
             if (!evaluate_trial(alpha)) return Next::abort;
             if (armijo(barrier_merit(trial(), Et, nu, nullptr), alpha, ref)) { accepted = true; break; }
             if (ls == 0) {
-                const Tried soc = second_order_correction(ref, &alpha);
-                if (soc == Tried::failed) return Next::abort;
-                if (soc == Tried::taken) { accepted = true; break; }
+                if (opt.second_order_correction) {
+                    const Tried soc = second_order_correction(ref, &alpha);
+                    if (soc == Tried::failed) return Next::abort;
+                    if (soc == Tried::taken) { accepted = true; break; }
+                }
                 // Close to a solution the merit function stops resolving progress: the full Newton step changes it by less than constraint
                 // curvature and round-off move it, and the backtracking then crawls with steps of 1e-6 for a hundred iterations.  There -- and
                 // wherever the line search has just cut three steps in a row below 30 % of the longest admissible step (`crawl`: the same effect

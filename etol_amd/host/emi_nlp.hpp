@@ -139,6 +139,8 @@ struct NlpOptions {
     int stagnation_iters = 12;          // iterations without 10 % progress of the barrier KKT residual before the inertia search starts
     int crawl_limit = 3;                // consecutive short steps (alpha < crawl_frac * alpha_max) before the crawl rule acts
     double crawl_frac = 0.3;
+    bool second_order_correction = true;    // false: a rejected first trial goes straight to the residual-based acceptance (the rule set of
+                                            // the lock-step device driver, emi_ipm_solve_shard_*: a CPU fixture runs it like for like)
     double rho_init = 10.0;             // exact-penalty weight of the elastic path rows (escalated x10 as needed)
     bool device_node_blocks = false;    // node blocks assembled and convexified by the backend (KktBackend::factor_terms) where it offers that
     double acceptable_factor = 100.0;   // "acceptable": KKT error <= acceptable_factor * tol ...

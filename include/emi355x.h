@@ -479,9 +479,15 @@ int emi_kkt_solve_refined_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned ch
  * still active, with the per-instance control (convergence test, penalty escalation, barrier update, merit weight, Armijo
  * backtracking) as kernels of one thread per instance (csrc/emi_ipm_solve.hip, the rules in csrc/emi_ipm_control.hpp).  Per round
  * a few bytes per instance reach the host: who is active, the factorisation's info / exact / status, who is still searching.
- * The rules are those of ETOL::mi355x::solve_nlp (host/emi_nlp.cpp) without second-order correction, residual-based acceptance
- * and crawl rule, inertia search, stagnation rule, variable and Jacobian-based scaling, warm-start multipliers, coupling rows and
- * time limit.
+ * The rules are those of ETOL::mi355x::solve_nlp (host/emi_nlp.cpp) without second-order correction, inertia search, stagnation
+ * rule, variable and Jacobian-based scaling, warm-start multipliers, coupling rows and time limit.
+ * Residual-based acceptance and the crawl rule are taken over behind opt.rules bit EMI_IPM_RULE_RESIDUAL: an instance whose first
+ * trial point (length apr) fails the Armijo test, and whose KKT error at mu = 0 is at most 1e-2 or whose last crawl_limit accepted
+ * steps were each shorter than crawl_frac apr, takes the full step (primal apr without the slack reset, multipliers with apr and
+ * adu), is evaluated with derivatives, and keeps the step if the KKT error of the present barrier problem is finite and at most
+ * 0.9 times what it was; otherwise its iterate is put back bit for bit and the backtracking goes on from apr / 2.  The attempt
+ * is one evaluation; results[b].newton_steps / restored_steps count the steps kept / taken back.  With rules == 0 the launches and
+ * every bit of every output are those of the driver without the rule, and none of the rule's arrays exists.
  *   dX[B][ns][M], dU[B][nc][M]   the start on entry (pushed into the bounds by the call), the final iterate on return
  *   dLamF[B][ns][M]              out: defect multipliers
  *   dLamC[B][np][M]              out: path-row multipliers in the caller's units (cscale Y), the Lagrangian of emi_hess_*: the
@@ -489,25 +495,34 @@ int emi_kkt_solve_refined_shard_dev(emi_ctx_t ctx, void* dRhs, const unsigned ch
  *   bd                           bounds as for emi_ipm_*: zl, zu [nsets][nv][M] (device in the _dev form), cl, cu, cscale host
  *   opt                          zero-initialised fields take solve_nlp's defaults: tol 1e-8, mu_init 0.1, bound_push and
  *                                bound_frac 1e-2, rho_init 10, acceptable_factor 100, max_iter 200, acceptable_iter 10,
- *                                max_futile_escalations 3
+ *                                max_futile_escalations 3; rules: bit set of EMI_IPM_RULE_* (0: none; an unknown bit is
+ *                                EMI_ERR_ARG); with EMI_IPM_RULE_RESIDUAL crawl_limit <= 0 takes 3 and crawl_frac <= 0 takes 0.3 (a
+ *                                crawl_limit beyond max_iter leaves the kkt_error <= 1e-2 branch only)
  *   results[B]                   host: status (EMI_IPM_*), iterations, evaluations, factorisations, steps of the convexified
- *                                matrix, and cost, KKT error at mu = 0, largest residual, largest elastic, mu, rho at the end
+ *                                matrix, and cost, KKT error at mu = 0, largest residual, largest elastic, mu, rho at the end;
+ *                                full steps kept / taken back on the KKT residual (0 without EMI_IPM_RULE_RESIDUAL)
  * Path-row partials: the list of emi_kkt_blocks_rows, or the default.  An instance that has ended is masked out of every call
  * that takes a mask and keeps every bit of its iterate; the call returns when none is active.  Two identical calls give the
  * same bits.  The iterate's slacks, multipliers, step, elimination arrays, trial point, H, Q, eigenpair lists, G and the state
- * records are device arrays of the context, created at the first call, grown when mesh or batch grow, freed with the context.
+ * records are device arrays of the context, created at the first call, grown when mesh or batch grow, freed with the context;
+ * with EMI_IPM_RULE_RESIDUAL also a kept iterate, a full-step point and a second RES / VALS / COST / G.
  * Returns EMI_OK when the run ended normally whatever the instances' statuses; EMI_ERR_UNSUPPORTED: f32 context, delays set,
  * ns + nc > 16, LU method;  EMI_ERR_STATE: mesh, model or batch not set;  EMI_ERR_ARG: a NULL argument that is not optional.
  * The _host form takes host arrays (zl, zu included), copies in, runs the _dev form, copies out and synchronises.            */
 enum { EMI_IPM_CONVERGED = 0, EMI_IPM_ACCEPTABLE = 1, EMI_IPM_MAX_ITER = 2, EMI_IPM_LINE_SEARCH = 3, EMI_IPM_INFEASIBLE = 4,
        EMI_IPM_FACTOR = 5 /* still singular after the dual ladder, or the instance left the Schur path */, EMI_IPM_NOT_FINITE = 6 };
+enum { EMI_IPM_RULE_RESIDUAL = 1 /* residual-based acceptance of the full step and the crawl rule */ };
 typedef struct emi_ipm_options {
   double tol, mu_init, bound_push, bound_frac, rho_init, acceptable_factor;
   int max_iter, acceptable_iter, max_futile_escalations;
+  int rules;
+  int crawl_limit;
+  double crawl_frac;
 } emi_ipm_options_t;
 typedef struct emi_ipm_result {
   int status, iterations, evaluations, factorisations, reflected_steps;
   double cost, kkt_error, constr_viol, emax, mu, rho;
+  int newton_steps, restored_steps;
 } emi_ipm_result_t;
 int emi_ipm_solve_shard_dev(emi_ctx_t ctx, void* dX, void* dU, const emi_ipm_bounds_t* bd, const emi_ipm_options_t* opt,
                             void* dLamF, void* dLamC, emi_ipm_result_t* results);
@@ -585,6 +600,15 @@ int emi_ipm_error_parts_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_
                             const emi_ipm_bounds_t* bd, const void* dPar, void* dOut);
 int emi_ipm_error_parts_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const double* RES, const double* G,
                              const emi_ipm_bounds_t* bd, const double* par, double* out);
+/* The iterate of the instances of a mask copied between the live arrays (pt, du) and a kept set of the same shapes (kept_pt,
+ * kept_du): restore == 0 live -> kept, otherwise kept -> live.  The iterate is X, U, S, E1, E2, LamF, Y, ZL, ZU, VL, VU, W1, W2;
+ * dMask [B] bytes (device; NULL: every instance); an instance with mask 0 keeps every bit on both sides.  One launch, no
+ * arithmetic: the copies are the source's bits.  The row arrays may be NULL without path rows.  Asynchronous on the context's
+ * stream; the _host form takes host arrays (the mask included) and synchronises.  Statuses as the emi_ipm_* calls.            */
+int emi_ipm_keep_dev(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const emi_ipm_point_t* kept_pt,
+                     const emi_ipm_duals_t* kept_du, const void* dMask, int restore);
+int emi_ipm_keep_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_duals_t* du, const emi_ipm_point_t* kept_pt,
+                      const emi_ipm_duals_t* kept_du, const unsigned char* mask, int restore);
 
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,

@@ -5,6 +5,9 @@ commit's and the changed one, each with its own built library -- and compare wha
    python tools/api_identity.py plan    OUT.json   emi_plan_pass (all fields) and emi_last_path over a grid; launches no kernel
    python tools/api_identity.py results OUT.json   SHA-256 of what every launch form computes, the kernel name, launch counts
    python tools/api_identity.py times   OUT.json   ms per default-dispatch pass at B = 1, 16, 128, 1024 (quadrotor, 1024 nodes)
+   python tools/api_identity.py lockstep OUT.json  SHA-256 of X, U, LamF, LamC and the result records of the lock-step solve (2 x 9
+                                                   instances of tests/lockstep_ref.py on 41 nodes) and of the ladder (21, 41) over
+                                                   them, default options: what a change behind an option that is off must keep
    python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case
 
 The library is the one of the tree the script lies in."""
@@ -258,6 +261,43 @@ def times():
     return out
 
 
+def lockstep():
+    import numpy as np
+    import torch
+    import etol_amd as E
+    import ladder_ref as LD
+    import lockstep_ref as LR
+    fields = ("status", "iterations", "evaluations", "factorisations", "reflected_steps", "cost", "kkt_error", "constr_viol", "emax", "mu", "rho")
+    rows = lambda res: [[q[k] for k in fields] for q in res]
+    out = {}
+    for tf in LR.TFS:
+        for name, insts, ladder in (("one mesh", LR.instances(tf), (LR.M_NODES,)), ("ladder", LD.instances(tf), tuple(LD.LADDER))):
+            B = len(insts)
+            ev = E.Evaluator(0)
+            ev.set_mesh(ladder[0], 0.0, tf)
+            ev.set_model(1, LR.QUAD_PARAMS)
+            ev.set_batch(B)
+            ev.set_path(np.stack([LR.records(i["discs"]) for i in insts]), 0, 1)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).to(ev.device)
+            z0 = np.stack([i["z0"] for i in insts]).reshape(B, 8, ladder[0])
+            X, U = up(z0[:, :6]), up(z0[:, 6:])
+            bounds = []
+            for M in ladder:
+                P = LD.quad_at(tf, M, LR.discs_of(LR.FIRST_DISCS[0]))
+                bounds.append(dict(zl=up(P.lo.reshape(1, 8, M)), zu=up(P.up.reshape(1, 8, M)), cl=LR.CL, cu=LR.CU, cscale=LR.CSCALE))
+            torch.cuda.synchronize()
+            if len(ladder) == 1:
+                LamF, LamC, res = ev.ipm_solve_shard(X, U, bounds[0], dict(tol=1e-8, max_iter=200))
+                res = [res]
+            else:
+                rungs = [dict(M=M, bounds=b, options=dict(tol=1e-8), repair=0) for M, b in zip(ladder, bounds)]
+                X, U, LamF, LamC, res = ev.ipm_solve_ladder(rungs, 0.0, tf, X, U)
+            ev.synchronize()
+            out[f"{name} tf={tf}"] = dict(X=sha(X), U=sha(U), LamF=sha(LamF), LamC=sha(LamC), results=[rows(r) for r in res])
+            ev.close()
+    return out
+
+
 def compare(pa, br):
     report = dict(equal=[], different=[], self_disagreeing=[])
     for name in sorted(set(pa) | set(br)):
@@ -286,6 +326,6 @@ if __name__ == "__main__":
         if len(sys.argv) > 4:
             json.dump(dict(rep, cases={k: dict(parent=pa.get(k), branch=br.get(k)) for k in sorted(set(pa) | set(br))}), open(sys.argv[4], "w"), indent=1)
         sys.exit(0 if rep["verdict"] == "identical" else 1)
-    res = plan_grid() if mode == "plan" else times() if mode == "times" else {name: run_case(c) for name, c in CASES.items()}
+    res = plan_grid() if mode == "plan" else times() if mode == "times" else lockstep() if mode == "lockstep" else {name: run_case(c) for name, c in CASES.items()}
     json.dump(res, open(sys.argv[2], "w"), indent=1 if mode != "plan" else None, sort_keys=True)
     print(mode, len(res), "entries ->", sys.argv[2], hashlib.sha256(json.dumps(res, sort_keys=True).encode()).hexdigest()[:16])

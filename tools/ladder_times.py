@@ -3,13 +3,14 @@
 emi_ipm_solve_shard_dev on the ladder's last mesh, same instances, same GPU.  Nothing is gated; one JSON line goes to
 profiles/ladder_times.jsonl.
 
-  python tools/ladder_times.py [--batch 64] [--ladder 33,65,129,257] [--rounds 3] [--max-iter 60] [--obstacles 20]
+  python tools/ladder_times.py [--batch 64] [--ladder 33,65,129,257] [--rounds 3] [--max-iter 60] [--obstacles 20] [--rules 0]
 
 Problem and instances: those of tools/lockstep_times.py (quadrotor, `--obstacles` random disc keep-outs per instance, straight-line
 starts with hover thrust, on the ladder's first mesh for the ladder and on its last for the cold call).  The ladder runs as
 solve() runs its own: default options on the first rung, the warm settings of the host solver (Alg::warm_mu_init 1e-5,
 warm_bound_push 1e-4 as bound_push and bound_frac) on the rungs above it, the keep-outs inflated per rung below the last by half
-the largest node spacing of the straight line (inflate_records of host/eMI355X.cpp), repair on.  After a warm-up call of either
+the largest node spacing of the straight line (inflate_records of host/eMI355X.cpp), repair on; --rules is the value of emi_ipm_options_t.rules on every rung and in the cold call (1: residual-based acceptance and
+the crawl rule).  After a warm-up call of either
 form, `rounds` rounds alternate between the two; each figure is the wall time of the synchronised call.  The share of prolongation
 and repair is measured apart: the same kernels on arrays of the ladder's shapes, by the context's event timer."""
 import argparse
@@ -48,6 +49,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=60)
     ap.add_argument("--obstacles", type=int, default=20)
+    ap.add_argument("--rules", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ladder_times.jsonl"))
     a = ap.parse_args()
     ladder = [int(m) for m in a.ladder.split(",")]
@@ -63,7 +65,7 @@ def main():
         per[M] = dict(zl=zl, zu=zu, X=np.repeat(X1[None], B, 0), U=np.repeat(U1[None], B, 0))
     rungs = []
     for g, M in enumerate(ladder):
-        opt = dict(tol=1e-8, max_iter=a.max_iter)
+        opt = dict(tol=1e-8, max_iter=a.max_iter, rules=a.rules)
         if g > 0:
             opt.update(mu_init=WARM_MU, bound_push=WARM_PUSH, bound_frac=WARM_PUSH)
         rungs.append(dict(M=M, bounds=dict(zl=up(per[M]["zl"]), zu=up(per[M]["zu"]), cl=cl, cu=cu), options=opt, repair=1,
@@ -80,7 +82,7 @@ def main():
     def cold():
         ev.set_mesh(ML, 0.0, LT.TF)
         ev.set_path(recs, 0, 1)
-        return LT.solve(ev, per[ML]["X"], per[ML]["U"], per[ML]["zl"], per[ML]["zu"], nobs, dict(tol=1e-8, max_iter=a.max_iter))
+        return LT.solve(ev, per[ML]["X"], per[ML]["U"], per[ML]["zl"], per[ML]["zu"], nobs, dict(tol=1e-8, max_iter=a.max_iter, rules=a.rules))
 
     climb(), cold()
     sec = dict(ladder=[], cold=[])
@@ -108,6 +110,10 @@ def main():
         aside += statistics.median(ms) * 1e-3
     status = lambda rows: {LT.STATUS[k]: sum(q["status"] == k for q in rows) for k in range(len(LT.STATUS))}
     rec = dict(B=B, ladder=ladder, obstacles=nobs, max_iter=a.max_iter, rounds=a.rounds, warm_mu_init=WARM_MU, warm_bound_push=WARM_PUSH,
+               rules=a.rules, evaluations_per_rung=[sum(q["evaluations"] for q in rows) for rows in rl],
+               newton_steps_per_rung=[sum(q["newton_steps"] for q in rows) for rows in rl],
+               restored_steps_per_rung=[sum(q["restored_steps"] for q in rows) for rows in rl],
+               evaluations_cold_last_mesh=sum(q["evaluations"] for q in rc),
                seconds_ladder=sec["ladder"], seconds_cold_last_mesh=sec["cold"],
                ms_per_instance_ladder=1e3 * statistics.median(sec["ladder"]) / B,
                ms_per_instance_cold_last_mesh=1e3 * statistics.median(sec["cold"]) / B,

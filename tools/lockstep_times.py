@@ -3,13 +3,14 @@
 same B instances solved one after the other by the same call on a B = 1 context, on the same GPU.  Nothing is gated; one JSON
 line per shape goes to profiles/lockstep_times.jsonl.
 
-  python tools/lockstep_times.py [--shapes 64x65,64x257] [--rounds 3] [--max-iter 60] [--obstacles 20]
+  python tools/lockstep_times.py [--shapes 64x65,64x257] [--rounds 3] [--max-iter 60] [--obstacles 20] [--rules 0,1] [--batch-only]
 
 Problem: the quadrotor (6 states, 2 controls) from (1, 1) at rest to (8, 6) at rest in 4 s, boxes as in tests/indep_nlp.py's
 quad_problem, `--obstacles` disc keep-outs per instance from workloads.quadrotor_batch (config 3), straight-line starts with
-hover thrust.  Random discs may cover a boundary state: such an instance has no feasible path and runs to --max-iter (the
-driver has no residual-based acceptance and no crawl rule yet); how many instances ended in each status
-is recorded beside the times.  Per shape: a warm-up call of either form, then `rounds` rounds that alternate between the two
+hover thrust.  Random discs may cover a boundary state: such an instance has no feasible path and, without residual-based
+acceptance and the crawl rule, runs to --max-iter.  --rules lists the variants to run, each a value of
+emi_ipm_options_t.rules (0: none, 1: EMI_IPM_RULE_RESIDUAL with crawl_limit 3, crawl_frac 0.3); how many instances ended in each
+status, and the full steps kept / taken back on the KKT residual, are recorded beside the times.  Per shape: a warm-up call of either form, then `rounds` rounds that alternate between the two
 forms; each figure is the wall time of the call(s), synchronised."""
 import argparse
 import json
@@ -70,10 +71,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=60)
     ap.add_argument("--obstacles", type=int, default=20)
+    ap.add_argument("--rules", default="0")
+    ap.add_argument("--batch-only", action="store_true", help="leave out the one-by-one form (its figures are recorded as empty)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lockstep_times.jsonl"))
     a = ap.parse_args()
-    opt = dict(tol=1e-8, max_iter=a.max_iter)
-    for shape in a.shapes.split(","):
+    for shape, rules in ((s, int(r)) for s in a.shapes.split(",") for r in a.rules.split(",")):
+        opt = dict(tol=1e-8, max_iter=a.max_iter, rules=rules)
         B, M = (int(x) for x in shape.split("x"))
         _, _, recs = W.quadrotor_batch(3, B, M, a.obstacles)
         ev = context(M, recs)
@@ -86,6 +89,8 @@ def main():
 
         def singles():
             total, res = 0.0, []
+            if a.batch_only:
+                return total, res
             for b in range(B):
                 ev1.set_path(recs[b:b + 1], 0, 1)
                 t, r = solve(ev1, X[b:b + 1], U[b:b + 1], zl, zu, a.obstacles, opt)
@@ -100,10 +105,11 @@ def main():
             sec["batch"].append(tb)
             sec["singles"].append(ts)
         its = [q["iterations"] for q in rb]
-        rec = dict(B=B, M=M, obstacles=a.obstacles, max_iter=a.max_iter, rounds=a.rounds,
+        rec = dict(B=B, M=M, obstacles=a.obstacles, max_iter=a.max_iter, rounds=a.rounds, rules=rules,
+                   newton_steps_sum=sum(q["newton_steps"] for q in rb), restored_steps_sum=sum(q["restored_steps"] for q in rb),
                    seconds_batch=sec["batch"], seconds_one_by_one=sec["singles"],
                    ms_per_instance_batch=1e3 * statistics.median(sec["batch"]) / B,
-                   ms_per_instance_one_by_one=1e3 * statistics.median(sec["singles"]) / B,
+                   ms_per_instance_one_by_one=None if a.batch_only else 1e3 * statistics.median(sec["singles"]) / B,
                    iterations=dict(min=min(its), median=statistics.median(its), max=max(its), sum=sum(its)),
                    iterations_one_by_one_sum=sum(q["iterations"] for q in rs),
                    evaluations_sum=sum(q["evaluations"] for q in rb), factorisations_sum=sum(q["factorisations"] for q in rb),
