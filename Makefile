@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-nlp
+.PHONY: all lib host oracle clean check-keep-record check-nlp check-ode-operator
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -49,8 +49,8 @@ $(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
 $(LIBDIR)/emi_comm.o: $(CSRC)/emi_comm.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
-LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_rtc emi_kkt emi_adjoint \
-           emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_host emi_comm
+LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_api_ode emi_rtc emi_kkt emi_adjoint \
+           emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_ode_error emi_host emi_comm
 $(LIBDIR)/libemi355x.so: $(LIB_OBJ:%=$(LIBDIR)/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
 
@@ -69,7 +69,8 @@ $(LIBDIR)/etol_mi355x_example1: etol_amd/examples/etol_mi355x_example1.cpp $(LIB
 $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $(LIBDIR)/libetol_mi355x.so
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
-HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp tests/harness/etol_harness_rescue.cpp
+HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp tests/harness/etol_harness_rescue.cpp \
+               tests/harness/etol_harness_ode_error.cpp
 tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR) $(CSRC)/emi_ipm_control.hpp
 	$(CXX) $(CXXFLAGS) -I$(HOST) -I$(CSRC) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
@@ -92,6 +93,13 @@ check-nlp: tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_n
 	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -I$(HOST) -o $(NLP_CHECK_OUT) tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(CSRC)/emi_host.cpp \
 		$(NLP_CHECK_OUT)_oracle.o -lm
 	$(NLP_CHECK_OUT)
+
+# the operator builder of the ODE-error call (emi_ode_error_operator, csrc/emi_host.cpp: host-only) as a stand-alone program under the
+# host sanitizers
+ODE_OP_CHECK_OUT ?= $(LIBDIR)/ode_operator_check
+check-ode-operator: tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -o $(ODE_OP_CHECK_OUT) tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp -lm
+	$(ODE_OP_CHECK_OUT)
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

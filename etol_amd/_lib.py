@@ -137,6 +137,10 @@ SYMBOLS = {
     "emi_repair_guess_dev": (C.c_int, [_P, _P]),
     "emi_ipm_solve_ladder_dev": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.POINTER(IpmResult)]),
     "emi_ipm_solve_ladder_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.POINTER(IpmResult)]),
+    "emi_ode_error_operator": (C.c_int, [C.c_int, _D, _D, _D, _D, _D]),
+    "emi_interp_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "emi_ode_error_dev": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
+    "emi_ode_error_host": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

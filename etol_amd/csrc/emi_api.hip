@@ -259,6 +259,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     c->t0 = t0;
     c->tf = tf;
     c->adj_dirty = true;
+    c->ode_dirty = true;
     c->delay_dirty = true;      // W(delay) is built for one mesh: [nd][M][M] on these nodes and this horizon
     c->adjw_dirty = true;
     emi::kkt_mesh_changed(c->kkt);

@@ -86,6 +86,22 @@ template <typename T> struct HessArgs {
     ModelParams<T> P;
 };
 
+// ODE-error residual at the Gauss points between the nodes (emi_ode_resid_kernel): point p = q (M-1) + k is Gauss point q of
+// interval k.  Zs rows (instance, state) hold [E x | E' x | D x] (np + np + M columns, row length lds), Zc rows (instance,
+// control) hold E u (row length ldc)
+template <typename T> struct OdeResidArgs {
+    const T* Zs;        // [B*ns][lds]
+    const T* Zc;        // [B*nc][ldc]
+    const T* tq;        // [5 (M-1)] times t0 + h (s_p + 1) of the points
+    const T* scale;     // [M-1]     (tau_{k+1} - tau_k) / 2 * h
+    const T* ul;        // [nc] control bounds (device); null: no clip
+    const T* uu;
+    T* eta;             // [B][ns][M-1]
+    int M, B, lds, ldc;
+    T h;
+    ModelParams<T> P;
+};
+
 struct SymDefectArgs {
     const double* X;
     const double* U;

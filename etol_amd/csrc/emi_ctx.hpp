@@ -124,6 +124,13 @@ struct emi_ctx_s {
     DevBuf d_adj_G;             // G of a certificate call that does not return it
     DevBuf d_adj_op;            // [B][ns][M] operator term of the side-by-side form (large batches)
     DevBuf s_G, s_cert, s_zl, s_zu, s_Gdel;
+    // relative local ODE error (emi_ode_error_*): the stacked operator [E | E' | D] of the mesh in force with rows of the even
+    // length M + (M & 1), the point times and interval scales, the control bounds of the last call and the workspace
+    bool ode_dirty = true;      // operator and times must be rebuilt (set wherever adj_dirty is)
+    emi::DeviceArray<double> d_ode_op;      // [2 * 5 (M-1) + M][ldk]
+    emi::DeviceArray<double> d_ode_tq;      // [5 (M-1)] times of the points, then [M-1] interval scales (tau_k+1 - tau_k) / 2 * h
+    emi::DeviceArray<double> d_ode_ub;      // [2][nc]: ul, uu
+    emi::DeviceArray<double> d_ode_ws;      // [B ns][2 * 5 (M-1) + M] | [B nc][5 (M-1)] | eta [B][ns][M-1]
     // node blocks of the Newton step (emi_kkt_blocks_*): the (variable, VALS entry) pairs of the path rows, the per-entry term
     // lists built from them (uploaded once per list) and the workspace of the kernels, grown on demand
     bool blk_rows_set = false;          // emi_kkt_blocks_rows was called (else: the layout's default for table rows)

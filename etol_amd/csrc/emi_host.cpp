@@ -113,6 +113,37 @@ int emi_model_dims(int model, int* ns, int* nc, int* nparams) {
     return EMI_OK;
 }
 
+// Interpolation operator E and its tau-derivative E' of the barycentric interpolant through the nodes (tau, w) at the five
+// Gauss-Legendre points of every mesh interval; point p = q (M-1) + k is Gauss point q of [tau_k, tau_k+1] (include/emi355x.h).
+// tq[p] is rounded to double first and the operator is that of the rounded abscissa, formed in extended precision:
+//   lam_j = (-1)^j sqrt(w_j) / (s - tau_j),  E_j = lam_j / sum lam,  E'_j = (E_j sum_i lam_i / (s - tau_i) - lam_j / (s - tau_j)) / sum lam
+int emi_ode_error_operator(int M, const double* tau, const double* w, double* E, double* Ed, double* tq) {
+    if (M < 2 || !tau || !w || !E || !Ed || !tq) return EMI_ERR_ARG;
+    static const long double gx[5] = {-0.906179845938663992797626878299392965L, -0.538469310105683091036314420700208805L, 0.0L,
+                                      0.538469310105683091036314420700208805L, 0.906179845938663992797626878299392965L};
+    const int nq = M - 1;
+    std::vector<long double> sw(M), lam(M);
+    for (int j = 0; j < M; ++j) sw[j] = ((j & 1) ? -1.0L : 1.0L) * sqrtl((long double)w[j]);
+    for (int q = 0; q < 5; ++q)
+        for (int k = 0; k < nq; ++k) {
+            const int p = q * nq + k;
+            tq[p] = (double)((long double)tau[k] + 0.5L * ((long double)tau[k + 1] - (long double)tau[k]) * (gx[q] + 1.0L));
+            const long double s = tq[p];
+            long double S = 0.0L, T = 0.0L;
+            for (int j = 0; j < M; ++j) {
+                lam[j] = sw[j] / (s - (long double)tau[j]);
+                S += lam[j];
+                T += lam[j] / (s - (long double)tau[j]);
+            }
+            for (int j = 0; j < M; ++j) {
+                const long double e = lam[j] / S;
+                E[(size_t)p * M + j] = (double)e;
+                Ed[(size_t)p * M + j] = (double)((e * T - lam[j] / (s - (long double)tau[j])) / S);
+            }
+        }
+    return EMI_OK;
+}
+
 // One polygon edge a->b as an ellipse keep-out record.  The reference evaluates
 // these constants inside the node loop (etol_psopt_example1.cpp:163-176); they
 // depend only on the XML, so they are computed once here -- same operations,

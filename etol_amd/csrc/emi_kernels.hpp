@@ -95,6 +95,31 @@ hipError_t launch_adjoint_nodes(const AdjointArgs& a, hipStream_t s);
 hipError_t launch_adjoint_add(const double* dGop, double* dG, int B, int ns, int nv, int M, hipStream_t s);
 hipError_t launch_kkt_certificate(const CertArgs& a, hipStream_t s);
 
+// the relative local ODE error of a batch (emi_ode_error.hip; the model's residual kernel: emi_node_kernels.hpp)
+// out[r][c] = sum_j V[r][j] OP[c][j]: V [R][K] rows one after the other, OP [N][ldk] (ldk even, >= K, rows zero padded), out rows
+// ldo long, columns N .. ldo-1 untouched
+struct InterpOpArgs {
+    const double* V;
+    const double* OP;
+    double* out;
+    int R, K, N, ldk, ldo;
+};
+hipError_t launch_interp_op(const InterpOpArgs& a, hipStream_t s);
+// dst[k][j] = D[k][j], rows padded with a zero to the even ldk: the D block of the stacked operator [E | E' | D]
+hipError_t launch_ode_copy_D(const double* D, double* dst, int M, int ldk, hipStream_t s);
+hipError_t launch_ode_resid(int model, const OdeResidArgs<double>& a, hipStream_t s);
+struct RtcModel;
+hipError_t rtc_launch_ode_resid(RtcModel* m, const OdeResidArgs<double>& a, hipStream_t s);
+struct OdeFinishArgs {
+    const double* X;        // [B][ns][M]
+    const double* Zs;       // [B*ns][lds]: the D x block starts at column dcol
+    const double* eta;      // [B][ns][M-1]
+    double* err;            // [B]
+    int B, M, ns, lds, dcol;
+    double h;
+};
+hipError_t launch_ode_finish(const OdeFinishArgs& a, hipStream_t s);
+
 // node blocks of the Newton step, assembled and made positive definite over [instance][node] (emi_kkt_blocks.hip)
 struct BlocksArgs {
     const double *H, *VALS, *Sigma, *SigT;      // [B][nh][M], [B][nvals][M], [B][nv][M], [B][np][M]

@@ -420,4 +420,54 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(HessArgs<T> 
     for (int q = 0; q < NH; ++q) Hb[(size_t)q * M + k] = H[q];
 }
 
+// ---------------------------------------------------------------------------
+// KO: ODE residual of the interpolated trajectory, integrated over every mesh interval (include/emi355x.h, emi_ode_error_*)
+//   eta[b][i][k] = (tau_{k+1} - tau_k)/2 h sum_q g_q | (E' x_i)(s_p) / h - f_i(z~(s_p), t_p) |,  p = q (M-1) + k
+// One thread per (instance, interval): for each of the five Gauss points the NV interpolated values and NS derivatives are
+// loaded coalesced along k (the point order is q-major), the controls clipped, f evaluated.  Sums in ascending q; a NaN anywhere
+// in the inputs of an interval stays in its eta.  No LDS.
+// ---------------------------------------------------------------------------
+template <typename T, class Model>
+__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_kernel(OdeResidArgs<T> a) {
+    constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV;
+    const int b = blockIdx.y, M = a.M, nq = M - 1;
+    const int k = blockIdx.x * EMI_NODE_THREADS + threadIdx.x;
+    if (k >= nq) return;
+    // 5-point Gauss-Legendre weights on [-1, 1]
+    const T g[5] = {T(0.2369268850561891), T(0.4786286704993665), T(0.5688888888888889), T(0.4786286704993665), T(0.2369268850561891)};
+    const int np = 5 * nq;
+    const T* __restrict__ zs = a.Zs + (size_t)b * NS * a.lds + k;
+    const T* __restrict__ zc = a.Zc + (size_t)b * NC * a.ldc + k;
+    T acc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) acc[i] = T(0);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const int p = q * nq;
+        T z[NV], f[NS], xd[NS];
+#pragma unroll
+        for (int v = 0; v < NS; ++v) {
+            z[v] = zs[(size_t)v * a.lds + p];
+            xd[v] = zs[(size_t)v * a.lds + np + p] / a.h;
+        }
+#pragma unroll
+        for (int v = 0; v < NC; ++v) {
+            T u = zc[(size_t)v * a.ldc + p];
+            if (a.ul && u - u == T(0)) {    // a finite value is clipped; a NaN or an infinity stays, and with it the estimate is not finite
+                const T lo = a.ul[v], up = a.uu[v];
+                u = u < lo ? lo : u;
+                u = u > up ? up : u;
+            }
+            z[NS + v] = u;
+        }
+        Model::f(a.P, z, a.tq[p + k], f);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) acc[i] += g[q] * fabs(xd[i] - f[i]);
+    }
+    const T sc = a.scale[k];
+    T* __restrict__ eo = a.eta + (size_t)b * NS * nq + k;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) eo[(size_t)i * nq] = sc * acc[i];
+}
+
 }  // namespace emi

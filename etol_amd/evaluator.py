@@ -644,6 +644,53 @@ class Evaluator:
         fields = [n for n, _ in L.IpmResult._fields_]
         return X, U, LamF, LamC, [[{n: getattr(res[r * B + b], n) for n in fields} for b in range(B)] for r in range(len(rungs))]
 
+    # ---- relative local ODE error of the batch on the collocation mesh (emi_ode_error_*, emi_interp_dev) ------------------------
+    @staticmethod
+    def ode_error_operator(M, mesh=None):
+        """(E, Ed, tq): interpolation operator and its tau-derivative [5 (M-1)][M] at the Gauss points tq [5 (M-1)] of the mesh
+        intervals, point q (M-1) + k = Gauss point q of interval k (host, emi_ode_error_operator); mesh: (tau, w, ..) of another
+        node set than lgl(M)"""
+        lib = L.load()
+        tau, w = (np.ascontiguousarray(a, dtype=np.float64) for a in (mesh if mesh is not None else lgl(M))[:2])
+        n = 5 * (int(M) - 1)
+        E, Ed, tq = np.empty((n, int(M))), np.empty((n, int(M))), np.empty(n)
+        L.check(lib.emi_ode_error_operator(int(M), _dp(tau), _dp(w), _dp(E), _dp(Ed), _dp(tq)), what="emi_ode_error_operator")
+        return E, Ed, tq
+
+    def interp(self, OP, V, K=None, out=None):
+        """out [.., :N] = V [.., K] OP[:, :K]^T on the matrix pipe (emi_interp_dev): OP [N][ldk] with ldk even and its rows zero
+        padded beyond K (default K = ldk), torch tensors, float64; out's rows may be longer than N, the rest is not written;
+        asynchronous"""
+        N, ldk = OP.shape
+        K = int(ldk if K is None else K)
+        assert V.shape[-1] == K and OP.is_contiguous() and V.is_contiguous()
+        R = V.numel() // K
+        if out is None:
+            out = torch.empty(tuple(V.shape[:-1]) + (N,), dtype=torch.float64, device=V.device)
+        assert out.is_contiguous() and out.numel() == R * out.shape[-1]
+        self._ck(self.lib.emi_interp_dev(self.ctx, K, int(N), int(ldk), C.c_void_p(OP.data_ptr()), C.c_void_p(V.data_ptr()), int(R),
+                                         int(out.shape[-1]), C.c_void_p(out.data_ptr())), "emi_interp_dev")
+        return out
+
+    def ode_error(self, X, U, ul=None, uu=None, eta=True, dev=True):
+        """(err [B], eta [B][ns][M-1] or None): the relative local ODE error of X [B][ns][M], U [B][nc][M] on the context's
+        collocation mesh (include/emi355x.h, emi_ode_error_*); ul, uu [nc]: the controls' bounds the interpolated controls are
+        clipped to.  dev=True: torch tensors on this device, asynchronous; dev=False: contiguous float64 numpy arrays."""
+        lay = self.layout
+        bd = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (ul, uu)]
+        pb = [None if a is None else _dp(a) for a in bd]
+        if dev:
+            kw = dict(dtype=torch.float64, device=X.device)
+            err = torch.empty((lay.B,), **kw)
+            Eta = torch.empty((lay.B, lay.ns, lay.M - 1), **kw) if eta else None
+        else:
+            assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in (X, U))
+            err, Eta = np.empty(lay.B), (np.empty((lay.B, lay.ns, lay.M - 1)) if eta else None)
+        A = self._ipm_addr
+        fn = self.lib.emi_ode_error_dev if dev else self.lib.emi_ode_error_host
+        self._ck(fn(self.ctx, A(X), A(U), pb[0], pb[1], A(Eta), A(err)), fn.__name__)
+        return err, Eta
+
     # ---- measurement -----------------------------------------------------------
     def timer_start(self):
         self._ck(self.lib.emi_timer_start(self.ctx), "emi_timer_start")

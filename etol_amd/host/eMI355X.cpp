@@ -754,6 +754,19 @@ double eMI355X::odeError(const std::vector<double>& z, std::vector<double>* z_fi
     const size_t ns = P.nstates, nc = P.ncontrols, nv = ns + nc, M = P.nodes;
     static const double gx[5] = {-0.9061798459386640, -0.5384693101056831, 0.0, 0.5384693101056831, 0.9061798459386640};
     static const double gw[5] = {0.2369268850561891, 0.4786286704993665, 0.5688888888888889, 0.4786286704993665, 0.2369268850561891};
+    if (_algorithm.ode_error == "device") {
+        // the whole estimate on the device, on the collocation mesh the context is on: nothing of the mesh goes up or changes
+        if (P.ndelayed > 0) die("Alg::ode_error = \"device\": problems with delays are not taken (f reads the delayed values); use \"host\"");
+        emi_ctx_t c = _dev->ctx;
+        if (_dev->nodes != (int)M) configureDevice(_dev.get());
+        double err = 0;
+        must(emi_ode_error_host(c, z.data(), z.data() + ns * M, nc ? P.control_lower.data() : nullptr, nc ? P.control_upper.data() : nullptr,
+                                nullptr, &err), c, "emi_ode_error_host");       // (stages z and calls emi_ode_error_dev, batch of 1)
+        if (z_fine) z_fine->clear();
+        if (nodes_fine) *nodes_fine = 0;
+        return err;
+    }
+    if (_algorithm.ode_error != "host") die("Alg::ode_error must be \"host\" or \"device\"");
     const size_t Q = 5, Mq = (M - 1) * Q;
     const double h = (P.tf - P.t0) / 2.0;
     std::vector<double> tq(Mq), wq(Mq, 0.0);

@@ -115,6 +115,10 @@ struct Alg {
     std::string node_blocks = "host";              // node blocks of the Newton step (assembly, Cholesky screen, eigen-fix): "host", or
                                                    // "device" (emi_kkt_blocks_dev + emi_kkt_factor_dev: the blocks stay in HBM for the
                                                    // factorisation) where the device factorises one problem at a time; else the host loop
+    std::string ode_error = "host";                // relative local ODE error of a mesh (odeError, the refinement criterion): "host" (interpolation
+                                                   // on the host, f at the points on a points-only mesh of the context, which is then put back on
+                                                   // the collocation mesh), or "device" (emi_ode_error_dev on the context's collocation mesh as it
+                                                   // stands: no mesh change; problems without delays)
     int nlp_iter_max = 200;                        // per NLP solve (one mesh, one start), as ePSOPT.cpp:66
     bool plan_second_start = true;                 // the route planned through the free space of the static keep-outs (clearance-weighted: planned_path_guess) is the
                                                    // second start of a mesh-ladder climb, before the bent lines (false: the last cold-start attempt only).  256-scenario

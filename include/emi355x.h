@@ -580,6 +580,40 @@ int emi_ipm_solve_ladder_dev(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* ru
                              const void* dU0, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
 int emi_ipm_solve_ladder_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const double* X0,
                               const double* U0, double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results);
+/* ---- Relative local ODE error of the context's batch on its collocation mesh: is the mesh fine enough? --------------------------
+ *
+ * The quantity PSOPT's mesh refinement compares with ode_tolerance (the reference's ePSOPT.cpp:69-71), for every instance of the
+ * batch at once (csrc/emi_ode_error.hip, DESIGN.md sections 3 and 6).  Mesh tau_0 < .. < tau_{M-1}, weights w, h = (tf - t0) / 2.
+ *   points          s_p, p = q (M-1) + k: the 5 Gauss-Legendre points q of the interval [tau_k, tau_k+1] (q-major: consecutive k
+ *                   are consecutive in memory); a Gauss point never coincides with a node
+ *   interpolation   E[p][j] = lam_j(s_p) / sum_i lam_i(s_p),  lam_j(s) = (-1)^j sqrt(w_j) / (s - tau_j)
+ *   derivative      E'[p][j] = (E[p][j] sum_i lam_i / (s_p - tau_i) - lam_j / (s_p - tau_j)) / sum_i lam_i   (d/dtau of the interpolant)
+ *   values          z~ = E z for all ns + nc variables of instance b; controls clipped to [ul_j, uu_j] where the caller gives
+ *                   bounds;  x~' = E' x / h
+ *   model           f = Model::f(params, z~, t0 + h (s_p + 1))
+ *   interval error  eta[b][i][k] = (tau_k+1 - tau_k) / 2 * h * sum_q g_q |x~'_i - f_i|      (g: the Gauss weights, sum 2)
+ *   state scale     W[b][i] = max_k max(|x_ik|, |(D x)_ik| / h)
+ *   estimate        err[b] = max_{i,k} eta[b][i][k] / (W[b][i] + 1)
+ * A trajectory that is not finite gives a non-finite err[b], for that instance only (the maxima carry a NaN; an interpolated
+ * control that is not finite is not clipped).
+ *
+ * emi_ode_error_operator (host, no device needed): E, Ed [5 (M-1)][M] row-major and tq [5 (M-1)] = s_p in the point order above;
+ * the operator is that of the rounded tq, formed in extended precision.  EMI_ERR_ARG: M < 2 or a NULL pointer.
+ * emi_interp_dev: the product alone, dOut[r][c] = sum_j dV[r][j] dOP[c][j] for R rows of K values and N outputs, on the matrix
+ * pipe; dOP [N][ldk] with ldk even and >= K, rows padded with zeros, on a 16-byte boundary; dOut rows ldo >= N long, columns
+ * N .. ldo-1 are not written.  Needs no mesh, model or batch; R = 0 is a no-op; K >= 2, N >= 1.  One writer per output, sums
+ * in ascending j: a row's bits depend on that row and dOP alone, two calls give the same bits.  Asynchronous.
+ * emi_ode_error_dev: dX [B][ns][M], dU [B][nc][M] -> dErr [B] and, where dEta is not NULL, dEta [B][ns][M-1].  ul, uu: host [nc]
+ * arrays (kept in a context buffer), a NULL pair means no clip.  Asynchronous on the context's stream (the first call on a mesh
+ * builds the operator: 2 * 5 (M-1) M doubles go up once).  The operator, the point times and the workspace are device arrays of
+ * the context (grown as needed, freed with it).  The context's mesh, tables and every other piece of state are as before the call.
+ * EMI_ERR_UNSUPPORTED: f32 context; context with delays (f reads the delayed values).  EMI_ERR_STATE: points-only mesh; mesh,
+ * model or batch not set.  Track and record tables play no part and are accepted as they are.  The _host form takes host arrays
+ * and synchronises.                                                                                                             */
+int emi_ode_error_operator(int M, const double* tau, const double* w, double* E, double* Ed, double* tq);
+int emi_interp_dev(emi_ctx_t ctx, int K, int N, int ldk, const void* dOP, const void* dV, int R, int ldo, void* dOut);
+int emi_ode_error_dev(emi_ctx_t ctx, const void* dX, const void* dU, const double* ul, const double* uu, void* dEta, void* dErr);
+int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const double* ul, const double* uu, double* Eta, double* Err);
 /* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
  * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
  * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
