@@ -81,6 +81,17 @@ class IpmRung(C.Structure):
     _fields_ = [("M", C.c_int), ("bd", IpmBounds), ("recs", _D), ("opt", IpmOptions), ("repair", C.c_int)]
 
 
+class IpmRefine(C.Structure):
+    """emi_ipm_refine_t: when an instance of emi_ipm_solve_refine_* retires"""
+    _fields_ = [("ode_tol", C.c_double), ("first_check", C.c_int), ("ul", _D), ("uu", _D)]
+
+
+class IpmRefineResult(C.Structure):
+    """emi_ipm_refine_result_t: where and how one instance of emi_ipm_solve_refine_* retired"""
+    _fields_ = [("rung", C.c_int), ("verdict", C.c_int), ("rungs_solved", C.c_int), ("err", C.c_double)]
+
+
+REFINE_MET, REFINE_NOT_MET, REFINE_FELL_BACK, REFINE_FAILED = range(4)
 IPM_RULE_RESIDUAL = 1   # emi_ipm_options_t.rules: residual-based acceptance of the full step and the crawl rule
 IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
 
@@ -141,6 +152,13 @@ SYMBOLS = {
     "emi_interp_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "emi_ode_error_dev": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
     "emi_ode_error_host": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
+    "emi_ipm_refine_decide": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _I]),
+    "emi_prolong_rows_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "emi_shard_move_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _I, C.POINTER(_P), _I, C.POINTER(_P), _I, C.c_int]),
+    "emi_ipm_solve_refine_dev": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), _P, _P, C.c_int,
+                                           _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
+    "emi_ipm_solve_refine_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), _P, _P, C.c_int,
+                                            _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

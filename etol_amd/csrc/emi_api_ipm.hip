@@ -1,6 +1,6 @@
 // emi_api_ipm.hip -- the interior-point part of the C ABI: the array arithmetic of an iteration over [instance][node] (emi_ipm.hip)
 // with its _host forms, the lock-step solve of a context's whole batch (driver: emi_ipm_solve.hip) and the mesh ladder over it
-// (kernels and driver: emi_ipm_ladder.hip).
+// (kernels and driver: emi_ipm_ladder.hip), with and without refinement.
 #include "emi_ctx.hpp"
 
 using namespace emi_api;
@@ -535,6 +535,89 @@ int emi_ipm_solve_ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* run
         g.bd.zu = s.place(g.bd.zu, bytes, true, false);
     }
     IPM_HOST_END(emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
+}
+
+// ---- the ladder with refinement: instances that meet the ODE tolerance leave the batch (kernels and driver: emi_ipm_ladder.hip) -------
+int emi_prolong_rows_dev(emi_ctx_t c, int Mc, int Mf, const void* dPT, const void* dVc, int R, const void* dRowMap, void* dVf) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_prolong_rows_dev: f64 contexts only");
+    if (Mc < 2 || Mf < 2 || R < 0 || !dPT || (R > 0 && (!dVc || !dVf))) return fail(c, EMI_ERR_ARG, "emi_prolong_rows_dev: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, emi::launch_prolong_rows((const double*)dPT, (const double*)dVc, (const int*)dRowMap, 1, (double*)dVf, Mc, Mf, R, c->stream));
+    return EMI_OK;
+}
+
+int emi_shard_move_dev(emi_ctx_t c, int n, const void* dSrcIdx, const void* dDstIdx, int narrays, const int* rows, const void* const* src,
+                       const int* src_ld, void* const* dst, const int* dst_ld, int len) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_shard_move_dev: f64 contexts only");
+    if (n < 0 || len < 0 || narrays < 1 || narrays > emi::SHARD_MOVE_ARRAYS || !rows || !src || !src_ld || !dst || !dst_ld)
+        return fail(c, EMI_ERR_ARG, "emi_shard_move_dev: bad argument (n >= 0, len >= 0, 1 .. %d arrays)", emi::SHARD_MOVE_ARRAYS);
+    emi::ShardMoveArgs a{};
+    for (int q = 0; q < narrays; ++q) {
+        if (rows[q] < 0 || src_ld[q] < len || dst_ld[q] < len || (rows[q] > 0 && n > 0 && len > 0 && (!src[q] || !dst[q])))
+            return fail(c, EMI_ERR_ARG, "emi_shard_move_dev: array %d: rows >= 0, leading dimensions >= len, no NULL array", q);
+        a.src[q] = (const double*)src[q]; a.dst[q] = (double*)dst[q]; a.rows[q] = rows[q]; a.sld[q] = src_ld[q]; a.dld[q] = dst_ld[q];
+    }
+    a.sidx = (const int*)dSrcIdx; a.didx = (const int*)dDstIdx; a.n = n; a.narrays = narrays; a.len = len;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, emi::launch_shard_move(a, c->stream));
+    return EMI_OK;
+}
+
+namespace {
+
+// what the refinement refuses beyond the ladder's list
+int refine_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t* rungs, const emi_ipm_refine_t* rf, int ldm, const void* err,
+                 const void* out) {
+    EMI_TRY(ladder_check(c, what, nrungs, rungs));
+    if (!rf || !err || !out) return fail(c, EMI_ERR_ARG, "%s: null argument", what);
+    if (!(rf->ode_tol >= 0.0)) return fail(c, EMI_ERR_ARG, "%s: ode_tol must be >= 0", what);
+    if (rf->first_check < 0 || rf->first_check >= nrungs) return fail(c, EMI_ERR_ARG, "%s: first_check %d outside the %d rungs", what, rf->first_check, nrungs);
+    if ((rf->ul == nullptr) != (rf->uu == nullptr)) return fail(c, EMI_ERR_ARG, "%s: ul and uu come as a pair", what);
+    if (c->B > 65535) return fail(c, EMI_ERR_UNSUPPORTED, "%s: up to 65535 instances", what);
+    for (int r = 0; r < nrungs; ++r) {
+        if (rungs[r].M > ldm) return fail(c, EMI_ERR_ARG, "%s: ldm %d is below rung %d's %d nodes", what, ldm, r, rungs[r].M);
+        if (rungs[r].bd.nsets != 1 && rungs[r].bd.nsets != c->B)
+            return fail(c, EMI_ERR_ARG, "%s: rung %d's bounds have %d sets (1 or the batch, %d)", what, r, rungs[r].bd.nsets, c->B);
+    }
+    return EMI_OK;
+}
+
+}  // namespace
+
+int emi_ipm_solve_refine_dev(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                             const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC,
+                             emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(refine_check(c, "emi_ipm_solve_refine_dev", nrungs, rungs, rf, ldm, err, out));
+    const int np = np_total(c);
+    if (!dX0 || !dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np > 0 && !dLamC) || !results)
+        return fail(c, EMI_ERR_ARG, "emi_ipm_solve_refine_dev: null argument");
+    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_ipm_solve_refine_dev: tf must exceed t0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return emi::ipm_solve_refine(c, nrungs, rungs, t0, tf, *rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC, results, err, out);
+}
+
+int emi_ipm_solve_refine_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                              const double* X0, const double* U0, int ldm, double* X, double* U, double* LamF, double* LamC,
+                              emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(refine_check(c, "emi_ipm_solve_refine_host", nrungs, rungs, rf, ldm, err, out));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostStager s(c);
+    const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, L = (size_t)ldm;
+    const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
+    // (in and out: the columns beyond an instance's mesh are the caller's)
+    void *dX = s.place(X, B * c->ns * L * 8, true, true), *dU = s.place(U, B * c->nc * L * 8, true, true);
+    void *dLF = s.place(LamF, B * c->ns * L * 8, true, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * L * 8, true, true);
+    std::vector<emi_ipm_rung_t> dr(rungs, rungs + nrungs);
+    for (emi_ipm_rung_t& g : dr) {
+        const size_t bytes = (size_t)std::max(g.bd.nsets, 0) * nv * (size_t)g.M * 8;
+        g.bd.zl = s.place(g.bd.zl, bytes, true, false);
+        g.bd.zu = s.place(g.bd.zu, bytes, true, false);
+    }
+    IPM_HOST_END(emi_ipm_solve_refine_dev(c, nrungs, dr.data(), t0, tf, rf, dX0, dU0, ldm, dX, dU, dLF, dLC, results, err, out));
 }
 
 }  // extern "C"

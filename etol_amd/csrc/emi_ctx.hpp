@@ -147,7 +147,7 @@ struct emi_ctx_s {
     std::vector<double> ipm_crow_h;     // [5][np]: cl, cu, cscale cl, cscale cu, cscale (what ipm_crow holds)
     emi::DeviceArray<double> ipm_crow, ipm_part;
     emi::IpmSolveWs* ipm_solve = nullptr;   // device arrays of the lock-step driver (emi_ipm_solve_shard_*), created at its first call
-    emi::IpmLadderWs* ipm_ladder = nullptr; // ... and of the mesh ladder over it (emi_ipm_solve_ladder_*)
+    emi::IpmLadderWs* ipm_ladder = nullptr; // ... and of the mesh ladder over it (emi_ipm_solve_ladder_*, emi_ipm_solve_refine_*)
     bool path_has_track = false;            // the record table holds a row of kind EMI_PATH_TRACK
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;

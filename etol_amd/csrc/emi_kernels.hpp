@@ -258,5 +258,22 @@ struct IpmLadderWs;
 void ipm_ladder_destroy(IpmLadderWs* w);
 int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
                      void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
+// the ladder with refinement (emi_ipm_solve_refine_*): the prolongation with a source row per output row, Vf[r] = P Vc[src(r)] with
+// src(r) = map[r / group] * group + r % group (map null: src(r) = r; group: rows that share one entry of the map); the move of the
+// instances of a list between two sets of arrays [instance][rows][ld], entry i: instance sidx[i] of src -> instance didx[i] of dst
+// (a null list: i), the first `len` values of every row; and the driver, which retires instances rung by rung
+hipError_t launch_prolong_rows(const double* PT, const double* Vc, const int* map, int group, double* Vf, int Mc, int Mf, int R, hipStream_t s);
+constexpr int SHARD_MOVE_ARRAYS = 4;
+struct ShardMoveArgs {
+    const double* src[SHARD_MOVE_ARRAYS];
+    double* dst[SHARD_MOVE_ARRAYS];
+    int rows[SHARD_MOVE_ARRAYS], sld[SHARD_MOVE_ARRAYS], dld[SHARD_MOVE_ARRAYS];
+    const int *sidx, *didx;
+    int n, narrays, len, first;         // first: the list entry of blockIdx.y == 0 (lists beyond one grid go out in pieces)
+};
+hipError_t launch_shard_move(ShardMoveArgs a, hipStream_t s);
+int ipm_solve_refine(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t& rf, const void* dX0,
+                     const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results, double* err,
+                     emi_ipm_refine_result_t* out);
 
 }  // namespace emi

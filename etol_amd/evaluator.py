@@ -600,14 +600,8 @@ class Evaluator:
         """interior nodes of X [B][ns][M] (device tensor, in place) inside a keep-out of the record table moved out of it; asynchronous"""
         self._ck(self.lib.emi_repair_guess_dev(self.ctx, C.c_void_p(X.data_ptr()) if X is not None else None), "emi_repair_guess_dev")
 
-    def ipm_solve_ladder(self, rungs, t0, tf, X0, U0, dev=True):
-        """rungs: list of dict M, bounds (as for the ipm_* calls, at this M), and optionally recs (record table of emi_set_path's
-        shape), options (dict of emi_ipm_options_t fields), repair.  X0 [B][ns][M_0], U0 [B][nc][M_0] are read only.  dev=True: torch
-        tensors on this device; dev=False: contiguous float64 numpy arrays.  Returns (X, U, LamF, LamC, results[rung][b]) on the last
-        rung's mesh, which is the context's mesh afterwards."""
-        lay = self.layout
-        B, ns, nc, npth, Ml = lay.B, lay.ns, lay.nc, lay.np, int(rungs[-1]["M"]) if rungs else 0
-        keep = []
+    def _ipm_rungs(self, rungs, keep):
+        """the emi_ipm_rung_t array of a list of dict M, bounds, recs, options, repair (ipm_solve_ladder); keep: what must outlive the call"""
         arr = (L.IpmRung * max(1, len(rungs)))()
         for g, r in zip(arr, rungs):
             g.M = int(r["M"])
@@ -626,6 +620,17 @@ class Evaluator:
             for k, v in (r.get("options") or {}).items():
                 setattr(g.opt, k, v)
             g.repair = int(bool(r.get("repair")))
+        return arr
+
+    def ipm_solve_ladder(self, rungs, t0, tf, X0, U0, dev=True):
+        """rungs: list of dict M, bounds (as for the ipm_* calls, at this M), and optionally recs (record table of emi_set_path's
+        shape), options (dict of emi_ipm_options_t fields), repair.  X0 [B][ns][M_0], U0 [B][nc][M_0] are read only.  dev=True: torch
+        tensors on this device; dev=False: contiguous float64 numpy arrays.  Returns (X, U, LamF, LamC, results[rung][b]) on the last
+        rung's mesh, which is the context's mesh afterwards."""
+        lay = self.layout
+        B, ns, nc, npth, Ml = lay.B, lay.ns, lay.nc, lay.np, int(rungs[-1]["M"]) if rungs else 0
+        keep = []
+        arr = self._ipm_rungs(rungs, keep)
         if dev:
             kw = dict(dtype=torch.float64, device=X0.device)
             new = lambda *s: torch.zeros(s, **kw)
@@ -643,6 +648,90 @@ class Evaluator:
         self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
         fields = [n for n, _ in L.IpmResult._fields_]
         return X, U, LamF, LamC, [[{n: getattr(res[r * B + b], n) for n in fields} for b in range(B)] for r in range(len(rungs))]
+
+    # ---- the ladder with refinement: instances that meet the ODE tolerance leave the batch (emi_ipm_solve_refine_*) -------------
+    @staticmethod
+    def refine_decide(status, err, ode_tol, has_good, is_last):
+        """(retires, verdict): the rule of emi_ipm_solve_refine_* for one instance after a solve (host, emi_ipm_refine_decide)"""
+        v = C.c_int(-1)
+        r = L.load().emi_ipm_refine_decide(int(status), float(err), float(ode_tol), int(bool(has_good)), int(bool(is_last)), C.byref(v))
+        return bool(r), v.value
+
+    def prolong_rows(self, PT, Vc, row_map=None, Vf=None):
+        """Vf [R][Mf]: row r = P Vc[row_map[r]] (row_map: int32 device tensor [R], None: the identity and R = the rows of Vc);
+        torch tensors, float64; asynchronous (emi_prolong_rows_dev)"""
+        Mc, Mf = PT.shape
+        assert Vc.shape[-1] == Mc and PT.is_contiguous() and Vc.is_contiguous()
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous()
+        R = Vc.numel() // Mc if row_map is None else row_map.numel()
+        if Vf is None:
+            Vf = torch.empty((R, Mf), dtype=torch.float64, device=Vc.device)
+        assert Vf.is_contiguous() and Vf.numel() == R * Mf
+        self._ck(self.lib.emi_prolong_rows_dev(self.ctx, int(Mc), int(Mf), C.c_void_p(PT.data_ptr()), C.c_void_p(Vc.data_ptr()), int(R),
+                                               self._ipm_addr(row_map), C.c_void_p(Vf.data_ptr())), "emi_prolong_rows_dev")
+        return Vf
+
+    def shard_move(self, src, dst, length, src_idx=None, dst_idx=None, n=None):
+        """the instances of a list moved between up to 4 pairs of arrays: src[a] [.., rows_a, src_ld_a] -> dst[a] [.., rows_a, dst_ld_a]
+        (float64 device tensors), entry i: the first `length` values of every row of instance src_idx[i] to instance dst_idx[i]
+        (int32 device tensors, None: 0 .. n-1); asynchronous (emi_shard_move_dev)"""
+        na = len(src)
+        assert na == len(dst) and all(a.is_contiguous() and a.dtype == torch.float64 for a in list(src) + list(dst))
+        for ix in (src_idx, dst_idx):
+            assert ix is None or (ix.dtype == torch.int32 and ix.is_contiguous())
+        if n is None:
+            n = next((ix.numel() for ix in (src_idx, dst_idx) if ix is not None), src[0].shape[0] if na else 0)
+        ints = lambda v: (C.c_int * max(1, na))(*v)
+        ptrs = lambda ts: (C.c_void_p * max(1, na))(*[t.data_ptr() for t in ts])
+        rows = [int(a.shape[-2]) for a in src]
+        assert rows == [int(a.shape[-2]) for a in dst]
+        self._ck(self.lib.emi_shard_move_dev(self.ctx, int(n), self._ipm_addr(src_idx), self._ipm_addr(dst_idx), na, ints(rows), ptrs(src),
+                                             ints([a.shape[-1] for a in src]), ptrs(dst), ints([a.shape[-1] for a in dst]), int(length)),
+                 "emi_shard_move_dev")
+
+    def ipm_solve_refine(self, rungs, t0, tf, X0, U0, ode_tol, first_check=0, ul=None, uu=None, ldm=None, out=None, dev=True):
+        """The ladder of ipm_solve_ladder with the instances retired as they meet ode_tol from rung first_check on (include/emi355x.h:
+        emi_ipm_solve_refine_*).  out: (X, U, LamF, LamC) [B][rows][ldm] to write into (the columns beyond an instance's mesh keep
+        their bits), None: zeros with ldm = the largest rung.  Returns (X, U, LamF, LamC, results[rung][b], err [rungs][B],
+        summary[b] = dict rung, verdict, rungs_solved, err).  The context is on the last solved rung's mesh afterwards."""
+        lay = self.layout
+        B, ns, nc, npth = lay.B, lay.ns, lay.nc, lay.np
+        keep = []
+        arr = self._ipm_rungs(rungs, keep)
+        ldm = int(ldm if ldm is not None else (out[0].shape[-1] if out is not None else max([int(r["M"]) for r in rungs] or [0])))
+        if out is not None:
+            X, U, LamF, LamC = out
+        elif dev:
+            kw = dict(dtype=torch.float64, device=X0.device)
+            X, U, LamF, LamC = (torch.zeros((B, r, ldm), **kw) for r in (ns, nc, ns, npth))
+        else:
+            X, U, LamF, LamC = (np.zeros((B, r, ldm)) for r in (ns, nc, ns, npth))
+        if not dev:
+            assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in (X0, U0, X, U, LamF, LamC))
+        rf = L.IpmRefine()
+        rf.ode_tol, rf.first_check = float(ode_tol), int(first_check)
+        for f, a in (("ul", ul), ("uu", uu)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                keep.append(a)
+                setattr(rf, f, _dp(a))
+        nr = len(rungs)
+        res = (L.IpmResult * max(1, nr * B))()
+        err = np.full((max(1, nr), B), np.nan)
+        summ = (L.IpmRefineResult * B)()
+        A = self._ipm_addr
+        fn = self.lib.emi_ipm_solve_refine_dev if dev else self.lib.emi_ipm_solve_refine_host
+        st = fn(self.ctx, nr, arr, float(t0), float(tf), C.byref(rf), A(X0), A(U0), ldm, A(X), A(U), A(LamF), A(LamC) if npth else None, res,
+                _dp(err), summ)
+        self._changed()
+        self._ck(st, fn.__name__)
+        Ml = self.layout.M
+        self.tau, self.w, self.D = lgl(Ml)
+        self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
+        fields = [n for n, _ in L.IpmResult._fields_]
+        results = [[{n: getattr(res[r * B + b], n) for n in fields} for b in range(B)] for r in range(nr)]
+        return X, U, LamF, LamC, results, err[:nr], [{n: getattr(q, n) for n, _ in L.IpmRefineResult._fields_} for q in summ]
 
     # ---- relative local ODE error of the batch on the collocation mesh (emi_ode_error_*, emi_interp_dev) ------------------------
     @staticmethod

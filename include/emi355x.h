@@ -614,6 +614,78 @@ int emi_ode_error_operator(int M, const double* tau, const double* w, double* E,
 int emi_interp_dev(emi_ctx_t ctx, int K, int N, int ldk, const void* dOP, const void* dV, int R, int ldo, void* dOut);
 int emi_ode_error_dev(emi_ctx_t ctx, const void* dX, const void* dU, const double* ul, const double* uu, void* dEta, void* dErr);
 int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const double* ul, const double* uu, double* Eta, double* Err);
+/* ---- Lock-step MESH REFINEMENT: the ladder, with the instances that meet the ODE tolerance retired rung by rung -----------------
+ *
+ * PSOPT's automatic mesh refinement (solve, estimate the ODE error, add nodes, solve again until ode_tolerance holds: the loop of
+ * ETOL::eMI355X::solve, host/eMI355X.cpp) for a whole batch: B coarse starts in, every instance back on the mesh it retired on
+ * (csrc/emi_ipm_ladder.hip).  An instance that is done leaves the batch: the rest are compacted into a
+ * smaller batch of the same context and only those are solved on the next rung.  Nothing of a trajectory's size visits the host.
+ *
+ * emi_ipm_refine_decide (host, no device needed): the rule, for one instance after its solve on a rung r >= first_check.
+ *   ok = status is EMI_IPM_CONVERGED or EMI_IPM_ACCEPTABLE;  met = err is finite and err <= ode_tol (a NaN or an infinite err: missed)
+ *   ok and met                    retires on r,     EMI_REFINE_MET
+ *   ok, missed, r the last rung   retires on r,     EMI_REFINE_NOT_MET
+ *   ok, missed, not the last      climbs; its rung-r iterate and multipliers are its good solution (*verdict = EMI_REFINE_NOT_MET,
+ *                                 what it would carry if the ladder ended here)
+ *   not ok, has_good              retires with the good solution of rung r-1, EMI_REFINE_FELL_BACK: a refinement solve that fails
+ *                                 does not take the converged coarser solution with it
+ *   not ok, no good solution      retires on r with whatever the solve left, EMI_REFINE_FAILED
+ * Returns 1 where the instance retires, 0 where it climbs; verdict may be NULL.
+ * emi_prolong_rows_dev: emi_prolong_dev with the source row of output row r taken from a list, Vf[r] = P Vc[dRowMap[r]] (device
+ * ints, any values in [0, rows of dVc): a permutation compacts, a repeated value copies).  The same fused multiply-adds in ascending
+ * j: row r has the bits emi_prolong_dev gives for row dRowMap[r] alone; dRowMap NULL is the identity, the bits of emi_prolong_dev.
+ * emi_shard_move_dev: the instances of a list moved between two sets of up to 4 arrays in one launch.  Array a holds rows[a] rows
+ * per instance of src_ld[a] (source) / dst_ld[a] (destination) doubles; entry i of the list copies the first len values of every
+ * row of instance dSrcIdx[i] of src[a] to instance dDstIdx[i] of dst[a] (device ints; a NULL list is 0, 1, .., n-1).  No
+ * arithmetic: the copies are the source's bits; what the list does not name, and the columns from len on, keep every bit.  The
+ * destination instances of a list must differ and no destination may overlap a source.  n = 0 is a no-op; a list beyond 65535 entries
+ * goes out in more than one launch.  Both calls: asynchronous on the context's stream, no mesh, model or batch needed, f64 contexts
+ * only (EMI_ERR_UNSUPPORTED); EMI_ERR_ARG: a count below 0, narrays outside 1 .. 4, rows < 0, len beyond a leading dimension, a NULL array.
+ *
+ * emi_ipm_solve_refine_dev: with live = every instance at the start, per rung r = 0 .. nrungs-1 while anybody is live
+ *   1. emi_lgl and emi_set_mesh(M_r, .., t0, tf);
+ *   2. emi_set_batch(n) for the n live instances and emi_set_path with their rows of the record table (the context's table is read
+ *      back once at entry; a rung's recs, given for all B instances in the caller's numbering, replaces that copy);
+ *   3. from the second rung on, X and U of the live instances prolonged from the previous rung's compact iterate: the row map of
+ *      emi_prolong_rows_dev does the compaction in the same pass;
+ *   4. a rung's bounds with nsets == B are given in the caller's numbering: the sets of the live instances are gathered
+ *      (emi_shard_move_dev) once somebody has left;
+ *   5. emi_repair_guess_dev where asked for, emi_ipm_solve_shard_dev on the compact batch;
+ *   6. below rf->first_check every live instance climbs, as in the ladder call.  From first_check on: emi_ode_error_dev (clip rf->ul,
+ *      rf->uu) on the compact iterate, n doubles come down, emi_ipm_refine_decide per instance, and the retirees' X, U, LamF, LamC
+ *      go into the caller's arrays by emi_shard_move_dev (one launch for those that return this rung's iterate, one for those that
+ *      fall back to the previous rung's); a few ints per live instance go up.
+ * dX [B][ns][ldm], dU [B][nc][ldm], dLamF [B][ns][ldm], dLamC [B][np][ldm] with ldm >= the largest rung: instance b holds
+ * M_{out[b].rung} values per row, the columns beyond keep the caller's bits.  results[r][b]: what emi_ipm_solve_shard_dev reported,
+ * status -1 (all else zero) on a rung the instance did not solve.  err[r][b]: the estimate, NaN where none was taken.  out[b]: the
+ * rung the returned trajectory is on, the verdict, the number of rungs the instance was solved on, the estimate on the returned
+ * rung (NaN without one).  The starts dX0 [B][ns][M_0], dU0 [B][nc][M_0] are only read.  While nobody has retired the launches on the
+ * trajectories are those of emi_ipm_solve_ladder_dev (into arrays of the context) and every bit of an iterate is that call's; an
+ * instance solved in a compacted batch agrees with the same instance solved alone as two batch sizes agree in
+ * emi_ipm_solve_shard_dev.  Two identical calls give the same bits.  On return, also after an error, the context has batch B again and
+ * the full record table (that of the last rung which brought one); it is on the mesh of the last rung that was solved.  The
+ * compact iterates and multipliers of two consecutive rungs, the gathered bounds and the lists are device arrays of the context.
+ * Statuses: those of emi_ipm_solve_ladder_dev, and EMI_ERR_ARG: rf NULL, ode_tol negative or NaN, first_check outside
+ * 0 .. nrungs-1, one of ul / uu without the other, ldm below the largest rung, a rung whose bounds have nsets other than 1 or B, a
+ * NULL err or out.  Instances are never masked instead of compacted.  The _host form takes host arrays (every rung's zl, zu included;
+ * X, U, LamF, LamC go in and come out, so that the columns beyond an instance's mesh are the caller's) and synchronises.         */
+enum { EMI_REFINE_MET = 0, EMI_REFINE_NOT_MET = 1, EMI_REFINE_FELL_BACK = 2, EMI_REFINE_FAILED = 3 };
+typedef struct emi_ipm_refine {
+  double ode_tol;          /* retire when err <= ode_tol; 0 retires nobody early, +inf everybody who solved at first_check */
+  int first_check;         /* rungs below it are mesh-sequencing rungs: every live instance climbs, as in the ladder call */
+  const double *ul, *uu;   /* host [nc], the clip of emi_ode_error_dev; a NULL pair: none */
+} emi_ipm_refine_t;
+typedef struct emi_ipm_refine_result { int rung, verdict, rungs_solved; double err; } emi_ipm_refine_result_t;
+int emi_ipm_refine_decide(int status, double err, double ode_tol, int has_good, int is_last, int* verdict);
+int emi_prolong_rows_dev(emi_ctx_t ctx, int Mc, int Mf, const void* dPT, const void* dVc, int R, const void* dRowMap, void* dVf);
+int emi_shard_move_dev(emi_ctx_t ctx, int n, const void* dSrcIdx, const void* dDstIdx, int narrays, const int* rows,
+                       const void* const* src, const int* src_ld, void* const* dst, const int* dst_ld, int len);
+int emi_ipm_solve_refine_dev(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                             const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC,
+                             emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out);
+int emi_ipm_solve_refine_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                              const double* X0, const double* U0, int ldm, double* X, double* U, double* LamF, double* LamC,
+                              emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out);
 /* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
  * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
  * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
