@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-nlp check-ode-operator
+.PHONY: all lib host oracle clean check-keep-record check-nlp check-mesh-driver check-ode-operator
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -54,7 +54,7 @@ LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api
 $(LIBDIR)/libemi355x.so: $(LIB_OBJ:%=$(LIBDIR)/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
 
-HOST_SRC := $(HOST)/TrajectoryOptimizer.cpp $(HOST)/eMI355X.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_trace.cpp
+HOST_SRC := $(HOST)/TrajectoryOptimizer.cpp $(HOST)/eMI355X.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_mesh_driver.cpp $(HOST)/emi_trace.cpp
 HOST_HDR := $(wildcard include/ETOL/*.hpp) $(wildcard $(HOST)/*.hpp) include/emi355x.h
 
 # the host side of the Newton step (block eigen-decompositions, r x r Cholesky of the low-rank correction) wants AVX2
@@ -93,6 +93,18 @@ check-nlp: tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(HOST)/emi_n
 	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -I$(HOST) -o $(NLP_CHECK_OUT) tests/harness/nlp_sanitize_main.cpp $(HOST)/emi_nlp.cpp $(CSRC)/emi_host.cpp \
 		$(NLP_CHECK_OUT)_oracle.o -lm
 	$(NLP_CHECK_OUT)
+
+# the mesh strategy of solve() (emi_mesh_driver.cpp: ladder, restarts, retries, budget, refinement) as a stand-alone program under the
+# host sanitizers, with a scripted solver behind its host interface: no Python, no device (the device library is linked for the
+# symbols of eMI355X.cpp, whose guess builders the strategy calls; none of them is called).  -O0: the program decides, it does not compute
+MESH_CHECK_OUT ?= $(LIBDIR)/mesh_driver_check
+MESH_CHECK_SRC := tests/harness/mesh_driver_main.cpp $(HOST_SRC) $(CSRC)/emi_host.cpp
+$(MESH_CHECK_OUT)_obj/%.o: %.cpp $(HOST_HDR)
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANITIZE:-O1=-O0) -std=c++17 -Iinclude -I$(HOST) $(XML2_INC) -c $< -o $@
+check-mesh-driver: $(MESH_CHECK_SRC:%.cpp=$(MESH_CHECK_OUT)_obj/%.o) $(LIBDIR)/libemi355x.so
+	$(CXX) $(SANITIZE) -o $(MESH_CHECK_OUT) $(filter %.o,$^) -L$(LIBDIR) -lemi355x $(XML2_LIB) -lm -Wl,-rpath,$(abspath $(LIBDIR))
+	$(MESH_CHECK_OUT)
 
 # the operator builder of the ODE-error call (emi_ode_error_operator, csrc/emi_host.cpp: host-only) as a stand-alone program under the
 # host sanitizers

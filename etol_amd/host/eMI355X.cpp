@@ -18,6 +18,7 @@
 #include <map>
 #include <mutex>
 
+#include "emi_mesh_driver.hpp"
 #include "emi_nlp.hpp"
 #include "emi_transcribe.hpp"
 #include "emi_trace.hpp"
@@ -719,27 +720,6 @@ void eMI355X::configureDevice(Device* dev) {
     must(emi_set_path(c, (int)(P.npath - P.npath_traced), 1, P.path_records.data(), (int)P.px, (int)P.py), c, "emi_set_path");
 }
 
-namespace {
-// Barycentric Lagrange interpolation from the LGL nodes (tau, w) to the points t2.  For LGL
-// nodes the barycentric weights are (-1)^j sqrt(w_j) up to a common factor, because
-// w_j = 2 / (N (N+1) P_N(tau_j)^2) and the Lagrange weights are proportional to 1 / P_N(tau_j).
-void interp_lgl(const std::vector<double>& tau, const std::vector<double>& w, const double* v, size_t M,
-                const std::vector<double>& t2, double* out) {
-    for (size_t q = 0; q < t2.size(); ++q) {
-        double num = 0, den = 0;
-        bool hit = false;
-        for (size_t j = 0; j < M; ++j) {
-            const double d = t2[q] - tau[j];
-            if (d == 0.0) { out[q] = v[j]; hit = true; break; }
-            const double lam = ((j & 1) ? -1.0 : 1.0) * std::sqrt(w[j]) / d;
-            num += lam * v[j];
-            den += lam;
-        }
-        if (!hit) out[q] = num / den;
-    }
-}
-}  // namespace
-
 // Relative local ODE error of the solution z on the current mesh, the quantity PSOPT's automatic mesh refinement
 // compares with ode_tolerance (ePSOPT.cpp:69-71; PSOPT 5.0.0 follows Betts' relative local error): between every two
 // consecutive nodes the ODE residual of the INTERPOLATED solution is integrated,
@@ -1164,17 +1144,43 @@ void eMI355X::evaluate(const std::vector<double>& z, std::vector<double>* res, s
     if (cost) *cost = c;
 }
 
+// What the mesh strategy (mi355x::MeshDriver) asks of the device, on this solver's context.
+struct eMI355X::Host : public mi355x::MeshHost {
+    eMI355X* self;
+    explicit Host(eMI355X* s) : self(s) {}
+    void set_mesh(size_t nodes) override {
+        self->setMesh(nodes);
+        self->configureDevice(self->_dev.get());
+    }
+    void reconfigure() override { self->configureDevice(self->_dev.get()); }
+    mi355x::NlpResult solve_nlp(mi355x::NlpProblem& nlp, const mi355x::NlpOptions& opt, const std::vector<double>& z0) override {
+        const mi355x::Prob& P = self->_problem;
+        const mi355x::Alg& A = self->_algorithm;
+        Device* const dev = self->_dev.get();
+        // Newton-step linear algebra: small KKT systems on the host, the rest on the device
+        const size_t kkt_rows = (2 * P.nstates + P.ncontrols) * P.nodes;
+        const bool dev_kkt = !P.lifted && (A.linear_solver == "device" || (A.linear_solver == "auto" && kkt_rows > 400));
+        // (a member of its mesh size at the shared rendezvous for as long as this one NLP solve iterates)
+        BatchedKkt shared(dev_kkt ? A.kkt_batcher.get() : nullptr, static_cast<mi355x::KktBackend*>(dev), dev->ctx, dev->nodes);
+        nlp.ev = dev;
+        nlp.kkt = dev_kkt ? (A.kkt_batcher ? static_cast<mi355x::KktBackend*>(&shared) : static_cast<mi355x::KktBackend*>(dev)) : nullptr;
+        self->_solution.linear_solver = dev_kkt ? "device: structured KKT factorisation (Schur complement + Cholesky), Woodbury-corrected" : "host LDL^T";
+        return mi355x::solve_nlp(nlp, opt, z0);
+    }
+    double ode_error(const std::vector<double>& z) override { return self->odeError(z); }
+};
+
 void eMI355X::solve() {
     if (!_dev || !_dev->ctx) die("solve() called before setup()");
     mi355x::Prob& P = _problem;
-    P.guess_clearance = _algorithm.plan_clearance;
     // Delayed states / controls (reference ePSOPT.cpp:231-248).  ePSOPT hands them to IPOPT through PSOPT like any other dependency of
     // the node functions.  Here the delayed values become variables of their node for the duration of the solve ("lifted"), tied to their
     // sources by linear coupling rows with the interpolation operators W(i dt) of the mesh: node functions, Jacobian entries and Hessian
     // blocks stay node-local (the device kernels on the extended node variables, unchanged), W appears as constant rows of the KKT matrix.
     // The Newton step of such a problem runs on the dense host backend (the structured device step has no place for a second operator
     // beside D yet), so the mesh is bounded; mesh sequencing and refinement are off (the ODE-error estimate evaluates between the nodes,
-    // where the delayed values of a points-only mesh are not defined).
+    // where the delayed values of a points-only mesh are not defined).  Which meshes are solved, from which guesses and with which
+    // options, is the MeshDriver's business (emi_mesh_driver.hpp); what is left here is the problem going in and the answer coming out.
     struct Lift {
         eMI355X* self;
         bool on;
@@ -1208,352 +1214,9 @@ void eMI355X::solve() {
     if (_algorithm.node_blocks == "device") opt.device_node_blocks = true;
     else if (_algorithm.node_blocks != "host") die("Alg::node_blocks must be \"host\" or \"device\"");
 
-    // the guess vectors of the problem are working storage of the mesh loop below; the caller's own guess
-    // (ePSOPT.cpp:47-56) is put back when solve() returns, so that a second solve() starts from it again
-    struct KeepGuess {
-        mi355x::Prob& P;
-        std::vector<double> gs, gc, lf, lc;
-        explicit KeepGuess(mi355x::Prob& p) : P(p), gs(p.guess_states), gc(p.guess_controls), lf(p.guess_lamF), lc(p.guess_lamC) {}
-        ~KeepGuess() { P.guess_states = gs; P.guess_controls = gc; P.guess_lamF = lf; P.guess_lamC = lc; }
-    } keep_guess(P);
-
-    mi355x::NlpResult r;
-    auto solve_current_mesh = [&](const mi355x::NlpOptions& o) {
-        mi355x::NlpProblem nlp = mi355x::make_nlp(P, _dev.get());
-        // Newton-step linear algebra: small KKT systems on the host, the rest on the device
-        const size_t kkt_rows = (2 * ns + nc) * P.nodes;
-        const bool dev_kkt = !P.lifted && (_algorithm.linear_solver == "device" ||
-                                           (_algorithm.linear_solver == "auto" && kkt_rows > 400));
-        BatchedKkt shared(dev_kkt ? _algorithm.kkt_batcher.get() : nullptr, static_cast<mi355x::KktBackend*>(_dev.get()), _dev->ctx, _dev->nodes);
-        nlp.kkt = dev_kkt ? (_algorithm.kkt_batcher ? static_cast<mi355x::KktBackend*>(&shared) : static_cast<mi355x::KktBackend*>(_dev.get()))
-                          : nullptr;
-        if (_algorithm.scaling == "automatic") nlp.vscale = mi355x::bound_scales(P);
-        else if (_algorithm.scaling != "none") die("Alg::scaling must be \"automatic\" or \"none\"");
-        if (_algorithm.defect_scaling == "jacobian-based") nlp.jacobian_defect_scaling = true;
-        else if (_algorithm.defect_scaling != "state-based") die("Alg::defect_scaling must be \"state-based\" or \"jacobian-based\"");
-        _solution.linear_solver = dev_kkt ? "device: structured KKT factorisation (Schur complement + Cholesky), Woodbury-corrected" : "host LDL^T";
-        if (P.guess_lamF.size() == ns * P.nodes) nlp.lamF0 = P.guess_lamF;
-        if (P.guess_lamC.size() == P.npath * P.nodes) nlp.lamC0 = P.guess_lamC;
-        mi355x::NlpOptions ob = o;
-        if (_algorithm.nlp_iter_budget > 0) {           // what is left of the solve()'s iteration budget
-            const int left = _algorithm.nlp_iter_budget - _solution.nlp_iterations_total;
-            if (left <= 0) {
-                r = mi355x::NlpResult();
-                r.msg = "iteration budget exhausted (" + std::to_string(_solution.nlp_iterations_total) + " iterations over all meshes and restarts)";
-                return;
-            }
-            ob.max_iter = std::min(ob.max_iter, left);
-        }
-        const auto t_run = std::chrono::steady_clock::now();
-        r = mi355x::solve_nlp(nlp, ob, mi355x::initial_guess(P));
-        _solution.nlp_iterations_total += r.iterations;
-        _solution.node_blocks = r.n_factor_terms > 0 ? "device" : "host";
-        _solution.nlp_runs.push_back({P.nodes, r.iterations, r.ok, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_run).count(),
-                                      r.t_eval, r.t_hess, r.t_factor, r.t_solve, r.t_lowrank, r.t_blocks, r.t_jt, r.t_matvec, r.n_factor, r.n_solve});
-        if (!r.ok && _algorithm.nlp_iter_budget > 0 && _solution.nlp_iterations_total >= _algorithm.nlp_iter_budget)
-            r.msg = "iteration budget exhausted (" + std::to_string(_solution.nlp_iterations_total) + " iterations over all meshes and restarts); last: " + r.msg;
-    };
-    // A warm start that wanders (no failure, just hundreds of regularised steps along a flat valley; Monte-Carlo scenario 10 of
-    // profiles/r02_notes.md section 12) is cut off after Alg::warm_patience iterations and repeated from the same interpolated
-    // guess with a 10 x larger barrier parameter
-    auto solve_warm = [&](const mi355x::NlpOptions& o) {
-        if (_algorithm.warm_patience <= 0 || _algorithm.warm_patience >= o.max_iter) { solve_current_mesh(o); return; }
-        mi355x::NlpOptions first = o;
-        first.max_iter = _algorithm.warm_patience;
-        solve_current_mesh(first);
-        if (r.ok || r.iterations < first.max_iter) return;                  // converged, or ended for another reason
-        if (_algorithm.print_level >= 5)
-            printf("warm start still running after %d iterations: again from the same guess with barrier parameter %.1e\n",
-                   first.max_iter, 10.0 * o.mu_init);
-        mi355x::NlpOptions again = o;
-        again.mu_init = 10.0 * o.mu_init;
-        solve_current_mesh(again);
-    };
-    // A cold start that ends locally infeasible (the path rows stay violated whatever the penalty weight: the iterate
-    // sits on the wrong side of a keep-out) is repeated from the straight line bent to either side, by 15 % and 35 %
-    // of its length.  IPOPT's restoration phase does this job for ePSOPT; here it is a search over homotopy classes,
-    // decided by the first start that converges.  Only for the default guess: a user's guess is taken as given.
-    auto solve_cold_with_retries = [&](const mi355x::NlpOptions& o) {
-        solve_current_mesh(o);
-        if (r.ok || P.npath == 0 || !P.guess_states.empty() || _algorithm.guess_retries <= 0) return;
-        const bool outer_planned = P.guess_planned;          // (a ladder climb that starts from the planned route: the bends follow without it)
-        P.guess_planned = false;
-        double span = 0;
-        if (P.event_lower.size() == 2 * ns) {
-            const double dx = 0.5 * (P.event_lower[ns + P.px] + P.event_upper[ns + P.px]) - 0.5 * (P.event_lower[P.px] + P.event_upper[P.px]);
-            const double dy = 0.5 * (P.event_lower[ns + P.py] + P.event_upper[ns + P.py]) - 0.5 * (P.event_lower[P.py] + P.event_upper[P.py]);
-            span = std::sqrt(dx * dx + dy * dy);
-        }
-        const double bends[4] = {0.15, -0.15, 0.35, -0.35};
-        for (int t = 0; t < 4 && t < _algorithm.guess_retries && !r.ok && span > 0; ++t) {
-            P.guess_bend = bends[t] * span;
-            if (_algorithm.print_level >= 5) printf("cold start failed (%s): retrying from the line bent by %+.3f\n", r.msg.c_str(), P.guess_bend);
-            solve_current_mesh(o);
-        }
-        P.guess_bend = 0;
-        // ... and last from a route planned through the free space of the static keep-outs (planned_path_guess), unless this cold start
-        // already began from it (a ladder climb's second start, Alg::plan_second_start).
-        if (!r.ok && span > 0 && _algorithm.guess_retries > 0 && !outer_planned) {
-            P.guess_planned = true;
-            if (_algorithm.print_level >= 5) printf("cold start failed (%s): retrying from a path planned through the free space\n", r.msg.c_str());
-            solve_current_mesh(o);
-            P.guess_planned = false;
-        }
-        P.guess_planned = outer_planned;
-    };
-    // Multipliers are NOT carried to the next mesh by default: measured over 32 Monte-Carlo scenarios at 257 nodes the
-    // costate-mapped warm start needed 112 iterations on average against 103 from zero multipliers (interior-point
-    // warm starts want centred pairs, which interpolated multipliers are not).  Alg::warm_multipliers enables it.
-    const bool warm_multipliers = _algorithm.warm_multipliers;
-    // the solution on the current mesh, interpolated to Mnew LGL nodes, becomes the guess there
-    auto remesh_with_guess = [&](size_t Mnew) {
-        const std::vector<double> tau = P.tau, w = P.w;
-        const size_t M = P.nodes;
-        setMesh(Mnew);
-        configureDevice(_dev.get());
-        P.guess_states.assign(ns * Mnew, 0.0);
-        P.guess_controls.assign(nc * Mnew, 0.0);
-        for (size_t i = 0; i < ns; ++i) interp_lgl(tau, w, &r.z[i * M], M, P.tau, &P.guess_states[i * Mnew]);
-        // the interpolant may cut through a keep-out between two old nodes
-        mi355x::repair_guess(P, &P.guess_states[P.px * Mnew], &P.guess_states[P.py * Mnew]);
-        for (size_t j = 0; j < nc; ++j) {
-            interp_lgl(tau, w, &r.z[(ns + j) * M], M, P.tau, &P.guess_controls[j * Mnew]);
-            for (size_t k = 0; k < Mnew; ++k)
-                P.guess_controls[j * Mnew + k] =
-                    std::min(std::max(P.guess_controls[j * Mnew + k], P.control_lower[j]), P.control_upper[j]);
-        }
-        // multipliers: lambda_k / w_k samples the costate (covector mapping of pseudospectral methods), which is what
-        // interpolates between meshes; the row multipliers of the keep-outs likewise
-        P.guess_lamF.clear();
-        P.guess_lamC.clear();
-        if (warm_multipliers && r.lamF.size() == ns * M && r.lamC.size() == P.npath * M) {
-            std::vector<double> tmp(M);
-            P.guess_lamF.assign(ns * Mnew, 0.0);
-            for (size_t i = 0; i < ns; ++i) {
-                for (size_t k = 0; k < M; ++k) tmp[k] = r.lamF[i * M + k] / w[k];
-                interp_lgl(tau, w, tmp.data(), M, P.tau, &P.guess_lamF[i * Mnew]);
-                for (size_t k = 0; k < Mnew; ++k) P.guess_lamF[i * Mnew + k] *= P.w[k];
-            }
-            P.guess_lamC.assign(P.npath * Mnew, 0.0);
-            for (size_t j = 0; j < P.npath; ++j) {
-                for (size_t k = 0; k < M; ++k) tmp[k] = r.lamC[j * M + k] / w[k];
-                interp_lgl(tau, w, tmp.data(), M, P.tau, &P.guess_lamC[j * Mnew]);
-                for (size_t k = 0; k < Mnew; ++k) P.guess_lamC[j * Mnew + k] *= P.w[k];
-            }
-        }
-    };
-    mi355x::NlpOptions warm = opt;      // started from an interpolated solution: stay close to it
-    warm.mu_init = _algorithm.warm_mu_init;               // (1e-3 .. 1e-5 measured, profiles/r01_notes.md)
-    warm.bound_push = warm.bound_frac = _algorithm.warm_bound_push;
-    warm.mu_restart = _algorithm.mu_restart;
-    _solution.mesh_iterations = 0;
-    _solution.nlp_iterations_total = 0;
-    _solution.nlp_runs.clear();
-    _solution.certificate = mi355x::Sol::Certificate();
-    _solution.lamF.clear();
-    _solution.lamC.clear();
-    _solution.ode_error = 0;
-    bool sequenced = false;             // the requested mesh is started from the sequencing ladder's solution
-    std::function<bool(double, bool)> climb;  // the ladder from its coarsest mesh with the straight-line guess bent by so much: true if every rung converged
-    double ladder_span = 0;
-    int ladder_next_start = 1;          // index of the first start (below) no climb has used yet
-    bool ladder_has_plan = false;       // Alg::plan_second_start, and the static keep-outs leave a route that planned_path_guess finds
-    bool ladder_first_rung_failed = false;
-    const double ladder_bends[4] = {0.15, -0.15, 0.35, -0.35};
-    // start k of a climb: 0 the straight line, then (Alg::plan_second_start, if there is one) the planned route, then the bends
-    // (Alg::plan_first_start, an experiment: the planned route FIRST and the straight line second)
-    auto ladder_start_planned = [&](int k) { return ladder_has_plan && k == (_algorithm.plan_first_start ? 0 : 1); };
-    auto ladder_start_bend = [&](int k) { const int b = k - 1 - (ladder_has_plan ? 1 : 0); return (b >= 0 && b < 4) ? ladder_bends[b] : 0.0; };
-    auto ladder_starts = [&]() { return 1 + (ladder_has_plan ? 1 : 0) + 4; };
-
-    // Mesh sequencing: a fine global mesh is reached through coarse ones (33, 65, 129, ... nodes), each
-    // solve started from the interpolated previous solution.  An interior-point iteration from a cold
-    // straight-line guess needs hundreds of Newton steps on a 1000-node mesh; from the interpolant of the
-    // next-coarser solution it needs a few dozen, and the coarse solves cost next to nothing.
-    // (PSOPT's own remedy is the same idea driven by the error estimate: start coarse, refine.)
-    // (function scope: the ladder is climbed again, from another guess, if the warm start on the requested mesh fails)
-    const size_t target = P.nodes;
-    std::vector<size_t> ladder;
-    const std::vector<double> true_records = P.path_records;
-    double span = 0;
-    if (_algorithm.mesh_sequencing && P.nodes > 80 && P.guess_states.empty() && !P.lifted) {
-        const size_t lr = (size_t)std::max(2, _algorithm.ladder_ratio);
-        for (size_t m = 33; m < target; m = lr * m - (lr - 1)) ladder.push_back(m);
-        // Constraints hold at the nodes only, so a coarse mesh can step over a thin keep-out ("tunnelling") and leave
-        // the finer meshes a start on the wrong side of it.  On the ladder the keep-outs of the record table are
-        // therefore inflated by half the largest node spacing of the straight line between the boundary positions
-        // (LGL nodes are (pi/2) / (m-1) of the span apart at mid-horizon); the requested mesh gets the true sizes back.
-        if (P.event_lower.size() == 2 * ns) {
-            const double dx = 0.5 * (P.event_lower[ns + P.px] + P.event_upper[ns + P.px]) - 0.5 * (P.event_lower[P.px] + P.event_upper[P.px]);
-            const double dy = 0.5 * (P.event_lower[ns + P.py] + P.event_upper[ns + P.py]) - 0.5 * (P.event_lower[P.py] + P.event_upper[P.py]);
-            span = std::sqrt(dx * dx + dy * dy);
-        }
-        auto inflate_records = [&, this](size_t m) {
-            P.path_records = true_records;
-            if (!_algorithm.inflate_keepouts || !(span > 0)) return;
-            const double delta = 0.5 * span * 1.5707963267948966 / (double)(m - 1);
-            for (size_t j = 0; j < P.npath - P.npath_traced; ++j) {
-                double* rec = &P.path_records[j * EMI_PATH_REC];
-                const int kind = (int)rec[0];
-                auto grow = [&](double& sq) { const double r0 = std::sqrt(std::max(sq, 0.0)) + delta; sq = r0 * r0; };
-                if (kind == EMI_PATH_ELLIPSE) { grow(rec[5]); grow(rec[6]); }
-                else if (kind == EMI_PATH_DISC) grow(rec[3]);
-                else grow(rec[2]);
-            }
-        };
-        // A rung that fails after the coarsest one converged (the interpolant runs into a corner the coarse mesh did not
-        // see) sends the whole ladder back to its start with the straight-line guess bent to one side: a cold start on
-        // 33 nodes costs a quarter of a second, whereas the fallback below -- cold starts on the requested mesh -- spent
-        // 4 x 400 iterations of a 513-node problem on one Monte-Carlo scenario (36 of its 41 s, profiles/r02_notes.md).
-        // Alg::plan_second_start: the route planned through the free space as the second start of a climb, before the bends.  (The SHORTEST
-        // route, which hugs the keep-outs, made things worse in that place: 138.7 against 129.7 iterations per scenario on the 64-scenario
-        // set, scenario 960 lost; charged for narrow places it takes that set to 127.0, the 256-scenario set from 135.2 to 125.5, scenario
-        // 960 from 870 to 235 iterations and scenario 17 from 685 to 313: profiles/r04_notes.md section 24.)
-        if (_algorithm.plan_second_start) {
-            std::vector<double> px(P.nodes), py(P.nodes);
-            ladder_has_plan = P.npath > 0 && span > 0 && _algorithm.guess_retries > 0 && mi355x::planned_path_guess(P, px.data(), py.data(), _algorithm.plan_clearance);
-        }
-        const int ladder_tries = (P.npath > 0 && span > 0) ? 1 + (ladder_has_plan ? 1 : 0) + std::min(4, std::max(0, _algorithm.guess_retries)) : 1;
-        ladder_span = ladder_tries > 1 ? span : 0.0;
-        climb = [&, this, inflate_records](double bend, bool planned) -> bool {
-            P.guess_states.clear();
-            P.guess_controls.clear();
-            P.guess_lamF.clear();
-            P.guess_lamC.clear();
-            warm.rho_init = opt.rho_init;
-            bool ok = true;
-            for (size_t li = 0; li < ladder.size() && ok; ++li) {
-                inflate_records(ladder[li]);
-                if (li == 0) setMesh(ladder[0]);
-                configureDevice(_dev.get());
-                mi355x::NlpOptions o = li == 0 ? opt : warm;
-                o.tol = std::max(opt.tol, _algorithm.rung_tolerance);          // intermediate meshes only feed the next guess
-                if (li > 0 && _algorithm.rung_patience > 0) o.max_iter = std::min(o.max_iter, _algorithm.rung_patience);
-                if (li == 0) {
-                    P.guess_bend = bend;
-                    P.guess_planned = planned;
-                    solve_cold_with_retries(o);
-                    P.guess_bend = 0;
-                    P.guess_planned = false;
-                } else {
-                    solve_warm(o);
-                }
-                ++_solution.mesh_iterations;
-                if (_algorithm.print_level >= 5)
-                    printf("mesh sequencing: %zu nodes, %d iterations, cost %.10e (%s)\n", P.nodes, r.iterations, r.cost,
-                           r.msg.c_str());
-                ok = r.ok;
-                warm.rho_init = std::max(warm.rho_init, r.rho);     // a penalty weight found too small stays raised
-                if (ok) {
-                    if (li + 1 == ladder.size()) P.path_records = true_records;       // the guess repair below sees the true sizes
-                    remesh_with_guess(li + 1 < ladder.size() ? ladder[li + 1] : target);
-                } else if (li == 0) {
-                    ladder_first_rung_failed = true;                   // the cold start already went through its own bends
-                }
-            }
-            P.path_records = true_records;
-            return ok;
-        };
-        bool chain_ok = false;
-        for (int ca = 0; ca < ladder_tries && !chain_ok && !ladder_first_rung_failed; ++ca) {
-            const bool planned = ladder_start_planned(ca);
-            const double bend = ladder_start_bend(ca) * span;
-            if (ca > 0 && _algorithm.print_level >= 5) {
-                if (planned) printf("mesh sequencing: a rung failed (%s), ladder restarted from the route planned through the free space\n", r.msg.c_str());
-                else printf("mesh sequencing: a rung failed (%s), ladder restarted from the line bent by %+.3f\n", r.msg.c_str(), bend);
-            }
-            chain_ok = climb(bend, planned);
-            ladder_next_start = ca + 1;             // starts 0 .. ca have been used (the climb is deterministic: none is worth repeating)
-        }
-        P.path_records = true_records;
-        if (chain_ok) {
-            sequenced = true;
-        } else {                                       // fall back to the cold start on the requested mesh
-            setMesh(target);
-            configureDevice(_dev.get());
-            P.guess_states.clear();
-            P.guess_controls.clear();
-            P.guess_lamF.clear();
-            P.guess_lamC.clear();
-        }
-    }
-
-    // PSOPT's mesh refinement ("automatic", ePSOPT.cpp:69-71): solve, estimate the ODE error,
-    // add nodes and re-solve from the interpolated solution until the tolerance is met.
-    const bool refine = _algorithm.mesh_refinement == "automatic" && !P.lifted;
-    mi355x::NlpResult r_good;           // last converged solution and its mesh
-    size_t M_good = 0;
-    for (int mr = 0;; ++mr) {
-        // The warm start on the requested mesh, while the ladder still has a start it has not used: at most Alg::target_patience iterations
-        // (converged ones take 11 at the median, 24 at the 90th percentile, 212 at most over 256 Monte-Carlo scenarios; the one that fails used
-        // all 400 of nlp_iter_max -- 20 s of a 1024-node problem -- before the next start got its turn: scenario 558, r04_notes.md section 26)
-        auto target_warm = [&]() {
-            mi355x::NlpOptions w = warm;
-            const bool more_starts = climb && ladder_span > 0 && !ladder_first_rung_failed && ladder_next_start < ladder_starts() &&
-                                     ladder_next_start - (ladder_has_plan ? 2 : 1) < _algorithm.guess_retries;
-            if (_algorithm.target_patience > 0 && more_starts) w.max_iter = std::min(w.max_iter, _algorithm.target_patience);
-            solve_warm(w);
-        };
-        if (mr == 0 && !sequenced) solve_cold_with_retries(opt);
-        else if (sequenced && mr == 0) target_warm();
-        else solve_current_mesh(opt);
-        ++_solution.mesh_iterations;
-        if (!r.ok && sequenced && mr == 0) {
-            // the ladder led into a corner (typically an interpolant cutting through a keep-out the coarse meshes
-            // did not see): start over on the requested mesh from the default guess
-            const size_t target_nodes = P.nodes;
-            // (from the first bend the ladder has not been climbed with yet: a Monte-Carlo scenario whose climb from the +15 % bend ended
-            // in a failed warm start used to climb from +15 % AGAIN, to the same failure, 117 iterations later)
-            for (int ca = ladder_next_start; climb && ca < ladder_starts() && ca - (ladder_has_plan ? 2 : 1) < _algorithm.guess_retries && ladder_span > 0 && !r.ok && !ladder_first_rung_failed; ++ca) {
-                const bool planned = ladder_start_planned(ca);
-                const double bend = ladder_start_bend(ca) * ladder_span;
-                if (_algorithm.print_level >= 5) {
-                    if (planned) printf("mesh sequencing: warm start on %zu nodes failed (%s), ladder restarted from the planned route\n", target_nodes, r.msg.c_str());
-                    else printf("mesh sequencing: warm start on %zu nodes failed (%s), ladder restarted from the line bent by %+.3f\n", target_nodes, r.msg.c_str(), bend);
-                }
-                ladder_next_start = ca + 1;
-                if (climb(bend, planned)) {
-                    target_warm();
-                    ++_solution.mesh_iterations;
-                } else {
-                    r.ok = false;
-                }
-            }
-            if (r.ok) goto target_solved;
-            if (P.nodes != target_nodes) { setMesh(target_nodes); configureDevice(_dev.get()); }
-            if (_algorithm.print_level >= 5) printf("mesh sequencing: warm start failed (%s), cold start on %zu nodes\n", r.msg.c_str(), P.nodes);
-            P.guess_states.clear();
-            P.guess_controls.clear();
-            P.guess_lamF.clear();
-            P.guess_lamC.clear();
-            solve_cold_with_retries(opt);
-            ++_solution.mesh_iterations;
-        }
-    target_solved:
-        if (!r.ok && mr > 0 && r_good.ok) {
-            // a refinement solve that fails does not take the converged coarser solution with it
-            if (_algorithm.print_level >= 5) printf("mesh iteration %d failed (%s): keeping the %zu-node solution\n", mr, r.msg.c_str(), M_good);
-            setMesh(M_good);
-            configureDevice(_dev.get());
-            r = r_good;
-            break;
-        }
-        if (!r.ok || !refine) break;
-        std::vector<double> zf;
-        size_t M2 = 0;
-        _solution.ode_error = odeError(r.z, &zf, &M2);
-        if (_algorithm.print_level >= 5)
-            printf("mesh iteration %d: %zu nodes, cost %.10e, relative ODE error %.3e\n", mr, P.nodes, r.cost,
-                   _solution.ode_error);
-        if (_solution.ode_error <= _algorithm.ode_tolerance || mr + 1 >= _algorithm.mr_max_iterations) break;
-        const size_t Mnew = std::min((size_t)_algorithm.mr_max_nodes, P.nodes + std::max<size_t>(4, (P.nodes - 1) / 2));
-        if (Mnew <= P.nodes) break;
-        // refined meshes start from the interpolated solution but with the cold-start barrier settings: the
-        // interpolant may cut through keep-outs between the old nodes, and the elastic rows need room to move
-        r_good = r;
-        M_good = P.nodes;
-        remesh_with_guess(Mnew);
-    }
+    mi355x::KeepGuess keep_guess(P);
+    Host host(this);
+    const mi355x::NlpResult r = mi355x::MeshDriver(P, _algorithm, _solution, host, opt).run();
     const size_t M = P.nodes;
 
     _solution.error_flag = r.ok ? 0 : 1;

@@ -18,6 +18,8 @@ namespace mi355x {
 NlpProblem make_nlp(const Prob& P, NlpEvaluator* ev);
 // zeros unless Prob::guess_* were pre-filled (reference ePSOPT.cpp:47-56)
 std::vector<double> initial_guess(const Prob& P);
+// nodes of a guess (positions xs, ys) that fall inside a keep-out of the record table are moved radially out of it
+void repair_guess(const Prob& P, double* xs, double* ys);
 // positions of the nodes along a shortest path through the free space of the static keep-outs (the last cold-start guess of solve()):
 // false if the problem has no such rows or no route exists
 // clearance_weight x span: the clearance at which a step of the route costs twice its length (0: the shortest route)

@@ -261,6 +261,7 @@ class eMI355X : public TrajectoryOptimizer {
  private:
     struct Device;                       // emi_ctx_t + NlpEvaluator / KktBackend adapter
     std::unique_ptr<Device> _dev;
+    struct Host;                         // what the mesh strategy of solve() asks of the device (mi355x::MeshHost, host/emi_mesh_driver.hpp)
     static std::vector<Device*>& device_pool();
     void traceCallbacks();               // calls every f_t once (see eMI355X_Types.hpp)
     void addBounds();

@@ -8,6 +8,7 @@
 
 #include <dlfcn.h>
 
+#include "emi_mesh_driver.hpp"
 #include "emi_nlp.hpp"
 #include "emi_transcribe.hpp"
 #include "emi_trace.hpp"
@@ -199,18 +200,12 @@ int g_defect_scaling = 0;         // 1: Alg::defect_scaling = "jacobian-based" (
 extern "C" void harness_set_defect_scaling(int jacobian_based) { g_defect_scaling = jacobian_based; }
 extern "C" int harness_kkt_standin_wrong_inertia(void) { return g_host_kkt.wrong_inertia; }
 
-extern "C" int harness_solve_example1_oracle(const char* xml, const char* oracle_so, int with_obstacles, double tol,
-                                             int print_level, int max_iter, double* cost, int* M, double* X, double* U,
-                                             int cap, int* iters) {
-    void* h = dlopen(oracle_so, RTLD_NOW);
-    if (!h) { g_out = dlerror(); return 3; }
-    OracleEval oe;
-    oe.ev = (orc_eval_t)dlsym(h, "orc_eval");
-    oe.hs = (orc_hess_t)dlsym(h, "orc_hess");
+namespace {
+// the example-1 problem of the configuration file as a Prob on `nodes` LGL nodes (0: nsteps + 1), for the oracle evaluator
+void example1_prob(const char* xml, int with_obstacles, size_t nodes, mx::Prob& P) {
     Plain t;
     t.loadConfigs(xml);
-    mx::Prob P;
-    P.nstates = 2; P.ncontrols = 2; P.nodes = t.getNSteps() + 1; P.t0 = 0; P.tf = t.getNSteps() * t.getDt();
+    P.nstates = 2; P.ncontrols = 2; P.nodes = nodes ? nodes : t.getNSteps() + 1; P.t0 = 0; P.tf = t.getNSteps() * t.getDt();
     P.model = EMI_MODEL_POINTMASS2D;
     P.tau.resize(P.nodes); P.w.resize(P.nodes); P.D.resize(P.nodes * P.nodes);
     emi_lgl((int)P.nodes, P.tau.data(), P.w.data(), P.D.data());
@@ -231,6 +226,9 @@ extern "C" int harness_solve_example1_oracle(const char* xml, const char* oracle
             emi_track_centres((int)tt.size(), tt.data(), xx.data(), yy.data(), (int)P.nodes, node_t.data(), xc.data(), yc.data());
             P.track_x.insert(P.track_x.end(), xc.begin(), xc.end());
             P.track_y.insert(P.track_y.end(), yc.begin(), yc.end());
+            mx::TrackTable tb;                       // (a mesh change tabulates the centres again: OracleMeshHost)
+            tb.radius = trk.radius; tb.t = tt; tb.x = xx; tb.y = yy;
+            P.tracks.push_back(tb);
             double rec[8] = {(double)EMI_PATH_TRACK, (double)P.ntracks++, trk.radius * trk.radius, 0, 0, 0, 0, 0};
             P.path_records.insert(P.path_records.end(), rec, rec + 8);
         }
@@ -241,6 +239,19 @@ extern "C" int harness_solve_example1_oracle(const char* xml, const char* oracle
     for (int i = 0; i < 2; ++i) { P.event_lower.push_back(t.getX0()[i]); P.event_upper.push_back(t.getX0()[i]); }
     for (int i = 0; i < 2; ++i) { P.event_lower.push_back(t.getXf()[i] - t.getXtol()[i]); P.event_upper.push_back(t.getXf()[i] + t.getXtol()[i]); }
     P.path_lower.assign(P.npath, -1000.0); P.path_upper.assign(P.npath, 0.0);
+}
+}  // namespace
+
+extern "C" int harness_solve_example1_oracle(const char* xml, const char* oracle_so, int with_obstacles, double tol,
+                                             int print_level, int max_iter, double* cost, int* M, double* X, double* U,
+                                             int cap, int* iters) {
+    void* h = dlopen(oracle_so, RTLD_NOW);
+    if (!h) { g_out = dlerror(); return 3; }
+    OracleEval oe;
+    oe.ev = (orc_eval_t)dlsym(h, "orc_eval");
+    oe.hs = (orc_hess_t)dlsym(h, "orc_hess");
+    mx::Prob P;
+    example1_prob(xml, with_obstacles, 0, P);
     oe.P = &P;
     mx::NlpProblem nlp = mx::make_nlp(P, &oe);
     if (g_scaling == 1) nlp.vscale = mx::bound_scales(P);
@@ -260,6 +271,77 @@ extern "C" int harness_solve_example1_oracle(const char* xml, const char* oracle
     *M = m; *cost = r.cost;
     for (int i = 0; i < 2 * m; ++i) { X[i] = r.z[i]; U[i] = r.z[2 * m + i]; }
     dlclose(h);
+    return 0;
+}
+
+// ---- the mesh strategy (mi355x::MeshDriver) on the CPU oracle: one real sequenced solve without a device.  The host interface of the
+// driver with the oracle as evaluator and the dense host Newton step; a mesh change does to the Prob what eMI355X::setMesh does.
+namespace {
+struct OracleMeshHost : public mx::MeshHost {
+    mx::Prob& P;
+    OracleEval& oe;
+    OracleMeshHost(mx::Prob& p, OracleEval& e) : P(p), oe(e) {}
+    void set_mesh(size_t nodes) override {
+        P.nodes = nodes;
+        P.tau.resize(nodes); P.w.resize(nodes); P.D.resize(nodes * nodes);
+        emi_lgl((int)nodes, P.tau.data(), P.w.data(), P.D.data());
+        std::vector<double> node_t(nodes);
+        for (size_t k = 0; k < nodes; ++k) node_t[k] = P.t0 + (P.tf - P.t0) / 2.0 * (P.tau[k] + 1.0);
+        P.track_x.assign(P.tracks.size() * nodes, 0.0);
+        P.track_y.assign(P.tracks.size() * nodes, 0.0);
+        for (size_t i = 0; i < P.tracks.size(); ++i) {
+            const mx::TrackTable& tb = P.tracks[i];
+            emi_track_centres((int)tb.t.size(), tb.t.data(), tb.x.data(), tb.y.data(), (int)nodes, node_t.data(), &P.track_x[i * nodes], &P.track_y[i * nodes]);
+        }
+    }
+    void reconfigure() override {}                  // (the oracle reads the record table of the Prob at every call)
+    mx::NlpResult solve_nlp(mx::NlpProblem& nlp, const mx::NlpOptions& opt, const std::vector<double>& z0) override {
+        nlp.ev = &oe;
+        nlp.kkt = nullptr;                          // the dense host Newton step
+        return mx::solve_nlp(nlp, opt, z0);
+    }
+    double ode_error(const std::vector<double>&) override { std::abort(); }     // (refinement is off)
+};
+}  // namespace
+
+// example 1 on `nodes` LGL nodes through the mesh ladder: Alg defaults but for the tolerance, no refinement.  runs: Sol::nlp_runs as
+// (nodes, iterations, converged) triples, at most runs_cap of them.  Returns 0 solved, 1 not, 2 a cap is too small, 3 no oracle.
+extern "C" int harness_solve_example1_sequenced_oracle(const char* xml, const char* oracle_so, int with_obstacles, int nodes, double tol,
+                                                       int print_level, double* cost, double* X, double* U, int cap, int* runs, int runs_cap,
+                                                       int* nruns, int* mesh_iterations) {
+    void* h = dlopen(oracle_so, RTLD_NOW);
+    if (!h) { g_out = dlerror(); return 3; }
+    OracleEval oe;
+    oe.ev = (orc_eval_t)dlsym(h, "orc_eval");
+    oe.hs = (orc_hess_t)dlsym(h, "orc_hess");
+    mx::Prob P;
+    example1_prob(xml, with_obstacles, (size_t)nodes, P);
+    oe.P = &P;
+    mx::Alg alg;
+    alg.nlp_tolerance = tol;
+    alg.mesh_refinement = "none";
+    alg.print_level = print_level;
+    mx::NlpOptions opt;
+    opt.tol = alg.nlp_tolerance; opt.max_iter = alg.nlp_iter_max; opt.print_level = print_level;
+    mx::Sol sol;
+    OracleMeshHost host(P, oe);
+    mx::NlpResult r;
+    {
+        mx::KeepGuess keep(P);
+        r = mx::MeshDriver(P, alg, sol, host, opt).run();
+    }
+    dlclose(h);
+    g_out = r.msg;
+    *nruns = (int)sol.nlp_runs.size();
+    *mesh_iterations = sol.mesh_iterations;
+    for (int i = 0; i < *nruns && i < runs_cap; ++i) {
+        runs[3 * i] = (int)sol.nlp_runs[i].nodes; runs[3 * i + 1] = sol.nlp_runs[i].iterations; runs[3 * i + 2] = sol.nlp_runs[i].converged;
+    }
+    if (!r.ok) return 1;
+    const int m = (int)P.nodes;
+    if (m > cap || *nruns > runs_cap) return 2;
+    *cost = r.cost;
+    for (int i = 0; i < 2 * m; ++i) { X[i] = r.z[i]; U[i] = r.z[2 * m + i]; }
     return 0;
 }
 

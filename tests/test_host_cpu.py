@@ -277,7 +277,7 @@ def test_host_sources_compile_against_the_reference_headers():
     TrajectoryOptimizer.hpp / ETOL_Types.hpp first on the include path (ours only supplies eMI355X*.hpp, emi355x.h)."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    srcs = ["etol_amd/host/eMI355X.cpp", "etol_amd/host/emi_nlp.cpp", "etol_amd/host/emi_trace.cpp",
+    srcs = ["etol_amd/host/eMI355X.cpp", "etol_amd/host/emi_nlp.cpp", "etol_amd/host/emi_mesh_driver.cpp", "etol_amd/host/emi_trace.cpp",
             "etol_amd/examples/etol_mi355x_example1.cpp", "etol_amd/examples/etol_mi355x_montecarlo.cpp"]
     for src in srcs:
         r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I/root/reference/include", "-Iinclude", "-Ietol_amd/host", src],

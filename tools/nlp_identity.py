@@ -4,6 +4,8 @@ parent commit's and the changed one, each with its own built libraries -- and co
 
    python tools/nlp_identity.py cpu OUT.json       the solves of tests/test_host_cpu.py (oracle evaluator, no device)
    python tools/nlp_identity.py gpu OUT.json       small solves of tests/test_gpu_solve.py / test_gpu_delays.py through eMI355X
+   python tools/nlp_identity.py strategy OUT.json  the mesh strategy's own paths (host/emi_mesh_driver.cpp): Monte-Carlo scenario sets whose solves
+                                                  restart the ladder, through etol_mi355x_montecarlo, one child process per set
    python tools/nlp_identity.py compare PARENT.json BRANCH.json [OUT.json]      equal or not, field by field (times are reported only)
    python tools/nlp_identity.py cpu-times LABEL OUT.jsonl      one more wall time per cpu case, appended as a line: run it in the two
                                                                trees in turn, round after round, so that both see the same machine
@@ -12,11 +14,13 @@ parent commit's and the changed one, each with its own built libraries -- and co
 
 Per case: SHA-256 of the bytes of the trajectory and the cost, iteration count, return code and message, and SHA-256 of the solve's
 stdout at print_level 6 (the per-iteration trace; the timing summary lines are cut out).  `cpu` adds three wall times of the call at
-print_level 0, `gpu` adds Sol::nlp_runs (nodes, iterations, converged).  The libraries are those of the tree the script lies in."""
+print_level 0, `gpu` adds Sol::nlp_runs (nodes, iterations, converged).  `strategy` records per scenario the return code, nodes,
+iterations, the printed cost, the runs list and the SHA-256 of the strategy's own printed lines, and the wall time of each child.  The libraries are those of the tree the script lies in."""
 import ctypes as C
 import hashlib
 import json
 import os
+import subprocess
 import sys
 import tempfile
 import time
@@ -190,6 +194,42 @@ def gpu(H, xml):
     return out
 
 
+# (arguments of etol_mi355x_montecarlo, extra environment, time limit of the child in seconds): the sets tests/test_gpu_solve.py uses,
+# and scenario 27 again with the straight line as the first start of a climb (EMI_MC_PLAN=1: the planned route second, 0: last) -- since
+# the planned route became the first start it climbs straight through, and with the line first its ladder fails and restarts
+STRATEGY_SETS = ((("10", "128", "8", "1"), {}, 300), (("32", "256", "10", "1"), {"EMI_MC_ONLY": "27"}, 300),
+                 (("32", "512", "20", "1"), {"EMI_MC_ONLY": "27"}, 300), (("32", "256", "10", "1"), {"EMI_MC_ONLY": "27", "EMI_MC_PLAN": "0"}, 300),
+                 (("32", "512", "20", "1"), {"EMI_MC_ONLY": "27", "EMI_MC_PLAN": "1"}, 300), (("32", "512", "20", "1"), {"EMI_MC_ONLY": "27", "EMI_MC_PLAN": "0"}, 300))
+STRATEGY_LINES = ("mesh sequencing:", "cold start", "warm start", "mesh iteration")
+
+
+def strategy():
+    exe = os.path.join(ROOT, "etol_amd", "lib", "etol_mi355x_montecarlo")
+    out = {}
+    for args, extra, limit in STRATEGY_SETS:
+        env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", EMI_MC_RUNS="1", EMI_MC_PRINT_LEVEL="5", EMI_MC_GATHER="0", **extra)
+        name = "montecarlo " + " ".join(args) + "".join(f" {k}={v}" for k, v in extra.items())
+        t0 = time.perf_counter()
+        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=limit, env=env)
+        seconds = time.perf_counter() - t0
+        if r.returncode not in (0, 2):          # (2: not every scenario solved)
+            json.dump(out, open(sys.argv[2], "w"), indent=1, sort_keys=True)
+            sys.exit(f"{name}: exit status {r.returncode}\n{r.stdout[-2000:]}{r.stderr[-2000:]}")
+        lines = r.stdout.split("\n")
+        printed = "\n".join(ln for ln in lines if ln.startswith(STRATEGY_LINES))
+        scenarios = {}
+        for ln in lines:
+            f = ln.split()
+            if ln.startswith("scenario") and "runs" in f:
+                scenarios[f[1]] = dict(rc=int(f[f.index("rc") + 1]), nodes=int(f[f.index("nodes") + 1]), iterations=int(f[f.index("iterations") + 1]),
+                                       cost=f[f.index("cost") + 1], runs=f[f.index("runs") + 1:])
+        out[name] = dict(exit_status=r.returncode, scenarios=scenarios, strategy_lines=sha(printed.encode()),
+                         strategy_line_count=printed.count("\n") + 1 if printed else 0, seconds=[seconds])
+        print(f"{seconds:8.2f} s  exit {r.returncode}  {len(scenarios)} scenarios  strategy lines {out[name]['strategy_lines'][:12]} "
+              f"({out[name]['strategy_line_count']})  {name}", flush=True)
+    return out
+
+
 def compare(pa, br):
     report = dict(equal=[], different={}, seconds={})
     for name in sorted(set(pa) | set(br)):
@@ -230,7 +270,7 @@ if __name__ == "__main__":
         with open(sys.argv[3], "a") as f:
             f.write(json.dumps(dict(label=sys.argv[2], seconds=cpu_times(harness(), xml))) + "\n")
         sys.exit(0)
-    res = (cpu if mode == "cpu" else gpu)(harness(), xml)
+    res = strategy() if mode == "strategy" else (cpu if mode == "cpu" else gpu)(harness(), xml)
     os.makedirs(os.path.dirname(os.path.abspath(sys.argv[2])), exist_ok=True)
     json.dump(res, open(sys.argv[2], "w"), indent=1, sort_keys=True)
     print(mode, len(res), "cases ->", sys.argv[2], sha(json.dumps({k: {f: v for f, v in r.items() if f != "seconds"} for k, r in res.items()},
