@@ -70,7 +70,7 @@ $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
 HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp tests/harness/etol_harness_rescue.cpp \
-               tests/harness/etol_harness_ode_error.cpp
+               tests/harness/etol_harness_ode_error.cpp tests/harness/etol_harness_track_ladder.cpp
 tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR) $(CSRC)/emi_ipm_control.hpp
 	$(CXX) $(CXXFLAGS) -I$(HOST) -I$(CSRC) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'

@@ -173,6 +173,9 @@ SYMBOLS = {
     "emi_set_batch": (C.c_int, [_P, C.c_int]),
     "emi_set_path": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.c_int]),
     "emi_set_tracks": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "emi_set_track_waypoints": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _I, _D, _D, _D]),
+    "emi_tracks_from_waypoints_dev": (C.c_int, [_P, C.c_int, _P]),
+    "emi_get_tracks": (C.c_int, [_P, _D, _D]),
     "emi_get_layout": (C.c_int, [_P, C.POINTER(Layout)]),
     "emi_jac_structure": (C.c_int, [_P, _I, _I]),
     "emi_invariant_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_ubyte), _I]),

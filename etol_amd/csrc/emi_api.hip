@@ -267,6 +267,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     // tables sized by M are stale now
     c->ntracks = 0;
     c->track_sets = 0;
+    c->wp_nt_dirty = true;      // (the waypoint tables themselves are not per mesh and stay)
     // the per-block cost partials are sized B * node_chunks(M): keep them valid for the batch already set
     if (c->B > 0) EMI_TRY(ensure(c, c->d_cost_part, (size_t)c->B * emi::node_chunks(M) * (c->f32 ? 4 : 8)));
     return EMI_OK;
@@ -424,6 +425,86 @@ int emi_set_tracks(emi_ctx_t c, int ntracks, int nsets, const double* xc, const 
     c->ntracks = ntracks;
     c->track_sets = ntracks > 0 ? nsets : 0;
     return EMI_OK;
+}
+
+int emi_set_track_waypoints(emi_ctx_t c, int ntracks, int nsets, int ld, const int* counts, const double* t, const double* x,
+                            const double* y) {
+    if (!c || ntracks < 0) return fail(c, EMI_ERR_ARG, "emi_set_track_waypoints: bad argument");
+    if (ntracks == 0) {
+        c->wp_ntracks = c->wp_sets = c->wp_ld = 0;
+        return EMI_OK;
+    }
+    if (!t || !x || !y || nsets < 1) return fail(c, EMI_ERR_ARG, "emi_set_track_waypoints: null table");
+    if (ld < 2) return fail(c, EMI_ERR_ARG, "emi_set_track_waypoints: ld %d is below the 2 waypoints a track needs", ld);
+    const size_t rows = (size_t)nsets * ntracks, n = rows * ld;
+    std::vector<int> cnt(rows, ld);
+    for (size_t r = 0; r < rows; ++r) {
+        const int set = (int)(r / ntracks), trk = (int)(r % ntracks);
+        if (counts) cnt[r] = counts[r];
+        if (cnt[r] < 2 || cnt[r] > ld)
+            return fail(c, EMI_ERR_ARG, "emi_set_track_waypoints: set %d, track %d has %d waypoints (2 .. ld = %d)", set, trk, cnt[r], ld);
+        for (int s = 0; s + 1 < cnt[r]; ++s)
+            if (!(t[r * ld + s + 1] > t[r * ld + s]))
+                return fail(c, EMI_ERR_ARG, "emi_set_track_waypoints: set %d, track %d: the times of waypoints %d and %d are not ascending", set,
+                            trk, s, s + 1);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // a launch in flight may still read tables that have to move
+    HIP_TRY(c, c->d_wp.reserve(3 * n));
+    HIP_TRY(c, c->d_wp_cnt.reserve(rows));
+    const double* src[3] = {t, x, y};
+    for (int q = 0; q < 3; ++q) HIP_TRY(c, hipMemcpyAsync(c->d_wp.p + q * n, src[q], n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_wp_cnt.p, cnt.data(), rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->wp_ntracks = ntracks;
+    c->wp_sets = nsets;
+    c->wp_ld = ld;
+    return EMI_OK;
+}
+
+int emi_tracks_from_waypoints_dev(emi_ctx_t c, int n, const void* dSetMap) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->M <= 0) return fail(c, EMI_ERR_STATE, "emi_set_mesh must precede emi_tracks_from_waypoints_dev");
+    if (c->wp_ntracks <= 0) return fail(c, EMI_ERR_STATE, "emi_tracks_from_waypoints_dev: emi_set_track_waypoints has not been called");
+    if (n < 0 || (!dSetMap && n != 0 && n != c->wp_sets) || (dSetMap && n == 0))
+        return fail(c, EMI_ERR_ARG, "emi_tracks_from_waypoints_dev: n = %d (without a map 0 or the table's %d sets, with one >= 1)", n, c->wp_sets);
+    const int sets = dSetMap ? n : c->wp_sets;
+    if ((long long)sets * c->wp_ntracks > 0x7fffffffLL) return fail(c, EMI_ERR_ARG, "emi_tracks_from_waypoints_dev: %d sets of %d tracks", sets, c->wp_ntracks);
+    c->keep.bump();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t total = (size_t)sets * c->wp_ntracks * c->M, rb = c->f32 ? 4 : 8, wn = (size_t)c->wp_sets * c->wp_ntracks * c->wp_ld;
+    EMI_TRY(ensure(c, c->d_trkx, total * rb));
+    EMI_TRY(ensure(c, c->d_trky, total * rb));
+    const double* node_t = (const double*)c->d_t.p;
+    if (c->f32) {               // d_t holds the rounded times; the centres are those of the double ones
+        if (c->wp_nt_dirty || c->d_wp_nt.cap < (size_t)c->M) {
+            const double h = (c->tf - c->t0) / 2.0;
+            std::vector<double> nt(c->M);
+            for (int k = 0; k < c->M; ++k) nt[k] = c->t0 + h * (c->h_tau[k] + 1.0);
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, c->d_wp_nt.reserve(nt.size()));
+            HIP_TRY(c, hipMemcpyAsync(c->d_wp_nt.p, nt.data(), nt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            c->wp_nt_dirty = false;
+        }
+        node_t = c->d_wp_nt.p;
+    }
+    const emi::TrackWaypointArgs a{c->d_wp.p, c->d_wp.p + wn, c->d_wp.p + 2 * wn, node_t, c->d_wp_cnt.p, (const int*)dSetMap,
+                                   c->d_trkx.p, c->d_trky.p, sets, c->wp_ntracks, c->wp_ld, c->M, 0};
+    HIP_TRY(c, c->f32 ? emi::launch_track_waypoints<float>(a, c->stream) : emi::launch_track_waypoints<double>(a, c->stream));
+    c->ntracks = c->wp_ntracks;
+    c->track_sets = sets;
+    return EMI_OK;
+}
+
+int emi_get_tracks(emi_ctx_t c, double* xc, double* yc) {
+    if (!c || !xc || !yc) return fail(c, EMI_ERR_ARG, "emi_get_tracks: null argument");
+    if (c->M <= 0 || c->ntracks <= 0 || c->track_sets <= 0)
+        return fail(c, EMI_ERR_STATE, "emi_get_tracks: the context holds no centres (emi_set_tracks or emi_tracks_from_waypoints_dev on this mesh)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->track_sets * c->ntracks * c->M;
+    EMI_TRY(download_real(c, xc, c->d_trkx.p, n));
+    return download_real(c, yc, c->d_trky.p, n);
 }
 
 int emi_get_layout(emi_ctx_t c, emi_layout_t* o) {

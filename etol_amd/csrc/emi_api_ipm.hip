@@ -499,8 +499,31 @@ int ladder_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t
         if (c->np <= 0) return fail(c, EMI_ERR_ARG, "%s: rung %d brings a record table and the context has none", what, r);
         for (size_t i = 0; i < (size_t)c->np * c->path_sets; ++i) track = track || (int)rungs[r].recs[i * EMI_PATH_REC] == EMI_PATH_TRACK;
     }
-    if (track)
+    if (!track) return EMI_OK;
+    // track rows: their centres are per mesh, and only waypoint tables on the device (emi_set_track_waypoints) let the call supply
+    // them rung by rung
+    if (c->wp_ntracks <= 0)
         return fail(c, EMI_ERR_UNSUPPORTED, "%s: rows of kind EMI_PATH_TRACK have their centres per mesh, which this call cannot supply", what);
+    if (c->wp_sets != 1 && c->wp_sets != c->B)
+        return fail(c, EMI_ERR_ARG, "%s: the waypoint table has %d sets (1 or the batch, %d)", what, c->wp_sets, c->B);
+    const size_t nrec = (size_t)c->np * c->path_sets;
+    const auto track_rows_ok = [&](const double* recs, const std::string& whose) {
+        for (size_t i = 0; i < nrec; ++i) {
+            const double* q = recs + i * EMI_PATH_REC;
+            if ((int)q[0] == EMI_PATH_TRACK && !(q[1] >= 0 && q[1] < c->wp_ntracks))
+                return fail(c, EMI_ERR_ARG, "%s: record %zu of %s names track %d and the waypoint table has %d", what, i, whose.c_str(), (int)q[1],
+                            c->wp_ntracks);
+        }
+        return (int)EMI_OK;
+    };
+    if (c->path_has_track) {
+        std::vector<double> table(nrec * EMI_PATH_REC);
+        HIP_TRY(c, hipSetDevice(c->device));
+        EMI_TRY(download_real(c, table.data(), c->d_path.p, table.size()));
+        EMI_TRY(track_rows_ok(table.data(), "the context's table"));
+    }
+    for (int r = 0; r < nrungs; ++r)
+        if (rungs[r].recs) EMI_TRY(track_rows_ok(rungs[r].recs, "the table of rung " + std::to_string(r)));
     return EMI_OK;
 }
 

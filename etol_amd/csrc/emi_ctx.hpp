@@ -78,6 +78,13 @@ struct emi_ctx_s {
     DevBuf d_path;
     int ntracks = 0, track_sets = 0;
     DevBuf d_trkx, d_trky;
+    // waypoint tables of the tracks (emi_set_track_waypoints): what emi_tracks_from_waypoints_dev makes the centres of, on whatever
+    // mesh the context is on.  Always doubles; independent of mesh, model and batch (only wp_ntracks = 0 drops them)
+    int wp_ntracks = 0, wp_sets = 0, wp_ld = 0;
+    emi::DeviceArray<double> d_wp;          // t | x | y, each [wp_sets][wp_ntracks][wp_ld]
+    emi::DeviceArray<int> d_wp_cnt;         // [wp_sets][wp_ntracks] waypoints of each track (2 .. wp_ld)
+    emi::DeviceArray<double> d_wp_nt;       // f32 contexts: the node times as doubles (d_t holds them rounded), rebuilt after emi_set_mesh
+    bool wp_nt_dirty = true;
     DevBuf d_cost_part;
     DevBuf d_slab;              // partial sums of a split-K defect launch
     DevBuf d_tile_ticket;       // ... and the tickets of its in-kernel combine (zero between launches)

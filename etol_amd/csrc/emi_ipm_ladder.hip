@@ -16,6 +16,9 @@
 //   emi_shard_move_kernel    the instances of a list copied between two sets of up to 4 arrays [instance][rows][ld] whose leading
 //                            dimensions differ (compact M against padded ldm): a thread owns one node and walks the rows, so every
 //                            access of a wave is a run of consecutive doubles along the node axis.  No arithmetic.
+//   emi_track_waypoints_kernel  the centres of the track rows on the context's mesh from waypoint tables kept on the device:
+//                            emi_track_centres (emi_host.cpp) with one thread per (result set, track, node), the waypoint set of a
+//                            result set taken from a list, so the compaction of a batch is part of the launch.  Contraction off.
 //   emi_ipm_refine_decide    host: what becomes of an instance after its solve on a rung (retire / climb, and the verdict)
 //   ipm_solve_refine         the ladder with the instances that meet the ODE tolerance retired rung by rung (emi_ode_error_dev per
 //                            rung, the rule on the host, the rest compacted into a smaller batch of the same context)
@@ -34,6 +37,7 @@ constexpr int PROLONG_T = 256;      // fine nodes per block
 constexpr int PROLONG_ROWS = 4;     // rows per thread
 constexpr int REPAIR_T = 256;
 constexpr int MOVE_T = 256;         // nodes per block
+constexpr int TRACK_T = 256;        // nodes per block
 
 __global__ __launch_bounds__(PROLONG_T) void emi_prolong_kernel(const double* __restrict__ PT, const double* __restrict__ Vc,
                                                                 double* __restrict__ Vf, int Mc, int Mf, int R) {
@@ -143,7 +147,49 @@ __global__ __launch_bounds__(REPAIR_T) void emi_repair_guess_kernel(RepairArgs a
     if (any) { *xp = x; *yp = y; }
 }
 
+// Grid (chunks of TRACK_T nodes, result sets x tracks): one writer per output, nothing shared between threads.  The statements of
+// emi_track_centres, each operation rounded once (contraction off, a true division): the stores are that function's bits, in an
+// f32 context after the conversion emi_set_tracks applies.  The waypoint row of a block is wave-uniform
+template <typename T>
+__global__ __launch_bounds__(TRACK_T) void emi_track_waypoints_kernel(TrackWaypointArgs a) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * TRACK_T + threadIdx.x, pair = a.first + blockIdx.y;
+    if (k >= a.M || pair >= a.n * a.ntracks) return;
+    const int i = pair / a.ntracks, trk = pair % a.ntracks;
+    const size_t row = (size_t)(a.map ? a.map[i] : i) * a.ntracks + trk;
+    const double *t = a.t + row * a.ld, *x = a.x + row * a.ld, *y = a.y + row * a.ld;
+    const int nway = a.cnt[row];
+    const double tv = a.node_t[k];
+    int j = 0;
+    if (tv > t[nway - 1]) {
+        j = nway - 2;
+    } else if (tv >= t[0]) {
+        for (int s = 0; s + 1 < nway; ++s)
+            if (tv >= t[s] && tv <= t[s + 1]) j = s;
+    }
+    const double dt = t[j + 1] - t[j];
+    const size_t out = (size_t)pair * a.M + k;
+    ((T*)a.xc)[out] = (T)((tv - t[j]) * (x[j + 1] - x[j]) / dt + x[j]);
+    ((T*)a.yc)[out] = (T)((tv - t[j]) * (y[j + 1] - y[j]) / dt + y[j]);
+}
+
 }  // namespace
+
+template <typename T>
+hipError_t launch_track_waypoints(TrackWaypointArgs a, hipStream_t s) {
+    if (a.n <= 0 || a.ntracks <= 0 || a.M <= 0) return hipSuccess;
+    if (a.ld < 2 || (long long)a.n * a.ntracks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int pairs = a.n * a.ntracks;
+    for (a.first = 0; a.first < pairs; a.first += 65535) {
+        const int ny = pairs - a.first < 65535 ? pairs - a.first : 65535;
+        hipLaunchKernelGGL(emi_track_waypoints_kernel<T>, dim3((a.M + TRACK_T - 1) / TRACK_T, ny), dim3(TRACK_T), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+template hipError_t launch_track_waypoints<double>(TrackWaypointArgs, hipStream_t);
+template hipError_t launch_track_waypoints<float>(TrackWaypointArgs, hipStream_t);
 
 hipError_t launch_prolong(const double* PT, const double* Vc, double* Vf, int Mc, int Mf, int R, hipStream_t s) {
     if (R <= 0) return hipSuccess;
@@ -226,6 +272,8 @@ int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, doubl
         L_TRY(emi_lgl(M, tau.data(), wt.data(), D.data()));
         L_TRY(emi_set_mesh(c, M, tau.data(), wt.data(), D.data(), t0, tf));
         if (g.recs) L_TRY(emi_set_path(c, c->np, c->path_sets, g.recs, c->px, c->py));
+        // track rows (the entry point has seen to the waypoints): their centres on this mesh, ahead of the repair, which reads them
+        if (c->np > 0 && c->path_has_track) L_TRY(emi_tracks_from_waypoints_dev(c, 0, nullptr));
         // where this rung's iterate lives: the caller's arrays on the last rung, else one of the two sets (not the previous rung's)
         void *cX = dX, *cU = dU, *cLF = dLamF, *cLC = dLamC;
         if (!last) {
@@ -302,6 +350,21 @@ int refine_rungs(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0
             L_TRY(refine_set_table(c, master, c->np, sets, live));
             table_changed = true;
         }
+        // the live list on the device, for whoever of this rung needs the caller's numbering (uploaded once)
+        bool live_up = false;
+        const auto need_live = [&]() -> int {
+            if (live_up) return EMI_OK;
+            L_HIP(hipMemcpyAsync(d_live, live.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            live_up = true;
+            return EMI_OK;
+        };
+        // track rows: the centres of the live instances on this mesh, the compaction done by the set map in the launch (a shared
+        // waypoint set serves whoever is live), ahead of the repair, which reads them
+        if (c->np > 0 && c->path_has_track) {
+            const bool per_instance = c->wp_sets == B && B > 1;
+            if (per_instance) L_TRY(need_live());
+            L_TRY(emi_tracks_from_waypoints_dev(c, per_instance ? n : 0, per_instance ? d_live : nullptr));
+        }
         double *cX = w.rX[cur].p, *cU = w.rU[cur].p, *cLF = w.rLamF[cur].p, *cLC = w.rLamC[cur].p;
         if (r == 0) {
             L_HIP(hipMemcpyAsync(cX, dX0, (size_t)B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -314,7 +377,7 @@ int refine_rungs(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0
         }
         emi_ipm_bounds_t bd = g.bd;
         if (bd.nsets == B && n < B) {               // per-instance bounds come in the caller's numbering
-            L_HIP(hipMemcpyAsync(d_live, live.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            L_TRY(need_live());
             ShardMoveArgs a{};
             a.src[0] = (const double*)g.bd.zl; a.src[1] = (const double*)g.bd.zu; a.dst[0] = w.zl.p; a.dst[1] = w.zu.p;
             a.rows[0] = a.rows[1] = nv; a.sld[0] = a.sld[1] = a.dld[0] = a.dld[1] = M;
@@ -395,11 +458,13 @@ int ipm_solve_refine(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, doubl
     if (c->np > 0) L_TRY(emi_api::download_real(c, master.data(), c->d_path.p, master.size()));
     bool table_changed = false;
     const int st = refine_rungs(c, nrungs, rungs, t0, tf, rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC, results, err, out, master, sets, table_changed);
-    // the context as the caller knows it: batch B, the full table -- also after an error (whose message stays)
+    // the context as the caller knows it: batch B, the full table, the centres of every set -- also after an error (whose message stays)
     const std::string msg = c->err;
     int back = EMI_OK;
     if (c->B != B) back = emi_set_batch(c, B);
     if (!back && table_changed) back = emi_set_path(c, c->np, sets, master.data(), c->px, c->py);
+    // ... and, where the table has track rows, the centres of all sets on the mesh the context is on
+    if (!back && c->np > 0 && c->path_has_track && c->wp_ntracks > 0 && c->M > 0) back = emi_tracks_from_waypoints_dev(c, 0, nullptr);
     if (st) { c->err = msg; return st; }
     return back;
 }

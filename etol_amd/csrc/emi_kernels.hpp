@@ -254,6 +254,16 @@ struct RepairArgs {
     int B, ns, M, np, path_sets, px, py, ntracks, track_sets;
 };
 hipError_t launch_repair_guess(const RepairArgs& a, hipStream_t s);
+// the centres of the track rows on a mesh from waypoint tables t, x, y [sets][ntracks][ld] (cnt [sets][ntracks] waypoints each):
+// xc, yc [n][ntracks][M] of type T at the node times node_t [M], result set i from waypoint set map[i] (a null map: i).  The
+// arithmetic of emi_track_centres (csrc/emi_host.cpp) per (set, track, node), in double, stored as T
+struct TrackWaypointArgs {
+    const double *t, *x, *y, *node_t;
+    const int *cnt, *map;
+    void *xc, *yc;
+    int n, ntracks, ld, M, first;       // first: the (set, track) pair of blockIdx.y == 0 (more pairs than one grid go out in pieces)
+};
+template <typename T> hipError_t launch_track_waypoints(TrackWaypointArgs a, hipStream_t s);
 struct IpmLadderWs;
 void ipm_ladder_destroy(IpmLadderWs* w);
 int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,

@@ -76,6 +76,8 @@ class Evaluator:
         self._nd = None         # batched user, and two ctypes round trips per pass show at 14 - 20 us passes; reset by every set_*
         self._kept = None       # the VALS tensor eval_dev last ran a full Jacobian pass into (held: its address cannot be recycled) ...
         self._kept_version = -1  # ... and its torch version counter then: any torch write to it since shows as another value
+        self._wp_shape = None   # (sets, tracks) of the waypoint tables the context holds ...
+        self._trk_shape = None  # ... and of its centres on the present mesh (emi_get_tracks takes arrays of that size on trust)
 
     def _changed(self):
         self._lay = None
@@ -102,6 +104,7 @@ class Evaluator:
         self.tau, self.w, self.D = (np.ascontiguousarray(a, dtype=np.float64) for a in (tau, w, D))
         self._ck(self.lib.emi_set_mesh(self.ctx, M, _dp(self.tau), _dp(self.w), _dp(self.D), t0, tf), "emi_set_mesh")
         self._changed()
+        self._trk_shape = None
         self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
 
     def set_model(self, model, params=(), maximize=False):
@@ -154,6 +157,43 @@ class Evaluator:
             xc, yc = xc[None], yc[None]
         self._ck(self.lib.emi_set_tracks(self.ctx, xc.shape[1], xc.shape[0], _dp(xc), _dp(yc)), "emi_set_tracks")
         self._changed()
+        self._trk_shape = (xc.shape[0], xc.shape[1]) if xc.shape[1] else None
+
+    def set_track_waypoints(self, t, x, y, counts=None):
+        """Waypoint tables of the tracks, kept on the device across meshes: t, x, y [nsets][ntracks][ld] (2-D: one shared set),
+        counts [nsets][ntracks] waypoints of each track (None: ld everywhere).  An empty table drops them (emi_set_track_waypoints)"""
+        t, x, y = (np.ascontiguousarray(v, dtype=np.float64) for v in (t, x, y))
+        if t.ndim == 2:
+            t, x, y = t[None], x[None], y[None]
+        assert t.ndim == 3 and t.shape == x.shape == y.shape
+        nsets, ntracks, ld = t.shape
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(nsets, ntracks)
+        self._ck(self.lib.emi_set_track_waypoints(self.ctx, ntracks, nsets, ld, cnt.ctypes.data_as(C.POINTER(C.c_int)) if cnt is not None else None,
+                                                  _dp(t) if t.size else None, _dp(x) if x.size else None, _dp(y) if y.size else None),
+                 "emi_set_track_waypoints")
+        self._wp_shape = (nsets, ntracks) if ntracks else None
+
+    def tracks_from_waypoints(self, set_map=None):
+        """The centres of the tracks on the present mesh from the waypoint tables, on the device (asynchronous): result set i from
+        waypoint set set_map[i] (int32 device tensor; None: every set in order) (emi_tracks_from_waypoints_dev)"""
+        if set_map is not None:
+            assert set_map.dtype == torch.int32 and set_map.is_contiguous()
+        n = 0 if set_map is None else set_map.numel()
+        self._ck(self.lib.emi_tracks_from_waypoints_dev(self.ctx, int(n), self._ipm_addr(set_map)), "emi_tracks_from_waypoints_dev")
+        self._changed()
+        self._trk_shape = (n or self._wp_shape[0], self._wp_shape[1])
+
+    def get_tracks(self):
+        """(xc, yc) [sets][ntracks][M]: the centres the context holds (synchronises; emi_get_tracks); EmiError where it holds none"""
+        sets, ntracks = self._trk_shape or (0, 0)
+        M = self.layout.M
+        xc, yc = np.empty((sets, ntracks, max(M, 1))), np.empty((sets, ntracks, max(M, 1)))
+        if xc.size == 0:        # nothing to come: the call says why
+            xc, yc = np.empty(1), np.empty(1)
+        self._ck(self.lib.emi_get_tracks(self.ctx, _dp(xc), _dp(yc)), "emi_get_tracks")
+        return xc, yc
 
     def use_stream(self, stream_ptr):
         self._ck(self.lib.emi_set_stream(self.ctx, C.c_void_p(stream_ptr)), "emi_set_stream")
@@ -643,6 +683,7 @@ class Evaluator:
         fn = self.lib.emi_ipm_solve_ladder_dev if dev else self.lib.emi_ipm_solve_ladder_host
         st = fn(self.ctx, len(rungs), arr, float(t0), float(tf), A(X0), A(U0), A(X), A(U), A(LamF), A(LamC) if npth else None, res)
         self._changed()
+        self._trk_shape = self._wp_shape    # (an upper bound after an error)
         self._ck(st, fn.__name__)
         self.tau, self.w, self.D = lgl(Ml)
         self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
@@ -725,6 +766,7 @@ class Evaluator:
         st = fn(self.ctx, nr, arr, float(t0), float(tf), C.byref(rf), A(X0), A(U0), ldm, A(X), A(U), A(LamF), A(LamC) if npth else None, res,
                 _dp(err), summ)
         self._changed()
+        self._trk_shape = self._wp_shape    # (an upper bound after an error)
         self._ck(st, fn.__name__)
         Ml = self.layout.M
         self.tau, self.w, self.D = lgl(Ml)

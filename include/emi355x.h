@@ -228,6 +228,29 @@ int emi_set_path(emi_ctx_t ctx, int np, int nsets, const double* recs,
 /* xc, yc: [nsets][ntracks][M] disc centres at the node times               */
 int emi_set_tracks(emi_ctx_t ctx, int ntracks, int nsets, const double* xc,
                    const double* yc);
+/* The centres of the tracks from WAYPOINT TABLES kept on the device, for whatever mesh the context is on -- the device route to what
+ * emi_track_centres per track plus emi_set_tracks do from the host, and what the mesh ladder calls per rung.
+ * emi_set_track_waypoints: t, x, y host [nsets][ntracks][ld]; counts host [nsets][ntracks], the waypoints of each track, each in
+ * 2 .. ld (NULL: ld everywhere; what lies behind a track's count is never read).  Times strictly ascending within a count, else
+ * EMI_ERR_ARG naming set and track; EMI_ERR_ARG also for a count outside 2 .. ld and a NULL table.  The tables are kept as
+ * doubles in every context and belong to no mesh, model or batch: they survive emi_set_mesh, emi_set_model* and emi_set_batch,
+ * and only ntracks = 0 drops them.  Needs no mesh; touches neither the centres the context holds nor the record of
+ * EMI_EVAL_KEEP_INVARIANT.  Synchronises.
+ * emi_tracks_from_waypoints_dev: writes the centre arrays of the context (those of emi_set_tracks) at the context's node times.
+ * dSetMap NULL (n = 0 or nsets): result set s from waypoint set s.  Otherwise n device ints in [0, nsets), result set i from
+ * waypoint set dSetMap[i]: a permutation compacts, a repeated value copies; values in range are the caller's duty.  Afterwards
+ * the context holds ntracks tracks in n (or nsets) sets, as after emi_set_tracks (also for EMI_EVAL_KEEP_INVARIANT); the batch
+ * need not match yet -- the next evaluation checks that.  Per (set, track, node) the statements of emi_track_centres, every
+ * operation rounded once, none fused: the bits are that function's; in an f32 context computed in double at the double node
+ * times and stored with the conversion of emi_set_tracks.  Asynchronous on the context's stream, one writer per output, two
+ * calls give the same bits.  EMI_ERR_STATE: no mesh, no waypoints.  EMI_ERR_ARG: n < 0, n other than 0 or nsets with a NULL map,
+ * n = 0 with a map.
+ * emi_get_tracks: synchronises and returns the centres the context holds, [sets][ntracks][M] doubles each; EMI_ERR_STATE where
+ * it holds none (no mesh, or none set since emi_set_mesh).                                                                    */
+int emi_set_track_waypoints(emi_ctx_t ctx, int ntracks, int nsets, int ld, const int* counts, const double* t, const double* x,
+                            const double* y);
+int emi_tracks_from_waypoints_dev(emi_ctx_t ctx, int n, const void* dSetMap);
+int emi_get_tracks(emi_ctx_t ctx, double* xc, double* yc);
 int emi_get_layout(emi_ctx_t ctx, emi_layout_t* out);
 
 /* ---- Newton step of the NLP iteration (batch of one, f64 contexts) --------
@@ -544,13 +567,16 @@ int emi_ipm_solve_shard_host(emi_ctx_t ctx, double* X, double* U, const emi_ipm_
  * context's mesh: an interior node whose position (px, py) lies inside a keep-out (quadratic form below 1.025) is moved out
  * radially to 1.05, from a dead centre (form below 1e-12) along the minor axis; up to 50 sweeps over the table rows in row
  * order, until a sweep moves nothing.  End nodes are never touched; rows of kind EMI_PATH_TRACK take their centres from the
- * arrays of emi_set_tracks (EMI_ERR_STATE without them); traced rows are skipped.  Single rounded operations, never fused: the
+ * arrays of emi_set_tracks / emi_tracks_from_waypoints_dev (EMI_ERR_STATE without them); traced rows are skipped.  Single rounded operations, never fused: the
  * bits are the formulas' bits.  Asynchronous.  EMI_ERR_UNSUPPORTED: f32 context;  EMI_ERR_STATE: mesh, model or batch not set.
  *
  * emi_ipm_solve_ladder_dev: per rung r = 0 .. nrungs-1
  *   1. emi_lgl and emi_set_mesh(M_r, .., t0, tf);
  *   2. emi_set_path with the rung's recs where given (np, nsets, px, py as the context has them: a caller inflates its
  *      keep-outs per rung this way); after the call the context holds what the last rung set;
+ *   2a. where the table now in force has rows of kind EMI_PATH_TRACK: emi_tracks_from_waypoints_dev (identity map), the centres of
+ *      the moving discs at this rung's node times from the waypoint tables of emi_set_track_waypoints -- one launch, nothing goes
+ *      up or down; after the call the context holds the centres of the last rung's mesh;
  *   3. from the second rung on, X and U prolonged from the previous rung's final iterate (emi_prolong_dev);
  *   4. emi_repair_guess_dev where the rung asks for it;
  *   5. emi_ipm_solve_shard_dev on this rung with the rung's bounds and options (its start pushes the prolonged point inside the
@@ -562,9 +588,12 @@ int emi_ipm_solve_shard_host(emi_ctx_t ctx, double* X, double* U, const emi_ipm_
  * size comes down.  On return the context is on the last rung's mesh.  A ladder of one rung runs the launches of
  * emi_ipm_solve_shard_dev on a copy of the start.
  * EMI_ERR_UNSUPPORTED: whatever emi_ipm_solve_shard_dev refuses, and a record table (the context's or a rung's) with a row of
- * kind EMI_PATH_TRACK: the centres of such rows are per mesh and this call has no way to supply them.  EMI_ERR_ARG: nrungs < 1,
- * a rung with M < 2, a NULL that is not optional, recs given while the context has no table.  EMI_ERR_STATE: model or batch
- * not set (whatever mesh the context is on is replaced).  The _host form takes host arrays (every rung's zl, zu included) and
+ * kind EMI_PATH_TRACK while the context holds NO waypoint tables: the centres of such rows are per mesh and without the tables
+ * this call has no way to supply them (centres set with emi_set_tracks go with the first emi_set_mesh).  EMI_ERR_ARG: nrungs < 1,
+ * a rung with M < 2, a NULL that is not optional, recs given while the context has no table; with track rows and waypoint
+ * tables: a track row (of the context's table or of a rung's) that names a track outside 0 .. ntracks-1 of the waypoint tables,
+ * and waypoint tables whose nsets is neither 1 nor B.  EMI_ERR_STATE: model or batch not set (whatever mesh the context is on
+ * is replaced).  The _host form takes host arrays (every rung's zl, zu included) and
  * synchronises.                                                                                                                 */
 typedef struct emi_ipm_rung {
   int M;                       /* LGL nodes of this rung */
@@ -646,6 +675,9 @@ int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const do
  *   1. emi_lgl and emi_set_mesh(M_r, .., t0, tf);
  *   2. emi_set_batch(n) for the n live instances and emi_set_path with their rows of the record table (the context's table is read
  *      back once at entry; a rung's recs, given for all B instances in the caller's numbering, replaces that copy);
+ *   2a. where the table has rows of kind EMI_PATH_TRACK: emi_tracks_from_waypoints_dev for the live instances -- waypoint tables with
+ *      one set per instance (nsets == B) are read through the live list as the set map, so the compaction of the centres happens
+ *      in the launch; a shared set (nsets == 1) serves whoever is live;
  *   3. from the second rung on, X and U of the live instances prolonged from the previous rung's compact iterate: the row map of
  *      emi_prolong_rows_dev does the compaction in the same pass;
  *   4. a rung's bounds with nsets == B are given in the caller's numbering: the sets of the live instances are gathered
@@ -662,10 +694,11 @@ int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const do
  * rung (NaN without one).  The starts dX0 [B][ns][M_0], dU0 [B][nc][M_0] are only read.  While nobody has retired the launches on the
  * trajectories are those of emi_ipm_solve_ladder_dev (into arrays of the context) and every bit of an iterate is that call's; an
  * instance solved in a compacted batch agrees with the same instance solved alone as two batch sizes agree in
- * emi_ipm_solve_shard_dev.  Two identical calls give the same bits.  On return, also after an error, the context has batch B again and
- * the full record table (that of the last rung which brought one); it is on the mesh of the last rung that was solved.  The
+ * emi_ipm_solve_shard_dev.  Two identical calls give the same bits.  On return, also after an error, the context has batch B again,
+ * the full record table (that of the last rung which brought one) and, with track rows, the centres of all sets of the waypoint
+ * tables on the mesh it is on; it is on the mesh of the last rung that was solved.  The
  * compact iterates and multipliers of two consecutive rungs, the gathered bounds and the lists are device arrays of the context.
- * Statuses: those of emi_ipm_solve_ladder_dev, and EMI_ERR_ARG: rf NULL, ode_tol negative or NaN, first_check outside
+ * Statuses: those of emi_ipm_solve_ladder_dev (track rows are taken with waypoint tables and refused without, as there), and EMI_ERR_ARG: rf NULL, ode_tol negative or NaN, first_check outside
  * 0 .. nrungs-1, one of ul / uu without the other, ldm below the largest rung, a rung whose bounds have nsets other than 1 or B, a
  * NULL err or out.  Instances are never masked instead of compacted.  The _host form takes host arrays (every rung's zl, zu included;
  * X, U, LamF, LamC go in and come out, so that the columns beyond an instance's mesh are the caller's) and synchronises.         */
