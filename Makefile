@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-nlp check-mesh-driver check-ode-operator
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -83,6 +83,14 @@ KEEP_CHECK_OUT ?= $(LIBDIR)/keep_record_check
 check-keep-record: tests/harness/keep_record_main.cpp $(CSRC)/emi_keep_record.hpp | $(LIBDIR)
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -I$(CSRC) -o $(KEEP_CHECK_OUT) $<
 	$(KEEP_CHECK_OUT)
+
+# the bookkeeping of the lock-step ladder and refinement (emi_refine_book.hpp, host-only: who is live, who retires where) as a
+# stand-alone program under the host sanitizers, with scripted statuses and estimates; the rule comes from emi_host.cpp
+BOOK_CHECK_OUT ?= $(LIBDIR)/refine_book_check
+check-refine-book: tests/harness/refine_book_main.cpp $(CSRC)/emi_refine_book.hpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Iinclude -I$(CSRC) -o $(BOOK_CHECK_OUT) \
+		tests/harness/refine_book_main.cpp $(CSRC)/emi_host.cpp -lm
+	$(BOOK_CHECK_OUT)
 
 # the NLP iteration (emi_nlp.cpp: its state object, the steps and iterates it copies and takes back) as a stand-alone program under
 # the host sanitizers, on the CPU oracle: no Python, no device

@@ -456,13 +456,22 @@ int emi_ipm_solve_shard_host(emi_ctx_t c, double* X, double* U, const emi_ipm_bo
 }
 
 // ---- the mesh ladder over the lock-step solve (kernels and driver: emi_ipm_ladder.hip) ---------------------------------------------
-int emi_prolong_dev(emi_ctx_t c, int Mc, int Mf, const void* dPT, const void* dVc, int R, void* dVf) {
+namespace {
+
+// emi_prolong_dev (no row map) and emi_prolong_rows_dev: one kernel
+int prolong(emi_ctx_t c, const char* what, int Mc, int Mf, const void* dPT, const void* dVc, int R, const void* dRowMap, void* dVf) {
     if (!c) return EMI_ERR_ARG;
-    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_prolong_dev: f64 contexts only");
-    if (Mc < 2 || Mf < 2 || R < 0 || !dPT || (R > 0 && (!dVc || !dVf))) return fail(c, EMI_ERR_ARG, "emi_prolong_dev: bad argument");
+    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "%s: f64 contexts only", what);
+    if (Mc < 2 || Mf < 2 || R < 0 || !dPT || (R > 0 && (!dVc || !dVf))) return fail(c, EMI_ERR_ARG, "%s: bad argument", what);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, emi::launch_prolong((const double*)dPT, (const double*)dVc, (double*)dVf, Mc, Mf, R, c->stream));
+    HIP_TRY(c, emi::launch_prolong_rows((const double*)dPT, (const double*)dVc, (const int*)dRowMap, 1, (double*)dVf, Mc, Mf, R, c->stream));
     return EMI_OK;
+}
+
+}  // namespace
+
+int emi_prolong_dev(emi_ctx_t c, int Mc, int Mf, const void* dPT, const void* dVc, int R, void* dVf) {
+    return prolong(c, "emi_prolong_dev", Mc, Mf, dPT, dVc, R, nullptr, dVf);
 }
 
 int emi_repair_guess_dev(emi_ctx_t c, void* dX) {
@@ -527,16 +536,44 @@ int ladder_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t
     return EMI_OK;
 }
 
+// what the _dev forms of the ladder, with and without refinement, ask of their arrays and of the horizon
+int ladder_args_check(emi_ctx_t c, const char* what, double t0, double tf, const void* dX0, const void* dU0, const void* dX, const void* dU,
+                      const void* dLamF, const void* dLamC, const void* results) {
+    if (!dX0 || !dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np_total(c) > 0 && !dLamC) || !results)
+        return fail(c, EMI_ERR_ARG, "%s: null argument", what);
+    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "%s: tf must exceed t0", what);
+    return EMI_OK;
+}
+
+// the two _host forms, after their checks: the starts, every rung's zl and zu and the outputs [B][rows][ld] staged, the _dev form run.
+// rf NULL: the ladder, whose outputs only come out; with refinement they go in too (the columns beyond an instance's mesh are the caller's)
+int ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf, const double* X0,
+                const double* U0, int ld, double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results, double* err,
+                emi_ipm_refine_result_t* out) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostStager s(c);
+    const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, L = (size_t)ld;
+    const bool in = rf != nullptr;
+    const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
+    void *dX = s.place(X, B * c->ns * L * 8, in, true), *dU = s.place(U, B * c->nc * L * 8, in, true);
+    void *dLF = s.place(LamF, B * c->ns * L * 8, in, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * L * 8, in, true);
+    std::vector<emi_ipm_rung_t> dr(rungs, rungs + nrungs);
+    for (emi_ipm_rung_t& g : dr) {
+        const size_t bytes = (size_t)std::max(g.bd.nsets, 0) * nv * (size_t)g.M * 8;
+        g.bd.zl = s.place(g.bd.zl, bytes, true, false);
+        g.bd.zu = s.place(g.bd.zu, bytes, true, false);
+    }
+    IPM_HOST_END(rf ? emi_ipm_solve_refine_dev(c, nrungs, dr.data(), t0, tf, rf, dX0, dU0, ld, dX, dU, dLF, dLC, results, err, out)
+                    : emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
+}
+
 }  // namespace
 
 int emi_ipm_solve_ladder_dev(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0,
                              void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(ladder_check(c, "emi_ipm_solve_ladder_dev", nrungs, rungs));
-    const int np = np_total(c);
-    if (!dX0 || !dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np > 0 && !dLamC) || !results)
-        return fail(c, EMI_ERR_ARG, "emi_ipm_solve_ladder_dev: null argument");
-    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_ipm_solve_ladder_dev: tf must exceed t0");
+    EMI_TRY(ladder_args_check(c, "emi_ipm_solve_ladder_dev", t0, tf, dX0, dU0, dX, dU, dLamF, dLamC, results));
     HIP_TRY(c, hipSetDevice(c->device));
     return emi::ipm_solve_ladder(c, nrungs, rungs, t0, tf, dX0, dU0, dX, dU, dLamF, dLamC, results);
 }
@@ -545,29 +582,12 @@ int emi_ipm_solve_ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* run
                               double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(ladder_check(c, "emi_ipm_solve_ladder_host", nrungs, rungs));
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostStager s(c);
-    const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, ML = (size_t)rungs[nrungs - 1].M;
-    const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
-    void *dX = s.place(X, B * c->ns * ML * 8, false, true), *dU = s.place(U, B * c->nc * ML * 8, false, true);
-    void *dLF = s.place(LamF, B * c->ns * ML * 8, false, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * ML * 8, false, true);
-    std::vector<emi_ipm_rung_t> dr(rungs, rungs + nrungs);
-    for (emi_ipm_rung_t& g : dr) {
-        const size_t bytes = (size_t)std::max(g.bd.nsets, 0) * nv * (size_t)g.M * 8;
-        g.bd.zl = s.place(g.bd.zl, bytes, true, false);
-        g.bd.zu = s.place(g.bd.zu, bytes, true, false);
-    }
-    IPM_HOST_END(emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
+    return ladder_host(c, nrungs, rungs, t0, tf, nullptr, X0, U0, rungs[nrungs - 1].M, X, U, LamF, LamC, results, nullptr, nullptr);
 }
 
 // ---- the ladder with refinement: instances that meet the ODE tolerance leave the batch (kernels and driver: emi_ipm_ladder.hip) -------
 int emi_prolong_rows_dev(emi_ctx_t c, int Mc, int Mf, const void* dPT, const void* dVc, int R, const void* dRowMap, void* dVf) {
-    if (!c) return EMI_ERR_ARG;
-    if (c->f32) return fail(c, EMI_ERR_UNSUPPORTED, "emi_prolong_rows_dev: f64 contexts only");
-    if (Mc < 2 || Mf < 2 || R < 0 || !dPT || (R > 0 && (!dVc || !dVf))) return fail(c, EMI_ERR_ARG, "emi_prolong_rows_dev: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, emi::launch_prolong_rows((const double*)dPT, (const double*)dVc, (const int*)dRowMap, 1, (double*)dVf, Mc, Mf, R, c->stream));
-    return EMI_OK;
+    return prolong(c, "emi_prolong_rows_dev", Mc, Mf, dPT, dVc, R, dRowMap, dVf);
 }
 
 int emi_shard_move_dev(emi_ctx_t c, int n, const void* dSrcIdx, const void* dDstIdx, int narrays, const int* rows, const void* const* src,
@@ -614,10 +634,7 @@ int emi_ipm_solve_refine_dev(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rung
                              emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(refine_check(c, "emi_ipm_solve_refine_dev", nrungs, rungs, rf, ldm, err, out));
-    const int np = np_total(c);
-    if (!dX0 || !dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np > 0 && !dLamC) || !results)
-        return fail(c, EMI_ERR_ARG, "emi_ipm_solve_refine_dev: null argument");
-    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "emi_ipm_solve_refine_dev: tf must exceed t0");
+    EMI_TRY(ladder_args_check(c, "emi_ipm_solve_refine_dev", t0, tf, dX0, dU0, dX, dU, dLamF, dLamC, results));
     HIP_TRY(c, hipSetDevice(c->device));
     return emi::ipm_solve_refine(c, nrungs, rungs, t0, tf, *rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC, results, err, out);
 }
@@ -627,20 +644,7 @@ int emi_ipm_solve_refine_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* run
                               emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(refine_check(c, "emi_ipm_solve_refine_host", nrungs, rungs, rf, ldm, err, out));
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostStager s(c);
-    const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, L = (size_t)ldm;
-    const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
-    // (in and out: the columns beyond an instance's mesh are the caller's)
-    void *dX = s.place(X, B * c->ns * L * 8, true, true), *dU = s.place(U, B * c->nc * L * 8, true, true);
-    void *dLF = s.place(LamF, B * c->ns * L * 8, true, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * L * 8, true, true);
-    std::vector<emi_ipm_rung_t> dr(rungs, rungs + nrungs);
-    for (emi_ipm_rung_t& g : dr) {
-        const size_t bytes = (size_t)std::max(g.bd.nsets, 0) * nv * (size_t)g.M * 8;
-        g.bd.zl = s.place(g.bd.zl, bytes, true, false);
-        g.bd.zu = s.place(g.bd.zu, bytes, true, false);
-    }
-    IPM_HOST_END(emi_ipm_solve_refine_dev(c, nrungs, dr.data(), t0, tf, rf, dX0, dU0, ldm, dX, dU, dLF, dLC, results, err, out));
+    return ladder_host(c, nrungs, rungs, t0, tf, rf, X0, U0, ldm, X, U, LamF, LamC, results, err, out);
 }
 
 }  // extern "C"

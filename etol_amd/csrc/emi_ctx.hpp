@@ -193,7 +193,7 @@ struct emi_ctx_s {
 #define HIP_TRY_AS(c, who, call)                                                                                        \
     do {                                                                                                                \
         const hipError_t e_ = (call);                                                                                   \
-        if (e_ != hipSuccess) return emi_api::fail((c), EMI_ERR_HIP, who ": %s failed: %s", #call, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return emi_api::fail((c), EMI_ERR_HIP, "%s: %s failed: %s", who, #call, hipGetErrorString(e_)); \
     } while (0)
 
 // a step that returns an EMI_* status: anything but EMI_OK ends the calling function with it

@@ -191,4 +191,34 @@ int emi_track_centres(int nway, const double* t, const double* x, const double* 
     return EMI_OK;
 }
 
+// Prolongation between two LGL meshes (the mesh ladder, emi_ipm_ladder.hip): P[Mf][Mc], row q = the Lagrange basis
+// polynomials of the coarse nodes at tau_f[q], barycentric second form with the weights (-1)^j sqrt(w_j) (interp_lgl of
+// host/eMI355X.cpp as a matrix).  No product feeds a sum here: there is nothing a compiler could contract.
+int emi_prolong_matrix(int Mc, const double* tau_c, const double* w_c, int Mf, const double* tau_f, double* P) {
+    if (Mc < 2 || Mf < 2 || !tau_c || !w_c || !tau_f || !P) return EMI_ERR_ARG;
+    for (int q = 0; q < Mf; ++q) {
+        double* row = P + (size_t)q * Mc;
+        int hit = -1;
+        double den = 0.0;
+        for (int j = 0; j < Mc; ++j) {
+            const double dlt = tau_f[q] - tau_c[j];
+            if (dlt == 0.0) { hit = j; break; }
+            row[j] = ((j & 1) ? -1.0 : 1.0) * std::sqrt(w_c[j]) / dlt;
+            den += row[j];
+        }
+        for (int j = 0; j < Mc; ++j) row[j] = hit >= 0 ? (j == hit ? 1.0 : 0.0) : row[j] / den;
+    }
+    return EMI_OK;
+}
+
+// What becomes of an instance of the lock-step mesh refinement after its solve on a rung: 1 where it retires, 0 where it
+// climbs, and the verdict (the table in emi355x.h).
+int emi_ipm_refine_decide(int status, double err, double ode_tol, int has_good, int is_last, int* verdict) {
+    const bool ok = status == EMI_IPM_CONVERGED || status == EMI_IPM_ACCEPTABLE;
+    const bool met = std::isfinite(err) && err <= ode_tol;
+    const int v = ok ? (met ? EMI_REFINE_MET : EMI_REFINE_NOT_MET) : (has_good ? EMI_REFINE_FELL_BACK : EMI_REFINE_FAILED);
+    if (verdict) *verdict = v;
+    return !(ok && !met && !is_last);
+}
+
 }  // extern "C"

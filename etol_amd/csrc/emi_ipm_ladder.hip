@@ -1,34 +1,32 @@
-// emi_ipm_ladder.hip -- the mesh ladder of a context's whole batch (emi_ipm_solve_ladder_*): prolongation between LGL meshes,
-// the repair of a guess that lies inside keep-outs, and the driver that takes the B instances from rung to rung.
+// emi_ipm_ladder.hip -- the mesh ladder of a context's whole batch (emi_ipm_solve_ladder_*, emi_ipm_solve_refine_*): prolongation
+// between LGL meshes, the repair of a guess that lies inside keep-outs, the moving discs' centres per mesh, and the one driver that
+// takes the B instances from rung to rung, with or without retiring those that meet the ODE tolerance.
 //
-//   emi_prolong_matrix       host: P[Mf][Mc], row q = the Lagrange basis polynomials of the coarse nodes at tau_f[q] (barycentric
-//                            second form, weights (-1)^j sqrt(w_j): interp_lgl of host/eMI355X.cpp as a matrix)
-//   emi_prolong_kernel       Vf[r][q] = sum_j PT[j][q] Vc[r][j]: a thread owns one fine node and PROLONG_ROWS rows, reads PT[j][q]
+//   emi_prolong_rows_kernel  Vf[r][q] = sum_j PT[j][q] Vc[src(r)][j]: a thread owns one fine node and PROLONG_ROWS rows, reads PT[j][q]
 //                            once per j (coalesced along q), the coarse values as wave-uniform loads, and accumulates with fma
-//                            in ascending j.  One writer per output; a row's bits depend on nothing but the row and P.
+//                            in ascending j.  One writer per output; a row's bits depend on nothing but its source row and P.  The
+//                            source row comes from a list (the gather that compacts a batch and the prolongation are one pass);
+//                            without a list it is the row itself (emi_prolong_dev)
 //   emi_repair_guess_kernel  mi355x::repair_guess (host/eMI355X.cpp) with one thread per (instance, interior node): nodes do not
 //                            interact, so the sweeps of a node are the host's sweeps of that node.  Contraction off.
-//   ipm_solve_ladder         per rung: emi_lgl + emi_set_mesh, emi_set_path where the rung brings a table, prolongation of X and U
-//                            from the previous rung's final iterate, the repair where asked for, emi_ipm_solve_shard_dev.  Nothing
-//                            of a trajectory's size crosses to the host between rungs.
-//   emi_prolong_rows_kernel  emi_prolong_kernel with the source row of an output row taken from a list: the gather that compacts a
-//                            batch and the prolongation are one pass.  The same sums: a row has the bits of its source row alone.
 //   emi_shard_move_kernel    the instances of a list copied between two sets of up to 4 arrays [instance][rows][ld] whose leading
 //                            dimensions differ (compact M against padded ldm): a thread owns one node and walks the rows, so every
 //                            access of a wave is a run of consecutive doubles along the node axis.  No arithmetic.
 //   emi_track_waypoints_kernel  the centres of the track rows on the context's mesh from waypoint tables kept on the device:
 //                            emi_track_centres (emi_host.cpp) with one thread per (result set, track, node), the waypoint set of a
 //                            result set taken from a list, so the compaction of a batch is part of the launch.  Contraction off.
-//   emi_ipm_refine_decide    host: what becomes of an instance after its solve on a rung (retire / climb, and the verdict)
-//   ipm_solve_refine         the ladder with the instances that meet the ODE tolerance retired rung by rung (emi_ode_error_dev per
-//                            rung, the rule on the host, the rest compacted into a smaller batch of the same context)
+//   LadderRun                the driver: one loop over the rungs in named phases, for the ladder with refinement and, as the run that
+//                            checks on no rung, for the plain ladder.  Who is live and who goes where is kept by a RefineBook
+//                            (emi_refine_book.hpp, host-only).  Nothing of a trajectory's size crosses to the host between rungs.
+// emi_prolong_matrix and emi_ipm_refine_decide, which need no device, are in emi_host.cpp.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <limits>
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "emi_ctx.hpp"
+#include "emi_refine_book.hpp"
 
 namespace emi {
 namespace {
@@ -39,31 +37,7 @@ constexpr int REPAIR_T = 256;
 constexpr int MOVE_T = 256;         // nodes per block
 constexpr int TRACK_T = 256;        // nodes per block
 
-__global__ __launch_bounds__(PROLONG_T) void emi_prolong_kernel(const double* __restrict__ PT, const double* __restrict__ Vc,
-                                                                double* __restrict__ Vf, int Mc, int Mf, int R) {
-    const int q = blockIdx.x * PROLONG_T + threadIdx.x;
-    if (q >= Mf) return;
-    for (int r0 = blockIdx.y * PROLONG_ROWS; r0 < R; r0 += gridDim.y * PROLONG_ROWS) {
-        const double* v[PROLONG_ROWS];
-        double acc[PROLONG_ROWS];
-#pragma unroll
-        for (int i = 0; i < PROLONG_ROWS; ++i) {
-            v[i] = Vc + (size_t)(r0 + i < R ? r0 + i : r0) * Mc;        // a row past the end reads the group's first (not stored)
-            acc[i] = 0.0;
-        }
-        for (int j = 0; j < Mc; ++j) {
-            const double p = PT[(size_t)j * Mf + q];
-#pragma unroll
-            for (int i = 0; i < PROLONG_ROWS; ++i) acc[i] = fma(p, v[i][j], acc[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < PROLONG_ROWS; ++i)
-            if (r0 + i < R) Vf[(size_t)(r0 + i) * Mf + q] = acc[i];
-    }
-}
-
-// emi_prolong_kernel with the source row from a list (the existing kernel and its bits stay as they are): the same loads of PT, the
-// same fused multiply-adds in ascending j
+// the source row of output row r: map[r / group] * group + r % group (map null: r)
 __global__ __launch_bounds__(PROLONG_T) void emi_prolong_rows_kernel(const double* __restrict__ PT, const double* __restrict__ Vc,
                                                                      const int* __restrict__ map, int group, double* __restrict__ Vf, int Mc,
                                                                      int Mf, int R) {
@@ -191,14 +165,6 @@ hipError_t launch_track_waypoints(TrackWaypointArgs a, hipStream_t s) {
 template hipError_t launch_track_waypoints<double>(TrackWaypointArgs, hipStream_t);
 template hipError_t launch_track_waypoints<float>(TrackWaypointArgs, hipStream_t);
 
-hipError_t launch_prolong(const double* PT, const double* Vc, double* Vf, int Mc, int Mf, int R, hipStream_t s) {
-    if (R <= 0) return hipSuccess;
-    const int groups = (R + PROLONG_ROWS - 1) / PROLONG_ROWS;
-    const dim3 grid((Mf + PROLONG_T - 1) / PROLONG_T, groups < 65535 ? groups : 65535);
-    hipLaunchKernelGGL(emi_prolong_kernel, grid, dim3(PROLONG_T), 0, s, PT, Vc, Vf, Mc, Mf, R);
-    return hipGetLastError();
-}
-
 hipError_t launch_prolong_rows(const double* PT, const double* Vc, const int* map, int group, double* Vf, int Mc, int Mf, int R, hipStream_t s) {
     if (R <= 0) return hipSuccess;
     if (group < 1) return hipErrorInvalidValue;
@@ -227,272 +193,258 @@ hipError_t launch_repair_guess(const RepairArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the arrays of the ladder between its rungs: P transposed for the present pair of rungs, two sets of iterates (the rung being
-// solved and the one before it), the multipliers of the rungs below the last
+// the arrays of a run between its rungs: P transposed for the present pair of rungs, the compact iterates and multipliers of two
+// consecutive rungs (a fall-back returns the older set), the gathered bounds of the live instances, the estimates, and the lists
+// [6][B]: row map | live | two (source, destination) pairs
 struct IpmLadderWs {
-    DeviceArray<double> PT, X[2], U[2], LamF, LamC;
-    // the ladder with refinement: compact iterates and multipliers of two consecutive rungs (a fall-back returns the older set), the
-    // gathered bounds of the live instances, the estimates, and the lists [6][B]: row map | live | two (source, destination) pairs
-    DeviceArray<double> rX[2], rU[2], rLamF[2], rLamC[2], zl, zu, err;
+    DeviceArray<double> PT, X[2], U[2], LamF[2], LamC[2], zl, zu, err;
     DeviceArray<int> lists;
 };
 
 void ipm_ladder_destroy(IpmLadderWs* w) { delete w; }
 
-// P transposed of the pair of rungs (Mc, M) into w.PT, complete on return (PT is rewritten for the next pair)
-static int ladder_prolong_matrix(emi_ctx_t c, IpmLadderWs& w, int Mc, const std::vector<double>& tau_c, const std::vector<double>& w_c, int M,
-                          const std::vector<double>& tau) {
-    std::vector<double> P((size_t)M * Mc), PT((size_t)M * Mc);
-    EMI_TRY(emi_prolong_matrix(Mc, tau_c.data(), w_c.data(), M, tau.data(), P.data()));
-    for (int q = 0; q < M; ++q)
-        for (int j = 0; j < Mc; ++j) PT[(size_t)j * M + q] = P[(size_t)q * Mc + j];
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, w.PT.reserve(PT.size()));
-    HIP_TRY(c, hipMemcpyAsync(w.PT.p, PT.data(), PT.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return EMI_OK;
-}
-
-#define L_HIP(call) HIP_TRY_AS(c, "emi_ipm_solve_ladder_dev", call)
-#define L_TRY EMI_TRY
-
-int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
-                     void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results) {
-    if (!c->ipm_ladder) c->ipm_ladder = new IpmLadderWs();
-    IpmLadderWs& w = *c->ipm_ladder;
-    const size_t B = (size_t)c->B, ns = (size_t)c->ns, nc = (size_t)c->nc, np = (size_t)emi_api::np_total(c);
-    const hipStream_t s = c->stream;
-    std::vector<double> tau, wt, D, tau_c, w_c;
-    const void *pX = nullptr, *pU = nullptr;        // the previous rung's final iterate
-    for (int r = 0; r < nrungs; ++r) {
-        const emi_ipm_rung_t& g = rungs[r];
-        const int M = g.M, Mc = r > 0 ? rungs[r - 1].M : 0;
-        const bool last = r + 1 == nrungs;
-        tau.resize(M); wt.resize(M); D.resize((size_t)M * M);
-        L_TRY(emi_lgl(M, tau.data(), wt.data(), D.data()));
-        L_TRY(emi_set_mesh(c, M, tau.data(), wt.data(), D.data(), t0, tf));
-        if (g.recs) L_TRY(emi_set_path(c, c->np, c->path_sets, g.recs, c->px, c->py));
-        // track rows (the entry point has seen to the waypoints): their centres on this mesh, ahead of the repair, which reads them
-        if (c->np > 0 && c->path_has_track) L_TRY(emi_tracks_from_waypoints_dev(c, 0, nullptr));
-        // where this rung's iterate lives: the caller's arrays on the last rung, else one of the two sets (not the previous rung's)
-        void *cX = dX, *cU = dU, *cLF = dLamF, *cLC = dLamC;
-        if (!last) {
-            L_HIP(hipStreamSynchronize(s));             // a launch in flight may still use an array that has to move
-            L_HIP(w.X[r & 1].reserve(B * ns * M)); L_HIP(w.U[r & 1].reserve(B * nc * M));
-            L_HIP(w.LamF.reserve(B * ns * M)); L_HIP(w.LamC.reserve(B * np * M));
-            cX = w.X[r & 1].p; cU = w.U[r & 1].p; cLF = w.LamF.p; cLC = w.LamC.p;
-        }
-        if (r == 0) {
-            L_HIP(hipMemcpyAsync(cX, dX0, B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-            if (nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, B * nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-        } else {
-            L_TRY(ladder_prolong_matrix(c, w, Mc, tau_c, w_c, M, tau));
-            L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pX, c->B * c->ns, cX));
-            if (nc > 0) L_TRY(emi_prolong_dev(c, Mc, M, w.PT.p, pU, c->B * c->nc, cU));
-        }
-        if (g.repair) L_TRY(emi_repair_guess_dev(c, cX));
-        L_TRY(emi_ipm_solve_shard_dev(c, cX, cU, &g.bd, &g.opt, cLF, cLC, results + (size_t)r * B));
-        pX = cX; pU = cU;
-        tau_c.swap(tau); w_c.swap(wt);
-    }
-    return EMI_OK;
-}
-
-
-#undef L_HIP
-#define L_HIP(call) HIP_TRY_AS(c, "emi_ipm_solve_refine_dev", call)
-
 namespace {
 
-// the rows of the live instances of the master table (shared table: as it is) as the context's table
-int refine_set_table(emi_ctx_t c, const std::vector<double>& master, int np, int sets, const std::vector<int>& live) {
-    if (np <= 0) return EMI_OK;
-    if (sets == 1) return emi_set_path(c, np, 1, master.data(), c->px, c->py);
-    const size_t per = (size_t)np * EMI_PATH_REC;
-    std::vector<double> t(live.size() * per);
-    for (size_t i = 0; i < live.size(); ++i) std::copy(master.begin() + live[i] * per, master.begin() + (live[i] + 1) * per, t.begin() + i * per);
-    return emi_set_path(c, np, (int)live.size(), t.data(), c->px, c->py);
-}
+#define L_HIP(call) HIP_TRY_AS(c, entry, call)
+#define L_TRY EMI_TRY
 
-int refine_rungs(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t& rf, const void* dX0,
-                 const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results, double* err,
-                 emi_ipm_refine_result_t* out, std::vector<double>& master, int sets, bool& table_changed) {
-    IpmLadderWs& w = *c->ipm_ladder;
-    const int B = c->B, ns = c->ns, nc = c->nc, nv = ns + nc, np = emi_api::np_total(c);
+// One call of emi_ipm_solve_ladder_dev / emi_ipm_solve_refine_dev.  The first block of members is the call as it came; rf null: no
+// rung checks the ODE error, and `book` was begun with RefineBook::NEVER
+struct LadderRun {
+    emi_ctx_t c;
+    const char* entry;                  // the entry point, for the messages
+    int nrungs;
+    const emi_ipm_rung_t* rungs;
+    double t0, tf;
+    const emi_ipm_refine_t* rf;
+    const void *dX0, *dU0;
+    int ldm;
+    void *dX, *dU, *dLamF, *dLamC;
+    RefineBook book;
+    // the context at entry
+    const int B = c->B, ns = c->ns, nc = c->nc, nv = ns + nc, np = emi_api::np_total(c), sets = c->path_sets;
     const hipStream_t s = c->stream;
-    int Mmax = 0;
-    for (int r = 0; r < nrungs; ++r) Mmax = std::max(Mmax, rungs[r].M);
-    L_HIP(hipStreamSynchronize(s));                 // a launch in flight may still use an array that has to move
-    for (int k = 0; k < 2; ++k) {
-        L_HIP(w.rX[k].reserve((size_t)B * ns * Mmax)); L_HIP(w.rU[k].reserve((size_t)B * nc * Mmax));
-        L_HIP(w.rLamF[k].reserve((size_t)B * ns * Mmax)); L_HIP(w.rLamC[k].reserve((size_t)B * np * Mmax));
-    }
-    L_HIP(w.zl.reserve((size_t)B * nv * Mmax)); L_HIP(w.zu.reserve((size_t)B * nv * Mmax));
-    L_HIP(w.err.reserve((size_t)B)); L_HIP(w.lists.reserve((size_t)6 * B));
-    int* const d_map = w.lists.p;
-    int* const d_live = d_map + B;
-    int* const d_pair[2][2] = {{d_map + 2 * B, d_map + 3 * B}, {d_map + 4 * B, d_map + 5 * B}};
+    IpmLadderWs* w = nullptr;
+    int *d_map = nullptr, *d_live = nullptr, *d_pair[2][2] = {};
+    // what restore_context has to undo
+    bool table_compacted = false, centres_compacted = false;
+    const double* master = nullptr;     // the record table in the caller's numbering: the last rung's that brought one, else `table`
+    std::vector<double> table;          // ... the context's, read back before its first compaction
+    // the rung
+    int r = 0, M = 0, Mc = 0, n = 0, cur = 0;
+    bool live_up = false;               // the live list of this rung is on the device
+    double *cX = nullptr, *cU = nullptr, *cLF = nullptr, *cLC = nullptr;
+    emi_ipm_bounds_t bd{};
+    std::vector<double> tau, wt, D, tau_c, w_c, herr;
+    std::vector<emi_ipm_result_t> res;
 
-    std::vector<int> live(B), pos(B);               // live: the caller's numbers, ascending; pos: where each sits in the previous rung's batch
-    for (int b = 0; b < B; ++b) live[b] = pos[b] = b;
-    std::vector<double> tau, wt, D, tau_c, w_c, herr(B);
-    std::vector<emi_ipm_result_t> res(B);
-    for (int r = 0; r < nrungs && !live.empty(); ++r) {
+    int run() {
+        const int st = climb();
+        // the context as the caller knows it -- also after an error (whose message stays)
+        const std::string msg = c->err;
+        const int back = restore_context();
+        if (st) { c->err = msg; return st; }
+        return back;
+    }
+
+    int climb() {
+        L_TRY(reserve());
+        for (r = 0; r < nrungs && !book.done(); ++r) {
+            L_TRY(enter_rung());
+            L_TRY(place_iterate());
+            L_TRY(gather_bounds());
+            L_TRY(solve());
+            L_TRY(check_and_retire());
+        }
+        return EMI_OK;
+    }
+
+    int reserve() {
+        if (!c->ipm_ladder) c->ipm_ladder = new IpmLadderWs();
+        w = c->ipm_ladder;
+        int Mmax = 0;
+        bool gathers = false;           // per-instance bounds come in the caller's numbering: gathered once somebody has left
+        for (int q = 0; q < nrungs; ++q) {
+            Mmax = std::max(Mmax, rungs[q].M);
+            gathers = gathers || (rf && B > 1 && rungs[q].bd.nsets == B);
+        }
+        L_HIP(hipStreamSynchronize(s));                 // a launch in flight may still use an array that has to move
+        for (int k = 0; k < 2 && k < nrungs; ++k) {
+            L_HIP(w->X[k].reserve((size_t)B * ns * Mmax)); L_HIP(w->U[k].reserve((size_t)B * nc * Mmax));
+            L_HIP(w->LamF[k].reserve((size_t)B * ns * Mmax)); L_HIP(w->LamC[k].reserve((size_t)B * np * Mmax));
+        }
+        if (gathers) { L_HIP(w->zl.reserve((size_t)B * nv * Mmax)); L_HIP(w->zu.reserve((size_t)B * nv * Mmax)); }
+        if (rf) L_HIP(w->err.reserve((size_t)B));
+        L_HIP(w->lists.reserve((size_t)6 * B));
+        d_map = w->lists.p;
+        d_live = d_map + B;
+        for (int k = 0; k < 2; ++k) { d_pair[k][0] = d_map + (2 + 2 * k) * B; d_pair[k][1] = d_map + (3 + 2 * k) * B; }
+        herr.resize(B); res.resize(B);
+        return EMI_OK;
+    }
+
+    // the live list on the device, for whoever of this rung needs the caller's numbering (uploaded once)
+    int need_live() {
+        if (live_up) return EMI_OK;
+        L_HIP(hipMemcpyAsync(d_live, book.caller_map(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+        live_up = true;
+        return EMI_OK;
+    }
+
+    // the master table as the context's: as it is while the batch is whole or the table shared, else the rows of the live instances
+    int set_table() {
+        const int* live = book.caller_map();
+        const size_t per = (size_t)c->np * EMI_PATH_REC;
+        if (!master) {
+            table.resize((size_t)sets * per);
+            L_TRY(emi_api::download_real(c, table.data(), c->d_path.p, table.size()));
+            master = table.data();
+        }
+        if (sets == 1 || !live) return emi_set_path(c, c->np, sets, master, c->px, c->py);
+        std::vector<double> t((size_t)n * per);
+        for (int i = 0; i < n; ++i) std::copy(master + live[i] * per, master + (live[i] + 1) * per, t.begin() + i * per);
+        table_compacted = true;
+        return emi_set_path(c, c->np, n, t.data(), c->px, c->py);
+    }
+
+    int enter_rung() {
         const emi_ipm_rung_t& g = rungs[r];
-        const int M = g.M, Mc = r > 0 ? rungs[r - 1].M : 0, n = (int)live.size(), cur = r & 1, old = cur ^ 1;
-        const bool last = r + 1 == nrungs;
+        M = g.M; Mc = r > 0 ? rungs[r - 1].M : 0; n = book.n(); cur = r & 1; live_up = false;
+        tau_c.swap(tau); w_c.swap(wt);                  // (the previous rung's, for the prolongation matrix)
         tau.resize(M); wt.resize(M); D.resize((size_t)M * M);
         L_TRY(emi_lgl(M, tau.data(), wt.data(), D.data()));
         L_TRY(emi_set_mesh(c, M, tau.data(), wt.data(), D.data(), t0, tf));
         if (n != c->B) L_TRY(emi_set_batch(c, n));
-        if (g.recs && c->np > 0) master.assign(g.recs, g.recs + (size_t)c->np * sets * EMI_PATH_REC);
-        if (c->np > 0 && (g.recs || (sets > 1 && c->path_sets != n))) {
-            L_TRY(refine_set_table(c, master, c->np, sets, live));
-            table_changed = true;
-        }
-        // the live list on the device, for whoever of this rung needs the caller's numbering (uploaded once)
-        bool live_up = false;
-        const auto need_live = [&]() -> int {
-            if (live_up) return EMI_OK;
-            L_HIP(hipMemcpyAsync(d_live, live.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-            live_up = true;
-            return EMI_OK;
-        };
-        // track rows: the centres of the live instances on this mesh, the compaction done by the set map in the launch (a shared
-        // waypoint set serves whoever is live), ahead of the repair, which reads them
+        if (g.recs && c->np > 0) master = g.recs;
+        if (c->np > 0 && (g.recs || (sets > 1 && c->path_sets != n))) L_TRY(set_table());
+        // track rows (the entry point has seen to the waypoints): the centres of the live instances on this mesh, ahead of the repair,
+        // which reads them.  The set map of the launch does the compaction; a shared waypoint set serves whoever is live
         if (c->np > 0 && c->path_has_track) {
-            const bool per_instance = c->wp_sets == B && B > 1;
-            if (per_instance) L_TRY(need_live());
-            L_TRY(emi_tracks_from_waypoints_dev(c, per_instance ? n : 0, per_instance ? d_live : nullptr));
+            const bool compact = c->wp_sets == B && B > 1 && book.caller_map();
+            if (compact) { L_TRY(need_live()); centres_compacted = true; }
+            L_TRY(emi_tracks_from_waypoints_dev(c, compact ? n : 0, compact ? d_live : nullptr));
         }
-        double *cX = w.rX[cur].p, *cU = w.rU[cur].p, *cLF = w.rLamF[cur].p, *cLC = w.rLamC[cur].p;
+        return EMI_OK;
+    }
+
+    // this rung's iterate in one of the two sets (not the previous rung's): the start, or the previous rung's final iterate prolonged,
+    // the rows of whoever left that batch skipped by the row map
+    int place_iterate() {
+        cX = w->X[cur].p; cU = w->U[cur].p; cLF = w->LamF[cur].p; cLC = w->LamC[cur].p;
         if (r == 0) {
             L_HIP(hipMemcpyAsync(cX, dX0, (size_t)B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
             if (nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, (size_t)B * nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-        } else {
-            L_TRY(ladder_prolong_matrix(c, w, Mc, tau_c, w_c, M, tau));
-            L_HIP(hipMemcpyAsync(d_map, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-            L_HIP(launch_prolong_rows(w.PT.p, w.rX[old].p, d_map, ns, cX, Mc, M, n * ns, s));
-            if (nc > 0) L_HIP(launch_prolong_rows(w.PT.p, w.rU[old].p, d_map, nc, cU, Mc, M, n * nc, s));
+            return EMI_OK;
         }
-        emi_ipm_bounds_t bd = g.bd;
-        if (bd.nsets == B && n < B) {               // per-instance bounds come in the caller's numbering
-            L_TRY(need_live());
-            ShardMoveArgs a{};
-            a.src[0] = (const double*)g.bd.zl; a.src[1] = (const double*)g.bd.zu; a.dst[0] = w.zl.p; a.dst[1] = w.zu.p;
-            a.rows[0] = a.rows[1] = nv; a.sld[0] = a.sld[1] = a.dld[0] = a.dld[1] = M;
-            a.sidx = d_live; a.n = n; a.narrays = 2; a.len = M;
-            L_HIP(launch_shard_move(a, s));
-            bd.zl = w.zl.p; bd.zu = w.zu.p; bd.nsets = n;
-        }
+        L_TRY(prolong_matrix());
+        const int* map = book.row_map();
+        if (map) L_HIP(hipMemcpyAsync(d_map, map, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+        L_HIP(launch_prolong_rows(w->PT.p, w->X[cur ^ 1].p, map ? d_map : nullptr, ns, cX, Mc, M, n * ns, s));
+        if (nc > 0) L_HIP(launch_prolong_rows(w->PT.p, w->U[cur ^ 1].p, map ? d_map : nullptr, nc, cU, Mc, M, n * nc, s));
+        return EMI_OK;
+    }
+
+    // P transposed of the pair of rungs (Mc, M) into w->PT, complete on return (PT is rewritten for the next pair)
+    int prolong_matrix() {
+        std::vector<double> P((size_t)M * Mc), PT((size_t)M * Mc);
+        L_TRY(emi_prolong_matrix(Mc, tau_c.data(), w_c.data(), M, tau.data(), P.data()));
+        for (int q = 0; q < M; ++q)
+            for (int j = 0; j < Mc; ++j) PT[(size_t)j * M + q] = P[(size_t)q * Mc + j];
+        L_HIP(hipStreamSynchronize(s));
+        L_HIP(w->PT.reserve(PT.size()));
+        L_HIP(hipMemcpyAsync(w->PT.p, PT.data(), PT.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        L_HIP(hipStreamSynchronize(s));
+        return EMI_OK;
+    }
+
+    int gather_bounds() {
+        bd = rungs[r].bd;
+        if (bd.nsets != B || n == B) return EMI_OK;     // shared, or everybody is still there
+        L_TRY(need_live());
+        ShardMoveArgs a{};
+        a.src[0] = (const double*)bd.zl; a.src[1] = (const double*)bd.zu; a.dst[0] = w->zl.p; a.dst[1] = w->zu.p;
+        a.rows[0] = a.rows[1] = nv; a.sld[0] = a.sld[1] = a.dld[0] = a.dld[1] = M;
+        a.sidx = d_live; a.n = n; a.narrays = 2; a.len = M;
+        L_HIP(launch_shard_move(a, s));
+        bd.zl = w->zl.p; bd.zu = w->zu.p; bd.nsets = n;
+        return EMI_OK;
+    }
+
+    int solve() {
+        const emi_ipm_rung_t& g = rungs[r];
         if (g.repair) L_TRY(emi_repair_guess_dev(c, cX));
         L_TRY(emi_ipm_solve_shard_dev(c, cX, cU, &bd, &g.opt, cLF, cLC, res.data()));
-        for (int i = 0; i < n; ++i) {
-            results[(size_t)r * B + live[i]] = res[i];
-            out[live[i]].rungs_solved = r + 1;
-        }
-        tau_c.swap(tau); w_c.swap(wt);
-        if (r < rf.first_check) {                   // a mesh-sequencing rung: everybody climbs
-            for (int i = 0; i < n; ++i) pos[i] = i;
-            continue;
-        }
-        L_TRY(emi_ode_error_dev(c, cX, cU, rf.ul, rf.uu, nullptr, w.err.p));
-        L_HIP(hipMemcpyAsync(herr.data(), w.err.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-        L_HIP(hipStreamSynchronize(s));
-        // the rule; list 0: retirees that return this rung's iterate, list 1: those that fall back to the previous rung's
-        std::vector<int> from[2], to[2], next, next_pos;
-        for (int i = 0; i < n; ++i) {
-            const int b = live[i];
-            const bool has_good = r > rf.first_check;           // whoever climbed from a checked rung was solved there
-            err[(size_t)r * B + b] = herr[i];
-            int verdict = 0;
-            if (!emi_ipm_refine_decide(res[i].status, herr[i], rf.ode_tol, has_good, last, &verdict)) {
-                next.push_back(b); next_pos.push_back(i);
-                continue;
-            }
-            const int k = verdict == EMI_REFINE_FELL_BACK ? 1 : 0;
-            from[k].push_back(k ? pos[i] : i); to[k].push_back(b);
-            out[b].verdict = verdict;
-            out[b].rung = r - k;
-            out[b].err = err[(size_t)(r - k) * B + b];
-        }
-        for (int k = 0; k < 2; ++k) {
-            const int m = (int)from[k].size();
-            if (m == 0) continue;
-            const int set = k ? old : cur, Mk = k ? Mc : M;
-            L_HIP(hipMemcpyAsync(d_pair[k][0], from[k].data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, s));
-            L_HIP(hipMemcpyAsync(d_pair[k][1], to[k].data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, s));
-            ShardMoveArgs a{};
-            int q = 0;
-            const auto add = [&](const double* src, void* dst, int rows) {
-                if (rows <= 0) return;
-                a.src[q] = src; a.dst[q] = (double*)dst; a.rows[q] = rows; a.sld[q] = Mk; a.dld[q] = ldm;
-                ++q;
-            };
-            add(w.rX[set].p, dX, ns); add(w.rU[set].p, dU, nc); add(w.rLamF[set].p, dLamF, ns); add(w.rLamC[set].p, dLamC, np);
-            a.sidx = d_pair[k][0]; a.didx = d_pair[k][1]; a.n = m; a.narrays = q; a.len = Mk;
-            L_HIP(launch_shard_move(a, s));
-        }
-        L_HIP(hipStreamSynchronize(s));             // (the lists are locals)
-        live.swap(next); pos.swap(next_pos);
+        book.record_solve(r, res.data());
+        return EMI_OK;
     }
-    return EMI_OK;
-}
+
+    // a group of retirees from one of the two sets (on Mk nodes) into the caller's arrays; k: which pair of lists carries it
+    int move_out(const RefineBook::Moves& m, int k, int set, int Mk) {
+        const int cnt = (int)m.from.size();
+        if (cnt == 0) return EMI_OK;
+        L_HIP(hipMemcpyAsync(d_pair[k][0], m.from.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, s));
+        L_HIP(hipMemcpyAsync(d_pair[k][1], m.to.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, s));
+        const double* const src[SHARD_MOVE_ARRAYS] = {w->X[set].p, w->U[set].p, w->LamF[set].p, w->LamC[set].p};
+        void* const dst[SHARD_MOVE_ARRAYS] = {dX, dU, dLamF, dLamC};
+        const int rows[SHARD_MOVE_ARRAYS] = {ns, nc, ns, np};
+        ShardMoveArgs a{};
+        int q = 0;
+        for (int i = 0; i < SHARD_MOVE_ARRAYS; ++i) {
+            if (rows[i] <= 0) continue;
+            a.src[q] = src[i]; a.dst[q] = (double*)dst[i]; a.rows[q] = rows[i]; a.sld[q] = Mk; a.dld[q] = ldm;
+            ++q;
+        }
+        a.sidx = d_pair[k][0]; a.didx = d_pair[k][1]; a.n = cnt; a.narrays = q; a.len = Mk;
+        L_HIP(launch_shard_move(a, s));
+        return EMI_OK;
+    }
+
+    int check_and_retire() {
+        const bool last = r + 1 == nrungs;
+        if (book.checks(r)) {
+            L_TRY(emi_ode_error_dev(c, cX, cU, rf->ul, rf->uu, nullptr, w->err.p));
+            L_HIP(hipMemcpyAsync(herr.data(), w->err.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+            L_HIP(hipStreamSynchronize(s));
+            book.decide(r, herr.data(), rf->ode_tol, last);
+        } else if (last) {
+            book.return_all(r);
+        } else {                                        // a mesh-sequencing rung: everybody climbs
+            book.climb_all();
+            return EMI_OK;
+        }
+        L_TRY(move_out(book.here, 0, cur, M));
+        L_TRY(move_out(book.older, 1, cur ^ 1, Mc));
+        L_HIP(hipStreamSynchronize(s));                 // (the lists are the book's, rewritten by the next decision)
+        return EMI_OK;
+    }
+
+    // only what the run changed: the batch size, a compacted table, compacted centres (on the mesh the context is on)
+    int restore_context() {
+        if (c->B != B) L_TRY(emi_set_batch(c, B));
+        if (table_compacted) L_TRY(emi_set_path(c, c->np, sets, master, c->px, c->py));
+        if (centres_compacted && c->M > 0) L_TRY(emi_tracks_from_waypoints_dev(c, 0, nullptr));
+        return EMI_OK;
+    }
+};
 
 }  // namespace
 
 int ipm_solve_refine(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t& rf, const void* dX0,
                      const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results, double* err,
                      emi_ipm_refine_result_t* out) {
-    if (!c->ipm_ladder) c->ipm_ladder = new IpmLadderWs();
-    const int B = c->B, sets = c->path_sets;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (size_t i = 0; i < (size_t)nrungs * B; ++i) {
-        results[i] = emi_ipm_result_t{};
-        results[i].status = -1;
-        err[i] = nan;
-    }
-    for (int b = 0; b < B; ++b) out[b] = emi_ipm_refine_result_t{-1, EMI_REFINE_FAILED, 0, nan};
-    // the master copy of the record table, in the caller's numbering
-    std::vector<double> master((size_t)c->np * sets * EMI_PATH_REC);
-    if (c->np > 0) L_TRY(emi_api::download_real(c, master.data(), c->d_path.p, master.size()));
-    bool table_changed = false;
-    const int st = refine_rungs(c, nrungs, rungs, t0, tf, rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC, results, err, out, master, sets, table_changed);
-    // the context as the caller knows it: batch B, the full table, the centres of every set -- also after an error (whose message stays)
-    const std::string msg = c->err;
-    int back = EMI_OK;
-    if (c->B != B) back = emi_set_batch(c, B);
-    if (!back && table_changed) back = emi_set_path(c, c->np, sets, master.data(), c->px, c->py);
-    // ... and, where the table has track rows, the centres of all sets on the mesh the context is on
-    if (!back && c->np > 0 && c->path_has_track && c->wp_ntracks > 0 && c->M > 0) back = emi_tracks_from_waypoints_dev(c, 0, nullptr);
-    if (st) { c->err = msg; return st; }
-    return back;
+    LadderRun run{c, "emi_ipm_solve_refine_dev", nrungs, rungs, t0, tf, &rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC};
+    run.book.begin(c->B, nrungs, rf.first_check, results, err, out);
+    return run.run();
+}
+
+// the run that never checks: after the last rung everybody goes to the caller's arrays, which are sized for that rung
+int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
+                     void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results) {
+    std::vector<double> err((size_t)nrungs * c->B);
+    std::vector<emi_ipm_refine_result_t> out(c->B);
+    LadderRun run{c, "emi_ipm_solve_ladder_dev", nrungs, rungs, t0, tf, nullptr, dX0, dU0, rungs[nrungs - 1].M, dX, dU, dLamF, dLamC};
+    run.book.begin(c->B, nrungs, RefineBook::NEVER, results, err.data(), out.data());
+    return run.run();
 }
 
 }  // namespace emi
-
-extern "C" int emi_prolong_matrix(int Mc, const double* tau_c, const double* w_c, int Mf, const double* tau_f, double* P) {
-#pragma clang fp contract(off)
-    if (Mc < 2 || Mf < 2 || !tau_c || !w_c || !tau_f || !P) return EMI_ERR_ARG;
-    for (int q = 0; q < Mf; ++q) {
-        double* row = P + (size_t)q * Mc;
-        int hit = -1;
-        double den = 0.0;
-        for (int j = 0; j < Mc; ++j) {
-            const double dlt = tau_f[q] - tau_c[j];
-            if (dlt == 0.0) { hit = j; break; }
-            row[j] = ((j & 1) ? -1.0 : 1.0) * std::sqrt(w_c[j]) / dlt;
-            den += row[j];
-        }
-        for (int j = 0; j < Mc; ++j) row[j] = hit >= 0 ? (j == hit ? 1.0 : 0.0) : row[j] / den;
-    }
-    return EMI_OK;
-}
-
-extern "C" int emi_ipm_refine_decide(int status, double err, double ode_tol, int has_good, int is_last, int* verdict) {
-    const bool ok = status == EMI_IPM_CONVERGED || status == EMI_IPM_ACCEPTABLE;
-    const bool met = std::isfinite(err) && err <= ode_tol;
-    const int v = ok ? (met ? EMI_REFINE_MET : EMI_REFINE_NOT_MET) : (has_good ? EMI_REFINE_FELL_BACK : EMI_REFINE_FAILED);
-    if (verdict) *verdict = v;
-    return !(ok && !met && !is_last);
-}

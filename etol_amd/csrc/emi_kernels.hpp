@@ -244,10 +244,11 @@ struct IpmKeepArgs {
 };
 hipError_t launch_ipm_keep(const IpmKeepArgs& a, hipStream_t s);
 
-// the mesh ladder of one context's batch (emi_ipm_ladder.hip): prolongation Vf[R][Mf] = Vc[R][Mc] P^T from PT[Mc][Mf], the repair
-// of the position states X[B][ns][M] against the record table (recs [path_sets][np][EMI_PATH_REC], tracks [track_sets][ntracks][M]),
+// the mesh ladder of one context's batch (emi_ipm_ladder.hip): prolongation Vf[r] = P Vc[src(r)] from PT[Mc][Mf] for R rows of Mf
+// values, src(r) = map[r / group] * group + r % group (map null: src(r) = r; group: rows that share one entry of the map); the repair
+// of the position states X[B][ns][M] against the record table (recs [path_sets][np][EMI_PATH_REC], tracks [track_sets][ntracks][M]);
 // and the driver over the rungs, whose device arrays live in an IpmLadderWs the context owns
-hipError_t launch_prolong(const double* PT, const double* Vc, double* Vf, int Mc, int Mf, int R, hipStream_t s);
+hipError_t launch_prolong_rows(const double* PT, const double* Vc, const int* map, int group, double* Vf, int Mc, int Mf, int R, hipStream_t s);
 struct RepairArgs {
     double* X;
     const double *recs, *trkx, *trky;
@@ -268,11 +269,9 @@ struct IpmLadderWs;
 void ipm_ladder_destroy(IpmLadderWs* w);
 int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
                      void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
-// the ladder with refinement (emi_ipm_solve_refine_*): the prolongation with a source row per output row, Vf[r] = P Vc[src(r)] with
-// src(r) = map[r / group] * group + r % group (map null: src(r) = r; group: rows that share one entry of the map); the move of the
-// instances of a list between two sets of arrays [instance][rows][ld], entry i: instance sidx[i] of src -> instance didx[i] of dst
-// (a null list: i), the first `len` values of every row; and the driver, which retires instances rung by rung
-hipError_t launch_prolong_rows(const double* PT, const double* Vc, const int* map, int group, double* Vf, int Mc, int Mf, int R, hipStream_t s);
+// the move of the instances of a list between two sets of arrays [instance][rows][ld], entry i: instance sidx[i] of src -> instance
+// didx[i] of dst (a null list: i), the first `len` values of every row; and the same driver with the instances that meet the ODE
+// tolerance retired rung by rung (emi_ipm_solve_refine_*)
 constexpr int SHARD_MOVE_ARRAYS = 4;
 struct ShardMoveArgs {
     const double* src[SHARD_MOVE_ARRAYS];

@@ -583,9 +583,11 @@ int emi_ipm_solve_shard_host(emi_ctx_t ctx, double* X, double* U, const emi_ipm_
  *      bounds).
  * Multipliers are not carried: LamF = 0 at every start.  Every instance climbs whatever its status on a rung; results[r][b] says
  * what happened (a non-finite iterate ends EMI_IPM_NOT_FINITE on the next rung).  dX0 [B][ns][M_0] and dU0 [B][nc][M_0] are only
- * read; dX, dU, dLamF, dLamC are sized for the LAST rung.  The interpolation matrix and the iterates of the rungs below the last
- * are device arrays of the context (grown as needed, freed with it); per rung pair Mc Mf doubles go up, nothing of a trajectory's
- * size comes down.  On return the context is on the last rung's mesh.  A ladder of one rung runs the launches of
+ * read; dX, dU, dLamF, dLamC are sized for the LAST rung.  The call is emi_ipm_solve_refine_dev's loop with a check on no rung: the
+ * interpolation matrix and the iterates and multipliers of two consecutive rungs, sized for the largest, are device arrays of the
+ * context (grown as needed, freed with it), every rung -- the last included -- is solved there, and one emi_shard_move_dev launch
+ * after the last solve takes everybody to the caller's arrays; per rung pair Mc Mf doubles go up, nothing of a trajectory's size
+ * comes down.  On return the context is on the last rung's mesh.  A ladder of one rung runs the launches of
  * emi_ipm_solve_shard_dev on a copy of the start.
  * EMI_ERR_UNSUPPORTED: whatever emi_ipm_solve_shard_dev refuses, and a record table (the context's or a rung's) with a row of
  * kind EMI_PATH_TRACK while the context holds NO waypoint tables: the centres of such rows are per mesh and without the tables
@@ -674,7 +676,7 @@ int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const do
  * emi_ipm_solve_refine_dev: with live = every instance at the start, per rung r = 0 .. nrungs-1 while anybody is live
  *   1. emi_lgl and emi_set_mesh(M_r, .., t0, tf);
  *   2. emi_set_batch(n) for the n live instances and emi_set_path with their rows of the record table (the context's table is read
- *      back once at entry; a rung's recs, given for all B instances in the caller's numbering, replaces that copy);
+ *      back before its first compaction; a rung's recs, given for all B instances in the caller's numbering, replaces that copy);
  *   2a. where the table has rows of kind EMI_PATH_TRACK: emi_tracks_from_waypoints_dev for the live instances -- waypoint tables with
  *      one set per instance (nsets == B) are read through the live list as the set map, so the compaction of the centres happens
  *      in the launch; a shared set (nsets == 1) serves whoever is live;

@@ -64,6 +64,32 @@ def test_prolongation_with_a_row_map(built, pair):
     ev.close()
 
 
+@pytest.mark.parametrize("pair", ((5, 9), (40, 41)), ids=lambda p: f"{p[0]}-{p[1]}")
+def test_the_two_prolongation_calls_are_one_kernel(built, pair):
+    """emi_prolong_dev and emi_prolong_rows_dev without a map: the same bits at R = 1, 5 and 9, the tail groups of the 4-row blocking;
+    a unit row of P (the end nodes, which every LGL mesh has) still copies the coarse value bit for bit"""
+    import torch
+    import etol_amd as E
+    ev, (mc, mf) = E.Evaluator(0), pair
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(ev.device)
+    P = ev.prolong_matrix(mc, mf)
+    unit = [(q, int(np.argmax(P[q]))) for q in range(mf) if np.count_nonzero(P[q]) == 1 and P[q].max() == 1.0]
+    assert {(0, 0), (mf - 1, mc - 1)} <= set(unit)
+    PT = up(P.T)
+    rng = np.random.default_rng(mc * 1000 + mf + 1)
+    for R in (1, 5, 9):
+        V = rng.standard_normal((R, mc)) * np.exp(3 * rng.standard_normal((R, 1)))
+        Vd = up(V)
+        torch.cuda.synchronize()
+        plain, rows = ev.prolong(PT, Vd), ev.prolong_rows(PT, Vd, None)
+        ev.synchronize()
+        plain, rows = plain.cpu().numpy(), rows.cpu().numpy()
+        assert plain.shape == (R, mf) and same(plain, rows), (pair, R)
+        for q, j in unit:
+            assert same(plain[:, q], V[:, j]), (pair, R, q, j)
+    ev.close()
+
+
 @pytest.mark.parametrize("M", (33, 300))
 @pytest.mark.parametrize("pad", (0, 7))
 def test_shard_move_copies_bits_and_touches_nothing_else(built, M, pad):

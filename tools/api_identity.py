@@ -6,8 +6,11 @@ commit's and the changed one, each with its own built library -- and compare wha
    python tools/api_identity.py results OUT.json   SHA-256 of what every launch form computes, the kernel name, launch counts
    python tools/api_identity.py times   OUT.json   ms per default-dispatch pass at B = 1, 16, 128, 1024 (quadrotor, 1024 nodes)
    python tools/api_identity.py lockstep OUT.json  SHA-256 of X, U, LamF, LamC and the result records of the lock-step solve (2 x 9
-                                                   instances of tests/lockstep_ref.py on 41 nodes) and of the ladder (21, 41) over
-                                                   them, default options: what a change behind an option that is off must keep
+                                                   instances of tests/lockstep_ref.py on 41 nodes), of the ladder (21, 41) over
+                                                   them, of the refinement of tests/refine_ref.py (bounds shared and per instance;
+                                                   with err and out) and of the moving-disc ladder and refinement of
+                                                   tests/track_ladder_ref.py, default options, each with the context the call left:
+                                                   what a change behind an option that is off, or to the drivers, must keep
    python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case
 
 The library is the one of the tree the script lies in."""
@@ -267,34 +270,75 @@ def lockstep():
     import etol_amd as E
     import ladder_ref as LD
     import lockstep_ref as LR
+    import refine_ref as RR
+    import track_ladder_ref as TR
     fields = ("status", "iterations", "evaluations", "factorisations", "reflected_steps", "cost", "kkt_error", "constr_viol", "emax", "mu", "rho")
     rows = lambda res: [[q[k] for k in fields] for q in res]
     out = {}
+
+    def context(ev, tracks):
+        """the context a call left: mesh and batch, and what its table (and centres) make of one fixed trajectory"""
+        lay = ev.layout
+        rng = np.random.default_rng(7)
+        kw = dict(dtype=torch.float64, device=ev.device)
+        X, U = (torch.from_numpy(rng.standard_normal((lay.B, r, lay.M))).to(ev.device) for r in (lay.ns, lay.nc))
+        RES, VALS, COST = torch.zeros((lay.B, lay.ns + lay.np, lay.M), **kw), torch.zeros((lay.B, lay.nvals, lay.M), **kw), torch.zeros(lay.B, **kw)
+        torch.cuda.synchronize()
+        ev.eval_dev(X, U, RES, VALS, COST)
+        ev.synchronize()
+        d = dict(M=lay.M, B=lay.B, np=lay.np, t0=lay.t0, tf=lay.tf, RES=sha(RES), VALS=sha(VALS), COST=sha(COST))
+        if tracks:
+            d["tracks"] = [sha(a) for a in ev.get_tracks()]
+        return d
+
+    def run(name, tf, insts, ladder, refine=None, replicate=False, tracks=False):
+        """refine: None (the one-mesh solve or the ladder), or (ode_tol, first_check)"""
+        B = len(insts)
+        ev = E.Evaluator(0)
+        ev.set_mesh(ladder[0], 0.0, tf)
+        ev.set_model(1, LR.QUAD_PARAMS)
+        ev.set_batch(B)
+        ev.set_path(np.stack([i["recs"] if tracks else LR.records(i["discs"]) for i in insts]), 0, 1)
+        if tracks:
+            ev.set_track_waypoints(*TR.stacked([i["way"] for i in insts]))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).to(ev.device)
+        z0 = np.stack([i["z0"] for i in insts]).reshape(B, 8, ladder[0])
+        X, U = up(z0[:, :6]), up(z0[:, 6:])
+        bounds = []
+        for M in ladder:
+            P = LD.quad_at(tf, M, LR.discs_of(LR.FIRST_DISCS[0]))
+            rep = B if replicate else 1
+            bounds.append(dict(zl=up(np.repeat(P.lo.reshape(1, 8, M), rep, 0)), zu=up(np.repeat(P.up.reshape(1, 8, M), rep, 0)), cl=LR.CL, cu=LR.CU,
+                               cscale=LR.CSCALE))
+        rungs = [dict(M=M, bounds=b, options=dict(tol=1e-8), repair=0) for M, b in zip(ladder, bounds)]
+        torch.cuda.synchronize()
+        extra = {}
+        if refine:
+            X, U, LamF, LamC, res, err, summ = ev.ipm_solve_refine(rungs, 0.0, tf, X, U, refine[0], refine[1], RR.UL, RR.UU)
+            extra = dict(err=sha(err), out=[[q["rung"], q["verdict"], q["rungs_solved"], repr(q["err"])] for q in summ])
+        elif len(ladder) == 1:
+            LamF, LamC, res = ev.ipm_solve_shard(X, U, bounds[0], dict(tol=1e-8, max_iter=200))
+            res = [res]
+        else:
+            X, U, LamF, LamC, res = ev.ipm_solve_ladder(rungs, 0.0, tf, X, U)
+        ev.synchronize()
+        out[name] = dict(X=sha(X), U=sha(U), LamF=sha(LamF), LamC=sha(LamC), results=[rows(r) for r in res], **extra)
+        if len(ladder) > 1:
+            out[name]["context"] = context(ev, tracks)
+        ev.close()
+
     for tf in LR.TFS:
-        for name, insts, ladder in (("one mesh", LR.instances(tf), (LR.M_NODES,)), ("ladder", LD.instances(tf), tuple(LD.LADDER))):
-            B = len(insts)
-            ev = E.Evaluator(0)
-            ev.set_mesh(ladder[0], 0.0, tf)
-            ev.set_model(1, LR.QUAD_PARAMS)
-            ev.set_batch(B)
-            ev.set_path(np.stack([LR.records(i["discs"]) for i in insts]), 0, 1)
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).to(ev.device)
-            z0 = np.stack([i["z0"] for i in insts]).reshape(B, 8, ladder[0])
-            X, U = up(z0[:, :6]), up(z0[:, 6:])
-            bounds = []
-            for M in ladder:
-                P = LD.quad_at(tf, M, LR.discs_of(LR.FIRST_DISCS[0]))
-                bounds.append(dict(zl=up(P.lo.reshape(1, 8, M)), zu=up(P.up.reshape(1, 8, M)), cl=LR.CL, cu=LR.CU, cscale=LR.CSCALE))
-            torch.cuda.synchronize()
-            if len(ladder) == 1:
-                LamF, LamC, res = ev.ipm_solve_shard(X, U, bounds[0], dict(tol=1e-8, max_iter=200))
-                res = [res]
-            else:
-                rungs = [dict(M=M, bounds=b, options=dict(tol=1e-8), repair=0) for M, b in zip(ladder, bounds)]
-                X, U, LamF, LamC, res = ev.ipm_solve_ladder(rungs, 0.0, tf, X, U)
-            ev.synchronize()
-            out[f"{name} tf={tf}"] = dict(X=sha(X), U=sha(U), LamF=sha(LamF), LamC=sha(LamC), results=[rows(r) for r in res])
-            ev.close()
+        run(f"one mesh tf={tf}", tf, LR.instances(tf), (LR.M_NODES,))
+        run(f"ladder tf={tf}", tf, LD.instances(tf), tuple(LD.LADDER))
+        # the refinement of tests/refine_ref.py, bounds shared and per instance
+        run(f"refine tf={tf}", tf, LD.instances(tf), RR.LADDER, refine=(RR.TOLS[tf], RR.FIRST_CHECK))
+        run(f"refine, bounds per instance tf={tf}", tf, LD.instances(tf), RR.LADDER, refine=(RR.TOLS[tf], RR.FIRST_CHECK), replicate=True)
+    # moving discs (tests/track_ladder_ref.py): the two-rung ladder, the refinement over it checked from the first rung on, and the
+    # refinement of the tracks at rest over the four rungs, which compacts the centres through the set map
+    tf = TR.TF
+    run("track ladder", tf, TR.moving_instances(), tuple(LD.LADDER), tracks=True)
+    run("track refine", tf, TR.moving_instances(), tuple(LD.LADDER), refine=(RR.TOLS[tf], 0), tracks=True)
+    run("track refine, four rungs", tf, TR.static_instances(tf), RR.LADDER, refine=(RR.TOLS[tf], RR.FIRST_CHECK), tracks=True)
     return out
 
 
