@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator check-plan-route
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -43,14 +43,15 @@ $(LIBDIR)/emi_rtc_sources.inc: $(RTC_HDR) tools/embed_src.py | $(LIBDIR)
 	python3 tools/embed_src.py $@ $(RTC_HDR)
 $(LIBDIR)/emi_rtc.o: $(CSRC)/emi_rtc.hip $(LIBDIR)/emi_rtc_sources.inc $(CSRC_HDR) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -I$(LIBDIR) -c $< -o $@
-$(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
-	$(CXX) $(CXXFLAGS) -c $< -o $@
+# -ffp-contract=off: emi_plan_route's bits are single rounded operations (emi_plan_route.hpp), whatever the target has
+$(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp $(CSRC)/emi_plan_route.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(CXXFLAGS) -ffp-contract=off -c $< -o $@
 # RCCL gather (librccl is dlopen'ed at first use, not linked)
 $(LIBDIR)/emi_comm.o: $(CSRC)/emi_comm.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
 LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_api_ode emi_rtc emi_kkt emi_adjoint \
-           emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_ode_error emi_host emi_comm
+           emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_ode_error emi_start_guess emi_api_start emi_host emi_comm
 $(LIBDIR)/libemi355x.so: $(LIB_OBJ:%=$(LIBDIR)/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
 
@@ -120,6 +121,13 @@ ODE_OP_CHECK_OUT ?= $(LIBDIR)/ode_operator_check
 check-ode-operator: tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -o $(ODE_OP_CHECK_OUT) tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp -lm
 	$(ODE_OP_CHECK_OUT)
+
+# the planned route (emi_plan_route, csrc/emi_host.cpp with csrc/emi_plan_route.hpp: host-only) on the fixtures of tests/golden as a
+# stand-alone program under the host sanitizers
+PLAN_CHECK_OUT ?= $(LIBDIR)/plan_route_check
+check-plan-route: tests/harness/plan_route_main.cpp $(CSRC)/emi_host.cpp $(CSRC)/emi_plan_route.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -ffp-contract=off -std=c++17 -Iinclude -o $(PLAN_CHECK_OUT) tests/harness/plan_route_main.cpp $(CSRC)/emi_host.cpp -lm
+	$(PLAN_CHECK_OUT) tests/golden/plan_cases.json
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

@@ -91,6 +91,13 @@ class IpmRefineResult(C.Structure):
     _fields_ = [("rung", C.c_int), ("verdict", C.c_int), ("rungs_solved", C.c_int), ("err", C.c_double)]
 
 
+class Start(C.Structure):
+    """emi_start_t: which start emi_start_guess_* writes, and from what"""
+    _fields_ = [("kind", C.c_int), ("nsets", C.c_int), ("xa", _D), ("xb", _D), ("box", _D), ("bend", C.c_double), ("clearance", C.c_double),
+                ("grid", C.c_int), ("repair", C.c_int)]
+
+
+START_LINE, START_BEND, START_PLANNED = range(3)
 REFINE_MET, REFINE_NOT_MET, REFINE_FELL_BACK, REFINE_FAILED = range(4)
 IPM_RULE_RESIDUAL = 1   # emi_ipm_options_t.rules: residual-based acceptance of the full step and the crawl rule
 IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
@@ -159,6 +166,9 @@ SYMBOLS = {
                                            _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
     "emi_ipm_solve_refine_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), _P, _P, C.c_int,
                                             _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
+    "emi_plan_route": (C.c_int, [C.c_int, _D, _D, _D, C.c_double, C.c_int, C.c_int, _D, _D, _D, _I, _D, _I, _I]),
+    "emi_start_guess_dev": (C.c_int, [_P, C.POINTER(Start), _P, _P]),
+    "emi_start_guess_host": (C.c_int, [_P, C.POINTER(Start), _P, _P]),
     "emi_kkt_last_regularisation": (C.c_int, [_P, _D, _D]),
     "emi_kkt_factor_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.POINTER(C.c_ubyte)), _D, _I]),
     "emi_kkt_solve_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_D)]),

@@ -155,6 +155,7 @@ struct emi_ctx_s {
     emi::DeviceArray<double> ipm_crow, ipm_part;
     emi::IpmSolveWs* ipm_solve = nullptr;   // device arrays of the lock-step driver (emi_ipm_solve_shard_*), created at its first call
     emi::IpmLadderWs* ipm_ladder = nullptr; // ... and of the mesh ladder over it (emi_ipm_solve_ladder_*, emi_ipm_solve_refine_*)
+    emi::StartGuessWs* start_guess = nullptr;   // ... and of the starts of the batch (emi_start_guess_*): grids, distances, paths
     bool path_has_track = false;            // the record table holds a row of kind EMI_PATH_TRACK
     // measurement
     hipEvent_t t_start = nullptr, t_stop = nullptr;
@@ -181,6 +182,7 @@ struct emi_ctx_s {
         for (emi::KktWorkspace* w : kkt_shard) emi::kkt_destroy(w);
         emi::ipm_solve_destroy(ipm_solve);
         emi::ipm_ladder_destroy(ipm_ladder);
+        emi::start_guess_destroy(start_guess);
     }
 };
 

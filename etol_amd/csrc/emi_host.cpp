@@ -7,11 +7,16 @@
 // the end points that ePSOPT::events reads (ePSOPT.cpp:281-291).  PSOPT's
 // sources are not part of the reference tree, so the construction below is the
 // textbook one, written from the defining formulas.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
+#include <queue>
+#include <utility>
 #include <vector>
 
 #include "emi355x.h"
+#include "emi_plan_route.hpp"
 
 namespace {
 
@@ -207,6 +212,59 @@ int emi_prolong_matrix(int Mc, const double* tau_c, const double* w_c, int Mf, c
             den += row[j];
         }
         for (int j = 0; j < Mc; ++j) row[j] = hit >= 0 ? (j == hit ? 1.0 : 0.0) : row[j] / den;
+    }
+    return EMI_OK;
+}
+
+// The route of planned_path_guess past the static records, as the header specifies it (arithmetic: emi_plan_route.hpp, shared with
+// the kernels of emi_start_guess_dev).  The distances here come from Dijkstra over all cells; the device relaxes to the same fixed point.
+int emi_plan_route(int np, const double* recs, const double ends[4], const double box[4], double clearance, int grid, int M,
+                   const double* tau, double* xs, double* ys, int* level, double* cost, int* cells, int* ncells) {
+    namespace P = emi_plan;
+    const int N = grid == 0 ? P::GRID_DEFAULT : grid;
+    if (np < 0 || (np > 0 && !recs) || !ends || !tau || !xs || !ys || !level || M < 2 || N < P::GRID_MIN || N > P::GRID_MAX ||
+        clearance != clearance)
+        return EMI_ERR_ARG;
+    if (cost) *cost = 0.0;
+    if (ncells) *ncells = 0;
+    const P::Geom g = P::geom(ends, box, clearance, N);
+    if (g.level == -2 || P::count_static(np, recs) == 0) { *level = -2; return EMI_OK; }
+    const size_t n2 = (size_t)N * N;
+    std::vector<double> cellcost(n2), dist(n2), px(n2), py(n2), arc(n2);
+    std::vector<unsigned char> bits(n2);
+    std::vector<int> path(n2);
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) P::cell_eval(g, np, recs, i, j, &cellcost[(size_t)i * N + j], &bits[(size_t)i * N + j]);
+    *level = -1;
+    for (int lv = 0; lv < P::LEVELS; ++lv) {
+        std::fill(dist.begin(), dist.end(), P::UNREACHED);
+        typedef std::pair<double, int> QE;
+        std::priority_queue<QE, std::vector<QE>, std::greater<QE>> pq;
+        dist[g.start] = 0.0;
+        pq.push({0.0, g.start});
+        while (!pq.empty()) {
+            const QE e = pq.top();
+            pq.pop();
+            if (e.first > dist[e.second]) continue;
+            const int i = e.second / N, j = e.second % N;
+            for (int di = -1; di <= 1; ++di)
+                for (int dj = -1; dj <= 1; ++dj) {
+                    const int a = i + di, b = j + dj;
+                    if ((!di && !dj) || a < 0 || b < 0 || a >= N || b >= N || P::is_blocked(g, bits.data(), a * N + b, lv)) continue;
+                    const double w = P::step_of(g, di, dj) * cellcost[(size_t)a * N + b];
+                    const double d = e.first + w;
+                    if (d < dist[(size_t)a * N + b]) { dist[(size_t)a * N + b] = d; pq.push({d, a * N + b}); }
+                }
+        }
+        if (!(dist[g.goal] < P::UNREACHED)) continue;       // no route with the keep-outs grown this much: try them smaller
+        const int L = P::trace(g, dist.data(), cellcost.data(), path.data(), px.data(), py.data(), arc.data());
+        if (L == 0) return EMI_OK;                          // (level -1)
+        for (int k = 0; k < M; ++k) P::resample(L, px.data(), py.data(), arc.data(), tau[k], &xs[k], &ys[k]);
+        *level = lv;
+        if (cost) *cost = dist[g.goal];
+        if (ncells) *ncells = L;
+        if (cells) std::copy(path.begin(), path.begin() + L, cells);
+        return EMI_OK;
     }
     return EMI_OK;
 }

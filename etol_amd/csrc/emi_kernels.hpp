@@ -267,6 +267,22 @@ struct TrackWaypointArgs {
 template <typename T> hipError_t launch_track_waypoints(TrackWaypointArgs a, hipStream_t s);
 struct IpmLadderWs;
 void ipm_ladder_destroy(IpmLadderWs* w);
+// the starts of one context's batch (emi_start_guess.hip): line, bend and planned route into X[B][ns][M].  par: per set xa [ns] |
+// xb [ns] | box [4]; tau, sine [M]; cost, dist, extra, cells, bits: [B][N^2] of the context's StartGuessWs (PLANNED only)
+struct StartArgs {
+    double* X;
+    int* level;
+    const double *recs, *par, *tau, *sine;
+    double *cost, *dist, *extra;
+    int* cells;
+    unsigned char* bits;
+    int B, ns, M, np, path_sets, px, py, nsets, kind, N, has_box;
+    double bend, clearance;
+};
+struct StartGuessWs;
+void start_guess_destroy(StartGuessWs* w);
+// the call after its checks: uploads the parameters (that copy drains the stream), launches the kernels, returns an EMI_* status
+int start_guess(emi_ctx_t c, const emi_start_t& st, void* dX, void* dLevel);
 int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const void* dX0, const void* dU0, void* dX,
                      void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results);
 // the move of the instances of a list between two sets of arrays [instance][rows][ld], entry i: instance sidx[i] of src -> instance

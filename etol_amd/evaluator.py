@@ -60,6 +60,26 @@ def invariant_rows(model, np_rows=0):
     return mask.astype(bool)
 
 
+def plan_route(recs, ends, tau, box=None, clearance=0.01, grid=0):
+    """The route of emi_plan_route (host) from (ends[0], ends[1]) to (ends[2], ends[3]) past the static records recs [np][PATH_REC],
+    resampled at the node abscissae tau: (xs, ys, level, cost, cells); xs, ys are None and cells is empty without a route
+    (level -1: none at any grow of the keep-outs, -2: nothing to plan)."""
+    lib = L.load()
+    recs = np.ascontiguousarray(recs, dtype=np.float64).reshape(-1, L.PATH_REC)
+    ends, tau = (np.ascontiguousarray(a, dtype=np.float64) for a in (ends, tau))
+    assert ends.shape == (4,)
+    bx = None if box is None else np.ascontiguousarray(box, dtype=np.float64)
+    N = int(grid) if grid else 161
+    xs, ys, cells = np.empty(len(tau)), np.empty(len(tau)), np.empty(max(N * N, 1), dtype=np.int32)
+    level, ncells, cost = C.c_int(), C.c_int(), C.c_double()
+    L.check(lib.emi_plan_route(len(recs), _dp(recs) if recs.size else None, _dp(ends), _dp(bx) if bx is not None else None, float(clearance),
+                               int(grid), len(tau), _dp(tau), _dp(xs), _dp(ys), C.byref(level), C.byref(cost),
+                               cells.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ncells)), what="emi_plan_route")
+    if level.value < 0:
+        return None, None, level.value, 0.0, cells[:0]
+    return xs, ys, level.value, cost.value, cells[:ncells.value].copy()
+
+
 class Evaluator:
     """One libemi355x context: mesh + model + batch, evaluated on one GPU."""
 
@@ -639,6 +659,32 @@ class Evaluator:
     def repair_guess(self, X):
         """interior nodes of X [B][ns][M] (device tensor, in place) inside a keep-out of the record table moved out of it; asynchronous"""
         self._ck(self.lib.emi_repair_guess_dev(self.ctx, C.c_void_p(X.data_ptr()) if X is not None else None), "emi_repair_guess_dev")
+
+    def start_guess(self, kind, xa, xb, box=None, bend=0.0, clearance=0.01, grid=0, repair=0, X=None, dev=True):
+        """The starts of the whole batch on the present mesh (emi_start_guess_*): kind START_LINE / START_BEND / START_PLANNED; xa, xb
+        [nsets][ns] (1-D: one shared set) the states at t0 and tf, box [nsets][4] {xl, xu, yl, yu} of the position states or None.
+        Returns (X [B][ns][M], level [B] int32): torch tensors on this device (asynchronous; X may be given), or numpy arrays
+        with dev=False."""
+        lay = self.layout
+        xa, xb = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1, lay.ns) for a in (xa, xb))
+        assert xa.shape == xb.shape
+        st = L.Start(kind=int(kind), nsets=xa.shape[0], xa=_dp(xa), xb=_dp(xb), bend=float(bend), clearance=float(clearance), grid=int(grid),
+                     repair=int(bool(repair)))
+        if box is not None:
+            box = np.ascontiguousarray(box, dtype=np.float64).reshape(-1, 4)
+            assert box.shape[0] == xa.shape[0]
+            st.box = _dp(box)
+        if dev:
+            if X is None:
+                X = torch.empty((lay.B, lay.ns, lay.M), dtype=torch.float64, device=self.device)
+            assert X.dtype == torch.float64 and X.is_contiguous() and tuple(X.shape) == (lay.B, lay.ns, lay.M)
+            level = torch.empty((lay.B,), dtype=torch.int32, device=self.device)
+            fn = self.lib.emi_start_guess_dev
+        else:
+            X, level = np.empty((lay.B, lay.ns, lay.M)), np.empty(lay.B, dtype=np.int32)
+            fn = self.lib.emi_start_guess_host
+        self._ck(fn(self.ctx, C.byref(st), self._ipm_addr(X), self._ipm_addr(level)), fn.__name__)
+        return X, level
 
     def _ipm_rungs(self, rungs, keep):
         """the emi_ipm_rung_t array of a list of dict M, bounds, recs, options, repair (ipm_solve_ladder); keep: what must outlive the call"""

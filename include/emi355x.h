@@ -721,6 +721,70 @@ int emi_ipm_solve_refine_dev(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* ru
 int emi_ipm_solve_refine_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
                               const double* X0, const double* U0, int ldm, double* X, double* U, double* LamF, double* LamC,
                               emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out);
+/* ---- starts of a context's whole batch: the straight line, the bent line, the route planned past the static keep-outs ----------
+ * What ETOL::mi355x::initial_guess does for the states of one problem, for every instance of the batch in one call, so that the
+ * lock-step calls above can be given the starts solve() owes its robustness to without a Dijkstra per instance on the host and
+ * without [B][ns][M] going up per attempt.  Controls are the caller's business.
+ *
+ * emi_plan_route (host, no device needed): the route of planned_path_guess (host/eMI355X.cpp) from (ends[0], ends[1]) to (ends[2],
+ * ends[3]) past the np records recs[np][EMI_PATH_REC], on a grid of `grid` points per axis (0: 161; else 9 .. 161), resampled at
+ * the M node abscissae tau (M >= 2) into xs[M], ys[M].  Cell (i, j) is the point (xl + i hx, yl + j hy) and has the number i grid + j.
+ *   span = max(|x1 - x0|, |y1 - y0|); the box {xl, xu, yl, yu}: an axis of `box` that is not inside (-1e18, 1e18) (or box NULL) is
+ *   [min - span, max + span] of the end points on that axis; hx = (xu - xl) / (grid - 1), hy likewise.
+ *   Static records: ellipses and discs with a^2 > 0 and b^2 > 0; rows of kind EMI_PATH_TRACK are ignored.
+ *   clear(cell) = min over static records of (sqrt(ex^2 / a^2 + ey^2 / b^2) - 1) sqrt(min(a^2, b^2)), (ex, ey) the cell's offset
+ *   from the centre in the record's axes; cellcost = 1 + (room / max(clear, 1e-3 span))^2 with room = clearance span (1 where
+ *   room is not positive); a cell is blocked at grow g in {0.25, 0.1, 0} where ex^2 / (a^2 G) + ey^2 / (b^2 G) < 1, G = (1 + g)^2,
+ *   for some static record; the cells of the two end points are never blocked.
+ *   *level: 0, 1, 2: the first of the three grows with a route; -1: none has one; -2: nothing to plan (no static record, a span
+ *   that is not positive, or a box without extent).  xs, ys, cells are written, and *cost, *ncells are non-zero, only with a route.
+ *   cells (NULL, or room for grid^2 numbers): the *ncells cells of the route from start to goal; *cost: its length, dist[goal].
+ * planned_path_guess term by term, with four exceptions that make a parallel evaluation possible and reproducible:
+ *   Distances are a fixed point, not Dijkstra's visiting order: dist[start] = 0, dist[c] = min over the 8 neighbours a of
+ *     fl(dist[a] + w(a -> c)), w = fl(step cellcost[c]), step = hx, hy or sd = sqrt(hx hx + hy hy) (computed once).  Rounded addition
+ *     is monotone and the weights are positive, so Dijkstra and a relaxation in any order from +inf reach the same bits: each value
+ *     is the least left-folded cost of a path.
+ *   The path is the backtrack from the goal: the predecessor of c is the first neighbour a, in the order di = -1 .. 1 outer,
+ *     dj = -1 .. 1 inner, with fl(dist[a] + w(a -> c)) == dist[c].  (A backtrack of more than grid^2 cells ends with level -1.)
+ *   sqrt(dx dx + dy dy) stands where the host function has hypot, floor(v + 0.5) where it has lround; single rounded operations,
+ *     never fused.
+ *   Distances are computed for all cells: no early exit at the goal.
+ * Three in-place passes of (1/4, 1/2, 1/4) smoothing, the arc length and the resampling at 0.5 (tau_k + 1) arc are the host's;
+ * the segment of a node is searched from the first one for every node (the same for ascending tau).
+ * EMI_ERR_ARG: np < 0, recs NULL with np > 0, a NULL among ends, tau, xs, ys, level, a grid outside 9 .. 161 and not 0, M < 2, a NaN
+ * clearance.
+ *
+ * emi_start_guess_dev writes dX[B][ns][M] on the context's mesh for its model, batch, record table (shared or per instance) and
+ * position states px, py (emi_set_path); asynchronous on the context's stream:
+ *   1. every state i: a_i + (b_i - a_i) 0.5 (tau_k + 1) with a = xa, b = xb of the instance's set;
+ *   2. EMI_START_PLANNED: rows px, py replaced by emi_plan_route's xs, ys (ends and box of the instance's set) where it has a route;
+ *   3. EMI_START_BEND, and PLANNED instances without a route while bend != 0: rows px, py bent by half a sine wave,
+ *      x - bend dy / len sin(pi/2 (tau_k + 1)), y + bend dx / len sin(..) with (dx, dy) the line's end-to-end vector, len its length,
+ *      clipped to the box (no clip with box NULL; the sines are the host's, one table per call);
+ *   4. emi_repair_guess_dev on the result where `repair` is set (track rows then need their centres, as there).
+ * dLevel int[B] (NULL: not wanted): emi_plan_route's level per instance; -2 everywhere for the other kinds.  The device's bits are
+ * emi_plan_route's.  The relaxation runs with one workgroup per instance over distances kept in a workspace of the context (161^2
+ * doubles do not fit the LDS), grown as needed and freed with the context.
+ * Statuses: EMI_ERR_UNSUPPORTED for an f32 context and for more than 65535 instances; EMI_ERR_STATE without mesh, model or batch;
+ * EMI_ERR_ARG for a NULL ctx, st, dX, xa or xb, a grid outside 9 .. 161 and not 0, an nsets that is neither 1 nor B, an unknown kind,
+ * a NaN in bend or clearance, px or py that is no state, a mesh of fewer than 2 nodes.  The _host form takes host arrays and synchronises. */
+enum { EMI_START_LINE = 0, EMI_START_BEND = 1, EMI_START_PLANNED = 2 };
+typedef struct emi_start {
+  int kind;
+  int nsets;            /* 1 or B: sets of xa, xb, box */
+  const double* xa;     /* host [nsets][ns]: states at t0 */
+  const double* xb;     /* host [nsets][ns]: states at tf */
+  const double* box;    /* host [nsets][4] {xl, xu, yl, yu} of the position states px, py; NULL or a non-finite entry:
+                           planned_path_guess's box of twice the span round the end points, and no clip of the bend */
+  double bend;          /* BEND, and PLANNED where no route exists: sideways offset as a length (Prob::guess_bend) */
+  double clearance;     /* PLANNED: Prob::guess_clearance (0: the shortest route) */
+  int grid;             /* PLANNED: grid points per axis, 0 = 161; 9 .. 161 */
+  int repair;           /* non-zero: emi_repair_guess_dev on the result */
+} emi_start_t;
+int emi_plan_route(int np, const double* recs, const double ends[4], const double box[4], double clearance, int grid, int M,
+                   const double* tau, double* xs, double* ys, int* level, double* cost, int* cells, int* ncells);
+int emi_start_guess_dev(emi_ctx_t ctx, const emi_start_t* st, void* dX, void* dLevel);
+int emi_start_guess_host(emi_ctx_t ctx, const emi_start_t* st, double* X, int* level);
 /* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
  * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
  * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
