@@ -65,6 +65,23 @@ int emi_api::HostStager::finish() {
     return EMI_OK;
 }
 
+bool emi_api::even_odd_halves(int M, const double* D, std::vector<double>& De, std::vector<double>& Do) {
+    if (M % 2 != 0) return false;
+    const int N = M - 1, Hh = M / 2;
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < M; ++j)
+            if (D[(size_t)i * M + j] != -D[(size_t)(N - i) * M + (N - j)]) return false;
+    De.assign((size_t)Hh * Hh, 0.0);
+    Do.assign((size_t)Hh * Hh, 0.0);
+    for (int i = 0; i < Hh; ++i)
+        for (int j = 0; j < Hh; ++j) {
+            const double p = D[(size_t)i * M + j], q = D[(size_t)i * M + (N - j)];
+            De[(size_t)i * Hh + j] = 0.5 * (p + q);
+            Do[(size_t)i * Hh + j] = 0.5 * (p - q);
+        }
+    return true;
+}
+
 namespace {
 
 // ---- emi_set_option: the plain options, one row each (what the name means is said at the member it sets) -------------------
@@ -104,6 +121,7 @@ const OptionRow OPTIONS[] = {
     {"sym_hs", &emi_ctx_s::sym_hs, within<0, 2>, as_given, "sym_hs must be 0 (by batch size), 1 or 2"},
     {"sym_ctc", &emi_ctx_s::sym_ctc, within<0, 2>, as_given, "sym_ctc must be 0 (by batch size), 1 or 2"},
     {"sym_bk", &emi_ctx_s::sym_bk, one_of<0, 8, 16>, as_given, "sym_bk must be 0 (by batch size), 8 or 16"},
+    {"sym_dop", &emi_ctx_s::sym_dop, within<0, 2>, as_given, "sym_dop must be 0 (by batch size), 1 (De / Do through the operand ring) or 2 (straight from L2)"},
     {"sym_cpart", &emi_ctx_s::sym_cpart, one_of<-1, 0, 1, 2, 4, 8>, as_given, "sym_cpart must be -1 (plain order), 0 (by mesh size), 1, 2, 4 or 8"},
     {"sym_gblk", &emi_ctx_s::sym_gblk, within<0, 64>, as_given, "sym_gblk must be 0 (off) .. 64 instance groups per super-block"},
     {"sym_cx", &emi_ctx_s::sym_cx, within<0, 64>, as_given, "sym_cx must be 0 (default) .. 64 column tiles per block"},
@@ -215,21 +233,17 @@ static int upload_operator(emi_ctx_t c, int M, const double* D) {
     }
     EMI_TRY(upload_real(c, c->d_D, D, (size_t)M * M));
     // even/odd split of D for the fused kernel: valid only for an exactly centro-antisymmetric D
-    if (M % 2 != 0) return EMI_OK;
-    const int N = M - 1, Hh = M / 2;
-    for (int i = 0; i < M; ++i)
-        for (int j = 0; j < M; ++j)
-            if (D[(size_t)i * M + j] != -D[(size_t)(N - i) * M + (N - j)]) return EMI_OK;
-    std::vector<double> De((size_t)Hh * Hh), Do((size_t)Hh * Hh);
-    for (int i = 0; i < Hh; ++i)
-        for (int j = 0; j < Hh; ++j) {
-            const double p = D[(size_t)i * M + j], q = D[(size_t)i * M + (N - j)];
-            De[(size_t)i * Hh + j] = 0.5 * (p + q);
-            Do[(size_t)i * Hh + j] = 0.5 * (p - q);
-        }
+    std::vector<double> De, Do;
+    if (!even_odd_halves(M, D, De, Do)) return EMI_OK;
     EMI_TRY(upload_real(c, c->d_De, De.data(), De.size()));
     EMI_TRY(upload_real(c, c->d_Do, Do.data(), Do.size()));
     c->symmetric = true;
+    if (M % 128 == 0) {         // what the one-launch pass takes: the same panels once more, in the order its MFMA waves consume them
+        std::vector<double> frag(De.size() + Do.size());
+        emi::operator_fragments(M, De.data(), Do.data(), frag.data());
+        EMI_TRY(upload_real(c, c->d_Dfrag, frag.data(), frag.size()));
+        c->has_dfrag = true;
+    }
     return EMI_OK;
 }
 
@@ -251,6 +265,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     EMI_TRY(upload_real(c, c->d_t, nt.data(), M));
     EMI_TRY(upload_real(c, c->d_Ddiag, dd.data(), M));
     c->symmetric = false;
+    c->has_dfrag = false;
     if (D) EMI_TRY(upload_operator(c, M, D));
     c->points_only = !D;
     c->h_tau.assign(tau, tau + M);

@@ -157,6 +157,17 @@ PassPlan plan_pass(emi_ctx_t c, int B, bool jac) {
     if (hs_want == 2 && !c->rtc && plan.ks == 1 && plan.ct == 1 && (plan.sw == 1 || plan.sw == 2) && plan.nst == 3 &&
         ((c->M / 2) / plan.bk) % 4 == 0)
         plan.hs = 2;
+    // De / Do fragments straight from L2 into the MFMA waves' registers instead of through the operand ring ("sym_dop" 2; built-in models,
+    // SW 1 or 2 of more states, 16-deep K tiles, unsplit, one sub-tile, three stages; the context holds the fragment-order copy)
+    // By itself from 216 tiles (432 instances) through the range of deep_large.  One box, M = 1024, ms per pass through the ring / straight
+    // from L2 (tools/mid_sweep.py dop1,dop2; profiles/r06_mid_sweep_dop.jsonl): 432 instances 0.0903 / 0.0865, 512: 0.1002 / 0.0975, 768: 0.1446 /
+    // 0.1412, 1024: 0.1879 / 0.1836, 1536: 0.2790 / 0.2735, 2048: 0.3771 / 0.3671.  Below that neither form is ahead: the pass time moves with how
+    // the workgroups of the two roles fill the chip, not with the K loop (128: 0.0261 / 0.0262, 176: 0.0412 / 0.0392, 224: 0.0425 / 0.0434, 288:
+    // 0.0614 / 0.0631, 352: 0.0774 / 0.0714, 416: 0.0824 / 0.0835; SW = 1: 80 instances 0.0192 / 0.0208, 96: 0.0246 / 0.0240), so those stay.
+    const int dop_want = c->sym_dop ? c->sym_dop : ((deep_large && p.tiles16 >= 216) ? 2 : 1);
+    if (dop_want == 2 && !c->rtc && c->has_dfrag && plan.bk == 16 && plan.ks == 1 && plan.ct == 1 && plan.hs == 1 && plan.nst == 3 &&
+        plan.sw != c->ns && (plan.sw == 1 || plan.sw == 2))
+        plan.dop = true;
     p.sym = plan;
     p.mfma_first = c->pass_order >= 0 ? c->pass_order
                                       : (deep_band ? 150 : (p.tiles16 < 208 ? 1 : (p.tiles16 < 384 ? 125 : (p.tiles16 < 768 ? 110 : 0))));
@@ -356,7 +367,8 @@ const char* name_defect_f64(bool small) { return small ? "emi_defect_small_f64_k
 std::string name_pass_f64(const emi::SymPlan& plan) {
     return "emi_pass_f64_kernel<SW=" + std::to_string(plan.sw) + "> (MFMA + node roles, one launch" +
            (plan.ks > 1 ? ", " + std::to_string(plan.ks) + " K slices per tile" : "") + ")" +
-           (plan.bk == 16 ? " [K tiles of 16]" : "") + (plan.ct == 2 ? " [128-column tiles]" : "") + (plan.hs == 2 ? " [K range in two halves per workgroup]" : "");
+           (plan.bk == 16 ? " [K tiles of 16]" : "") + (plan.ct == 2 ? " [128-column tiles]" : "") + (plan.hs == 2 ? " [K range in two halves per workgroup]" : "") +
+           (plan.dop ? " [De/Do from L2]" : "");
 }
 std::string name_symdefect(emi_ctx_t c, const emi::SymPlan& plan, bool in_kernel_combine) {
     if (plan.ring1) return c->sym_ct == 1 || c->sym_ct == 2 ? "emi_symdefect_f64_kernel" : NAME_RING1_F64;
@@ -373,6 +385,7 @@ emi::SymDefectArgs sym_defect_args(emi_ctx_t c, Launch L, const PassIO& io) {
     sa.node_t = (const double*)c->d_t.p;
     sa.De = (const double*)c->d_De.p;
     sa.Do = (const double*)c->d_Do.p;
+    sa.Dfrag = c->has_dfrag ? (const double*)c->d_Dfrag.p : nullptr;
     sa.M = c->M;
     sa.B = L.B;
     sa.nres = nres_of(c);
@@ -806,6 +819,14 @@ int emi_debug_tile_order2(int ns, int B, int M, int sym_ct, int sym_cpart, int s
         const emi::RingTile rt = emi::ring_tile_of(t, ntiles, ngrp, p.cpart, p.cx, ns / p.sw);
         out_tile[t] = rt.ntile + ntiles * rt.grp;
     }
+    return EMI_OK;
+}
+
+int emi_debug_operator_fragments(int M, const double* D, double* out) {
+    if (M < 128 || M % 128 != 0 || !D || !out) return EMI_ERR_ARG;
+    std::vector<double> De, Do;
+    if (!even_odd_halves(M, D, De, Do)) return EMI_ERR_UNSUPPORTED;
+    emi::operator_fragments(M, De.data(), Do.data(), out);
     return EMI_OK;
 }
 

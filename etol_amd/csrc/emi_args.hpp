@@ -126,6 +126,8 @@ struct SymDefectArgs {
                             //  cpart = -G: grouped order, super-blocks of G instance groups per XCD, column blocks of cx: ring_tile_of)
     double h;
     ModelParams<double> P;
+    const double* Dfrag;    // De / Do once more, in the order the MFMA role's waves consume them (operator_fragments): read only by the
+                            // "De / Do from L2" form of the one-launch pass, nullptr where the context holds none
 };
 
 struct DefectArgs {

@@ -52,6 +52,8 @@ struct emi_ctx_s {
     double t0 = 0, tf = 0;
     DevBuf d_w, d_t, d_Ddiag, d_D, d_De, d_Do;
     bool symmetric = false;   // D is exactly centro-antisymmetric and M is even: De/Do are valid
+    DevBuf d_Dfrag;           // De / Do in the MFMA role's fragment order (emi::operator_fragments), as large as the two together
+    bool has_dfrag = false;   // ... valid: a symmetric D on a mesh of whole 128-node tiles (rebuilt by every emi_set_mesh)
     bool points_only = false; // emi_set_mesh(D = NULL): abscissae without a differentiation matrix
     int allow_fused = 1;          // "overlap" option: even/odd MFMA defect kernel || node kernel on two streams
     int sym_ct = 0;               // MFMA kernel variant (emi_symdefect.hip): 0 = chosen from the batch, 3 = LDS-DMA ring, 5..8 state-split ring, 1/2 = register-staged
@@ -95,6 +97,8 @@ struct emi_ctx_s {
     int sym_hs = 0;             // "sym_hs": 2: K range of a tile in two halves inside the workgroup (512 threads); 1: undivided; 0: by batch size
     int sym_ctc = 0;            // "sym_ctc": 64-column sub-tiles per MFMA workgroup of the one-launch pass (1 or 2; 0: by batch size, plan_pass)
     int sym_bk = 0;             // "sym_bk": depth of a K tile of the one-launch pass (8 or 16; 0: by batch size, plan_pass)
+    int sym_dop = 0;            // "sym_dop": where the MFMA role's De / Do fragments come from: 1 through the operand ring, 2 straight from L2
+                                // (unsplit 16-deep form, SW 1 / 2); 0: by batch size, plan_pass
     // delayed values (emi_set_delays): x_horizon - 1 delayed copies of every state and u_horizon of every control, appended to the
     // controls the node functions see: nc = nc_free + nch; W[d] = interpolation matrix of delay (d + 1) dt on this mesh
     int xh = 0, uh = 0, nch = 0;
@@ -226,6 +230,9 @@ int upload_bytes(emi_ctx_t c, DevBuf& b, const void* src, size_t bytes);
 // upload a host double array in the context's real type
 int upload_real(emi_ctx_t c, DevBuf& b, const double* src, size_t n);
 int download_real(emi_ctx_t c, double* dst, const void* dsrc, size_t n);
+// the even / odd halves De, Do ([M/2][M/2] each) of a differentiation matrix; false (nothing written) unless M is even and D exactly
+// centro-antisymmetric
+bool even_odd_halves(int M, const double* D, std::vector<double>& De, std::vector<double>& Do);
 // the staging buffer of VALS (host forms): a buffer that has to grow is a new, unwritten one -- also where the allocator hands
 // back the old address, so the record is told before the old one goes
 int ensure_vals_staging(emi_ctx_t c, size_t bytes);

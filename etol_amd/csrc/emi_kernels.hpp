@@ -42,12 +42,32 @@ struct SymPlan {
     int bk = 8;               // depth of a K tile of the one-launch pass (8, or 16: SW 1 / 2 with three stages)
     int hs = 1;               // 2: the K range of a tile in two halves inside a 512-thread workgroup, combined through LDS (SW 1 / 2, unsplit, one sub-tile)
     int ct = 1;               // 64-column sub-tiles per MFMA workgroup of the one-launch pass (2: SW = 2, unsplit, M % 256 == 0)
+    bool dop = false;         // one-launch pass: the MFMA role's De / Do fragments straight from L2, not through the ring (SW 1 / 2, bk 16, unsplit,
+                              // one sub-tile, three stages; needs SymDefectArgs::Dfrag)
     size_t slab_bytes = 0;
     int cpart = 0, cx = 0;    // tile order (SymDefectArgs::cpart, cx): 0 = plain, > 0 column partitions, < 0 grouped (-G)
     int tiles = 0;            // tiles of the launch (instance groups x column tiles x state groups): tickets of an in-kernel combine
 };
 SymPlan plan_symdefect(int ns, int B, int M, int ct, int ksplit_opt, int cpart_opt = 0, int gblk_opt = 0, int cx_opt = 0, int bk_opt = 8, int ct_cols = 1);
 hipError_t launch_symdefect(int model, const SymDefectArgs& a, hipStream_t s, bool set_attr, int ct, const SymPlan& plan);
+// The fragment-order copy of De / Do, for 16-deep K tiles and 64-column tiles: the 16 bytes lane `lane` of wave w loads as piece q of K tile
+// kt of column tile ct are double2 number (((ct*4 + w)*nkt + kt)*4 + q)*64 + lane, nkt = M/32, q = 2h + odd, lane = 16 kq + r16; they hold
+// P[64 ct + 16 w + r16][16 kt + 8 h + 2 kq] and its right neighbour, P = De (odd = 0) or Do (odd = 1) -- the bits and the k order that the
+// fragment reads of the staged form take out of the ring.  One function for the upload and for emi_debug_operator_fragments.
+inline void operator_fragments(int M, const double* De, const double* Do, double* out) {
+    const int Hh = M / 2, nkt = Hh / 16;
+    for (int ct = 0; ct < Hh / 64; ++ct)
+        for (int w = 0; w < 4; ++w)
+            for (int kt = 0; kt < nkt; ++kt)
+                for (int q = 0; q < 4; ++q)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const double* row = ((q & 1) ? Do : De) + (size_t)(64 * ct + 16 * w + (lane & 15)) * Hh + 16 * kt + 8 * (q >> 1) + 2 * (lane >> 4);
+                        double* o = out + ((((size_t)(ct * 4 + w) * nkt + kt) * 4 + q) * 64 + lane) * 2;
+                        o[0] = row[0];
+                        o[1] = row[1];
+                    }
+}
+
 // the whole pass as one launch (MFMA-role and node-role workgroups in one grid; COST finished in-kernel)
 bool pass_supported(int model, int ns, int B, int M, const SymPlan& plan);
 hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& plan);

@@ -165,7 +165,7 @@ static hipError_t launch_ring2_planned(const SymDefectArgs& a, hipStream_t s, co
 
 // ---------------------------------------------------------------------------------------------
 // the pass as one launch (emi_pass_f64_kernel): MFMA-role and node-role workgroups interleaved per XCD
-template <class Model, int SW, int NST, int BK = 8, int CT = 1, int HS = 1>
+template <class Model, int SW, int NST, int BK = 8, int CT = 1, int HS = 1, bool DOP = false>
 static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s) {
     constexpr int NS = Model::NS;
     PassArgs a;
@@ -179,7 +179,10 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     a.nn = nn;
     a.nm8 = (nm + 7) / 8;
     a.nn8 = ((nn + HS - 1) / HS + 7) / 8;          // node-role WORKGROUPS per XCD: one takes HS chunks
-    const size_t lds = (size_t)HS * NST * ((2 * SW * FUSED_TI + 2 * 64 * CT + 63) / 64 * 64) * BK * sizeof(double);
+    // a ring stage: forward and mirrored x rows, De and Do rows, in whole DMA instructions -- DOP: the x rows only (whole instructions as they are)
+    const size_t lds = DOP ? (size_t)NST * (2 * SW * FUSED_TI) * BK * sizeof(double)
+                           : (size_t)HS * NST * ((2 * SW * FUSED_TI + 2 * 64 * CT + 63) / 64 * 64) * BK * sizeof(double);
+    if (DOP && (!sa.Dfrag || sa.ksplit > 1)) return hipErrorInvalidValue;
     const int st = (na.store_mode >= 0 && na.store_mode <= 3) ? na.store_mode : 0;   // result stores: plain / sc1 (write-through) / non-temporal / nt sc1
     // The KEEP instantiations (na.keep: the node role leaves the model-invariant VALS rows alone) exist for the forms the default
     // dispatch chooses: three ring stages, undivided K range.  The forms only an option reaches write everything, which is always right.
@@ -187,9 +190,9 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     const bool keep = HAS_KEEP && na.keep;
     auto pick = [&](auto keep_c) {
         constexpr bool K = decltype(keep_c)::value;
-        return st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS, K>
-             : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS, K>
-                        : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS, K> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS, K>));
+        return st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS, K, DOP>
+             : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS, K, DOP>
+                        : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS, K, DOP> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS, K, DOP>));
     };
     auto kern = pick(std::false_type{});
     if constexpr (HAS_KEEP) {
@@ -212,6 +215,7 @@ static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<do
     if constexpr (NS > 2 && NS % 2 == 0) {
         if (p.sw == 2 && p.hs == 2 && p.ct == 1) return p.bk == 16 ? launch_pass_model<Model, 2, 3, 16, 1, 2>(sa, na, s) : launch_pass_model<Model, 2, 3, 8, 1, 2>(sa, na, s);
         if (p.sw == 2 && p.ct == 2) return p.bk == 16 ? launch_pass_model<Model, 2, 3, 16, 2>(sa, na, s) : launch_pass_model<Model, 2, 3, 8, 2>(sa, na, s);
+        if (p.sw == 2 && p.bk == 16 && p.dop) return launch_pass_model<Model, 2, 3, 16, 1, 1, true>(sa, na, s);
         if (p.sw == 2 && p.bk == 16) return launch_pass_model<Model, 2, 3, 16>(sa, na, s);
         if (p.sw == 2) return p.nst > 3 ? launch_pass_model<Model, 2, 4>(sa, na, s) : launch_pass_model<Model, 2, 3>(sa, na, s);
     }
@@ -219,6 +223,7 @@ static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<do
         if (p.sw == 3) return launch_pass_model<Model, 3, 3>(sa, na, s);
     }
     if (p.hs == 2) return p.bk == 16 ? launch_pass_model<Model, 1, 3, 16, 1, 2>(sa, na, s) : launch_pass_model<Model, 1, 3, 8, 1, 2>(sa, na, s);
+    if (p.bk == 16 && p.dop) return launch_pass_model<Model, 1, 3, 16, 1, 1, true>(sa, na, s);
     if (p.bk == 16) return launch_pass_model<Model, 1, 3, 16>(sa, na, s);
     return p.nst > 3 ? launch_pass_model<Model, 1, 4>(sa, na, s) : launch_pass_model<Model, 1, 3>(sa, na, s);
 }
@@ -228,6 +233,8 @@ static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<do
 bool pass_supported(int model, int ns, int B, int M, const SymPlan& p) {
     if (p.ring1 || p.sw < 1 || (model != EMI_MODEL_POINTMASS2D && model != EMI_MODEL_QUADROTOR2D)) return false;
     if (M % 128 != 0 || ns % p.sw != 0) return false;
+    // (De / Do from L2: the unsplit 16-deep form of one or two states per workgroup, one sub-tile, three stages)
+    if (p.dop && !(p.bk == 16 && p.ks == 1 && p.ct == 1 && p.hs == 1 && p.nst == 3 && p.sw != ns && (p.sw == 1 || p.sw == 2))) return false;
     return B >= 1;
 }
 

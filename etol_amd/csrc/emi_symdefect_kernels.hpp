@@ -8,6 +8,9 @@
 namespace emi {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));      // a 16-byte fragment as ONE register operand of an inline-assembly statement
+template <bool C, class A, class B> struct emi_pick { typedef A type; };
+template <class A, class B> struct emi_pick<false, A, B> { typedef B type; };
 
 // CT = 16-column tiles per wave (4 waves side by side): tile = 16 instances x 64*CT half-indices.
 // CT = 1 keeps a wave at ~216 registers, so three 96-register waves of the node kernel fit on
@@ -533,7 +536,13 @@ EMI_DEV void ring_epilogue(const SymDefectArgs& a, const d4 (&acc_a)[SW], const 
 // in LDS (in the ring it no longer needs) and the first adds them and runs the epilogue.  What K slices through the slab do for small
 // batches (a shorter dependency chain, two MFMA waves per SIMD filling each other's gaps) without a second workgroup, global partial
 // sums or a ticket.  The sums of the two halves are added once: not the bits of the unsplit form, the same values to rounding.
-template <class Model, int SW, int NST = 3, int BK = 8, int CT = 1, int HS = 1>
+// DOP (round 6, "De / Do from L2"): the De / Do rows of a wave are read by that wave alone (off_b: row c*64 + wid*16 + r16), so the ring is
+// only a landing buffer for them -- four of the six DMA pieces and four of the twelve fragment reads of a 16-deep tile at SW = 2.  With DOP
+// a stage holds the x rows only (8 KB at SW = 2) and the wave's be / bo fragments of tile kt+1 come straight into registers: four contiguous
+// 1 KB global_load_dwordx4 from the fragment-order copy of the panels (SymDefectArgs::Dfrag, built once per mesh), scalar base, constant lane
+// offset, dealt into the first gaps of tile kt's MFMAs.  Same operands, same MFMA order: the defect rows are bitwise those of the staged form.
+// Unsplit form only: SW 1 / 2, 16-deep tiles, one sub-tile, three stages.  (tools/diag/mfma_mix_probe.hip, profiles/r06_notes.md.)
+template <class Model, int SW, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool DOP = false>
 EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-slice id, XCD-local runs */) {
     constexpr int NS = Model::NS;
     constexpr int TI = FUSED_TI, TM = SW * TI, TN = 64 * CT, CH = BK / 2, NSG = NS / SW;
@@ -542,8 +551,9 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
     constexpr int RPI = 64 / CH;                         // rows one DMA wave instruction moves (1 KB)
     static_assert(BK == 8 || BK == 16, "K tiles of 8 or 16");
     constexpr int LOOK = NST - 1;                        // K tiles in flight ahead of the one being multiplied
-    constexpr int ROWS = 2 * TM + 2 * TN;
-    constexpr int ROWS_PAD = (ROWS + 63) / 64 * 64;      // a DMA wave instruction moves RPI rows: whole instructions for 4 waves
+    static_assert(!DOP || (SW <= 2 && NST == 3 && BK == 16 && CT == 1 && HS == 1), "De / Do from L2: the unsplit 16-deep form only");
+    constexpr int ROWS = 2 * TM + (DOP ? 0 : 2 * TN);
+    constexpr int ROWS_PAD = DOP ? (ROWS + 4 * RPI - 1) / (4 * RPI) * (4 * RPI) : (ROWS + 63) / 64 * 64;   // a DMA wave instruction moves RPI rows: whole instructions for 4 waves
     constexpr int STAGE = ROWS_PAD * BK;                 // doubles per ring stage
     constexpr int L = ROWS_PAD * CH / 256;               // LDS-DMA instructions per wave and stage (1 KB each)
     static_assert(NS % SW == 0, "states split evenly over workgroups");
@@ -555,7 +565,7 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
 
     const int M = a.M, Hh = M >> 1, B = a.B;
     const int ntiles = Hh / TN;
-    const int KS = (HS == 1 && a.ksplit > 1) ? a.ksplit : 1;            // (slices through the slab: the undivided workgroup only)
+    const int KS = (HS == 1 && !DOP && a.ksplit > 1) ? a.ksplit : 1;    // (slices through the slab: the undivided workgroup only)
     const int kslice = bid % KS;
     // Which tile.  bid / KS counts tiles in XCD-local runs (an XCD gets a contiguous range).  Plain order: the ntiles
     // column tiles of an X tile (same instance group, same states) are neighbours, so an XCD's L2 sees each X tile once --
@@ -638,6 +648,13 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
 #pragma unroll
         for (int t = 0; t < L; ++t) issue_one(t);
     };
+    // DOP: where the wave's fragments of the next tile are in Dfrag (wave-uniform; 4 KB per wave and K tile, a lane's 16 bytes at lane * 16
+    // of each of the tile's ND pieces)
+    constexpr int ND = DOP ? 2 * KH : 0;                // direct loads per wave and K tile: (De, Do) of each half
+    unsigned long long fnext = 0;
+    const unsigned foff = (unsigned)lane * 16u;
+    if constexpr (DOP)
+        fnext = (unsigned long long)(a.Dfrag + ((size_t)(((a.ablate & 64) ? 0 : ntile) * 4 + wid) * (Hh / BK) + kt0) * (ND * 64 * 2));
 
     d4 acc_a[SW][CT], acc_b[SW][CT];
 #pragma unroll
@@ -683,20 +700,49 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
     // sp = forward + mirrored x, dm = forward - mirrored x for the tile's two k-steps.  They are formed when the x fragments have
     // arrived (in the gaps of the PREVIOUS tile's MFMAs), not in front of the MFMA that consumes them: a v_add_f64 directly ahead of
     // its MFMA holds the matrix pipe for the result (the same finding as the shift subtractions of the fp32 kernel, r03_notes.md).
+    typedef typename emi_pick<DOP, d2, double2>::type BFrag;    // (DOP: the destination of a load issued from inline assembly)
     struct Frag {
-        double2 be[CT][KH], bo[CT][KH], sp[SW][KH], dm[SW][KH];
+        BFrag be[CT][KH], bo[CT][KH];
+        double2 sp[SW][KH], dm[SW][KH];
     };
     double2 txf[SW][KH], txm[SW][KH];                   // x fragments between their read and their sums
-    constexpr int NRH = 2 * CT + 2 * SW;                // fragment reads per half of a tile
+    constexpr int NB = DOP ? 0 : 2 * CT;                // ... of them De / Do rows
+    constexpr int NRH = NB + 2 * SW;                    // fragment reads per half of a tile
     constexpr int NR = NRH * KH, NM = 4 * SW * CT * KH; // fragment reads / MFMAs per wave and K tile
     // read r of a tile: half h = r / NRH, then (De, Do) of every sub-tile and (forward, mirrored) x of every state
     auto read_one = [&](Frag& f, const double* S, int r) {
         const int h = r / NRH, q = r % NRH;
-        if (q < 2 * CT) {
-            if (q & 1) f.bo[q >> 1][h] = *reinterpret_cast<const double2*>(S + (2 * TM + TN) * BK + off_b[q >> 1][h]);
-            else f.be[q >> 1][h] = *reinterpret_cast<const double2*>(S + 2 * TM * BK + off_b[q >> 1][h]);
-        } else if (q & 1) txm[(q - 2 * CT) >> 1][h] = *reinterpret_cast<const double2*>(S + off_m[(q - 2 * CT) >> 1][h]);
-        else txf[(q - 2 * CT) >> 1][h] = *reinterpret_cast<const double2*>(S + off_f[(q - 2 * CT) >> 1][h]);
+        if (q < NB) {
+            if constexpr (NB > 0) {
+                if (q & 1) f.bo[q >> 1][h] = *reinterpret_cast<const double2*>(S + (2 * TM + TN) * BK + off_b[q >> 1][h]);
+                else f.be[q >> 1][h] = *reinterpret_cast<const double2*>(S + 2 * TM * BK + off_b[q >> 1][h]);
+            }
+        } else if (q & 1) txm[(q - NB) >> 1][h] = *reinterpret_cast<const double2*>(S + off_m[(q - NB) >> 1][h]);
+        else txf[(q - NB) >> 1][h] = *reinterpret_cast<const double2*>(S + off_f[(q - NB) >> 1][h]);
+    };
+    // DOP: direct load q = 2h + odd of the next tile (De / Do rows of half h); the last one moves on to the next tile.  Inline assembly for
+    // the same reason as the DMA: loads return in order, so these and the DMA pieces share ONE vmcnt sequence -- a load the compiler knew
+    // about would make it count its own loads only and wait the younger x pieces out.  The price: the compiler does not know the registers
+    // are in flight, so nothing may touch them before the counted wait, through which they pass as in / out operands (wait_counted / wait_all).
+    auto dload_one = [&](Frag& f, int q) {
+        if constexpr (DOP) {
+            d2& dst = (q & 1) ? f.bo[0][q >> 1] : f.be[0][q >> 1];
+            if (q == 0) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(foff), "s"(fnext) : "memory");
+            if (q == 1) asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(dst) : "v"(foff), "s"(fnext) : "memory");
+            if (q == 2) asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "=v"(dst) : "v"(foff), "s"(fnext) : "memory");
+            if (q == 3) asm volatile("global_load_dwordx4 %0, %1, %2 offset:3072" : "=v"(dst) : "v"(foff), "s"(fnext) : "memory");
+            if (q == ND - 1) fnext += (unsigned long long)(ND * 1024);
+        }
+    };
+    // the counted wait ahead of a tile's barrier: all but the youngest n vector-memory instructions have landed.  DOP: among them the direct
+    // loads into f's De / Do fragments, which become usable HERE (in / out operands: no copy or use of them can be scheduled ahead of the wait)
+    auto wait_counted = [&](Frag& f) {                  // ... the L (LOOK - 1) youngest: the DMA pieces of the tiles still ahead
+        if constexpr (DOP) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(f.be[0][0]), "+v"(f.bo[0][0]), "+v"(f.be[0][1]), "+v"(f.bo[0][1]) : "n"(L * (LOOK - 1)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L * (LOOK - 1)) : "memory");
+    };
+    auto wait_all = [&](Frag& f) {
+        if constexpr (DOP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(f.be[0][0]), "+v"(f.bo[0][0]), "+v"(f.be[0][1]), "+v"(f.bo[0][1]) :: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     // k = 8h + 2kq (+1): forward x_k in xf.x (.y), its mirror x_(N-k) at position BK-1-k of the mirrored tile: xm.y (.x)
     auto sums_one = [&](Frag& f, int s) {
@@ -741,12 +787,22 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
         // instruction or a few reads per gap; sched_barrier pins that order (the scheduler sinks the reads behind the
         // MFMAs otherwise).  Stage (kt+1+LOOK) % NST is the stage of tile kt (NST = LOOK + 1), whose fragment reads every
         // wave has completed before it arrives at the barrier (lgkmcnt(0) ahead of it).
-        constexpr int RPG = (NR + (NM - L) - 1) / (NM - L);     // fragment reads per gap
+        // DOP: the direct loads of tile kt+1 go first, one per gap with SW x reads beside each (they have the longer way), then the DMA.
+        // In flight at the wait that opens tile kt, oldest first: x(kt+1) | De / Do (kt) | x(kt+2) -- all but the L youngest, as without DOP.
+        constexpr int RPG = DOP ? NR / ND : (NR + (NM - L) - 1) / (NM - L);     // fragment reads per gap
         constexpr int GR = (NR + RPG - 1) / RPG;                // gaps that take reads: the first GR; then L gaps with a DMA each
         static_assert(NM > L && GR + L <= NM, "a gap for every DMA instruction after the reads");
-        auto step = [&](const Frag& cur, Frag& nxt, int kt) {   // kt + 1 < nkt: MFMAs of tile kt, tile kt+1 made ready
-            if (kt + LOOK < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L * (LOOK - 1)) : "memory");
-            else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        static_assert(!DOP || GR == ND, "a direct load in every gap that takes reads");
+        // DOP: which of the two waits a step opens with is said by the caller (`tail`), not found out at run time: two assembly statements
+        // that both hand the fragments on meet in a copy, and the compiler put that copy AHEAD of the drained wait (read in the ISA).
+        struct Ahead { enum { drained = 0 }; };                 // tiles still ahead of tile kt+1 in the ring
+        struct Tail { enum { drained = 1 }; };
+        auto step = [&](Frag& cur, Frag& nxt, int kt, auto tail) {   // kt + 1 < nkt: MFMAs of tile kt, tile kt+1 made ready
+            if constexpr (DOP) {
+                if constexpr (decltype(tail)::drained) wait_all(cur);
+                else wait_counted(cur);
+            } else if (kt + LOOK < nkt) wait_counted(cur);
+            else wait_all(cur);
             __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0), as an instruction the compiler's own wait counting sees
             asm volatile("s_barrier" ::: "memory");     // tile kt+1 has landed for every wave; the stage of tile kt is free
             const bool more = nd < nkt;                 // (nd == kt + 1 + LOOK while there are tiles left)
@@ -755,6 +811,7 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
 #pragma unroll
             for (int i = 0; i < NM; ++i) {
                 mfma_one(cur, i);
+                if (DOP && i < ND) dload_one(nxt, i);
                 if (i < GR) {
 #pragma unroll
                     for (int r = i * RPG; r < (i + 1) * RPG && r < NR; ++r) read_one(nxt, S, r);
@@ -766,8 +823,12 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
             }
         };
         Frag f0, f1;
-        if (nkt > LOOK - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L * (LOOK - 1)) : "memory");
-        else                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (DOP) {                            // De / Do of tile 0 (behind x of tiles 0 and 1, which land with it)
+#pragma unroll
+            for (int q = 0; q < ND; ++q) dload_one(f0, q);
+            wait_all(f0);
+        } else if (nkt > LOOK - 1) wait_counted(f0);
+        else wait_all(f0);
         asm volatile("s_barrier" ::: "memory");
         if (LOOK < nkt) issue();
         // scalar loads of arguments the epilogue needs are still pending in the compiler's model here; with them pending it
@@ -775,11 +836,12 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
         __builtin_amdgcn_s_waitcnt(0xC07F);
         read_frag(f0);
         int kt = 0;                                     // nkt is even (M % 128 == 0, ksplit a power of two <= 8)
-        for (; kt + 2 < nkt; kt += 2) {
-            step(f0, f1, kt);
-            step(f1, f0, kt + 1);
+        for (; kt + 2 < nkt; kt += 2) {                 // (so kt + 1 + LOOK < nkt throughout: LOOK = 2 where DOP relies on it)
+            step(f0, f1, kt, Ahead{});
+            step(f1, f0, kt + 1, Ahead{});
         }
-        step(f0, f1, kt);
+        step(f0, f1, kt, Tail{});
+        if constexpr (DOP) wait_all(f1);                // De / Do of the last tile (its x fragments came through LDS)
         multiply(f1);
     } else {
         // all states in one workgroup: two fragment sets (2 x 56 registers) beside 96 accumulator registers would spill;
@@ -950,7 +1012,8 @@ __global__ __launch_bounds__(256) void emi_symdefect_combine_kernel(SymDefectArg
 #define EMI_PASS_OCC __attribute__((amdgpu_waves_per_eu(SW > 3 ? 1 : 2, 2)))
 #endif
 // KEEP: the node role leaves the model-invariant VALS rows as an earlier full pass wrote them (emi_nodes_body); the MFMA role is the same.
-template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool KEEP = false>
+// DOP: the MFMA role takes its De / Do fragments straight from L2 (emi_ring2_body); the node role is the same.
+template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool KEEP = false, bool DOP = false>
 __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(PassArgs a) {
 #ifdef EMI_ENTRY_PAD_NOPS      // build-time experiment (tools/ab_build.sh): shift the whole instruction stream by 4-byte steps
     asm volatile(".rept " EMI_STR(EMI_ENTRY_PAD_NOPS) "\n\ts_nop 0\n\t.endr" ::: "memory");
@@ -964,7 +1027,7 @@ __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(Pas
         // the MFMA role is the latency chain of a small pass (64 dependent K tiles); the streaming role beside it on the
         // same SIMDs waits on memory most of the time: instruction arbitration goes to the MFMA waves first
         __builtin_amdgcn_s_setprio(3);
-        emi_ring2_body<Model, SW, NST, BK, CT, HS>(a.s, tid);
+        emi_ring2_body<Model, SW, NST, BK, CT, HS, DOP>(a.s, tid);
     } else {
         // a.nn counts node chunks; a workgroup of HS x 256 threads takes HS neighbouring ones (a half that has none leaves:
         // barriers only count the waves still running)

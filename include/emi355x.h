@@ -1017,6 +1017,11 @@ int emi_debug_tile_order(int ns, int B, int M, int sym_ct, int sym_cpart, int* o
 /* ... the same with the grouped order's options "sym_gblk" / "sym_cx" (*cpart comes back negative, -gblk, when the plan takes it) */
 int emi_debug_tile_order2(int ns, int B, int M, int sym_ct, int sym_cpart, int sym_gblk, int sym_cx, int* out_tile, int out_cap,
                           int* ntiles_total, int* cpart, int* cx);
+/* Diagnostics, no device needed: De / Do of the M x M differentiation matrix D (exactly centro-antisymmetric, M a multiple of 128) in the
+ * order the MFMA role of the one-launch pass loads them straight into registers (the "sym_dop" 2 form; a context builds the same copy
+ * at emi_set_mesh).  out holds 2 (M/2)^2 doubles: pair (((ct*4 + w)*nkt + kt)*4 + q)*64 + lane, nkt = M/32, q = 2h + odd, lane = 16 kq + r16,
+ * is {P[64 ct + 16 w + r16][16 kt + 8 h + 2 kq], its right neighbour}, P = De (odd = 0) or Do (odd = 1).                           */
+int emi_debug_operator_fragments(int M, const double* D, double* out);
 /* Diagnostics, no device needed: how the one-launch pass deals an XCD's nm MFMA-role and nn node-role blocks ("pass_order":
  * 0 evenly interleaved, 1 MFMA blocks first, >= 100 interleaved at order / 100 times the even MFMA density).  out_role[j] =
  * MFMA block index (>= 0) or -1 - node block index; every index of either role must occur exactly once.                      */

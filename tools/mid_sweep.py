@@ -168,8 +168,11 @@ FORMS = {
     "one_sw1_g4c2": dict(overlap_mode=3, sym_ct=7, sym_gblk=4, sym_cx=2),
     "one_sw1_g4c4": dict(overlap_mode=3, sym_ct=7, sym_gblk=4, sym_cx=4),
     "one_sw3_cp4": dict(overlap_mode=3, sym_ct=8, sym_cpart=4),
+    # De / Do of the MFMA role through the operand ring (1) or straight from L2 (2), in whatever form the default dispatch takes; the role alone
+    "dop1": dict(sym_dop=1), "dop2": dict(sym_dop=2), "dop1_node_off": dict(sym_dop=1, sym_ablate=32), "dop2_node_off": dict(sym_dop=2, sym_ablate=32),
+    "dop1_node_off_epi_off": dict(sym_dop=1, sym_ablate=36), "dop2_node_off_epi_off": dict(sym_dop=2, sym_ablate=36),
 }
-RESET = dict(small_rows=24, overlap_mode=0, sym_ct=0, pass_order=-1, slice=0, node_store=-1, sym_cpart=0, sym_gblk=0, sym_cx=0, sym_nst=3, sym_ksplit=0, sym_ablate=0, sym_bk=0, sym_ctc=0, sym_hs=0)
+RESET = dict(small_rows=24, overlap_mode=0, sym_ct=0, pass_order=-1, slice=0, node_store=-1, sym_cpart=0, sym_gblk=0, sym_cx=0, sym_nst=3, sym_ksplit=0, sym_ablate=0, sym_bk=0, sym_ctc=0, sym_hs=0, sym_dop=0)
 
 
 def main():
