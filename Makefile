@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator check-plan-route
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -128,6 +128,13 @@ PLAN_CHECK_OUT ?= $(LIBDIR)/plan_route_check
 check-plan-route: tests/harness/plan_route_main.cpp $(CSRC)/emi_host.cpp $(CSRC)/emi_plan_route.hpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -ffp-contract=off -std=c++17 -Iinclude -o $(PLAN_CHECK_OUT) tests/harness/plan_route_main.cpp $(CSRC)/emi_host.cpp -lm
 	$(PLAN_CHECK_OUT) tests/golden/plan_cases.json
+
+# the launch policy of the fp64 evaluation pass (emi_pass_plan.hpp, host-only: form table, bands, resolve_form, plan_pass, plan_piece) as a
+# stand-alone program under the host sanitizers, over the grid of tools/api_identity.py plan
+PASS_PLAN_CHECK_OUT ?= $(LIBDIR)/pass_plan_check
+check-pass-plan: tests/harness/pass_plan_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_PLAN_CHECK_OUT) tests/harness/pass_plan_main.cpp
+	$(PASS_PLAN_CHECK_OUT)
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

@@ -1,195 +1,43 @@
-// emi_api_pass.hip -- the evaluation pass of the C ABI: the launch policy (plan_pass, plan_piece, choose_form: the ONE definition of
-// each), one function per launch form, emi_eval_* / emi_hess_*, the delayed values, and what reports the policy (emi_plan_pass,
-// emi_last_path, emi_last_defect_kernel, the emi_debug_* calls).
+// emi_api_pass.hip -- the evaluation pass of the C ABI: choose_form (the ONE place that picks among the launch forms, by the policy of
+// emi_pass_plan.hpp, which policy_in hands the context to), one function per launch form, emi_eval_* / emi_hess_*, the delayed values, and
+// what reports the policy (emi_plan_pass, emi_last_path, emi_last_defect_kernel, the emi_debug_* calls).
 #include "emi_ctx.hpp"
 
 using namespace emi_api;
 
 namespace {
 
-// the even/odd MFMA defect kernel beside the node kernel: needs an exactly centro-antisymmetric D
-bool overlapped_path(emi_ctx_t c) {
-    if (c->f32 || !c->allow_fused || !c->symmetric || c->M <= 0 || c->model < 0) return false;
-    if (c->model == EMI_MODEL_SOURCE) return emi::rtc_has_symdefect(c->rtc) && c->M % 128 == 0;
-    return emi::fused_supported(c->model, c->M, c->sym_ct);
-}
-
-// the one-launch pass in its small-batch form (SW = 1, plain stores) is available to this context by the default dispatch
-bool pass_takes_small_batches(emi_ctx_t c, int B) {
-    if (!overlapped_path(c) || (c->overlap_mode != 0 && c->overlap_mode != 3) || c->M % 128 != 0) return false;
-    if (c->rtc) return emi::rtc_pass_supported(c->rtc, B, c->M, 1, 1, 0);
-    const emi::SymPlan p = emi::plan_symdefect(c->ns, B, c->M, 7, 1, c->sym_cpart, c->sym_gblk, c->sym_cx);
-    return emi::pass_supported(c->model, c->ns, B, c->M, p);
-}
-
-// Result-store flavour of the node role for a launch of B instances ("node_store" forces it).  Non-temporal once a pass writes
-// about what the Infinity Cache holds (256 MB; RES + VALS above 230 MiB): measured on the one-launch pass, M = 1024
-// (profiles/r03_mid_sweep.json): 256 instances (244 MiB) 0.0581 ms against 0.0720 with plain stores, 320: 0.0749 / 0.0973,
-// 384: 0.0879 / 0.1050; 224 instances (214 MiB): plain 0.0557 / nt 0.0606, 128: 0.0338 / 0.0354.  (Round 2 switched at 300 MB of
-// VALS, i.e. above 384 instances: the 256 .. 384 band ran 20 % slow.)
-// Below that: write-through (sc1) stores for the built-in fp64 models since the end of round 4 -- plain stores leave a small pass's results
-// dirty in L2 for the write-back at the end of the kernel, write-through streams them out while the kernel runs.  One box, ms per pass plain /
-// sc1 (profiles/r04_mid_sweep_sc1_stores.jsonl): 1 instance 0.0125 / 0.0105, 16: 0.0149 / 0.0128, 32: 0.0176 / 0.0172, 64: 0.0209 / 0.0215,
-// 80: 0.0233 / 0.0221, 112: 0.0290 / 0.0283, 128: 0.0291 / 0.0286, 144: 0.0305 / 0.0296, 192: 0.0434 / 0.0430, 224: 0.0532 / 0.0505.
-// (Run-time compiled models hold a plain and a non-temporal instantiation only.)
-int store_mode_for(emi_ctx_t c, int B) {
-    if (c->node_store >= 0) return c->node_store;
-    if ((size_t)B * (nvals_of(c) + nres_of(c)) * c->M * (c->f32 ? 4 : 8) > ((size_t)230 << 20)) return 2;
-    // (17 .. 32 tiles -- 33 .. 64 instances at 1024 nodes, the two-slice band -- are the one place where plain stores stay ahead: 48 instances
-    // 0.0197 / 0.0203, 64: 0.0209 / 0.0215)
-    const int tiles16 = ((B + 15) / 16) * (c->M / 128);
-    if (tiles16 > 16 && tiles16 <= 32) return 0;
-    return (!c->rtc && !c->f32) ? 1 : 0;
-}
-
-// Everything the default dispatch decides about ONE launch of the evaluation pass as emi_pass_f64_kernel, in one place:
-// plan_pass() is what choose_form / form_pass_f64 launch by and what emi_plan_pass reports (tests and tools read the policy from the
-// library instead of restating it).
-struct PassPlan {
-    bool one_launch = false;    // the pass goes out as ONE launch (MFMA-role + node-role workgroups)
-    emi::SymPlan sym;           // MFMA role: states per workgroup, K slices per tile, ring stages, tile order
-    int tiles16 = 0;            // 16-instance x 128-node tiles of the launch (what the thresholds below are written in)
-    int store_mode = 0;         // node role: 0 plain, 1 sc1, 2 non-temporal, 3 nt sc1
-    int mfma_first = 0;         // block order (pass_role_of): 1 MFMA workgroups first, 0 evenly interleaved, >= 100: at that % of the even density
-};
-
-// The pass as ONE launch: MFMA-role and node-role workgroups in one grid, COST finished in-kernel -- since round 3 at EVERY
-// batch size (round 2: two streams between 384 and 767 instances, which ran 20 - 25 % under the rest).  One box, interleaved
-// rounds, M = 1024, ms per pass, best one-launch form against the round-2 choice (profiles/r03_mid_sweep.json): 256: 0.0581 /
-// 0.0731, 320: 0.0749 / 0.0927, 384: 0.0879 / 0.1177 (two streams), 448: 0.1035 / 0.1038, 512: 0.1188 / 0.1162, 576: 0.1332 /
-// 0.1777, 640: 0.146 / 0.155, 704: 0.160 / 0.181.
-//   * SW (states per MFMA workgroup): 1 below 128 sixteen-instance x 128-node tiles (more workgroups than CUs), else 2;
-//   * K slices per tile ("sym_ksplit"; partial sums combined in-kernel by ticket, in slice order).  By itself only where the MFMA
-//     role has fewer workgroups than the chip has places for them, i.e. where a pass waits for one 64-tile dependency chain per
-//     workgroup: 4 slices while that keeps the role within 256 workgroups, 2 within 512.  One box, M = 1024, ms per pass
-//     unsplit / 2 / 4 slices (tools/mid_sweep.py, profiles/r03_notes.md section 7): B = 8: 0.0204 / 0.0148 / 0.0140,
-//     16: 0.0235 / 0.0179 / 0.0155, 32: 0.0242 / 0.0190 / 0.0192, 64: 0.0257 / 0.0218 / 0.0261, 80: 0.0263 / 0.0249 / 0.0312,
-//     96: 0.0288 / 0.0290 / 0.0407, 128: 0.0333 / 0.0387 / 0.0496 (from ~500 workgroups the split loses: three and more MFMA
-//     waves per SIMD share the matrix pipe and the node role starts behind them);
-//   * block order (pass_role_of): MFMA workgroups first below 208 tiles (their 64-tile dependency chains start at once, the
-//     streaming workgroups fill in behind; since the end of round 4 only below 144 tiles: 1.5 x the even density from there, see
-//     deep_band below), at 1.25 x the even density up to 384 tiles, at 1.1 x up to 768, evenly interleaved
-//     from there (B >= 768, where "first" would hold the node role back: 0.288 against 0.222 at 1024).  (Round 2 measured
-//     "first" against "interleaved" WITH PLAIN STORES at 256 instances and found interleaved ahead, 0.0727 / 0.0748; with
-//     non-temporal stores "first" wins up to 448 instances: 256: 0.0581 against 0.0756 interleaved.  End of round 3, one box,
-//     e9 node-evals/s at first / 1.25 x / 1.5 x / even: 448 instances 4.21 / 4.41 / 4.22 / 4.31, 512: 3.60 / 4.32 / 4.38 / 4.22,
-//     640: 3.76 / 4.48 / 4.37 / 4.37, 704: 3.89 / 4.63 / 4.45 / 4.50; ms per pass at even / 1.1 x / 1.25 x: 768: 0.1747 /
-//     0.1696 / 0.1760, 896: 0.1964 / 0.1959 / 0.2022, 1024: 0.2230 / 0.2200 / 0.2304, 1536: 0.3215 / 0.3219 / 0.3411,
-//     2048: 0.4239 / 0.4227 / 0.4415);
-//   * tile order: grouped (an XCD's MFMA tiles and node workgroups walk the same instance groups together) for launches of more
-//     than 2048 instances in whole super-blocks, else column partitions by mesh size (plan_symdefect);
-//   * stores: store_mode_for (non-temporal from about 256 instances).
-// Every choice can be forced through emi_set_option (sym_ct, sym_ksplit, sym_cpart, sym_gblk, sym_cx, sym_nst, pass_order,
-// node_store); a run-time compiled model holds two instantiations of the pass kernel -- SW = 1 with plain stores (small batches)
-// and SW = 2 (1 for an odd number of states) with non-temporal stores (large ones) -- and is planned within those.
-PassPlan plan_pass(emi_ctx_t c, int B, bool jac) {
-    PassPlan p;
-    p.tiles16 = ((B + 15) / 16) * (c->M / 128);
-    p.store_mode = store_mode_for(c, B);
-    const bool auto_mode = c->overlap_mode == 0;
-    if (!((c->overlap_mode == 3 || auto_mode) && jac) || c->M % 128 != 0) return p;
-    const bool auto_ct = auto_mode && (c->sym_ct == 0 || c->sym_ct == 4);
-    const int gblk = (c->sym_gblk == 0 && c->sym_cpart == 0 && B > 2048 && B % 256 == 0) ? 2 : c->sym_gblk;
-    const int gblk_first = (auto_ct || c->rtc) ? gblk : c->sym_gblk;
-    int ct = c->sym_ct;                                  // 5 / 6 / 7 / 8 = SW NS / 2 / 1 / 3 (plan_symdefect)
-    // Round 4: between 64 and 127 tiles (128 .. 255 instances at 1024 nodes: the shard of config 4) two states per workgroup with K
-    // tiles of 16 -- half the barriers and counted waits of the MFMA role's dependency chain, which is what such a pass waits for.
-    // One box, ms per pass, SW = 1 / 8-deep (the round-3 choice) against SW = 2 / 16-deep (profiles/r04_mid_sweep.jsonl): 128 instances
-    // 0.0320 / 0.0300, 192: 0.0482 / 0.0442; at 64 instances the sliced SW = 1 form stays ahead (0.0210 / 0.0269), from 256 the 8-deep
-    // SW = 2 form (0.0548 / 0.0617).
-    // End of round 4 (profiles/r04_mid_sweep_small_72_120.jsonl, one box, ms per pass): the rule "2 K slices while the MFMA role stays within
-    // 512 workgroups" held up to 80 instances, where the finer sweep found 0.0324 ms against 0.0208 at 64 and 0.0277 at 96.  SW = 1 with 2
-    // slices / SW = 1 unsplit 8-deep / SW = 1 unsplit 16-deep / SW = 2 unsplit 16-deep: 72 instances 0.0323 / 0.0246 / 0.0231 / 0.0261, 80:
-    // 0.0324 / 0.0248 / 0.0234 / 0.0267, 96: 0.0363 / 0.0278 / 0.0266 / 0.0278, 112: 0.0411 / 0.0338 / 0.0335 / 0.0291.  So: above 32 tiles
-    // (64 instances) no slices any more; 33 .. 48 tiles one state per workgroup with 16-deep K tiles (deep_small), from 49 tiles two states
-    // (deep_mid, which began at 64 tiles).
-    const bool deep_base = auto_ct && !c->rtc && c->sym_bk == 0 && c->sym_ksplit == 0 && c->sym_nst == 3;
-    // (both for an even number of states above two, where they were measured: the 6-state quadrotor)
-    const bool deep_mid = deep_base && c->ns % 2 == 0 && c->ns > 2 && p.tiles16 >= 49 && p.tiles16 < 128;
-    const bool deep_small = deep_base && c->ns % 2 == 0 && c->ns > 2 && p.tiles16 >= 33 && p.tiles16 < 49;
-    if (c->rtc) ct = (p.store_mode == 2 && emi::rtc_pass_sw_large(c->rtc) == 2) ? 6 : 7;
-    else if (auto_ct) ct = (p.tiles16 < 128 && !deep_mid) ? 7 : 6;
-    emi::SymPlan plan = emi::plan_symdefect(c->ns, B, c->M, ct, 1, c->sym_cpart, gblk_first, c->sym_cx);
-    if (plan.ring1) plan = emi::plan_symdefect(c->ns, B, c->M, 5, 1, c->sym_cpart, c->sym_gblk, c->sym_cx);
-    int ks_want = c->sym_ksplit;
-    if (ks_want == 0 && auto_ct && !deep_mid && !deep_small) ks_want = plan.tiles * 4 <= 256 ? 4 : (plan.tiles * 2 <= 512 ? 2 : 1);
-    if (ks_want > 1) {
-        const int ct_now = plan.sw == c->ns ? 5 : (plan.sw == 2 ? 6 : (plan.sw == 3 ? 8 : 7));
-        plan = emi::plan_symdefect(c->ns, B, c->M, ct_now, ks_want, c->sym_cpart, c->rtc ? gblk : c->sym_gblk, c->sym_cx);
-    } else {
-        plan.ks = 1;
-    }
-    plan.nst = c->rtc ? 3 : c->sym_nst;
-    // K tiles of 16 (built-in models, SW 1 or 2, three stages, unsplit): "sym_bk" 16 forces them
-    // ... and between 208 and 767 tiles (416 .. 1535 instances, SW = 2 at 1.25 x / 1.1 x the even MFMA density): one box, ms per pass 8- /
-    // 16-deep, 448 instances 0.1112 / 0.1018, 512: 0.1226 / 0.1151, 576: 0.1351 / 0.1277, 640: 0.1492 / 0.1431, 768: 0.1675 / 0.1649,
-    // 896: 0.1921 / 0.1896, 1024: 0.2164 / 0.2143; not at 256 .. 384 instances (MFMA workgroups first: 320: 0.0752 / 0.0924) nor from 2048
-    // (0.4147 / 0.4205; 4096 in the grouped order 1.081 / 1.175)
-    // (up to 1024 tiles -- 2048 instances -- since the end of round 4: with the pass kernel's register allocation stated, 8- / 16-deep at 1536
-    // instances 0.3204 / 0.3117, 1792: 0.3725 / 0.3611, 2048: 0.4441 / 0.4322, profiles/r04_mid_sweep_1280_2048.jsonl)
-    const bool deep_large = auto_ct && !c->rtc && c->sym_bk == 0 && c->sym_nst == 3 && c->pass_order < 0 && p.tiles16 >= 208 && p.tiles16 <= 1024;
-    // ... and between 144 and 207 tiles (288 .. 415 instances) TOGETHER with the MFMA workgroups at 1.5 x the even density instead of all
-    // of them first: from ~300 instances the role's 3 x tiles workgroups no longer fit beside the node role (64 places per XCD), which then
-    // starts a workgroup generation late.  End of round 4, one box, ms per pass, first + 8-deep (the choice until then) / 1.5 x + 16-deep:
-    // 288 instances 0.0730 / 0.0699, 320: 0.0859 / 0.0754, 352: 0.1004 / 0.0820, 384: 0.1022 / 0.0875; 272: 0.0644 / 0.0698 (stays),
-    // 416 (1.25 x + 16-deep already): 0.0946 / 0.0951 (profiles/r04_mid_sweep_band_288_416.jsonl)
-    const bool deep_band = auto_ct && !c->rtc && c->sym_bk == 0 && c->sym_nst == 3 && c->pass_order < 0 && c->ns % 2 == 0 && c->ns > 2 &&
-                           p.tiles16 >= 144 && p.tiles16 < 208;
-    const int bk_want = c->sym_bk ? c->sym_bk : ((deep_mid || deep_small || deep_large || deep_band) ? 16 : 8);
-    if (bk_want == 16 && !c->rtc && plan.ks == 1 && (plan.sw == 1 || plan.sw == 2) && plan.nst == 3) plan.bk = 16;
-    // two column sub-tiles per MFMA workgroup ("sym_ctc" 2; built-in models, SW = 2, unsplit, three stages): the plan is made again with
-    // the wider tiles (tile counts and tile order change with the column width)
-    // By itself for launches of more than 2048 instances (the grouped tile order; inputs beyond the Infinity Cache, where every operand
-    // read is an HBM read): one box, ms per pass one / two sub-tiles, 4096 instances 1.181 / 1.101, 16384: 4.407 / 4.044 (3.81e9 -> 4.15e9
-    // node-evals/s) with column blocks of one 128-column tile; at 2048 instances 0.4736 / 0.4636, at 1024 and below the narrow form is ahead
-    // (0.2222 / 0.2425: the wide workgroups need 60 KB of LDS and 160 registers) (profiles/r04_mid_sweep.jsonl)
-    const bool wide_large = auto_ct && c->sym_ctc == 0 && B > 2048 && B % 256 == 0 && c->sym_cpart == 0;
-    const int ctc_want = c->sym_ctc ? c->sym_ctc : (wide_large ? 2 : 1);
-    if (ctc_want == 2 && !c->rtc && plan.ks == 1 && plan.sw == 2 && plan.nst == 3 && c->M % 256 == 0) {
-        const int bk_keep = plan.bk;
-        plan = emi::plan_symdefect(c->ns, B, c->M, 6, 1, c->sym_cpart, gblk_first, (wide_large && c->sym_cx == 0) ? 1 : c->sym_cx, bk_keep, 2);
-        plan.ks = 1;
-        plan.nst = 3;
-        plan.bk = bk_keep;
-    }
-    // the K range in two halves inside the workgroup ("sym_hs" 2; built-in models, SW 1 or 2, unsplit, one sub-tile, three stages)
-    const int hs_want = c->sym_hs ? c->sym_hs : 1;
-    if (hs_want == 2 && !c->rtc && plan.ks == 1 && plan.ct == 1 && (plan.sw == 1 || plan.sw == 2) && plan.nst == 3 &&
-        ((c->M / 2) / plan.bk) % 4 == 0)
-        plan.hs = 2;
-    // De / Do fragments straight from L2 into the MFMA waves' registers instead of through the operand ring ("sym_dop" 2; built-in models,
-    // SW 1 or 2 of more states, 16-deep K tiles, unsplit, one sub-tile, three stages; the context holds the fragment-order copy)
-    // By itself from 216 tiles (432 instances) through the range of deep_large.  One box, M = 1024, ms per pass through the ring / straight
-    // from L2 (tools/mid_sweep.py dop1,dop2; profiles/r06_mid_sweep_dop.jsonl): 432 instances 0.0903 / 0.0865, 512: 0.1002 / 0.0975, 768: 0.1446 /
-    // 0.1412, 1024: 0.1879 / 0.1836, 1536: 0.2790 / 0.2735, 2048: 0.3771 / 0.3671.  Below that neither form is ahead: the pass time moves with how
-    // the workgroups of the two roles fill the chip, not with the K loop (128: 0.0261 / 0.0262, 176: 0.0412 / 0.0392, 224: 0.0425 / 0.0434, 288:
-    // 0.0614 / 0.0631, 352: 0.0774 / 0.0714, 416: 0.0824 / 0.0835; SW = 1: 80 instances 0.0192 / 0.0208, 96: 0.0246 / 0.0240), so those stay.
-    const int dop_want = c->sym_dop ? c->sym_dop : ((deep_large && p.tiles16 >= 216) ? 2 : 1);
-    if (dop_want == 2 && !c->rtc && c->has_dfrag && plan.bk == 16 && plan.ks == 1 && plan.ct == 1 && plan.hs == 1 && plan.nst == 3 &&
-        plan.sw != c->ns && (plan.sw == 1 || plan.sw == 2))
-        plan.dop = true;
-    p.sym = plan;
-    p.mfma_first = c->pass_order >= 0 ? c->pass_order
-                                      : (deep_band ? 150 : (p.tiles16 < 208 ? 1 : (p.tiles16 < 384 ? 125 : (p.tiles16 < 768 ? 110 : 0))));
-    p.one_launch = c->rtc ? emi::rtc_pass_supported(c->rtc, B, c->M, plan.sw, plan.ks, p.store_mode)
-                          : emi::pass_supported(c->model, c->ns, B, c->M, plan);
-    return p;
-}
-
-// Large batches: the instances one launch of emi_eval_dev's default dispatch takes (0: the whole batch in one).  Round 2 cut
-// everything above 2048 instances into 1024-instance launches (the two-stream form drifted apart on long launches); with the pass
-// as ONE launch that buys nothing, and inputs of more than ~256 MB no longer stay in the Infinity Cache from one pass to the next,
-// which is what really slows a large batch (B = 16384: 3.47e9 node-evals/s sliced or not, profiles/r03_notes.md).  Now: one launch
-// over the whole batch in the GROUPED tile order: 4.10e9 /s at 16384 instances, 4.13e9 at 4096.  Pieces remain only where
-// something forces them: the "slice" option (> 0: pieces of that many instances once B > 2 slice), the 32-bit operand offsets of
-// the MFMA role (X of a launch below 4 GB), and a remainder that is not a multiple of 256 instances (the grouped order wants whole
-// super-blocks on every XCD) as a second launch.
-int plan_piece(emi_ctx_t c, int B) {
-    const long long cap = ((0xFFFFFFFFLL / ((long long)c->ns * c->M * 8)) / 256) * 256;     // instances whose X stays below 4 GB
-    int piece = 0;
-    if (c->slice > 0) { if (B > 2 * c->slice) piece = c->slice; }
-    else if (B > 2048) piece = (int)std::min<long long>(cap > 0 ? cap : 256, B - B % 256);
-    return piece >= B ? 0 : piece;
+// What the launch policy reads of a context (emi_pass_plan.hpp: plan_pass, plan_piece, store_mode_for, report_pass are pure functions of
+// this and the batch).  The one place where the policy meets emi_ctx_t.
+emi::PassPolicyIn policy_in(emi_ctx_t c) {
+    emi::PassPolicyIn in;
+    in.ns = c->ns;
+    in.M = c->M;
+    in.real_bytes = c->f32 ? 4 : 8;
+    in.rows = nres_of(c) + nvals_of(c);
+    if (c->model == EMI_MODEL_SOURCE) in.model_class = emi::rtc_has_symdefect(c->rtc) ? emi::PASS_MODEL_RTC : emi::PASS_MODEL_NONE;
+    else in.model_class = emi::pass_model_supported(c->model) ? emi::PASS_MODEL_BUILTIN : emi::PASS_MODEL_NONE;
+    in.rtc_sw_large = emi::rtc_pass_sw_large(c->rtc);
+    in.f32 = c->f32;
+    in.symmetric = c->symmetric;
+    in.has_dfrag = c->has_dfrag;
+    in.allow_fused = c->allow_fused;
+    in.overlap_mode = c->overlap_mode;
+    in.sym_ct = c->sym_ct;
+    in.sym_ksplit = c->sym_ksplit;
+    in.sym_cpart = c->sym_cpart;
+    in.sym_gblk = c->sym_gblk;
+    in.sym_cx = c->sym_cx;
+    in.sym_nst = c->sym_nst;
+    in.sym_hs = c->sym_hs;
+    in.sym_ctc = c->sym_ctc;
+    in.sym_bk = c->sym_bk;
+    in.sym_dop = c->sym_dop;
+    in.pass_order = c->pass_order;
+    in.node_store = c->node_store;
+    in.slice = c->slice;
+    in.small_rows = c->small_rows;
+    return in;
 }
 
 // One launch of the evaluation pass: instances [first, first + B) of the context's batch.  The whole batch as a rule; pieces of it
@@ -229,7 +77,7 @@ void fill_node_args(emi_ctx_t c, Launch L, emi::NodeArgs<T>& a, const PassIO& io
     a.ntracks = c->ntracks;
     a.px = c->px;
     a.py = c->py;
-    a.store_mode = store_mode_for(c, L.B);
+    a.store_mode = emi::store_mode_for(policy_in(c), L.B);
     a.keep = L.keep ? 1 : 0;
     a.h = (T)((c->tf - c->t0) / 2.0);
     a.sgn = c->maximize ? T(-1) : T(1);
@@ -313,20 +161,21 @@ enum class Form {
 struct FormChoice {
     Form form = Form::Sequential;
     bool small = false;     // Sequential: the skinny streaming defect kernel instead of the MFMA one
-    PassPlan plan;          // PassF64 (and TwoKernelF64, which it declined): what plan_pass decided
+    emi::PassPlan plan;     // PassF64 (and TwoKernelF64, which it declined): what plan_pass (emi_pass_plan.hpp) decided
     bool overlapped() const { return form == Form::PassF64 || form == Form::TwoKernelF64; }
 };
 
 FormChoice choose_form(emi_ctx_t c, Launch L, unsigned flags) {
     const bool nodes = flags & EMI_EVAL_NODES, defect = flags & EMI_EVAL_DEFECT, jac = !(flags & EMI_EVAL_NOJAC);
     FormChoice ch;
+    const emi::PassPolicyIn in = policy_in(c);
     // a handful of instances: the stand-alone MFMA kernels would have a few workgroups to run and a skinny streaming product wins
     // (21 us at B = 1) -- unless the whole pass can go as ONE launch with its K range sliced, which is faster still (13 - 15 us for
     // any batch up to 16 instances: profiles/r03_notes.md section 7)
-    ch.small = defect && !c->f32 && L.B > 0 && L.B * c->ns <= c->small_rows && emi::defect_small_supported(L.B * c->ns) &&
-               !(nodes && jac && pass_takes_small_batches(c, L.B));
-    if (nodes && defect && !ch.small && overlapped_path(c)) {
-        ch.plan = plan_pass(c, L.B, jac);
+    ch.small = defect && !c->f32 && L.B > 0 && L.B * c->ns <= in.small_rows && emi::defect_small_supported(L.B * c->ns) &&
+               !(nodes && jac && emi::pass_takes_small_batches(in));
+    if (nodes && defect && !ch.small && emi::pass_overlapped(in)) {
+        ch.plan = emi::plan_pass(in, L.B, jac);
         ch.form = ch.plan.one_launch ? Form::PassF64 : Form::TwoKernelF64;
     } else if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused) {
         if ((c->overlap_mode == 3 || (c->overlap_mode == 0 && c->f32_one_launch)) && emi::pass_f32_supported(c->model, L.B * c->ns, c->M, L.B))
@@ -407,7 +256,7 @@ emi::DefectArgsF32 defect_args_f32(emi_ctx_t c, Launch L, const PassIO& io) {
 
 // The fp64 pass as ONE launch, by the plan the chooser made: MFMA-role and node-role workgroups in one grid, K slices combined
 // and COST finished in-kernel by ticket.
-int form_pass_f64(emi_ctx_t c, Launch L, const PassIO& io, const PassPlan& pp, ProfEvents* pe) {
+int form_pass_f64(emi_ctx_t c, Launch L, const PassIO& io, const emi::PassPlan& pp, ProfEvents* pe) {
     const emi::SymPlan& plan = pp.sym;
     emi::SymDefectArgs sa = sym_defect_args(c, L, io);
     emi::NodeArgs<double> na;
@@ -665,9 +514,10 @@ int emi_eval_dev(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* 
     if (c->nch > 0 && dX && dU && (st = extend_controls(c, dX, dU, &dU))) return st;     // delayed values appended to the controls
     // large batches go out in pieces only where something forces them (plan_piece); not while per-kernel profiling is on
     int piece = 0;
-    if (!c->profile && !c->f32 && (flags & EMI_EVAL_ALL) == EMI_EVAL_ALL && overlapped_path(c) && dX && dU && dRES && dCOST &&
+    const emi::PassPolicyIn in = policy_in(c);
+    if (!c->profile && (flags & EMI_EVAL_ALL) == EMI_EVAL_ALL && emi::pass_overlapped(in) && dX && dU && dRES && dCOST &&
         (dVALS || (flags & EMI_EVAL_NOJAC)))
-        piece = plan_piece(c, c->B);
+        piece = emi::plan_piece(in, c->B);
     const PassIO io{dX, dU, dRES, dVALS, dCOST};
     // EMI_EVAL_KEEP_INVARIANT: honoured where this pass writes the Jacobian into the buffer the record names, under the generation
     // it was made in; any other Jacobian pass writes everything and renews the record -- once ALL its pieces are out.  Passes that
@@ -763,26 +613,7 @@ int emi_plan_pass(emi_ctx_t c, int B, emi_pass_plan_t* out) {
     if (!c || !out || B < 1) return EMI_ERR_ARG;
     if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "emi_plan_pass: mesh and model must be set");
     memset(out, 0, sizeof *out);
-    const int piece = (!c->f32 && overlapped_path(c)) ? plan_piece(c, B) : 0;
-    const int first = piece > 0 ? piece : B;    // instances of the first launch
-    out->piece = piece;
-    out->tail = piece > 0 ? B % piece : 0;
-    if (!c->f32 && overlapped_path(c)) {
-        const PassPlan p = plan_pass(c, first, true);
-        out->one_launch = p.one_launch ? 1 : 0;
-        out->sw = p.sym.sw;
-        out->ksplit = p.sym.ks;
-        out->ring_stages = p.sym.nst;
-        out->k_tile = p.sym.bk;
-        out->column_tiles = p.sym.ct;
-        out->k_halves = p.sym.hs;
-        out->cpart = p.sym.cpart;
-        out->cx = p.sym.cx;
-        out->mfma_workgroups = p.sym.tiles * p.sym.ks;
-        out->store_mode = p.store_mode;
-        out->block_order = p.mfma_first;
-        out->tiles16 = p.tiles16;
-    }
+    emi::report_pass(policy_in(c), B, out);
     return EMI_OK;
 }
 

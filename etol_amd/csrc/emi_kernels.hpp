@@ -8,12 +8,15 @@
 
 #include "emi355x.h"
 #include "emi_args.hpp"
+#include "emi_pass_plan.hpp"
 
 // emi_args.hpp repeats these for run-time compiled model programs
 static_assert(EMI_PATH_ELLIPSE == 0 && EMI_PATH_DISC == 1 && EMI_PATH_TRACK == 2 && EMI_PATH_REC == 8,
               "emi_args.hpp and emi355x.h disagree");
 
 namespace emi {
+
+static_assert(PASS_TI == FUSED_TI, "emi_pass_plan.hpp and emi_args.hpp disagree");
 
 int node_chunks(int M);
 bool invariant_rows(int model, int np, unsigned char* mask);    // [ns nv + 2 np + nv] bytes, 1 = row invariant; false: not a built-in model
@@ -33,22 +36,7 @@ hipError_t defect_f64_set_attr();
 template <typename T>
 hipError_t launch_cost_finish(const T* part, T* cost, int B, int nchunks, T scale, hipStream_t s);
 bool fused_supported(int model, int M, int ct);
-// which even/odd MFMA defect kernel a launch uses (emi_symdefect.hip, plan_symdefect)
-struct SymPlan {
-    bool ring1 = false;       // the one-workgroup-per-CU ring kernel / register-staged forms (sym_ct 1..3)
-    int sw = 0;               // state-split ring: states per workgroup
-    int ks = 1;               // ... and K slices per tile (> 1: partial sums through a slab, combined in-kernel by ticket or by a second launch)
-    int nst = 3;              // ring stages of the one-launch pass (3 or 4: K tiles in flight = nst - 1)
-    int bk = 8;               // depth of a K tile of the one-launch pass (8, or 16: SW 1 / 2 with three stages)
-    int hs = 1;               // 2: the K range of a tile in two halves inside a 512-thread workgroup, combined through LDS (SW 1 / 2, unsplit, one sub-tile)
-    int ct = 1;               // 64-column sub-tiles per MFMA workgroup of the one-launch pass (2: SW = 2, unsplit, M % 256 == 0)
-    bool dop = false;         // one-launch pass: the MFMA role's De / Do fragments straight from L2, not through the ring (SW 1 / 2, bk 16, unsplit,
-                              // one sub-tile, three stages; needs SymDefectArgs::Dfrag)
-    size_t slab_bytes = 0;
-    int cpart = 0, cx = 0;    // tile order (SymDefectArgs::cpart, cx): 0 = plain, > 0 column partitions, < 0 grouped (-G)
-    int tiles = 0;            // tiles of the launch (instance groups x column tiles x state groups): tickets of an in-kernel combine
-};
-SymPlan plan_symdefect(int ns, int B, int M, int ct, int ksplit_opt, int cpart_opt = 0, int gblk_opt = 0, int cx_opt = 0, int bk_opt = 8, int ct_cols = 1);
+// SymPlan (which even/odd MFMA defect kernel a launch uses) and plan_symdefect: emi_pass_plan.hpp
 hipError_t launch_symdefect(int model, const SymDefectArgs& a, hipStream_t s, bool set_attr, int ct, const SymPlan& plan);
 // The fragment-order copy of De / Do, for 16-deep K tiles and 64-column tiles: the 16 bytes lane `lane` of wave w loads as piece q of K tile
 // kt of column tile ct are double2 number (((ct*4 + w)*nkt + kt)*4 + q)*64 + lane, nkt = M/32, q = 2h + odd, lane = 16 kq + r16; they hold
@@ -68,8 +56,9 @@ inline void operator_fragments(int M, const double* De, const double* Do, double
                     }
 }
 
-// the whole pass as one launch (MFMA-role and node-role workgroups in one grid; COST finished in-kernel)
-bool pass_supported(int model, int ns, int B, int M, const SymPlan& plan);
+// the whole pass as one launch (MFMA-role and node-role workgroups in one grid; COST finished in-kernel), in the form of the plan: a row
+// of EMI_PASS_FORMS (emi_pass_plan.hpp), anything else is an error
+bool pass_model_supported(int model);
 hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& plan);
 
 // the adjoint pass (emi_adjoint.hip): Lagrangian gradient G[B][ns+nc][M] and the per-instance KKT certificate, fp64
@@ -205,7 +194,6 @@ hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t
 // the one-launch pass of a run-time compiled model: which state split it was compiled with for large batches (small ones take
 // SW = 1), whether (sw, store mode) is available, and the launch
 int rtc_pass_sw_large(const RtcModel* m);
-bool rtc_pass_supported(const RtcModel* m, int B, int M, int sw, int ks, int store_mode);
 hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s);
 hipError_t rtc_launch_nodes_nt(RtcModel* m, const NodeArgs<double>& a, hipStream_t s);   // vec2, Jacobian, no defect rows, non-temporal stores
 

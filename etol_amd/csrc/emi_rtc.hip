@@ -28,11 +28,10 @@ struct RtcModel {
     hipFunction_t hess = nullptr;
     hipFunction_t ode_resid = nullptr;   // ODE-error residual at the Gauss points (f64 programs)
     hipFunction_t ring = nullptr;        // even/odd MFMA defect kernel (f64, LDS permitting)
-    hipFunction_t pass_small = nullptr;  // the pass as one launch: SW = 1, plain stores (small batches)
-    hipFunction_t pass_large = nullptr;  //                          SW = sw_large, non-temporal stores (large batches)
+    hipFunction_t pass[N_PASS_FORMS_RTC] = {};   // the pass as one launch: the rows of EMI_PASS_FORMS_RTC (emi_pass_plan.hpp)
     hipFunction_t node_nt = nullptr;     // node kernel (vec2, Jacobian, no defect rows) with non-temporal stores
     bool f32 = false;
-    int ns = 0, nc = 0, sw_large = 0;
+    int ns = 0, nc = 0;
     size_t ring_lds = 0;
 };
 
@@ -50,9 +49,8 @@ size_t ring_lds_bytes(int ns) { return (size_t)3 * (2 * ns * FUSED_TI + 2 * 64) 
 bool ring_fits(int ns) { return ns <= 8 && ring_lds_bytes(ns) <= 160 * 1024; }
 
 struct Names {
-    std::string nodes[2][2][2], hess, ode_resid, ring, pass_small, pass_large, node_nt;
+    std::string nodes[2][2][2], hess, ode_resid, ring, pass[N_PASS_FORMS_RTC], node_nt;
 };
-int pass_sw_large(int ns) { return (ns % 2 == 0 && ns > 2) ? 2 : 1; }
 
 Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
     Names n;
@@ -67,8 +65,11 @@ Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
     if (!f32) n.ode_resid = "emi::emi_ode_resid_kernel<double, " + model + ">";
     if (with_ring) {
         n.ring = "emi::emi_symdefect_ring_f64_kernel<" + model + ">";
-        n.pass_small = "emi::emi_pass_f64_kernel<" + model + ", 1, 2, 0, 3>";
-        n.pass_large = "emi::emi_pass_f64_kernel<" + model + ", " + std::to_string(pass_sw_large(ns)) + ", 2, 2, 3>";
+        for (int i = 0; i < N_PASS_FORMS_RTC; ++i) {       // <Model, SW, 2, stores, ring stages>: the rows hold the plain form only
+            const PassForm& f = PASS_FORMS_RTC[i];
+            n.pass[i] = "emi::emi_pass_f64_kernel<" + model + ", " + std::to_string(pass_class_sw(f.cls, ns)) + ", 2, " + std::to_string(f.stores) + ", " +
+                        std::to_string(f.nst) + ">";
+        }
         n.node_nt = "emi::emi_nodes_kernel<double, " + model + ", 2, true, false, 2>";
     }
     return n;
@@ -114,8 +115,7 @@ int compile(bool f32, const char* sn, const char* source, int ns, int nc, int np
     if (!f32) order.push_back(&nm.ode_resid);
     if (with_ring) {
         order.push_back(&nm.ring);
-        order.push_back(&nm.pass_small);
-        order.push_back(&nm.pass_large);
+        for (const std::string& f : nm.pass) order.push_back(&f);
         order.push_back(&nm.node_nt);
     }
     for (const std::string* s : order) hiprtcAddNameExpression(p, s->c_str());
@@ -225,10 +225,8 @@ int rtc_build(bool f32, const char* struct_name, const char* source, int ns, int
     if (e == hipSuccess && ring) {
         e = hipModuleGetFunction(&m->ring, m->mod, low[i++].c_str());
         m->ring_lds = ring_lds_bytes(ns);
-        if (e == hipSuccess) e = hipModuleGetFunction(&m->pass_small, m->mod, low[i++].c_str());
-        if (e == hipSuccess) e = hipModuleGetFunction(&m->pass_large, m->mod, low[i++].c_str());
+        for (int k = 0; k < N_PASS_FORMS_RTC && e == hipSuccess; ++k) e = hipModuleGetFunction(&m->pass[k], m->mod, low[i++].c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m->node_nt, m->mod, low[i++].c_str());
-        m->sw_large = pass_sw_large(ns);
     }
     if (e != hipSuccess) {
         if (log) *log = std::string("loading the model code object failed: ") + hipGetErrorString(e);
@@ -274,16 +272,17 @@ hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t
     return launch(m->ring, dim3(mtiles * ntiles), dim3(256), m->ring_lds, s, &a, sizeof a);
 }
 
-int rtc_pass_sw_large(const RtcModel* m) { return m ? m->sw_large : 0; }
+int rtc_pass_sw_large(const RtcModel* m) { return m ? pass_class_sw(SWC_LARGE, m->ns) : 0; }
 
-// as pass_supported (emi_symdefect.hip) for the two instantiations a model program holds
-bool rtc_pass_supported(const RtcModel* m, int B, int M, int sw, int ks, int store_mode) {
-    if (!m || !m->pass_small || ks < 1 || M % 128 != 0) return false;       // (K slices are a run-time argument of the kernel)
-    if (!((sw == 1 && store_mode != 2) || (sw == m->sw_large && store_mode == 2))) return false;
-    return B >= 1 && m->ns % sw == 0;
-}
-
+// the row of EMI_PASS_FORMS_RTC for sw states per workgroup and the store flavour of na (plan_pass resolves to one; none is an error)
 hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s) {
+    PassShape shape;
+    shape.ns = m->ns;
+    shape.M = sa.M;
+    shape.model_class = PASS_MODEL_RTC;
+    shape.store_mode = na.store_mode;
+    const PassForm* f = find_form(shape, sw, sa.ksplit > 1, 3, 8, 1, 1, false);
+    if (!f || !m->pass[f - PASS_FORMS_RTC]) return hipErrorInvalidDeviceFunction;
     PassArgs a;
     a.s = sa;
     a.n = na;
@@ -295,8 +294,8 @@ hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<
     a.nn = nn;
     a.nm8 = (nm + 7) / 8;
     a.nn8 = (nn + 7) / 8;
-    const size_t lds = (size_t)3 * ((2 * sw * FUSED_TI + 2 * 64 + 63) / 64 * 64) * 8 * sizeof(double);     // 3 ring stages
-    return launch(na.store_mode == 2 ? m->pass_large : m->pass_small, dim3(8 * (a.nm8 + a.nn8)), dim3(256), lds, s, &a, sizeof a);
+    const size_t lds = (size_t)f->nst * ((2 * sw * FUSED_TI + 2 * 64 + 63) / 64 * 64) * f->bk * sizeof(double);     // the ring stages
+    return launch(m->pass[f - PASS_FORMS_RTC], dim3(8 * (a.nm8 + a.nn8)), dim3(256), lds, s, &a, sizeof a);
 }
 
 hipError_t rtc_launch_nodes_nt(RtcModel* m, const NodeArgs<double>& a, hipStream_t s) {

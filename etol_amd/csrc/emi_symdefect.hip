@@ -8,15 +8,20 @@
 //     De = (D[i][j] + D[i][N-j])/2, Do = (D[i][j] - D[i][N-j])/2 are built once on the host.
 //   * Epilogue: accumulator rows are ordered state-major inside a workgroup (row = state*16 +
 //     instance), so one lane holds all NS components of D.X for its (instance, node) pairs: it
-//     evaluates f there and writes  defect = D.X - h f  directly.  The kernel therefore depends
-//     only on X and U and runs CONCURRENTLY with the streaming node kernel (emi_kernels.hip) on a
-//     second HIP stream: the matrix pipe works under the ~1 KB/node of HBM stores.
-//     (Two single-kernel fusions were built and measured first -- node work inside this kernel's
-//     K loop, and MFMA / streaming workgroup roles in one launch.  Both lost to the two-stream
-//     form: all workgroups follow one schedule, so the chip alternates between all-MFMA and
-//     all-store phases; vmcnt retires in order, so an operand wait also waits for every older
-//     store; and a kernel that holds 96 accumulator registers caps the streaming waves at 2 per
-//     SIMD, which is too few to keep HBM busy.  profiles/r01_notes.md has the numbers.)
+//     evaluates f there and writes  defect = D.X - h f  directly.  The MFMA work therefore depends
+//     only on X and U and runs BESIDE the streaming node work (emi_kernels.hip), the matrix pipe
+//     under the ~1 KB/node of HBM stores.  By default the two go out as ONE launch at every batch
+//     size (emi_pass_f64_kernel, emi_symdefect_kernels.hpp): MFMA-role and node-role workgroups in
+//     one grid, dealt to the XCDs in the block order of the plan, K slices combined and COST finished
+//     in-kernel by ticket.  Which instantiation a launch takes is the form table of emi_pass_plan.hpp
+//     (EMI_PASS_FORMS), walked by launch_pass_planned below; the policy that picks it is plan_pass
+//     there.  The stand-alone kernels of this file -- the one-workgroup-per-CU ring, the register-staged
+//     forms and the state-split ring, concurrent with the node kernel on a second HIP stream or back to
+//     back on one -- remain behind "overlap_mode" 1 / 2 and for passes without a Jacobian.
+//     (Round 1 measured two single-kernel fusions against the two-stream form and both lost: node work
+//     inside the K loop, and roles that all followed one schedule, so that the chip alternated between
+//     all-MFMA and all-store phases; profiles/r01_notes.md has the numbers.  The one-launch pass of
+//     round 3 gives each role its own workgroups and register budget: profiles/r03_notes.md.)
 //
 // Workgroup = 256 threads = 4 waves; tile = 16 instances x 64*CT half-indices i (nodes i and N-i);
 // each wave owns NS x CT x 2 accumulator tiles (96*CT registers for 6 states), one workgroup per CU.  LDS: two buffers (register prefetch of the next K tile) of E,O [NS*16][18], De,Do
@@ -28,7 +33,6 @@
 // checks); every other shape takes the general defect kernel of emi_kernels.hip.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <type_traits>
 
 #include "emi_kernels.hpp"
@@ -91,65 +95,6 @@ static hipError_t launch_ring2_model(const SymDefectArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// The variant for a batch, by what was measured on MI355X with the node kernel running beside it
-// (profiles/r02_pass_variants.json; 6-state model, 1024 nodes; "tiles" = 16-instance x 64-half-index tiles):
-//   >= 448 tiles (B = 1024: 512): SW = 2 -- 78 registers and 36 KB of LDS per workgroup leave the streaming
-//      kernel's waves the room they need on every CU (pass 0.24-0.25 ms against 0.26-0.27 with 60 KB workgroup pairs);
-//   320 .. 447 tiles (B = 768): SW = NS, all workgroups resident at once, two per CU (0.172 ms against 0.198);
-//   192 .. 319 tiles (B = 512): the one-workgroup-per-CU ring kernel, whose grid is then a single round;
-//   fewer (the shard of config 4: 128 instances = 64 tiles for 256 CUs): SW = 1 (<= 96 tiles) or 2, i.e. more workgroups
-//      than CUs (0.055 ms at 128 instances; SW = NS with 4 K slices, the choice before the K loop was software-pipelined: 0.089).
-// ct 5 / 6 / 7 / 8 force SW = NS / 2 / 1 / 3; ksplit_opt > 0 forces the slice count.
-SymPlan plan_symdefect(int ns, int B, int M, int ct, int ksplit_opt, int cpart_opt, int gblk_opt, int cx_opt, int bk_opt, int ct_cols) {
-    SymPlan p;
-    p.bk = bk_opt == 16 ? 16 : 8;
-    const int tiles = ((B + FUSED_TI - 1) / FUSED_TI) * ((M / 2) / 64);    // in 64-column tiles: what the thresholds below are written in
-    const int nkt = (M / 2) / p.bk;
-    if (ct == 0 || ct == 4) {
-        if (tiles >= 448) p.sw = (ns % 2 == 0 && ns > 2) ? 2 : ns;
-        else if (tiles >= 320) p.sw = ns;
-        else if (tiles >= 192) { p.ring1 = true; return p; }
-        else p.sw = (tiles <= 96 || ns % 2 != 0 || ns <= 2) ? 1 : 2;
-    } else if (ct >= 5 && ct <= 8) {
-        p.sw = ct == 5 ? ns : (ct == 6 ? 2 : (ct == 8 ? 3 : 1));
-        if (ns % p.sw != 0) p.sw = 1;
-    } else {
-        p.ring1 = true;
-        return p;
-    }
-    if (ksplit_opt > 0) p.ks = ksplit_opt;
-    while (p.ks > 1 && (nkt % p.ks != 0 || nkt / p.ks < 2 || (nkt / p.ks) % 2 != 0)) p.ks >>= 1;
-    p.ct = (ct_cols == 2 && p.sw == 2 && p.ks == 1 && M % 256 == 0) ? 2 : 1;      // column sub-tiles per workgroup (one-launch pass, SW = 2, unsplit)
-    const int TNp = 64 * p.ct;
-    p.tiles = (tiles / p.ct) * (ns / p.sw);
-    {   // tile order: the share of De / Do an XCD works on should stay in its 4 MB L2 beside everything else (<= 2 MB)
-        const int ntiles = (M / 2) / TNp, ngrp = ((B + FUSED_TI - 1) / FUSED_TI) * (ns / p.sw);
-        const int target_cols = std::max(1, 4096 / M / p.ct);   // column tiles whose two panels (512 M bytes each per 64 columns) make 2 MB
-        auto valid = [&](int cp) { return cp >= 1 && cp <= 8 && ntiles % cp == 0 && ngrp % (8 / cp) == 0 && (ngrp * ntiles) % 8 == 0; };
-        int cp = 0;
-        if (cpart_opt > 0) cp = valid(cpart_opt) ? cpart_opt : 0;
-        else if (cpart_opt == 0 && tiles >= 192)    // (small batches: an XCD's few tiles do not walk the panels often enough to matter)
-            for (int c = 1; c <= 8 && !cp; c *= 2)
-                if (valid(c) && (ntiles / c <= target_cols || c == 8 || !valid(2 * c))) cp = c;
-        const int mtiles = (B + FUSED_TI - 1) / FUSED_TI;
-        if (gblk_opt > 0 && mtiles % (8 * gblk_opt) == 0 && (ngrp * ntiles) % 8 == 0) {
-            // grouped order ("sym_gblk"): super-blocks of gblk instance groups per XCD, column blocks of cx tiles
-            int cxg = cx_opt > 0 ? cx_opt : 2;
-            while (cxg > 1 && ntiles % cxg != 0) --cxg;
-            p.cpart = -gblk_opt;
-            p.cx = cxg;
-        } else if (cp > 0) {
-            p.cpart = cp;
-            p.cx = 1;                                            // largest divisor of the partition's column count within the target
-            for (int d = 1; d <= std::min(ntiles / cp, target_cols); ++d)
-                if ((ntiles / cp) % d == 0) p.cx = d;
-            if (cp == 1 && p.cx == ntiles) p.cpart = p.cx = 0;   // that is the plain order
-        }
-    }
-    if (p.ks > 1) p.slab_bytes = (size_t)p.tiles * p.ks * (2 * p.sw * 4) * 256 * sizeof(double);
-    return p;
-}
-
 template <class Model>
 static hipError_t launch_ring2_planned(const SymDefectArgs& a, hipStream_t s, const SymPlan& p) {
     constexpr int NS = Model::NS;
@@ -208,35 +153,23 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     return hipGetLastError();
 }
 
+// The form of the plan, by walking the form table (EMI_PASS_FORMS, emi_pass_plan.hpp): a row is instantiated here and nowhere else, for the
+// models its SW class applies to.  plan_pass resolves every plan to a row; a plan that names none is an error, not another kernel.
 template <class Model>
 static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p) {
     constexpr int NS = Model::NS;
-    if (p.sw == NS) return launch_pass_model<Model, NS, 3>(sa, na, s);
-    if constexpr (NS > 2 && NS % 2 == 0) {
-        if (p.sw == 2 && p.hs == 2 && p.ct == 1) return p.bk == 16 ? launch_pass_model<Model, 2, 3, 16, 1, 2>(sa, na, s) : launch_pass_model<Model, 2, 3, 8, 1, 2>(sa, na, s);
-        if (p.sw == 2 && p.ct == 2) return p.bk == 16 ? launch_pass_model<Model, 2, 3, 16, 2>(sa, na, s) : launch_pass_model<Model, 2, 3, 8, 2>(sa, na, s);
-        if (p.sw == 2 && p.bk == 16 && p.dop) return launch_pass_model<Model, 2, 3, 16, 1, 1, true>(sa, na, s);
-        if (p.sw == 2 && p.bk == 16) return launch_pass_model<Model, 2, 3, 16>(sa, na, s);
-        if (p.sw == 2) return p.nst > 3 ? launch_pass_model<Model, 2, 4>(sa, na, s) : launch_pass_model<Model, 2, 3>(sa, na, s);
+#define EMI_PASS_FORM_LAUNCH(CLS, NST, BK, CT, HS, DOP, SLICES, STORES)                                                                   \
+    if constexpr (pass_class_applies(CLS, NS)) {                                                                                          \
+        if (p.sw == pass_class_sw(CLS, NS) && p.nst == NST && p.bk == BK && p.ct == CT && p.hs == HS && p.dop == DOP && (SLICES || p.ks == 1)) \
+            return launch_pass_model<Model, pass_class_sw(CLS, NS), NST, BK, CT, HS, DOP>(sa, na, s);                                    \
     }
-    if constexpr (NS > 3 && NS % 3 == 0) {
-        if (p.sw == 3) return launch_pass_model<Model, 3, 3>(sa, na, s);
-    }
-    if (p.hs == 2) return p.bk == 16 ? launch_pass_model<Model, 1, 3, 16, 1, 2>(sa, na, s) : launch_pass_model<Model, 1, 3, 8, 1, 2>(sa, na, s);
-    if (p.bk == 16 && p.dop) return launch_pass_model<Model, 1, 3, 16, 1, 1, true>(sa, na, s);
-    if (p.bk == 16) return launch_pass_model<Model, 1, 3, 16>(sa, na, s);
-    return p.nst > 3 ? launch_pass_model<Model, 1, 4>(sa, na, s) : launch_pass_model<Model, 1, 3>(sa, na, s);
+    EMI_PASS_FORMS(EMI_PASS_FORM_LAUNCH)
+#undef EMI_PASS_FORM_LAUNCH
+    return hipErrorInvalidValue;
 }
 
-// true if the pass can go out as one launch with this plan (state-split ring role, K slices combined in-kernel by
-// ticket, whole XCD shares)
-bool pass_supported(int model, int ns, int B, int M, const SymPlan& p) {
-    if (p.ring1 || p.sw < 1 || (model != EMI_MODEL_POINTMASS2D && model != EMI_MODEL_QUADROTOR2D)) return false;
-    if (M % 128 != 0 || ns % p.sw != 0) return false;
-    // (De / Do from L2: the unsplit 16-deep form of one or two states per workgroup, one sub-tile, three stages)
-    if (p.dop && !(p.bk == 16 && p.ks == 1 && p.ct == 1 && p.hs == 1 && p.nst == 3 && p.sw != ns && (p.sw == 1 || p.sw == 2))) return false;
-    return B >= 1;
-}
+// the built-in models the pass kernels (and the even/odd MFMA defect kernels) are instantiated for
+bool pass_model_supported(int model) { return model == EMI_MODEL_POINTMASS2D || model == EMI_MODEL_QUADROTOR2D; }
 
 hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p) {
     if (model == EMI_MODEL_POINTMASS2D) return launch_pass_planned<PointMass2D<double>>(sa, na, s, p);
@@ -245,11 +178,7 @@ hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double
 }
 
 bool fused_supported(int model, int M, int ct) {
-    if (ct == 0 || (ct >= 4 && ct <= 8))
-        return (model == EMI_MODEL_POINTMASS2D || model == EMI_MODEL_QUADROTOR2D) && M >= 128 && M % 128 == 0;
-    const int w = ct == 2 ? 2 : 1;     // ct == 3 is the ring variant of the 64-column tiling
-    return (model == EMI_MODEL_POINTMASS2D || model == EMI_MODEL_QUADROTOR2D) && ct >= 1 && ct <= 3 &&
-           M >= 128 * w && M % (128 * w) == 0;
+    return pass_model_supported(model) && symdefect_shape_ok(M, ct);
 }
 
 hipError_t launch_symdefect(int model, const SymDefectArgs& a, hipStream_t s, bool set_attr, int ct, const SymPlan& plan) {

@@ -817,7 +817,8 @@ int emi_ipm_keep_host(emi_ctx_t ctx, const emi_ipm_point_t* pt, const emi_ipm_du
 
 /* What emi_eval_dev's default dispatch would do with a batch of B instances on this
  * context (mesh, model, options as set): the one definition of the launch policy,
- * for reports, tools and tests (csrc/emi_api_pass.hip: plan_pass, plan_piece).      */
+ * for reports, tools and tests (csrc/emi_pass_plan.hpp: plan_pass, plan_piece; the
+ * form fields are those of the kernel that is launched).                            */
 typedef struct emi_pass_plan {
   int one_launch;      /* 1: the pass goes out as ONE launch (emi_pass_f64_kernel: MFMA-role + node-role workgroups) */
   int sw;              /* states per MFMA workgroup */

@@ -6,6 +6,7 @@ import pytest
 
 import cases
 import oracle_lib as O
+from pinned_plans import PINNED_PLANS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -932,20 +933,89 @@ def test_mfma_defect_kernel_variants_for_the_two_state_model(built, sym_ct):
     ev.close()
 
 
+def _pass_form_rows():
+    """the rows of the built-in form table, read from the list the library instantiates and dispatches by (EMI_PASS_FORMS)"""
+    import re
+    text = open(os.path.join(ROOT, "etol_amd", "csrc", "emi_pass_plan.hpp")).read()
+    body = text[text.index("#define EMI_PASS_FORMS(X)"):text.index("#define EMI_PASS_FORMS_RTC(X)")]
+    rows = re.findall(r"X\(SWC_(\w+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false), -1\)", body)
+    assert len(rows) == 16 and len(set(rows)) == 16, rows
+    return [dict(cls=c, nst=int(nst), bk=int(bk), ct=int(ct), hs=int(hs), dop=dop == "true", slices=sl == "true") for c, nst, bk, ct, hs, dop, sl in rows]
+
+
+@pytest.mark.parametrize("model", ["pointmass2", "quadrotor6"])
+def test_every_row_of_the_pass_form_table_is_reached_and_matches_the_oracle(built, model):
+    """Every instantiation of emi_pass_f64_kernel the library holds for a built-in model (the rows of EMI_PASS_FORMS, for the models their SW
+    class applies to), reached through options as one launch: 17 instances (a full instance group and a ragged one) on 128 nodes (256 for
+    the rows with two column sub-tiles), and 5 instances with two K slices for the rows that allow slices, ellipse rows present.  The
+    outputs are poisoned first and held to the CPU oracle at the bounds of test_eval_matches_oracle; emi_plan_pass must report the row
+    asked for and emi_last_defect_kernel carry its name."""
+    import torch
+    import etol_amd as E
+    ns = 2 if model == "pointmass2" else 6
+    applies = dict(NS=True, **{"1": True, "2": ns > 2 and ns % 2 == 0, "3": ns > 3 and ns % 3 == 0})
+    rows = [r for r in _pass_form_rows() if applies[r["cls"]]]
+    assert len(rows) == (7 if ns == 2 else 16)
+    reached = 0
+    for M in (128, 256):
+        mine = [r for r in rows if (r["ct"] == 2) == (M == 256)]
+        for B, ks in ((17, 1), (5, 2)):
+            todo = [r for r in mine if ks == 1 or r["slices"]]
+            if not todo:
+                continue
+            ev = E.Evaluator(0)
+            if ns == 2:
+                ev.set_mesh(M, 0.0, 16.0)
+                ev.set_model(E.MODEL_POINTMASS2D, [])
+                ev.set_batch(B)
+                X, U = cases.W.pointmass_batch(5, B, M)
+                recs, tx, ty = cases.ocp2d_tables(E.edge_ellipse, E.track_centres, ev.node_t)
+                ev.set_tracks(tx, ty)
+                ev.set_path(recs, 0, 1)
+                ref = O.evaluate(E.MODEL_POINTMASS2D, [], M, (ev.tau, ev.w, ev.D), 0.0, 16.0, X, U, recs, (tx, ty))
+            else:
+                ev.set_mesh(M, 0.0, 9.0)
+                ev.set_model(E.MODEL_QUADROTOR2D, cases.W.QUAD_PARAMS)
+                ev.set_batch(B)
+                X, U, recs = cases.W.quadrotor_batch(21, B, M, 3)
+                ev.set_path(recs[:1], 0, 1)
+                ref = O.evaluate(E.MODEL_QUADROTOR2D, cases.W.QUAD_PARAMS, M, (ev.tau, ev.w, ev.D), 0.0, 9.0, X, U, recs[:1])
+            dX, dU = torch.from_numpy(X).cuda(), torch.from_numpy(U).cuda()
+            outs = ev.alloc_outputs()
+            ev.set_option("overlap_mode", 3)
+            for r in todo:
+                sw = ns if r["cls"] == "NS" else int(r["cls"])
+                for opt, v in (("sym_ct", dict(NS=5, **{"2": 6, "3": 8, "1": 7})[r["cls"]]), ("sym_ksplit", ks), ("sym_nst", r["nst"]), ("sym_bk", r["bk"]),
+                               ("sym_ctc", r["ct"]), ("sym_hs", r["hs"]), ("sym_dop", 2 if r["dop"] else 1)):
+                    ev.set_option(opt, v)
+                plan = ev.plan(B)
+                want = dict(one_launch=1, sw=sw, ksplit=ks, ring_stages=r["nst"], k_tile=r["bk"], column_tiles=r["ct"], k_halves=r["hs"], piece=0)
+                assert {k: plan[k] for k in want} == want, (r, B, plan)
+                for t in outs:
+                    t.fill_(float("nan"))
+                torch.cuda.synchronize()                 # (the fills run on torch's stream, the evaluator launches on its own)
+                ev.eval_dev(dX, dU, *outs)
+                ev.synchronize()
+                name = (f"emi_pass_f64_kernel<SW={sw}> (MFMA + node roles, one launch" + (f", {ks} K slices per tile" if ks > 1 else "") + ")" +
+                        (" [K tiles of 16]" if r["bk"] == 16 else "") + (" [128-column tiles]" if r["ct"] == 2 else "") +
+                        (" [K range in two halves per workgroup]" if r["hs"] == 2 else "") + (" [De/Do from L2]" if r["dop"] else ""))
+                assert ev.last_defect_kernel == name, (r, B, ev.last_defect_kernel)
+                got = [t.cpu().numpy() for t in outs]
+                assert not any(np.isnan(g).any() for g in got), (r, B)          # every row of every instance was written
+                check(dict(X=X), ev, got, ref)
+                reached += 1
+            ev.close()
+    assert reached == len(rows) + sum(r["slices"] for r in rows)
+
+
 def _expected_default_form(ev, B):
     """The name emi_eval_dev reports for the LAST launch of a batch of B instances, from the library's own statement of its
-    launch policy (emi_plan_pass: csrc/emi_api_pass.hip plan_pass / plan_piece are the one definition; nothing is restated here)."""
+    launch policy (emi_plan_pass: csrc/emi_pass_plan.hpp plan_pass / plan_piece are the one definition; nothing is restated here)."""
     p = ev.plan(B)
     last = p["tail"] if p["tail"] else (p["piece"] if p["piece"] else B)
     q = ev.plan(last)
     assert q["one_launch"] == 1 and q["piece"] == 0
     return (f"emi_pass_f64_kernel<SW={q['sw']}> (MFMA + node roles, one launch" + (f", {q['ksplit']} K slices" if q["ksplit"] > 1 else ")")), q
-
-
-# the shapes the benchmark lines and the profiles quote, pinned: a policy change has to be made here as well as in plan_pass
-PINNED_PLANS = {128: dict(sw=2, ksplit=1, k_tile=16, store_mode=1, block_order=1, piece=0), 1024: dict(sw=2, ksplit=1, k_tile=16, store_mode=2, piece=0),
-                16: dict(sw=1, ksplit=4), 64: dict(sw=1, ksplit=2), 80: dict(sw=1, ksplit=1, k_tile=16), 112: dict(sw=2, ksplit=1, k_tile=16),
-                320: dict(sw=2, ksplit=1, k_tile=16, block_order=150), 4096: dict(sw=2, k_tile=8, column_tiles=2, store_mode=2, piece=0), 256: dict(sw=2, k_tile=8), 512: dict(sw=2, k_tile=16)}
 
 
 @pytest.mark.parametrize("B", [1, 3, 5, 16, 64, 80, 112, 128, 256, 320, 512, 1024, 2064, 2560, 4096])

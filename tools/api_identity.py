@@ -11,24 +11,27 @@ commit's and the changed one, each with its own built library -- and compare wha
                                                    with err and out) and of the moving-disc ladder and refinement of
                                                    tests/track_ladder_ref.py, default options, each with the context the call left:
                                                    what a change behind an option that is off, or to the drivers, must keep
-   python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case
+   python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case ("report_only": the cases
+                                                   that differ in REPORT_ONLY fields alone, see there)
 
 The library is the one of the tree the script lies in."""
 import hashlib
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-# every threshold of plan_pass / plan_piece: 16-instance x 128-node tiles (last below, first above), then instances
+# every threshold of plan_pass / plan_piece (csrc/emi_pass_plan.hpp): 16-instance x 128-node tiles (last below, first above), then instances.
+# tests/harness/pass_plan_main.cpp walks the same grid without a device (tests/test_pass_plan_cpu.py holds its case names to plan_cases()).
 TILE_STEPS = [(32, 33), (48, 49), (127, 128), (143, 144), (207, 208), (383, 384), (767, 768), (1024, 1025)]
 INSTANCES = [1, 16, 64, 2048, 2049, 4096, 16384]
 FORCED = {"sym_ct": range(0, 9), "sym_ksplit": (0, 1, 2, 4, 8), "sym_bk": (0, 8, 16), "sym_ctc": (0, 1, 2), "sym_hs": (0, 1, 2),
           "sym_nst": (3, 4), "sym_cpart": (-1, 0, 1, 2, 4, 8), "sym_gblk": (0, 1, 2, 4, 8, 64), "pass_order": (-1, 0, 1, 100, 125, 150),
-          "node_store": (-1, 0, 1, 2, 3), "overlap_mode": (0, 1, 2, 3), "slice": (0, 16, 256, 1024)}
+          "node_store": (-1, 0, 1, 2, 3), "overlap_mode": (0, 1, 2, 3), "slice": (0, 16, 256, 1024), "sym_dop": (0, 1, 2), "sym_cx": (0, 1, 2)}
 DEFAULTS = {"sym_nst": 3, "sym_cpart": 0, "pass_order": -1, "node_store": -1}
 
 
@@ -40,14 +43,28 @@ def batches(M):
     return sorted((b for b in out if b >= 1), reverse=True)        # (descending: the context's buffers are sized once)
 
 
+# the models of the plan grid by their number of states: which forms exist goes by it (the 2-state model's SW = 2 is all its states)
+PLAN_MODELS = {2: "pointmass2", 6: "quadrotor6", 12: "fixedwing12"}
+PLAN_MESHES = (128, 256, 1024)
+
+
+def plan_cases(ns_axis=tuple(PLAN_MODELS)):
+    """the grid as (case name, ns, M, option, value, B), in the order plan_grid walks it"""
+    for ns in ns_axis:
+        for M in PLAN_MESHES:
+            for opt, value in [(None, None)] + [(o, v) for o, vs in FORCED.items() for v in vs]:
+                for B in batches(M):
+                    yield f"{PLAN_MODELS[ns]} M={M} {opt}={value} B={B}", ns, M, opt, value, B
+
+
 def plan_grid():
     import etol_amd as E
     from etol_amd import workloads as W
     models = {"pointmass2": (E.MODEL_POINTMASS2D, ()), "quadrotor6": (E.MODEL_QUADROTOR2D, W.QUAD_PARAMS),
               "fixedwing12": (E.MODEL_FIXEDWING12, W.FW_PARAMS)}
     out = {}
-    for mname, (model, params) in models.items():
-        for M in (128, 256, 1024):
+    for mname, (model, params) in ((PLAN_MODELS[ns], models[PLAN_MODELS[ns]]) for ns in PLAN_MODELS):
+        for M in PLAN_MESHES:
             ev = E.Evaluator(0)
             ev.set_mesh(M, 0.0, 2.0)
             ev.set_model(model, params)
@@ -85,6 +102,8 @@ CASES = {
     "pass 128-column tiles": dict(Q, B=64, opts=dict(sym_ct=6, sym_ksplit=1, sym_ctc=2)),
     "pass halved K": dict(Q, B=64, opts=dict(sym_ksplit=1, sym_hs=2)),
     "pass pointmass": dict(model="pm", M=256, B=16), "pass one instance": dict(Q, B=1),
+    # (all the states of the 2-state model in one workgroup, in the range where two states of a larger model take 16-deep K tiles)
+    "pass pointmass 1024": dict(model="pm", M=1024, B=1024),
     # fp64, two kernels
     **{f"two kernels mode {m} combine {sc} cost_in_kernel {ck}": dict(Q, B=32, opts=dict(overlap_mode=m, sym_ct=7, sym_ksplit=2, sym_combine=sc,
                                                                                          cost_in_kernel=ck))
@@ -342,8 +361,26 @@ def lockstep():
     return out
 
 
+# what may differ between two trees where one of them REPORTED a feature of the MFMA role that it has no kernel for and launched the
+# plain form (SW = all the states, or 3): the depth of a K tile, the K halves, the ring stages, the column sub-tiles (and with them
+# the workgroup count) and the kernel's name -- never what is launched or computed
+REPORT_ONLY = ("k_tile", "k_halves", "ring_stages", "column_tiles", "mfma_workgroups", "kernel")
+
+
+def report_only(name, a, b):
+    """a and b differ in REPORT_ONLY fields alone; for a plan, in a case whose SW is all the states of its model, or 3"""
+    def strip(d):
+        return {k: strip(v) for k, v in d.items() if k not in REPORT_ONLY} if isinstance(d, dict) else d
+    if not (isinstance(a, dict) and isinstance(b, dict)) or strip(a) != strip(b):
+        return False
+    if "sw" in a:
+        ns = {v: k for k, v in PLAN_MODELS.items()}[name.split()[0]]
+        return a["sw"] == b["sw"] and a["sw"] in (ns, 3)
+    return True
+
+
 def compare(pa, br):
-    report = dict(equal=[], different=[], self_disagreeing=[])
+    report = dict(equal=[], different=[], self_disagreeing=[], report_only=[])
     for name in sorted(set(pa) | set(br)):
         a, b = pa.get(name), br.get(name)
         unstable = isinstance(a, dict) and "repeats" in a and len(set(a["repeats"]) | {a["eval_dev"]["RES"]}) > 1
@@ -355,10 +392,39 @@ def compare(pa, br):
                 report["different"].append(name)
         elif a == b:
             report["equal"].append(name)
+        elif report_only(name, a, b):
+            report["report_only"].append(name)
         else:
             report["different"].append(name)
     report["verdict"] = "identical" if not report["different"] else "DIFFERENT"
     return report
+
+
+def changes(pa, br):
+    """the cases that are not equal, by what changed in them ({field: [parent, branch]}, nested fields by their path); the case names of
+    a plan grid ("model M=.. option=value B=..") gathered by model, mesh and batch sizes"""
+    def leaves(d, at=""):
+        return {k: v for key, val in d.items() for k, v in leaves(val, f"{at}{key}.").items()} if isinstance(d, dict) else {at[:-1]: d}
+    kinds = {}
+    for name in sorted(set(pa) | set(br)):
+        a, b = leaves(pa.get(name, {})), leaves(br.get(name, {}))
+        if a != b:
+            changed = json.dumps({k: [a.get(k), b.get(k)] for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)})
+            kind = kinds.setdefault(changed, dict(changed=json.loads(changed), n=0, cases={}))
+            kind["n"] += 1
+            if name.count(" ") == 3 and " B=" in name:
+                model, M, opt, B = name.split()
+                kind["cases"].setdefault(f"{model} {M}", {}).setdefault(opt, []).append(int(B[2:]))
+            else:
+                kind["cases"][name] = 1
+    for kind in kinds.values():         # options with the same batches together: {model M=..: [{B: [...], options: [...]}]}
+        for group, opts in kind["cases"].items():
+            if isinstance(opts, dict):
+                same = {}
+                for opt, bs in opts.items():
+                    same.setdefault(tuple(bs), []).append(opt)
+                kind["cases"][group] = [dict(B=sorted(bs), options=o) for bs, o in same.items()]
+    return list(kinds.values())
 
 
 if __name__ == "__main__":
@@ -368,7 +434,12 @@ if __name__ == "__main__":
         rep = compare(pa, br)
         print(json.dumps({k: (v if k == "verdict" or k == "self_disagreeing" else len(v)) for k, v in rep.items()} | {"different": rep["different"][:20]}))
         if len(sys.argv) > 4:
-            json.dump(dict(rep, cases={k: dict(parent=pa.get(k), branch=br.get(k)) for k in sorted(set(pa) | set(br))}), open(sys.argv[4], "w"), indent=1)
+            sha = lambda d: hashlib.sha256(json.dumps(d, sort_keys=True).encode()).hexdigest()
+            text = json.dumps(dict(rep, equal=len(rep["equal"]), report_only=len(rep["report_only"]), sha256=dict(parent=sha(pa), branch=sha(br)),
+                           changes=changes(pa, br)), indent=1)
+            for flat in (r"\[\s+([^][{}]*?)\s+\]", r"\{\s+([^{}]*?)\s+\}"):       # lists of numbers and names, then flat objects, on one line each
+                text = re.sub(flat, lambda m: m.group(0)[0] + " ".join(m.group(1).split()) + m.group(0)[-1], text)
+            open(sys.argv[4], "w").write(text + "\n")
         sys.exit(0 if rep["verdict"] == "identical" else 1)
     res = plan_grid() if mode == "plan" else times() if mode == "times" else lockstep() if mode == "lockstep" else {name: run_case(c) for name, c in CASES.items()}
     json.dump(res, open(sys.argv[2], "w"), indent=1 if mode != "plan" else None, sort_keys=True)
