@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -92,6 +92,14 @@ check-refine-book: tests/harness/refine_book_main.cpp $(CSRC)/emi_refine_book.hp
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Iinclude -I$(CSRC) -o $(BOOK_CHECK_OUT) \
 		tests/harness/refine_book_main.cpp $(CSRC)/emi_host.cpp -lm
 	$(BOOK_CHECK_OUT)
+
+# the bookkeeping of the ladder restarts (emi_restart_book.hpp over emi_refine_book.hpp, host-only: who is pending, which attempt owns
+# an instance's output, the drop rule) as a stand-alone program under the host sanitizers, with scripted statuses and estimates
+RESTART_CHECK_OUT ?= $(LIBDIR)/restart_book_check
+check-restart-book: tests/harness/restart_book_main.cpp $(CSRC)/emi_restart_book.hpp $(CSRC)/emi_refine_book.hpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Iinclude -I$(CSRC) -o $(RESTART_CHECK_OUT) \
+		tests/harness/restart_book_main.cpp $(CSRC)/emi_host.cpp -lm
+	$(RESTART_CHECK_OUT)
 
 # the NLP iteration (emi_nlp.cpp: its state object, the steps and iterates it copies and takes back) as a stand-alone program under
 # the host sanitizers, on the CPU oracle: no Python, no device

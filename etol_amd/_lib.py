@@ -97,7 +97,18 @@ class Start(C.Structure):
                 ("grid", C.c_int), ("repair", C.c_int)]
 
 
+class IpmRestart(C.Structure):
+    """emi_ipm_restart_t: the starts of emi_ipm_solve_restart_* and who goes to the next one"""
+    _fields_ = [("nstarts", C.c_int), ("starts", C.POINTER(Start)), ("patience", _I), ("retry_mask", C.c_int), ("flags", C.c_int)]
+
+
+class IpmRestartResult(C.Structure):
+    """emi_ipm_restart_result_t: which attempt of emi_ipm_solve_restart_* an instance's trajectory comes from, and how it ended"""
+    _fields_ = [("attempt", C.c_int), ("attempts", C.c_int), ("level", C.c_int), ("refine", IpmRefineResult)]
+
+
 START_LINE, START_BEND, START_PLANNED = range(3)
+RESTART_DROP_FAILED = 1   # emi_ipm_restart_t.flags: a rung that fails ends the instance's climb at once
 REFINE_MET, REFINE_NOT_MET, REFINE_FELL_BACK, REFINE_FAILED = range(4)
 IPM_RULE_RESIDUAL = 1   # emi_ipm_options_t.rules: residual-based acceptance of the full step and the crawl rule
 IPM_CONVERGED, IPM_ACCEPTABLE, IPM_MAX_ITER, IPM_LINE_SEARCH, IPM_INFEASIBLE, IPM_FACTOR, IPM_NOT_FINITE = range(7)
@@ -166,6 +177,11 @@ SYMBOLS = {
                                            _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
     "emi_ipm_solve_refine_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), _P, _P, C.c_int,
                                             _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRefineResult)]),
+    "emi_ipm_restart_decide": (C.c_int, [C.c_int, C.c_int]),
+    "emi_ipm_solve_restart_dev": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), C.POINTER(IpmRestart),
+                                            _P, _P, C.c_int, _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRestartResult)]),
+    "emi_ipm_solve_restart_host": (C.c_int, [_P, C.c_int, C.POINTER(IpmRung), C.c_double, C.c_double, C.POINTER(IpmRefine), C.POINTER(IpmRestart),
+                                             _P, _P, C.c_int, _P, _P, _P, _P, C.POINTER(IpmResult), _D, C.POINTER(IpmRestartResult)]),
     "emi_plan_route": (C.c_int, [C.c_int, _D, _D, _D, C.c_double, C.c_int, C.c_int, _D, _D, _D, _I, _D, _I, _I]),
     "emi_start_guess_dev": (C.c_int, [_P, C.POINTER(Start), _P, _P]),
     "emi_start_guess_host": (C.c_int, [_P, C.POINTER(Start), _P, _P]),

@@ -2,6 +2,7 @@
 // with its _host forms, the lock-step solve of a context's whole batch (driver: emi_ipm_solve.hip) and the mesh ladder over it
 // (kernels and driver: emi_ipm_ladder.hip), with and without refinement.
 #include "emi_ctx.hpp"
+#include "emi_restart_book.hpp"
 
 using namespace emi_api;
 
@@ -547,13 +548,14 @@ int ladder_args_check(emi_ctx_t c, const char* what, double t0, double tf, const
 
 // the two _host forms, after their checks: the starts, every rung's zl and zu and the outputs [B][rows][ld] staged, the _dev form run.
 // rf NULL: the ladder, whose outputs only come out; with refinement they go in too (the columns beyond an instance's mesh are the caller's)
-int ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf, const double* X0,
-                const double* U0, int ld, double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results, double* err,
-                emi_ipm_refine_result_t* out) {
+// rs given: the restart run over either, whose outputs go in and come out as with refinement (X0 may be NULL there)
+int ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf, const emi_ipm_restart_t* rs,
+                const double* X0, const double* U0, int ld, double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results,
+                double* err, emi_ipm_refine_result_t* out, emi_ipm_restart_result_t* rout) {
     HIP_TRY(c, hipSetDevice(c->device));
     HostStager s(c);
     const size_t B = (size_t)c->B, nv = (size_t)(c->ns + c->nc), M0 = (size_t)rungs[0].M, L = (size_t)ld;
-    const bool in = rf != nullptr;
+    const bool in = rf != nullptr || rs != nullptr;
     const void *dX0 = s.place(X0, B * c->ns * M0 * 8, true, false), *dU0 = s.place(U0, B * c->nc * M0 * 8, true, false);
     void *dX = s.place(X, B * c->ns * L * 8, in, true), *dU = s.place(U, B * c->nc * L * 8, in, true);
     void *dLF = s.place(LamF, B * c->ns * L * 8, in, true), *dLC = s.place(LamC, B * (size_t)np_total(c) * L * 8, in, true);
@@ -563,8 +565,9 @@ int ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0,
         g.bd.zl = s.place(g.bd.zl, bytes, true, false);
         g.bd.zu = s.place(g.bd.zu, bytes, true, false);
     }
-    IPM_HOST_END(rf ? emi_ipm_solve_refine_dev(c, nrungs, dr.data(), t0, tf, rf, dX0, dU0, ld, dX, dU, dLF, dLC, results, err, out)
-                    : emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
+    IPM_HOST_END(rs   ? emi_ipm_solve_restart_dev(c, nrungs, dr.data(), t0, tf, rf, rs, dX0, dU0, ld, dX, dU, dLF, dLC, results, err, rout)
+                 : rf ? emi_ipm_solve_refine_dev(c, nrungs, dr.data(), t0, tf, rf, dX0, dU0, ld, dX, dU, dLF, dLC, results, err, out)
+                      : emi_ipm_solve_ladder_dev(c, nrungs, dr.data(), t0, tf, dX0, dU0, dX, dU, dLF, dLC, results));
 }
 
 }  // namespace
@@ -582,7 +585,7 @@ int emi_ipm_solve_ladder_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* run
                               double* X, double* U, double* LamF, double* LamC, emi_ipm_result_t* results) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(ladder_check(c, "emi_ipm_solve_ladder_host", nrungs, rungs));
-    return ladder_host(c, nrungs, rungs, t0, tf, nullptr, X0, U0, rungs[nrungs - 1].M, X, U, LamF, LamC, results, nullptr, nullptr);
+    return ladder_host(c, nrungs, rungs, t0, tf, nullptr, nullptr, X0, U0, rungs[nrungs - 1].M, X, U, LamF, LamC, results, nullptr, nullptr, nullptr);
 }
 
 // ---- the ladder with refinement: instances that meet the ODE tolerance leave the batch (kernels and driver: emi_ipm_ladder.hip) -------
@@ -610,6 +613,17 @@ int emi_shard_move_dev(emi_ctx_t c, int n, const void* dSrcIdx, const void* dDst
 
 namespace {
 
+// what a call whose instances leave the batch asks of the caller's padded arrays and of the rungs' bounds
+int compaction_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t* rungs, int ldm) {
+    if (c->B > 65535) return fail(c, EMI_ERR_UNSUPPORTED, "%s: up to 65535 instances", what);
+    for (int r = 0; r < nrungs; ++r) {
+        if (rungs[r].M > ldm) return fail(c, EMI_ERR_ARG, "%s: ldm %d is below rung %d's %d nodes", what, ldm, r, rungs[r].M);
+        if (rungs[r].bd.nsets != 1 && rungs[r].bd.nsets != c->B)
+            return fail(c, EMI_ERR_ARG, "%s: rung %d's bounds have %d sets (1 or the batch, %d)", what, r, rungs[r].bd.nsets, c->B);
+    }
+    return EMI_OK;
+}
+
 // what the refinement refuses beyond the ladder's list
 int refine_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t* rungs, const emi_ipm_refine_t* rf, int ldm, const void* err,
                  const void* out) {
@@ -618,12 +632,30 @@ int refine_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t
     if (!(rf->ode_tol >= 0.0)) return fail(c, EMI_ERR_ARG, "%s: ode_tol must be >= 0", what);
     if (rf->first_check < 0 || rf->first_check >= nrungs) return fail(c, EMI_ERR_ARG, "%s: first_check %d outside the %d rungs", what, rf->first_check, nrungs);
     if ((rf->ul == nullptr) != (rf->uu == nullptr)) return fail(c, EMI_ERR_ARG, "%s: ul and uu come as a pair", what);
-    if (c->B > 65535) return fail(c, EMI_ERR_UNSUPPORTED, "%s: up to 65535 instances", what);
-    for (int r = 0; r < nrungs; ++r) {
-        if (rungs[r].M > ldm) return fail(c, EMI_ERR_ARG, "%s: ldm %d is below rung %d's %d nodes", what, ldm, r, rungs[r].M);
-        if (rungs[r].bd.nsets != 1 && rungs[r].bd.nsets != c->B)
-            return fail(c, EMI_ERR_ARG, "%s: rung %d's bounds have %d sets (1 or the batch, %d)", what, r, rungs[r].bd.nsets, c->B);
+    return compaction_check(c, what, nrungs, rungs, ldm);
+}
+
+// what the restart run refuses beyond the list of the refinement (rf NULL: of the ladder)
+int restart_check(emi_ctx_t c, const char* what, int nrungs, const emi_ipm_rung_t* rungs, const emi_ipm_refine_t* rf, const emi_ipm_restart_t* rs,
+                  bool has_x0, int ldm, const void* err, const void* out) {
+    if (rf) EMI_TRY(refine_check(c, what, nrungs, rungs, rf, ldm, err, out));
+    else {
+        EMI_TRY(ladder_check(c, what, nrungs, rungs));
+        if (!err || !out) return fail(c, EMI_ERR_ARG, "%s: null argument", what);
+        EMI_TRY(compaction_check(c, what, nrungs, rungs, ldm));
     }
+    if (!rs) return fail(c, EMI_ERR_ARG, "%s: rs is NULL", what);
+    if (rs->nstarts < 0 || (rs->nstarts > 0 && !rs->starts)) return fail(c, EMI_ERR_ARG, "%s: %d starts and no array of them", what, rs->nstarts);
+    const long long A = (long long)rs->nstarts + (has_x0 ? 1 : 0);
+    if (A < 1 || A > emi::RestartBook::MAX_ATTEMPTS)
+        return fail(c, EMI_ERR_ARG, "%s: %lld attempts (a guess and the starts: 1 .. %d)", what, A, emi::RestartBook::MAX_ATTEMPTS);
+    for (int i = 0; i < rs->nstarts; ++i)
+        if (rs->starts[i].nsets != 1 && rs->starts[i].nsets != c->B)
+            return fail(c, EMI_ERR_ARG, "%s: start %d has %d sets of end states (1 or the batch, %d)", what, i, rs->starts[i].nsets, c->B);
+    for (int a = 0; rs->patience && a < A; ++a)
+        if (rs->patience[a] < 0) return fail(c, EMI_ERR_ARG, "%s: patience[%d] is negative", what, a);
+    if (rs->retry_mask & ~((1 << (EMI_REFINE_FAILED + 1)) - 1)) return fail(c, EMI_ERR_ARG, "%s: retry_mask %d has bits beyond the four verdicts", what, rs->retry_mask);
+    if (rs->flags & ~EMI_RESTART_DROP_FAILED) return fail(c, EMI_ERR_ARG, "%s: unknown flag in %d", what, rs->flags);
     return EMI_OK;
 }
 
@@ -644,7 +676,28 @@ int emi_ipm_solve_refine_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* run
                               emi_ipm_result_t* results, double* err, emi_ipm_refine_result_t* out) {
     if (!c) return EMI_ERR_ARG;
     EMI_TRY(refine_check(c, "emi_ipm_solve_refine_host", nrungs, rungs, rf, ldm, err, out));
-    return ladder_host(c, nrungs, rungs, t0, tf, rf, X0, U0, ldm, X, U, LamF, LamC, results, err, out);
+    return ladder_host(c, nrungs, rungs, t0, tf, rf, nullptr, X0, U0, ldm, X, U, LamF, LamC, results, err, out, nullptr);
+}
+
+// ---- ladder restarts: the instances an attempt did not solve are solved again from the next start (driver: emi_ipm_ladder.hip) ------
+int emi_ipm_solve_restart_dev(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                              const emi_ipm_restart_t* rs, const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF,
+                              void* dLamC, emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out) {
+    const char* what = "emi_ipm_solve_restart_dev";
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(restart_check(c, what, nrungs, rungs, rf, rs, dX0 != nullptr, ldm, err, out));
+    if (!dX || (c->nc > 0 && (!dU0 || !dU)) || !dLamF || (np_total(c) > 0 && !dLamC) || !results) return fail(c, EMI_ERR_ARG, "%s: null argument", what);
+    if (!(tf > t0)) return fail(c, EMI_ERR_ARG, "%s: tf must exceed t0", what);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return emi::ipm_solve_restart(c, nrungs, rungs, t0, tf, rf, *rs, dX0, dU0, ldm, dX, dU, dLamF, dLamC, results, err, out);
+}
+
+int emi_ipm_solve_restart_host(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                               const emi_ipm_restart_t* rs, const double* X0, const double* U0, int ldm, double* X, double* U,
+                               double* LamF, double* LamC, emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out) {
+    if (!c) return EMI_ERR_ARG;
+    EMI_TRY(restart_check(c, "emi_ipm_solve_restart_host", nrungs, rungs, rf, rs, X0 != nullptr, ldm, err, out));
+    return ladder_host(c, nrungs, rungs, t0, tf, rf, rs, X0, U0, ldm, X, U, LamF, LamC, results, err, nullptr, out);
 }
 
 }  // extern "C"

@@ -279,4 +279,11 @@ int emi_ipm_refine_decide(int status, double err, double ode_tol, int has_good, 
     return !(ok && !met && !is_last);
 }
 
+// Whether an instance that ended an attempt of emi_ipm_solve_restart_* with this verdict is solved again from the next start.
+int emi_ipm_restart_decide(int verdict, int retry_mask) {
+    if (verdict < EMI_REFINE_MET || verdict > EMI_REFINE_FAILED) return 0;
+    const int mask = retry_mask ? retry_mask : 1 << EMI_REFINE_FAILED;
+    return (mask >> verdict) & 1;
+}
+
 }  // extern "C"

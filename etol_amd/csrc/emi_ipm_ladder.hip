@@ -1,6 +1,7 @@
-// emi_ipm_ladder.hip -- the mesh ladder of a context's whole batch (emi_ipm_solve_ladder_*, emi_ipm_solve_refine_*): prolongation
-// between LGL meshes, the repair of a guess that lies inside keep-outs, the moving discs' centres per mesh, and the one driver that
-// takes the B instances from rung to rung, with or without retiring those that meet the ODE tolerance.
+// emi_ipm_ladder.hip -- the mesh ladder of a context's whole batch (emi_ipm_solve_ladder_*, emi_ipm_solve_refine_*,
+// emi_ipm_solve_restart_*): prolongation between LGL meshes, the repair of a guess that lies inside keep-outs, the moving discs'
+// centres per mesh, the one driver that takes the B instances from rung to rung, with or without retiring those that meet the ODE
+// tolerance, and the loop that runs that driver again, from the next start, on the instances an attempt did not solve.
 //
 //   emi_prolong_rows_kernel  Vf[r][q] = sum_j PT[j][q] Vc[src(r)][j]: a thread owns one fine node and PROLONG_ROWS rows, reads PT[j][q]
 //                            once per j (coalesced along q), the coarse values as wave-uniform loads, and accumulates with fma
@@ -18,6 +19,9 @@
 //   LadderRun                the driver: one loop over the rungs in named phases, for the ladder with refinement and, as the run that
 //                            checks on no rung, for the plain ladder.  Who is live and who goes where is kept by a RefineBook
 //                            (emi_refine_book.hpp, host-only).  Nothing of a trajectory's size crosses to the host between rungs.
+//   ipm_solve_restart        one LadderRun per attempt on the pending instances, who they are kept by a RestartBook
+//                            (emi_restart_book.hpp, host-only).  A restart adds no kernel: the start of a compact batch is
+//                            emi_start_guess_dev on that batch, its controls come through emi_shard_move_kernel.
 // emi_prolong_matrix and emi_ipm_refine_decide, which need no device, are in emi_host.cpp.
 #include <hip/hip_runtime.h>
 
@@ -27,6 +31,7 @@
 
 #include "emi_ctx.hpp"
 #include "emi_refine_book.hpp"
+#include "emi_restart_book.hpp"
 
 namespace emi {
 namespace {
@@ -195,7 +200,7 @@ hipError_t launch_repair_guess(const RepairArgs& a, hipStream_t s) {
 
 // the arrays of a run between its rungs: P transposed for the present pair of rungs, the compact iterates and multipliers of two
 // consecutive rungs (a fall-back returns the older set), the gathered bounds of the live instances, the estimates, and the lists
-// [6][B]: row map | live | two (source, destination) pairs
+// [7][B]: row map | live | two (source, destination) pairs | the levels of emi_start_guess_dev
 struct IpmLadderWs {
     DeviceArray<double> PT, X[2], U[2], LamF[2], LamC[2], zl, zu, err;
     DeviceArray<int> lists;
@@ -208,8 +213,8 @@ namespace {
 #define L_HIP(call) HIP_TRY_AS(c, entry, call)
 #define L_TRY EMI_TRY
 
-// One call of emi_ipm_solve_ladder_dev / emi_ipm_solve_refine_dev.  The first block of members is the call as it came; rf null: no
-// rung checks the ODE error, and `book` was begun with RefineBook::NEVER
+// One call of emi_ipm_solve_ladder_dev / emi_ipm_solve_refine_dev, or one attempt of emi_ipm_solve_restart_dev.  The first block of
+// members is the call as it came; rf null: no rung checks the ODE error, and `book` was begun with RefineBook::NEVER
 struct LadderRun {
     emi_ctx_t c;
     const char* entry;                  // the entry point, for the messages
@@ -221,11 +226,18 @@ struct LadderRun {
     int ldm;
     void *dX, *dU, *dLamF, *dLamC;
     RefineBook book;
+    // an attempt of a restart run (rb null: none).  The book may begin from a subset; start: where the states of rung 0 come from
+    // when dX0 is null, its sets those of the batch of rung 0; drop: EMI_RESTART_DROP_FAILED
+    RestartBook* rb = nullptr;
+    int attempt = 0;
+    const emi_start_t* start = nullptr;
+    bool drop = false;
     // the context at entry
     const int B = c->B, ns = c->ns, nc = c->nc, nv = ns + nc, np = emi_api::np_total(c), sets = c->path_sets;
     const hipStream_t s = c->stream;
     IpmLadderWs* w = nullptr;
-    int *d_map = nullptr, *d_live = nullptr, *d_pair[2][2] = {};
+    int *d_map = nullptr, *d_live = nullptr, *d_pair[2][2] = {}, *d_level = nullptr;
+    RefineBook::Moves sent[2];          // the groups of retirees as they went up (a restart run leaves out who is to be solved again)
     // what restore_context has to undo
     bool table_compacted = false, centres_compacted = false;
     const double* master = nullptr;     // the record table in the caller's numbering: the last rung's that brought one, else `table`
@@ -266,7 +278,7 @@ struct LadderRun {
         bool gathers = false;           // per-instance bounds come in the caller's numbering: gathered once somebody has left
         for (int q = 0; q < nrungs; ++q) {
             Mmax = std::max(Mmax, rungs[q].M);
-            gathers = gathers || (rf && B > 1 && rungs[q].bd.nsets == B);
+            gathers = gathers || ((rf || rb) && B > 1 && rungs[q].bd.nsets == B);
         }
         L_HIP(hipStreamSynchronize(s));                 // a launch in flight may still use an array that has to move
         for (int k = 0; k < 2 && k < nrungs; ++k) {
@@ -275,10 +287,11 @@ struct LadderRun {
         }
         if (gathers) { L_HIP(w->zl.reserve((size_t)B * nv * Mmax)); L_HIP(w->zu.reserve((size_t)B * nv * Mmax)); }
         if (rf) L_HIP(w->err.reserve((size_t)B));
-        L_HIP(w->lists.reserve((size_t)6 * B));
+        L_HIP(w->lists.reserve((size_t)7 * B));
         d_map = w->lists.p;
         d_live = d_map + B;
         for (int k = 0; k < 2; ++k) { d_pair[k][0] = d_map + (2 + 2 * k) * B; d_pair[k][1] = d_map + (3 + 2 * k) * B; }
+        d_level = d_map + 6 * B;
         herr.resize(B); res.resize(B);
         return EMI_OK;
     }
@@ -327,15 +340,36 @@ struct LadderRun {
         return EMI_OK;
     }
 
+    // the start of rung 0.  A whole batch with dX0: two copies.  A batch that begins from a subset: the rows of the live instances
+    // through the live list (one emi_shard_move_kernel launch).  Without dX0 the states are emi_start_guess_dev's for the batch as the
+    // context now holds it (mesh, table and centres of the live instances), n levels come down
+    int place_start() {
+        const bool whole = n == B;
+        if (whole) {
+            if (dX0) L_HIP(hipMemcpyAsync(cX, dX0, (size_t)B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+            if (nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, (size_t)B * nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+        } else if (dX0 || nc > 0) {
+            L_TRY(need_live());
+            ShardMoveArgs a{};
+            int q = 0;
+            if (dX0) { a.src[q] = (const double*)dX0; a.dst[q] = cX; a.rows[q] = ns; ++q; }
+            if (nc > 0) { a.src[q] = (const double*)dU0; a.dst[q] = cU; a.rows[q] = nc; ++q; }
+            for (int i = 0; i < q; ++i) a.sld[i] = a.dld[i] = M;
+            a.sidx = d_live; a.n = n; a.narrays = q; a.len = M;
+            L_HIP(launch_shard_move(a, s));
+        }
+        if (dX0) return EMI_OK;
+        L_TRY(emi_start_guess_dev(c, start, cX, d_level));
+        L_HIP(hipMemcpyAsync(rb->level.data(), d_level, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        L_HIP(hipStreamSynchronize(s));
+        return EMI_OK;
+    }
+
     // this rung's iterate in one of the two sets (not the previous rung's): the start, or the previous rung's final iterate prolonged,
     // the rows of whoever left that batch skipped by the row map
     int place_iterate() {
         cX = w->X[cur].p; cU = w->U[cur].p; cLF = w->LamF[cur].p; cLC = w->LamC[cur].p;
-        if (r == 0) {
-            L_HIP(hipMemcpyAsync(cX, dX0, (size_t)B * ns * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-            if (nc > 0) L_HIP(hipMemcpyAsync(cU, dU0, (size_t)B * nc * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-            return EMI_OK;
-        }
+        if (r == 0) return place_start();
         L_TRY(prolong_matrix());
         const int* map = book.row_map();
         if (map) L_HIP(hipMemcpyAsync(d_map, map, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
@@ -379,7 +413,13 @@ struct LadderRun {
     }
 
     // a group of retirees from one of the two sets (on Mk nodes) into the caller's arrays; k: which pair of lists carries it
-    int move_out(const RefineBook::Moves& m, int k, int set, int Mk) {
+    int move_out(const RefineBook::Moves& all, int k, int set, int Mk) {
+        RefineBook::Moves& m = sent[k];
+        m = RefineBook::Moves{};
+        for (size_t i = 0; i < all.to.size(); ++i) {
+            if (rb && !rb->writes(attempt, book.verdict_of(all.to[i]))) continue;
+            m.from.push_back(all.from[i]); m.to.push_back(all.to[i]);
+        }
         const int cnt = (int)m.from.size();
         if (cnt == 0) return EMI_OK;
         L_HIP(hipMemcpyAsync(d_pair[k][0], m.from.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, s));
@@ -406,6 +446,8 @@ struct LadderRun {
             L_HIP(hipMemcpyAsync(herr.data(), w->err.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
             L_HIP(hipStreamSynchronize(s));
             book.decide(r, herr.data(), rf->ode_tol, last);
+        } else if (drop) {
+            book.drop_or_climb(r, last);
         } else if (last) {
             book.return_all(r);
         } else {                                        // a mesh-sequencing rung: everybody climbs
@@ -414,7 +456,7 @@ struct LadderRun {
         }
         L_TRY(move_out(book.here, 0, cur, M));
         L_TRY(move_out(book.older, 1, cur ^ 1, Mc));
-        L_HIP(hipStreamSynchronize(s));                 // (the lists are the book's, rewritten by the next decision)
+        L_HIP(hipStreamSynchronize(s));                 // (the lists are `sent`, rewritten at the next decision)
         return EMI_OK;
     }
 
@@ -445,6 +487,53 @@ int ipm_solve_ladder(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, doubl
     LadderRun run{c, "emi_ipm_solve_ladder_dev", nrungs, rungs, t0, tf, nullptr, dX0, dU0, rungs[nrungs - 1].M, dX, dU, dLamF, dLamC};
     run.book.begin(c->B, nrungs, RefineBook::NEVER, results, err.data(), out.data());
     return run.run();
+}
+
+// One LadderRun per attempt on the instances that are still pending.  Every attempt leaves the context as the refine call does (batch
+// B, the full table, the centres of all sets), so the next one compacts from the caller's numbering again; a table that a rung
+// brought is replaced by the one the context came with before rung 0 is solved again
+int ipm_solve_restart(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                      const emi_ipm_restart_t& rs, const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC,
+                      emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out) {
+    const char* entry = "emi_ipm_solve_restart_dev";
+    const int B = c->B, ns = c->ns, A = (dX0 ? 1 : 0) + rs.nstarts;
+    RestartBook rb;
+    rb.begin(B, A, nrungs, rf ? rf->first_check : RefineBook::NEVER, rs.retry_mask, results, err, out);
+    bool brings_table = false;
+    for (int r = 0; r < nrungs; ++r) brings_table = brings_table || rungs[r].recs;
+    std::vector<double> table;          // the context's record table at entry
+    if (brings_table && A > 1) {
+        table.resize((size_t)c->path_sets * c->np * EMI_PATH_REC);
+        EMI_TRY(emi_api::download_real(c, table.data(), c->d_path.p, table.size()));
+    }
+    std::vector<emi_ipm_rung_t> rg(rungs, rungs + nrungs);
+    std::vector<double> xa, xb, box;    // the sets of the pending instances of a start with one set per instance
+    for (int a = 0; a < A && !rb.done(); ++a) {
+        rg[0].opt.max_iter = rs.patience && rs.patience[a] > 0 ? rs.patience[a] : rungs[0].opt.max_iter;
+        const bool guess = dX0 && a == 0;
+        emi_start_t st{};
+        if (!guess) {
+            st = rs.starts[a - (dX0 ? 1 : 0)];
+            if (st.nsets == B && rb.n() != B) {
+                const int n = rb.n();
+                xa.resize((size_t)n * ns); xb.resize((size_t)n * ns); box.resize((size_t)n * 4);
+                for (int i = 0; i < n; ++i) {
+                    const size_t b = (size_t)rb.pending[i];
+                    std::copy(st.xa + b * ns, st.xa + (b + 1) * ns, xa.begin() + (size_t)i * ns);
+                    std::copy(st.xb + b * ns, st.xb + (b + 1) * ns, xb.begin() + (size_t)i * ns);
+                    if (st.box) std::copy(st.box + b * 4, st.box + (b + 1) * 4, box.begin() + (size_t)i * 4);
+                }
+                st.xa = xa.data(); st.xb = xb.data(); st.box = st.box ? box.data() : nullptr; st.nsets = n;
+            }
+        }
+        if (a > 0 && !table.empty()) EMI_TRY(emi_set_path(c, c->np, c->path_sets, table.data(), c->px, c->py));
+        LadderRun run{c, entry, nrungs, rg.data(), t0, tf, rf, guess ? dX0 : nullptr, dU0, ldm, dX, dU, dLamF, dLamC};
+        run.rb = &rb; run.attempt = a; run.start = guess ? nullptr : &st; run.drop = (rs.flags & EMI_RESTART_DROP_FAILED) != 0;
+        rb.open(a, run.book);
+        EMI_TRY(run.run());
+        rb.close(a, run.book);
+    }
+    return EMI_OK;
 }
 
 }  // namespace emi

@@ -308,5 +308,9 @@ hipError_t launch_shard_move(ShardMoveArgs a, hipStream_t s);
 int ipm_solve_refine(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t& rf, const void* dX0,
                      const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results, double* err,
                      emi_ipm_refine_result_t* out);
+// ... and that driver once per attempt, from one start after another, on the instances no earlier attempt solved (emi_ipm_solve_restart_*)
+int ipm_solve_restart(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                      const emi_ipm_restart_t& rs, const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC,
+                      emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out);
 
 }  // namespace emi

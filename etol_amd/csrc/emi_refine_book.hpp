@@ -7,10 +7,13 @@
 // stand-alone program can walk it under a host sanitizer with scripted statuses and estimates (tests/harness/refine_book_main.cpp).
 //
 //   begin          everybody is live; the caller's records say "never solved" until a rung writes them
+//   keep           ... only the instances of a list are: a run that begins from a subset (a later attempt of emi_ipm_solve_restart_*)
 //   record_solve   the results of a rung's solve, compact -> the caller's numbering
 //   climb_all      a rung without a check: the next batch is this one
 //   decide         a rung with a check: the estimates in, the two groups of retirees and the next batch out
 //   return_all     the last rung of a run that never checks (the plain ladder): everybody returns this rung's iterate
+//   drop_or_climb  a rung without a check under EMI_RESTART_DROP_FAILED: whoever was not solved leaves here, the rest climb or return
+//   verdict_of     the verdict of an instance that has left; in a run that never checks, by the solve on the rung it ended on
 //   row_map        where the rows of the next prolongation come from; null while nobody left the batch of the rung before
 //   caller_map     the live instances in the caller's numbering; null while the batch is whole
 #pragma once
@@ -51,6 +54,13 @@ struct RefineBook {
         prev_n = B;
         here = older = Moves{};
     }
+    // the batch of the first rung is the instances who[0 .. n) (the caller's numbers, ascending) and not everybody
+    void keep(const int* who, int n_) {
+        live.assign(who, who + n_); pos.resize(n_);
+        for (int i = 0; i < n_; ++i) pos[i] = i;
+        prev_n = n_;
+    }
+    static bool solved(int status) { return status == EMI_IPM_CONVERGED || status == EMI_IPM_ACCEPTABLE; }
     int n() const { return (int)live.size(); }
     bool done() const { return live.empty(); }
     bool checks(int r) const { return r >= first_check; }
@@ -77,6 +87,28 @@ struct RefineBook {
         }
         prev_n = n();
         live.clear(); pos.clear();
+    }
+    // The drop rule on rung r < first_check (where decide applies, it is that rule's "not ok, no good solution"): an instance whose
+    // solve on r is neither converged nor acceptable has nothing good from an earlier rung either, and leaves on r with
+    // EMI_REFINE_FAILED and what the solve left.  The rest climb; on the last rung of a run that never checks they return as in return_all
+    void drop_or_climb(int r, bool last) {
+        std::vector<int> next, next_pos;
+        here = older = Moves{};
+        for (int i = 0; i < n(); ++i) {
+            const int b = live[i];
+            if (!last && solved(results[(size_t)r * B + b].status)) {
+                next.push_back(b); next_pos.push_back(i);
+                continue;
+            }
+            here.from.push_back(i); here.to.push_back(b);
+            out[b].rung = r;
+        }
+        prev_n = n();
+        live.swap(next); pos.swap(next_pos);
+    }
+    int verdict_of(int b) const {
+        if (first_check != NEVER || out[b].rung < 0) return out[b].verdict;
+        return solved(results[(size_t)out[b].rung * B + b].status) ? EMI_REFINE_MET : EMI_REFINE_FAILED;
     }
     // herr [n]: the estimates of rung r in the order of the batch (the statuses are those of record_solve); last: r is the last
     // rung, which retires everybody

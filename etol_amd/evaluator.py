@@ -821,6 +821,92 @@ class Evaluator:
         results = [[{n: getattr(res[r * B + b], n) for n in fields} for b in range(B)] for r in range(nr)]
         return X, U, LamF, LamC, results, err[:nr], [{n: getattr(q, n) for n, _ in L.IpmRefineResult._fields_} for q in summ]
 
+    # ---- ladder restarts: the instances an attempt did not solve are solved again from the next start (emi_ipm_solve_restart_*) ---
+    @staticmethod
+    def restart_decide(verdict, retry_mask=0):
+        """whether an instance that ended an attempt with `verdict` goes to the next attempt (host, emi_ipm_restart_decide)"""
+        return bool(L.load().emi_ipm_restart_decide(int(verdict), int(retry_mask)))
+
+    def _ipm_starts(self, starts, keep):
+        """the emi_start_t array of a list of dict kind, xa, xb and optionally box, bend, clearance, grid, repair (the arguments of
+        start_guess); keep: what must outlive the call"""
+        ns = self.layout.ns
+        arr = (L.Start * max(1, len(starts)))()
+        for g, d in zip(arr, starts):
+            xa, xb = (np.ascontiguousarray(d[k], dtype=np.float64).reshape(-1, ns) for k in ("xa", "xb"))
+            assert xa.shape == xb.shape
+            keep += [xa, xb]
+            g.kind, g.nsets, g.xa, g.xb = int(d["kind"]), xa.shape[0], _dp(xa), _dp(xb)
+            if d.get("box") is not None:
+                box = np.ascontiguousarray(d["box"], dtype=np.float64).reshape(-1, 4)
+                assert box.shape[0] == xa.shape[0]
+                keep.append(box)
+                g.box = _dp(box)
+            g.bend, g.clearance = float(d.get("bend", 0.0)), float(d.get("clearance", 0.01))
+            g.grid, g.repair = int(d.get("grid", 0)), int(bool(d.get("repair")))
+        return arr
+
+    def ipm_solve_restart(self, rungs, t0, tf, starts, U0, X0=None, ode_tol=None, first_check=0, ul=None, uu=None, patience=None,
+                          retry_mask=0, flags=0, ldm=None, out=None, dev=True):
+        """The rung loop of ipm_solve_refine (ode_tol None: of ipm_solve_ladder) run again from the next start on the instances an
+        attempt did not solve (include/emi355x.h: emi_ipm_solve_restart_*).  Attempt 0 starts from X0 where given; the others from
+        `starts`, a list of dict kind, xa, xb, box, bend, clearance, grid, repair as for start_guess.  patience: list of max_iter of
+        rung 0 per attempt (0: the rung's own); flags: RESTART_DROP_FAILED.  out: (X, U, LamF, LamC) [B][rows][ldm] to write into.
+        Returns (X, U, LamF, LamC, results[attempt][rung][b], err [attempts][rungs][B], summary[b] = dict attempt, attempts, level,
+        rung, verdict, rungs_solved, err)."""
+        lay = self.layout
+        B, ns, nc, npth = lay.B, lay.ns, lay.nc, lay.np
+        keep = []
+        arr = self._ipm_rungs(rungs, keep)
+        ldm = int(ldm if ldm is not None else (out[0].shape[-1] if out is not None else max([int(r["M"]) for r in rungs] or [0])))
+        if out is not None:
+            X, U, LamF, LamC = out
+        elif dev:
+            kw = dict(dtype=torch.float64, device=U0.device)
+            X, U, LamF, LamC = (torch.zeros((B, r, ldm), **kw) for r in (ns, nc, ns, npth))
+        else:
+            X, U, LamF, LamC = (np.zeros((B, r, ldm)) for r in (ns, nc, ns, npth))
+        if not dev:
+            assert all(a is None or (a.dtype == np.float64 and a.flags.c_contiguous) for a in (X0, U0, X, U, LamF, LamC))
+        rf = None
+        if ode_tol is not None:
+            rf = L.IpmRefine()
+            rf.ode_tol, rf.first_check = float(ode_tol), int(first_check)
+            for f, a in (("ul", ul), ("uu", uu)):
+                if a is not None:
+                    a = np.ascontiguousarray(a, dtype=np.float64)
+                    keep.append(a)
+                    setattr(rf, f, _dp(a))
+        rs = L.IpmRestart()
+        rs.nstarts, rs.retry_mask, rs.flags = len(starts), int(retry_mask), int(flags)
+        if len(starts):
+            rs.starts = self._ipm_starts(starts, keep)
+        nat = max(1, min(len(starts) + (X0 is not None), 8))
+        if patience is not None:
+            pat = np.ascontiguousarray(patience, dtype=np.int32)
+            assert pat.size >= nat
+            keep.append(pat)
+            rs.patience = pat.ctypes.data_as(C.POINTER(C.c_int))
+        nr = len(rungs)
+        res = (L.IpmResult * max(1, nat * nr * B))()
+        err = np.full((nat, max(1, nr), B), np.nan)
+        summ = (L.IpmRestartResult * B)()
+        A = self._ipm_addr
+        fn = self.lib.emi_ipm_solve_restart_dev if dev else self.lib.emi_ipm_solve_restart_host
+        st = fn(self.ctx, nr, arr, float(t0), float(tf), C.byref(rf) if rf is not None else None, C.byref(rs), A(X0), A(U0), ldm, A(X), A(U),
+                A(LamF), A(LamC) if npth else None, res, _dp(err), summ)
+        self._changed()
+        self._trk_shape = self._wp_shape    # (an upper bound after an error)
+        self._ck(st, fn.__name__)
+        Ml = self.layout.M
+        self.tau, self.w, self.D = lgl(Ml)
+        self.node_t = t0 + (tf - t0) / 2.0 * (self.tau + 1.0)
+        fields = [n for n, _ in L.IpmResult._fields_]
+        results = [[[{n: getattr(res[(a * nr + r) * B + b], n) for n in fields} for b in range(B)] for r in range(nr)] for a in range(nat)]
+        summary = [dict(attempt=q.attempt, attempts=q.attempts, level=q.level,
+                        **{n: getattr(q.refine, n) for n, _ in L.IpmRefineResult._fields_}) for q in summ]
+        return X, U, LamF, LamC, results, err[:, :nr], summary
+
     # ---- relative local ODE error of the batch on the collocation mesh (emi_ode_error_*, emi_interp_dev) ------------------------
     @staticmethod
     def ode_error_operator(M, mesh=None):

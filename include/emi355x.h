@@ -785,6 +785,72 @@ int emi_plan_route(int np, const double* recs, const double ends[4], const doubl
                    const double* tau, double* xs, double* ys, int* level, double* cost, int* cells, int* ncells);
 int emi_start_guess_dev(emi_ctx_t ctx, const emi_start_t* st, void* dX, void* dLevel);
 int emi_start_guess_host(emi_ctx_t ctx, const emi_start_t* st, double* X, int* level);
+/* ---- Lock-step ladder RESTARTS: the instances an attempt did not solve are solved again from the next start ---------------------
+ *
+ * What ETOL::eMI355X::solve owes its robustness to (host/emi_mesh_driver.cpp: cold_start_with_retries, run_ladder,
+ * restart_after_failed_target), for a whole batch: a climb that fails goes back to the coarsest mesh with the next start, and a rung
+ * that fails ends the climb at once (csrc/emi_ipm_ladder.hip, csrc/emi_restart_book.hpp).
+ *
+ * emi_ipm_restart_decide (host, no device needed): 1 where an instance that ended an attempt with `verdict` (EMI_REFINE_*) goes to
+ * the next attempt: bit `verdict` of retry_mask is set, a retry_mask of 0 standing for 1 << EMI_REFINE_FAILED; 0 for any other verdict.
+ *
+ * emi_ipm_solve_restart_dev: the attempts are numbered 0 .. A-1, A = (dX0 ? 1 : 0) + rs->nstarts, 1 <= A <= 8.  With dX0 given
+ * attempt 0 starts from dX0 [B][ns][M_0], a user's guess; every other attempt starts from emi_start_guess_dev with the next entry
+ * of rs->starts on rung 0's mesh (whose `repair` applies as there; the rung's `repair` flag applies as in the ladder call).  The
+ * controls start from dU0 [B][nc][M_0] in every attempt; dX0 and dU0 are only read.
+ *   Attempt 0 runs the rung loop of emi_ipm_solve_refine_dev (rf NULL: of emi_ipm_solve_ladder_dev) on all B instances.  After an
+ *   attempt every instance whose verdict emi_ipm_restart_decide sends on is pending; with rf NULL the verdict is EMI_REFINE_MET where
+ *   the solve on the rung the instance ended on is converged or acceptable, else EMI_REFINE_FAILED.  The next attempt runs the same
+ *   loop on the pending instances only, a compact batch of the same context from rung 0 on: their rows of the record table go in
+ *   through emi_set_path, their waypoint sets through the set map of emi_tracks_from_waypoints_dev, their bounds sets (nsets == B)
+ *   and their rows of dU0 are gathered by emi_shard_move_dev, their xa, xb and box sets (a start with nsets == B, given in the
+ *   CALLER's numbering) on the host; emi_start_guess_dev then writes the compact batch's states.  A record table that a rung brought
+ *   is replaced by the one the context came with before rung 0 is solved again.
+ *   The first attempt that gives an instance a verdict outside retry_mask writes its X, U, LamF, LamC into the caller's arrays
+ *   [B][rows][ldm], on the mesh it retired on, as the refine call does; nothing later touches that instance.  An instance that is
+ *   still pending after the last attempt keeps what attempt 0 left: out[b].attempt = 0, out[b].attempts = A.
+ *   EMI_RESTART_DROP_FAILED: an instance whose solve on a rung is neither converged nor acceptable, and that has no good solution from
+ *   an earlier rung of this attempt (emi_ipm_refine_decide's has_good), leaves the attempt on that rung with EMI_REFINE_FAILED -- also
+ *   below rf->first_check and with rf NULL, where without the flag everybody climbs.  That is how the host driver's climb ends at a
+ *   failed rung, and what makes a restart cheap: the failure is known after a cold start on the coarsest mesh.  Without the flag the
+ *   rung loop's rules are exactly those of the ladder and refine calls.
+ *   rs->patience[a] (NULL, or A entries; 0: the rung's own) replaces rungs[0].opt.max_iter in attempt a only: an early start does not
+ *   get the full budget while other starts are unused (the host driver's warm_patience / target_patience).
+ * results [A][nrungs][B], err [A][nrungs][B]: per attempt as in the refine call, status -1 and NaN where the instance was not
+ * solved (with rf NULL no estimate is taken).  out[b]: the attempt whose trajectory the caller's arrays hold, the number of attempts
+ * the instance was solved in, emi_plan_route's level in that attempt (-2 for the other kinds and for dX0), and the refine call's
+ * out[b] of that attempt.  Nothing of a trajectory's size crosses to the host: per attempt a few ints per instance go up, statuses,
+ * levels and estimates come down.  An attempt on all B instances runs the launches of the refine / ladder call, and every bit is that
+ * call's; an instance solved in a compacted batch agrees with the same instance in a whole batch as two batch sizes agree in
+ * emi_ipm_solve_shard_dev, so the number of instances a restart run solves is a count, not a guarantee.  Two identical calls give
+ * the same bits.  On return, also after an error, the context is as the refine call leaves it: batch B, the full record table, the
+ * centres of all sets, on the mesh of the last rung that was solved.  The workspaces are those of the ladder call (device arrays of
+ * the context, grown as needed, freed with it).
+ * Statuses: whatever emi_ipm_solve_refine_dev (rf NULL: emi_ipm_solve_ladder_dev; ldm and the bounds' nsets are checked as in the
+ * refine call) and emi_start_guess_dev return, and EMI_ERR_ARG: rs NULL, A outside 1 .. 8, nstarts < 0, starts NULL with nstarts > 0,
+ * a start whose nsets is neither 1 nor B, a negative patience entry, a retry_mask with bits beyond the four verdicts, an unknown
+ * flag, a NULL err or out.  The _host form takes host arrays as emi_ipm_solve_refine_host does (X0 may be NULL) and synchronises. */
+enum { EMI_RESTART_DROP_FAILED = 1 };
+typedef struct emi_ipm_restart {
+  int nstarts;                 /* entries of starts */
+  const emi_start_t* starts;   /* [nstarts]; nsets 1 or B, sets in the CALLER's numbering */
+  const int* patience;         /* NULL, or [attempts]: max_iter of rung 0 in that attempt (0: the rung's own) */
+  int retry_mask;              /* bit v set: verdict v (EMI_REFINE_*) sends the instance to the next attempt; 0 takes 1 << EMI_REFINE_FAILED */
+  int flags;                   /* EMI_RESTART_* */
+} emi_ipm_restart_t;
+typedef struct emi_ipm_restart_result {
+  int attempt;                 /* the attempt whose trajectory the caller's arrays hold */
+  int attempts;                /* attempts this instance was solved in */
+  int level;                   /* emi_plan_route's level in that attempt (-2 for the other kinds and for dX0) */
+  emi_ipm_refine_result_t refine;   /* rung, verdict, rungs_solved, err of that attempt */
+} emi_ipm_restart_result_t;
+int emi_ipm_restart_decide(int verdict, int retry_mask);
+int emi_ipm_solve_restart_dev(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                              const emi_ipm_restart_t* rs, const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF,
+                              void* dLamC, emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out);
+int emi_ipm_solve_restart_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t* rf,
+                               const emi_ipm_restart_t* rs, const double* X0, const double* U0, int ldm, double* X, double* U,
+                               double* LamF, double* LamC, emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out);
 /* The components of emi_ipm_error's scaled KKT error, out[B][8] = {ed, sd, ep, sc, pmin, pmax, emax, ymax}: ed, ep, sd, sc and emax
  * as there; pmin / pmax the smallest and largest complementarity product (gap times multiplier); ymax = max |Y|.  For ANY
  * barrier parameter mu_t:  kkt_error(mu_t) = max(ed / sd, ep, max(0, pmax - mu_t, mu_t - pmin) / sc)  -- one launch serves the
