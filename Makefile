@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -143,6 +143,19 @@ PASS_PLAN_CHECK_OUT ?= $(LIBDIR)/pass_plan_check
 check-pass-plan: tests/harness/pass_plan_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_PLAN_CHECK_OUT) tests/harness/pass_plan_main.cpp
 	$(PASS_PLAN_CHECK_OUT)
+
+# the residency rule of that policy ("sym_res": three resident workgroups per CU only with a direct-operator row, the default by band, built-in
+# models only, the order in which resolve_form grants the wants) as a stand-alone program under the host sanitizers
+PASS_RES_CHECK_OUT ?= $(LIBDIR)/pass_residency_check
+check-pass-residency: tests/harness/pass_residency_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_RES_CHECK_OUT) tests/harness/pass_residency_main.cpp
+	$(PASS_RES_CHECK_OUT)
+
+# the register budget of emi_pass_f64_kernel: every instantiation compiled for $(ARCH) (device code only, nothing is kept) and held to the
+# resident workgroups per CU it states -- 3: occupancy 3, at most 168 registers, no scratch; 2: no scratch and what tools/pass_registers.json
+# records.  No device needed.
+check-pass-registers: tools/check_pass_registers.py tools/pass_registers.json $(CSRC)/emi_symdefect.hip $(CSRC_HDR)
+	python3 tools/check_pass_registers.py --hipcc $(HIPCC) --arch $(ARCH)
 
 clean:
 	rm -rf $(LIBDIR) tests/harness/*.so

@@ -122,6 +122,8 @@ const OptionRow OPTIONS[] = {
     {"sym_ctc", &emi_ctx_s::sym_ctc, within<0, 2>, as_given, "sym_ctc must be 0 (by batch size), 1 or 2"},
     {"sym_bk", &emi_ctx_s::sym_bk, one_of<0, 8, 16>, as_given, "sym_bk must be 0 (by batch size), 8 or 16"},
     {"sym_dop", &emi_ctx_s::sym_dop, within<0, 2>, as_given, "sym_dop must be 0 (by batch size), 1 (De / Do through the operand ring) or 2 (straight from L2)"},
+    {"sym_res", &emi_ctx_s::sym_res, one_of<0, 2, 3>, as_given,
+     "sym_res must be 0 (by batch size), 2 or 3 resident workgroups per CU (3: granted to the De / Do from L2 forms only)"},
     {"sym_cpart", &emi_ctx_s::sym_cpart, one_of<-1, 0, 1, 2, 4, 8>, as_given, "sym_cpart must be -1 (plain order), 0 (by mesh size), 1, 2, 4 or 8"},
     {"sym_gblk", &emi_ctx_s::sym_gblk, within<0, 64>, as_given, "sym_gblk must be 0 (off) .. 64 instance groups per super-block"},
     {"sym_cx", &emi_ctx_s::sym_cx, within<0, 64>, as_given, "sym_cx must be 0 (default) .. 64 column tiles per block"},

@@ -33,6 +33,7 @@ emi::PassPolicyIn policy_in(emi_ctx_t c) {
     in.sym_ctc = c->sym_ctc;
     in.sym_bk = c->sym_bk;
     in.sym_dop = c->sym_dop;
+    in.sym_res = c->sym_res;
     in.pass_order = c->pass_order;
     in.node_store = c->node_store;
     in.slice = c->slice;
@@ -614,6 +615,15 @@ int emi_plan_pass(emi_ctx_t c, int B, emi_pass_plan_t* out) {
     if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "emi_plan_pass: mesh and model must be set");
     memset(out, 0, sizeof *out);
     emi::report_pass(policy_in(c), B, out);
+    return EMI_OK;
+}
+
+int emi_plan_pass_residency(emi_ctx_t c, int B, int* res) {
+    if (!c || !res || B < 1) return EMI_ERR_ARG;
+    if (c->M <= 0 || c->model < 0) return fail(c, EMI_ERR_STATE, "emi_plan_pass_residency: mesh and model must be set");
+    emi_pass_plan_t plan;
+    memset(&plan, 0, sizeof plan);
+    emi::report_pass(policy_in(c), B, &plan, nullptr, res);
     return EMI_OK;
 }
 

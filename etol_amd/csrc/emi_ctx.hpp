@@ -99,6 +99,8 @@ struct emi_ctx_s {
     int sym_bk = 0;             // "sym_bk": depth of a K tile of the one-launch pass (8 or 16; 0: by batch size, plan_pass)
     int sym_dop = 0;            // "sym_dop": where the MFMA role's De / Do fragments come from: 1 through the operand ring, 2 straight from L2
                                 // (unsplit 16-deep form, SW 1 / 2); 0: by batch size, plan_pass
+    int sym_res = 0;            // "sym_res": resident workgroups per CU the one-launch pass states: 2, or 3 (the De / Do from L2 forms only); 0: by
+                                // batch size, plan_pass
     // delayed values (emi_set_delays): x_horizon - 1 delayed copies of every state and u_horizon of every control, appended to the
     // controls the node functions see: nc = nc_free + nch; W[d] = interpolation matrix of delay (d + 1) dt on this mesh
     int xh = 0, uh = 0, nch = 0;

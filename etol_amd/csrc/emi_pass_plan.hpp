@@ -31,6 +31,7 @@ struct SymPlan {
     int ct = 1;               // 64-column sub-tiles per MFMA workgroup of the one-launch pass (2: SW = 2, unsplit, M % 256 == 0)
     bool dop = false;         // one-launch pass: the MFMA role's De / Do fragments straight from L2, not through the ring (SW 1 / 2, bk 16, unsplit,
                               // one sub-tile, three stages; needs SymDefectArgs::Dfrag)
+    int res = 2;              // one-launch pass: resident workgroups per CU the launch states (3: the direct-operator forms only, "sym_res")
     size_t slab_bytes = 0;
     int cpart = 0, cx = 0;    // tile order (SymDefectArgs::cpart, cx): 0 = plain, > 0 column partitions, < 0 grouped (-G)
     int tiles = 0;            // tiles of the launch (instance groups x column tiles x state groups): tickets of an in-kernel combine
@@ -172,10 +173,16 @@ struct PassShape {
 struct PassWants {
     int sw = 0, ks = 1, nst = 3, bk = 8, ct = 1, hs = 1;
     bool dop = false;
+    int res = 2;        // resident workgroups per CU the launch states: 2 or 3
 };
+// Resident workgroups per CU a launch of a row may state.  Not a column of the table: every row states 2, and a direct-operator row (12 /
+// 24 KB of LDS, at most 160 registers) is held a second time with an allocation that admits a third (launch_pass_model instantiates it
+// beside KEEP and the store flavour).  The staged rows need 72 KB of LDS at 16-deep tiles: a third workgroup never fits.
+constexpr int pass_form_max_res(const PassForm& f) { return f.dop ? 3 : 2; }
 struct PassResolved {
     const PassForm* row = nullptr;      // null: no form for this model and shape
     int sw = 0, ks = 1;
+    int res = 2;                        // resident workgroups per CU granted
     explicit operator bool() const { return row != nullptr; }
 };
 
@@ -209,7 +216,8 @@ inline const PassForm* find_form(const PassShape& s, int sw, bool sliced, int ns
 //   2. K tiles of 16              (only with three stages and unsplit);
 //   3. two column sub-tiles       (SW = 2, unsplit, three stages, M % 256 == 0; keeps the K-tile depth granted);
 //   4. the K range in two halves  (so: ct = 2 before hs = 2; unsplit, three stages);
-//   5. De / Do from L2            (so: hs = 2 before dop; 16-deep, unsplit, one sub-tile, three stages, the fragment copy in place).
+//   5. De / Do from L2            (so: hs = 2 before dop; 16-deep, unsplit, one sub-tile, three stages, the fragment copy in place);
+//   6. three resident workgroups  (last: only with a row that takes De / Do from L2, pass_form_max_res; it picks no other row).
 // A want no row holds is dropped, never the launch: SW = NS and SW = 3 have the plain form only.
 inline PassResolved resolve_form(const PassWants& w, const PassShape& s) {
     PassResolved r;
@@ -225,6 +233,7 @@ inline PassResolved resolve_form(const PassWants& w, const PassShape& s) {
     r.row = find_form(s, w.sw, sliced, nst, bk, ct, hs, dop);
     r.sw = w.sw;
     r.ks = w.ks;
+    r.res = (w.res == 3 && r.row && pass_form_max_res(*r.row) >= 3) ? 3 : 2;
     return r;
 }
 
@@ -238,7 +247,7 @@ struct PassPolicyIn {
     bool f32 = false, symmetric = false, has_dfrag = false;
     // the options (emi_set_option), as the context holds them
     int allow_fused = 1, overlap_mode = 0, sym_ct = 0, sym_ksplit = 0, sym_cpart = 0, sym_gblk = 0, sym_cx = 0, sym_nst = 3, sym_hs = 0, sym_ctc = 0,
-        sym_bk = 0, sym_dop = 0, pass_order = -1, node_store = -1, slice = 0, small_rows = 24;
+        sym_bk = 0, sym_dop = 0, sym_res = 0, pass_order = -1, node_store = -1, slice = 0, small_rows = 24;
 };
 
 // the even/odd MFMA defect kernel beside the node kernel (or both roles in one launch): needs an exactly centro-antisymmetric D
@@ -286,6 +295,9 @@ enum PassBandNeeds : unsigned {
     BAND_FREE_DEPTH = 4u,   // "sym_bk" unset and three ring stages ("sym_nst")
     BAND_FREE_ORDER = 8u,   // "pass_order" unset
     BAND_DEFAULT = 16u,     // built-in model, default dispatch
+    BAND_FREE_RES = 32u,    // "sym_res" unset and neither "sym_dop" 1 nor K halves, wide tiles or K slices asked for: free to state three resident
+                            // workgroups (a row whose order and operand source were measured with them; otherwise it stands back and the row
+                            // behind it, measured with two, holds the launch)
 };
 enum PassKsRule {
     KS_UNSPLIT,
@@ -306,6 +318,7 @@ struct PassBand {
     int bk;             // K-tile depth
     int dop;            // operand source: 1 De / Do through the ring, 2 straight from L2
     int order;          // block order (pass_role_of): 1 MFMA workgroups first, 0 evenly interleaved, >= 100: at that % of the even density
+    int res = 2;        // resident workgroups per CU the launch states ("sym_res"): 3 only beside dop 2, and only where it was measured ahead
 };
 constexpr unsigned BAND_DEEP = BAND_DEFAULT | BAND_FREE_DEPTH;
 inline constexpr PassBand PASS_BANDS[] = {
@@ -322,6 +335,13 @@ inline constexpr PassBand PASS_BANDS[] = {
     // (deep_mid, which began at 64 tiles).
     // (both for an even number of states above two, where they were measured: the 6-state quadrotor)
     {33, 48, BAND_DEEP | BAND_FREE_KS | BAND_EVEN_NS, 7, KS_UNSPLIT, 16, 1, 1},            // deep_small
+    // Three resident workgroups per CU ("sym_res" 3: the direct-operator form with a register allocation that admits a third wave per SIMD,
+    // 768 places on the chip instead of 512) at 80 tiles (145 .. 160 instances): the first size whose workgroups of both roles (240 + 320) are no
+    // longer all resident at two per CU.  One box each, ms per pass median (min - max), deep_mid / direct form, three resident, MFMA workgroups
+    // first (profiles/residency_sweep.jsonl, profiles/residency_notes.md section 3): 152 instances 0.0334 (0.0334 - 0.0334) / 0.0310 (0.0309 -
+    // 0.0311), 160: 0.0333 (0.0333 - 0.0333) / 0.0311 (0.0311 - 0.0312), and 0.0342 (0.0342 - 0.0343) / 0.0312 (0.0311 - 0.0314) on another box.
+    // Not at 144 (0.0271 either way) nor at 176 (0.0408 / 0.0425) and 192 (0.0411 / 0.0439).
+    {80, 80, BAND_DEEP | BAND_FREE_KS | BAND_EVEN_NS | BAND_FREE_RES, 6, KS_UNSPLIT, 16, 2, 1, 3},     // deep_mid, three resident
     {49, 127, BAND_DEEP | BAND_FREE_KS | BAND_EVEN_NS, 6, KS_UNSPLIT, 16, 1, 1},           // deep_mid
     // ... and between 144 and 207 tiles (288 .. 415 instances) TOGETHER with the MFMA workgroups at 1.5 x the even density instead of all
     // of them first: from ~300 instances the role's 3 x tiles workgroups no longer fit beside the node role (64 places per XCD), which then
@@ -343,6 +363,17 @@ inline constexpr PassBand PASS_BANDS[] = {
     // 0.1412, 1024: 0.1879 / 0.1836, 1536: 0.2790 / 0.2735, 2048: 0.3771 / 0.3671.  Below that neither form is ahead: the pass time moves with how
     // the workgroups of the two roles fill the chip, not with the K loop (128: 0.0261 / 0.0262, 176: 0.0412 / 0.0392, 224: 0.0425 / 0.0434, 288:
     // 0.0614 / 0.0631, 352: 0.0774 / 0.0714, 416: 0.0824 / 0.0835; SW = 1: 80 instances 0.0192 / 0.0208, 96: 0.0246 / 0.0240), so those stay.
+    // ... with three resident workgroups per CU and the MFMA workgroups at 1.1 x the even density from 512 tiles (1024 .. 2048 instances): node
+    // workgroups that wait on the write stream no longer hold the places MFMA workgroups could compute in.  One box, timed regions of 0.4 s, five
+    // interleaved rounds, ms per pass median (min - max), shipped choice (two resident; 1.1 x up to 1535 instances, even from there) / three
+    // resident at 1.1 x (profiles/residency_sweep.jsonl, "sweep": "large"): 1024 instances 0.1794 (0.1793 - 0.1796) / 0.1747 (0.1744 - 0.1748),
+    // 1152: 0.2007 (0.2005 - 0.2008) / 0.1950 (0.1948 - 0.1951), 1280: 0.2219 (0.2217 - 0.2221) / 0.2150 (0.2148 - 0.2151), 1536: 0.2669 (0.2666 -
+    // 0.2670) / 0.2555 (0.2554 - 0.2556), 1792: 0.3101 (0.3100 - 0.3106) / 0.2963 (0.2962 - 0.2972), 2048: 0.3541 (0.3537 - 0.3545) / 0.3367 (0.3366 -
+    // 0.3370): 2.6 - 4.9 %, 13 - 27 times the shipped choice's spread, every run below every run.  Two resident at 1.1 x from 1536 instances gains
+    // 0 - 1 % only, so it is the residency.  Not below: 768 instances 0.1371 / 0.1361 (twice the spread), 896: 0.1581 / 0.1553 with one run of
+    // the five at 0.1685; at 432 and 512 nothing is gained at any of five orders (0.0854 / 0.0849 and 0.0981 / 0.0995 at best).
+    // (for an even number of states above two, where it was measured, and unless an option says otherwise: BAND_FREE_RES)
+    {512, 1024, BAND_DEEP | BAND_FREE_ORDER | BAND_EVEN_NS | BAND_FREE_RES, 6, KS_BY_WORKGROUPS, 16, 2, 110, 3},   // deep_large, De / Do from L2, three resident
     {216, 383, BAND_DEEP | BAND_FREE_ORDER, 6, KS_BY_WORKGROUPS, 16, 2, 125},              // deep_large, De / Do from L2
     {384, 767, BAND_DEEP | BAND_FREE_ORDER, 6, KS_BY_WORKGROUPS, 16, 2, 110},
     {768, 1024, BAND_DEEP | BAND_FREE_ORDER, 6, KS_BY_WORKGROUPS, 16, 2, 0},
@@ -382,6 +413,8 @@ inline const PassBand& band_for(const PassPolicyIn& in, int tiles16, bool auto_c
     if (in.sym_ksplit == 0) met |= BAND_FREE_KS;
     if (in.sym_bk == 0 && in.sym_nst == 3) met |= BAND_FREE_DEPTH;
     if (in.pass_order < 0) met |= BAND_FREE_ORDER;
+    // (three resident workgroups come with the direct form only: an option that takes that form away -- resolve_form -- takes the row away)
+    if (in.sym_res == 0 && in.sym_dop != 1 && in.sym_hs <= 1 && in.sym_ctc <= 1 && in.sym_ksplit <= 1) met |= BAND_FREE_RES;
     if (auto_ct && in.model_class == PASS_MODEL_BUILTIN) met |= BAND_DEFAULT;
     const PassBand* b = PASS_BANDS;
     while (!(tiles16 >= b->lo && tiles16 <= b->hi && (b->needs & ~met) == 0)) ++b;      // (the unconditional rows hold every launch)
@@ -412,11 +445,12 @@ inline SymPlan plan_tiles(const PassPolicyIn& in, int B, const PassWants& w, con
     p.ct = f.ct;
     p.hs = f.hs;
     p.dop = f.dop;
+    p.res = r.res;
     return p;
 }
 
 // Every choice can be forced through emi_set_option (sym_ct, sym_ksplit, sym_cpart, sym_gblk, sym_cx, sym_nst, sym_bk, sym_ctc, sym_hs,
-// sym_dop, pass_order, node_store); a run-time compiled model is planned within its two instantiations.
+// sym_dop, sym_res, pass_order, node_store); a run-time compiled model is planned within its two instantiations.
 inline PassPlan plan_pass(const PassPolicyIn& in, int B, bool jac) {
     PassPlan p;
     p.tiles16 = pass_tiles16(in, B);
@@ -444,6 +478,7 @@ inline PassPlan plan_pass(const PassPolicyIn& in, int B, bool jac) {
     w.ct = in.sym_ctc ? in.sym_ctc : (wide_large ? PASS_LARGE_BATCH.ct : 1);
     w.hs = in.sym_hs ? in.sym_hs : 1;
     w.dop = (in.sym_dop ? in.sym_dop : band.dop) == 2;
+    w.res = (in.sym_res ? in.sym_res : band.res) == 3 ? 3 : 2;
     // (the grouped order by default: not for a built-in model whose K slices an option set)
     const int gblk = (large && in.sym_gblk == 0 && (rtc || (auto_ct && w.ks == 1))) ? PASS_LARGE_BATCH.gblk : in.sym_gblk;
     // 3. the form that exists, and its tiles
@@ -490,9 +525,10 @@ inline int plan_piece(const PassPolicyIn& in, int B) {
 }
 
 // what emi_plan_pass reports for a batch of B instances (*out zeroed by the caller); *dop: the operand source of the form, which the
-// report has no field for
-inline void report_pass(const PassPolicyIn& in, int B, emi_pass_plan_t* out, bool* dop = nullptr) {
+// report has no field for, *res: the resident workgroups per CU it states, likewise (0: the pass does not go out as one launch)
+inline void report_pass(const PassPolicyIn& in, int B, emi_pass_plan_t* out, bool* dop = nullptr, int* res = nullptr) {
     if (dop) *dop = false;
+    if (res) *res = 0;
     if (!pass_overlapped(in)) return;
     const int piece = plan_piece(in, B);
     out->piece = piece;
@@ -512,6 +548,7 @@ inline void report_pass(const PassPolicyIn& in, int B, emi_pass_plan_t* out, boo
     out->block_order = p.mfma_first;
     out->tiles16 = p.tiles16;
     if (dop) *dop = p.sym.dop;
+    if (res) *res = p.one_launch ? p.sym.res : 0;
 }
 
 }  // namespace emi

@@ -111,7 +111,7 @@ static hipError_t launch_ring2_planned(const SymDefectArgs& a, hipStream_t s, co
 // ---------------------------------------------------------------------------------------------
 // the pass as one launch (emi_pass_f64_kernel): MFMA-role and node-role workgroups interleaved per XCD
 template <class Model, int SW, int NST, int BK = 8, int CT = 1, int HS = 1, bool DOP = false>
-static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s) {
+static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, int res) {
     constexpr int NS = Model::NS;
     PassArgs a;
     a.s = sa;
@@ -133,21 +133,33 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     // dispatch chooses: three ring stages, undivided K range.  The forms only an option reaches write everything, which is always right.
     constexpr bool HAS_KEEP = NST == 3 && HS == 1;
     const bool keep = HAS_KEEP && na.keep;
-    auto pick = [&](auto keep_c) {
+    // Three resident workgroups per CU (SymPlan::res, "sym_res"): the same kernel with a register allocation that admits a third wave per
+    // SIMD, held for the direct-operator forms only (a staged form's LDS never admits a third workgroup); anything else states two.
+    const bool res3 = DOP && res == 3;
+    auto pick = [&](auto keep_c, auto res_c) {
         constexpr bool K = decltype(keep_c)::value;
-        return st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS, K, DOP>
-             : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS, K, DOP>
-                        : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS, K, DOP> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS, K, DOP>));
+        constexpr int R = decltype(res_c)::value;
+        return st == 2 ? emi_pass_f64_kernel<Model, SW, 2, 2, NST, BK, CT, HS, K, DOP, R>
+             : (st == 1 ? emi_pass_f64_kernel<Model, SW, 2, 1, NST, BK, CT, HS, K, DOP, R>
+                        : (st == 3 ? emi_pass_f64_kernel<Model, SW, 2, 3, NST, BK, CT, HS, K, DOP, R> : emi_pass_f64_kernel<Model, SW, 2, 0, NST, BK, CT, HS, K, DOP, R>));
     };
-    auto kern = pick(std::false_type{});
+    using res2_t = std::integral_constant<int, 2>;
+    using res3_t = std::integral_constant<int, 3>;
+    auto kern = pick(std::false_type{}, res2_t{});
     if constexpr (HAS_KEEP) {
-        if (keep) kern = pick(std::true_type{});
+        if (keep) kern = pick(std::true_type{}, res2_t{});
     }
-    static bool attr_done[2][4] = {};
-    if (!attr_done[keep][st]) {
+    if constexpr (DOP) {
+        if (res3) kern = pick(std::false_type{}, res3_t{});
+        if constexpr (HAS_KEEP) {
+            if (res3 && keep) kern = pick(std::true_type{}, res3_t{});
+        }
+    }
+    static bool attr_done[2][2][4] = {};
+    if (!attr_done[res3][keep][st]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        attr_done[keep][st] = true;
+        attr_done[res3][keep][st] = true;
     }
     hipLaunchKernelGGL(kern, dim3(8 * (a.nm8 + a.nn8)), dim3(256 * HS), lds, s, a);
     return hipGetLastError();
@@ -161,7 +173,7 @@ static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<do
 #define EMI_PASS_FORM_LAUNCH(CLS, NST, BK, CT, HS, DOP, SLICES, STORES)                                                                   \
     if constexpr (pass_class_applies(CLS, NS)) {                                                                                          \
         if (p.sw == pass_class_sw(CLS, NS) && p.nst == NST && p.bk == BK && p.ct == CT && p.hs == HS && p.dop == DOP && (SLICES || p.ks == 1)) \
-            return launch_pass_model<Model, pass_class_sw(CLS, NS), NST, BK, CT, HS, DOP>(sa, na, s);                                    \
+            return launch_pass_model<Model, pass_class_sw(CLS, NS), NST, BK, CT, HS, DOP>(sa, na, s, p.res);                             \
     }
     EMI_PASS_FORMS(EMI_PASS_FORM_LAUNCH)
 #undef EMI_PASS_FORM_LAUNCH

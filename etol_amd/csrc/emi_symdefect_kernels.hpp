@@ -1009,12 +1009,18 @@ __global__ __launch_bounds__(256) void emi_symdefect_combine_kernel(SymDefectArg
 // count of this kernel swings with details of the source (the 128-column form came out at 224 or at 280 registers for the same
 // arithmetic) -- beyond 256 only ONE workgroup fits a CU and the roles no longer overlap.
 // (The all-states form, SW > 3, holds 96 accumulator registers and has always run one workgroup per CU.)
-#define EMI_PASS_OCC __attribute__((amdgpu_waves_per_eu(SW > 3 ? 1 : 2, 2)))
+// RES states the resident workgroups per CU (= waves per SIMD) of a launch: 2, or 3 for the direct-operator forms, whose 24 KB (SW = 2) /
+// 12 KB (SW = 1) of LDS and 160 / 128 registers leave a third workgroup room -- (2, 2) makes the compiler pad the allocation so that none
+// fits.  (2, 3) caps the allocation at 168 registers, silently no longer once the source needs more: `make check-pass-registers` holds
+// every instantiation to what it states.
+#define EMI_PASS_OCC __attribute__((amdgpu_waves_per_eu(SW > 3 ? 1 : 2, RES)))
 #endif
 // KEEP: the node role leaves the model-invariant VALS rows as an earlier full pass wrote them (emi_nodes_body); the MFMA role is the same.
 // DOP: the MFMA role takes its De / Do fragments straight from L2 (emi_ring2_body); the node role is the same.
-template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool KEEP = false, bool DOP = false>
+// RES: resident workgroups per CU the launch states (2; 3: DOP only).  Same code, a smaller register allocation.
+template <class Model, int SW, int VEC, int ST, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool KEEP = false, bool DOP = false, int RES = 2>
 __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(PassArgs a) {
+    static_assert(RES == 2 || (RES == 3 && DOP), "three resident workgroups per CU: direct-operator forms only");
 #ifdef EMI_ENTRY_PAD_NOPS      // build-time experiment (tools/ab_build.sh): shift the whole instruction stream by 4-byte steps
     asm volatile(".rept " EMI_STR(EMI_ENTRY_PAD_NOPS) "\n\ts_nop 0\n\t.endr" ::: "memory");
 #endif

@@ -984,6 +984,12 @@ class Evaluator:
         self._ck(self.lib.emi_plan_pass(self.ctx, int(B if B is not None else self.layout.B), C.byref(p)), "emi_plan_pass")
         return {n: getattr(p, n) for n, _ in L.PassPlan._fields_}
 
+    def plan_residency(self, B=None):
+        """Resident workgroups per CU the (first) launch of plan(B) states: 2 or 3; 0 where the pass does not go out as one launch."""
+        res = C.c_int(0)
+        self._ck(self.lib.emi_plan_pass_residency(self.ctx, int(B if B is not None else self.layout.B), C.byref(res)), "emi_plan_pass_residency")
+        return res.value
+
     @property
     def last_defect_kernel(self):
         return self.lib.emi_last_defect_kernel(self.ctx).decode()

@@ -901,6 +901,9 @@ typedef struct emi_pass_plan {
   int k_halves;        /* 2: the K range of a tile in two halves inside a 512-thread workgroup */
 } emi_pass_plan_t;
 int emi_plan_pass(emi_ctx_t ctx, int B, emi_pass_plan_t* out);
+/* ... and what the report has no field for: the resident workgroups per CU the (first) launch of that plan states ("sym_res": 2,
+ * or 3, which only the forms that take De / Do straight from L2 are granted); *res = 0 where the pass does not go out as one launch. */
+int emi_plan_pass_residency(emi_ctx_t ctx, int B, int* res);
 
 /* COO pattern of VALS in per-instance NLP numbering:
  * rows/cols have nvals*M entries ordered like VALS; cost-gradient entries

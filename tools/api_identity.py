@@ -11,6 +11,9 @@ commit's and the changed one, each with its own built library -- and compare wha
                                                    with err and out) and of the moving-disc ladder and refinement of
                                                    tests/track_ladder_ref.py, default options, each with the context the call left:
                                                    what a change behind an option that is off, or to the drivers, must keep
+   ... plan / results / times OUT.json name=value ...   with these options set on every context first: a default that moved behind an
+                                                   option is compared with the parent through the option value that restores the
+                                                   parent's choice ("sym_res=2": two resident workgroups per CU in every band)
    python tools/api_identity.py compare PARENT.json BRANCH.json [OUT.json]     equal or not, case by case ("report_only": the cases
                                                    that differ in REPORT_ONLY fields alone, see there)
 
@@ -33,6 +36,7 @@ FORCED = {"sym_ct": range(0, 9), "sym_ksplit": (0, 1, 2, 4, 8), "sym_bk": (0, 8,
           "sym_nst": (3, 4), "sym_cpart": (-1, 0, 1, 2, 4, 8), "sym_gblk": (0, 1, 2, 4, 8, 64), "pass_order": (-1, 0, 1, 100, 125, 150),
           "node_store": (-1, 0, 1, 2, 3), "overlap_mode": (0, 1, 2, 3), "slice": (0, 16, 256, 1024), "sym_dop": (0, 1, 2), "sym_cx": (0, 1, 2)}
 DEFAULTS = {"sym_nst": 3, "sym_cpart": 0, "pass_order": -1, "node_store": -1}
+BASE = {}       # options set on every context before anything else (name=value arguments)
 
 
 def batches(M):
@@ -68,6 +72,8 @@ def plan_grid():
             ev = E.Evaluator(0)
             ev.set_mesh(M, 0.0, 2.0)
             ev.set_model(model, params)
+            for k, v in BASE.items():
+                ev.set_option(k, v)
             for opt, value in [(None, None)] + [(o, v) for o, vs in FORCED.items() for v in vs]:
                 if opt:
                     ev.set_option(opt, value)
@@ -154,7 +160,7 @@ def run_case(c):
         recs = rep(recs)
         recs[:, :, 1] += 0.001 * np.arange(B)[:, None]           # a table per instance: a piece must read its own
         ev.set_path(recs, 0, 1)
-    for k, v in c.get("opts", {}).items():
+    for k, v in {**BASE, **c.get("opts", {})}.items():
         ev.set_option(k, v)
     lay = ev.layout
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if f32 else np.float64)).cuda()
@@ -262,6 +268,8 @@ def times():
         ev.set_mesh(1024, 0.0, 2.0)
         ev.set_model(E.MODEL_QUADROTOR2D, W.QUAD_PARAMS)
         ev.set_batch(B)
+        for k, v in BASE.items():
+            ev.set_option(k, v)
         X, U, _ = W.quadrotor_batch(2, min(B, 16), 1024, 0)
         dX, dU = (torch.from_numpy(a).cuda().repeat((B + 15) // 16, 1, 1)[:B].contiguous() for a in (X, U))
         outs = ev.alloc_outputs()
@@ -441,6 +449,7 @@ if __name__ == "__main__":
                 text = re.sub(flat, lambda m: m.group(0)[0] + " ".join(m.group(1).split()) + m.group(0)[-1], text)
             open(sys.argv[4], "w").write(text + "\n")
         sys.exit(0 if rep["verdict"] == "identical" else 1)
+    BASE.update({k: int(v) for k, v in (arg.split("=") for arg in sys.argv[3:])})
     res = plan_grid() if mode == "plan" else times() if mode == "times" else lockstep() if mode == "lockstep" else {name: run_case(c) for name, c in CASES.items()}
     json.dump(res, open(sys.argv[2], "w"), indent=1 if mode != "plan" else None, sort_keys=True)
     print(mode, len(res), "entries ->", sys.argv[2], hashlib.sha256(json.dumps(res, sort_keys=True).encode()).hexdigest()[:16])

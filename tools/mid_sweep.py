@@ -171,8 +171,20 @@ FORMS = {
     # De / Do of the MFMA role through the operand ring (1) or straight from L2 (2), in whatever form the default dispatch takes; the role alone
     "dop1": dict(sym_dop=1), "dop2": dict(sym_dop=2), "dop1_node_off": dict(sym_dop=1, sym_ablate=32), "dop2_node_off": dict(sym_dop=2, sym_ablate=32),
     "dop1_node_off_epi_off": dict(sym_dop=1, sym_ablate=36), "dop2_node_off_epi_off": dict(sym_dop=2, sym_ablate=36),
+    # resident workgroups per CU stated ("sym_res" 2 / 3), in whatever form the default dispatch takes; the MFMA role alone
+    "res2": dict(sym_res=2), "res3": dict(sym_res=3), "res2_node_off": dict(sym_res=2, sym_ablate=32), "res3_node_off": dict(sym_res=3, sym_ablate=32),
 }
-RESET = dict(small_rows=24, overlap_mode=0, sym_ct=0, pass_order=-1, slice=0, node_store=-1, sym_cpart=0, sym_gblk=0, sym_cx=0, sym_nst=3, sym_ksplit=0, sym_ablate=0, sym_bk=0, sym_ctc=0, sym_hs=0, sym_dop=0)
+# ... crossed with the block order and the operand source: r<res>_d<dop>_o<order> (order "first" = MFMA workgroups first).  Wants on the
+# default dispatch (overlap_mode 0), two states per workgroup and unsplit at every batch size, WITH "sym_bk" 16: "pass_order" alone falls back to
+# the bands that were measured with any order, whose K tiles are 8 deep (profiles/r05_notes.md section 5).  Three resident workgroups are
+# granted with "sym_dop" 2 only, so r3_d1 is not a form.
+RES_ORDERS = {"first": 1, "100": 100, "110": 110, "125": 125, "150": 150}
+for _res, _dop in ((2, 1), (2, 2), (3, 2)):
+    for _oname, _order in RES_ORDERS.items():
+        FORMS[f"r{_res}_d{_dop}_o{_oname}"] = dict(sym_ct=6, sym_bk=16, sym_dop=_dop, sym_res=_res, pass_order=_order)
+RES_SWEEP = ["default"] + [f for f in FORMS if f.startswith(("r2_d", "r3_d"))]     # --forms res_sweep
+RESET = dict(small_rows=24, overlap_mode=0, sym_ct=0, pass_order=-1, slice=0, node_store=-1, sym_cpart=0, sym_gblk=0, sym_cx=0, sym_nst=3, sym_ksplit=0, sym_ablate=0, sym_bk=0, sym_ctc=0, sym_hs=0, sym_dop=0,
+             sym_res=0)
 
 
 def main():
@@ -205,9 +217,9 @@ def main():
         if a.touch:
             ev.use_stream(torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
-        forms = [f for f in a.forms.split(",") if f]
+        forms = [g for f in a.forms.split(",") if f for g in (RES_SWEEP if f == "res_sweep" else [f])]
         times = {f: [] for f in forms}
-        names = {}
+        names, resident, orders = {}, {}, {}
         t_end = time.perf_counter() + 0.3
         while time.perf_counter() < t_end:          # clocks up
             ev.eval_dev(dX, dU, *outs)
@@ -230,11 +242,13 @@ def main():
                 ev.synchronize()
                 times[f].append((time.perf_counter() - t0) / steps)
                 names[f] = ev.last_defect_kernel
+                resident[f] = ev.plan_residency()
+                orders[f] = ev.plan()["block_order"]
         with open(a.out, "a") as fo:
             for f in forms:
                 ms = 1e3 * float(np.median(times[f]))
                 rec = dict(B=B, M=M, form=f, rotate=a.rotate, touch=a.touch, ms_per_pass=round(ms, 5), node_evals_per_s=float("%.4g" % (B * M / (ms * 1e-3))),
-                           kernel=names[f], rounds=a.rounds, ms_min=round(1e3 * min(times[f]), 5), ms_max=round(1e3 * max(times[f]), 5))
+                           kernel=names[f], resident=resident[f], block_order=orders[f], rounds=a.rounds, ms_min=round(1e3 * min(times[f]), 5), ms_max=round(1e3 * max(times[f]), 5))
                 fo.write(json.dumps(rec) + "\n")
                 print(f"B={B:6d} {f:16s} {ms:9.4f} ms  {rec['node_evals_per_s']:.3e}/s  {names[f][:60]}", flush=True)
         ev.close()
