@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-ode-delay-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -71,7 +71,7 @@ $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
 HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp tests/harness/etol_harness_rescue.cpp \
-               tests/harness/etol_harness_ode_error.cpp tests/harness/etol_harness_track_ladder.cpp
+               tests/harness/etol_harness_ode_error.cpp tests/harness/etol_harness_track_ladder.cpp tests/harness/etol_harness_delay_ode_error.cpp
 tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR) $(CSRC)/emi_ipm_control.hpp
 	$(CXX) $(CXXFLAGS) -I$(HOST) -I$(CSRC) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
@@ -129,6 +129,12 @@ ODE_OP_CHECK_OUT ?= $(LIBDIR)/ode_operator_check
 check-ode-operator: tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -std=c++17 -Iinclude -o $(ODE_OP_CHECK_OUT) tests/harness/ode_operator_main.cpp $(CSRC)/emi_host.cpp -lm
 	$(ODE_OP_CHECK_OUT)
+
+# the operator of one delay between the nodes (emi_ode_error_delay_operator, csrc/emi_host.cpp: host-only), the same way
+ODE_DEL_CHECK_OUT ?= $(LIBDIR)/ode_delay_operator_check
+check-ode-delay-operator: tests/harness/ode_delay_operator_main.cpp $(CSRC)/emi_host.cpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -ffp-contract=off -std=c++17 -Iinclude -o $(ODE_DEL_CHECK_OUT) tests/harness/ode_delay_operator_main.cpp $(CSRC)/emi_host.cpp -lm
+	$(ODE_DEL_CHECK_OUT)
 
 # the planned route (emi_plan_route, csrc/emi_host.cpp with csrc/emi_plan_route.hpp: host-only) on the fixtures of tests/golden as a
 # stand-alone program under the host sanitizers

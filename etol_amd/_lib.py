@@ -170,6 +170,9 @@ SYMBOLS = {
     "emi_interp_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "emi_ode_error_dev": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
     "emi_ode_error_host": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
+    "emi_ode_error_delay_operator": (C.c_int, [C.c_int, _D, _D, C.c_double, C.c_double, C.c_double, _D]),
+    "emi_ode_error_total_dev": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
+    "emi_ode_error_total_host": (C.c_int, [_P, _P, _P, _D, _D, _P, _P]),
     "emi_ipm_refine_decide": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _I]),
     "emi_prolong_rows_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "emi_shard_move_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _I, C.POINTER(_P), _I, C.POINTER(_P), _I, C.c_int]),

@@ -278,6 +278,7 @@ int emi_set_mesh(emi_ctx_t c, int M, const double* tau, const double* w, const d
     c->adj_dirty = true;
     c->ode_dirty = true;
     c->delay_dirty = true;      // W(delay) is built for one mesh: [nd][M][M] on these nodes and this horizon
+    c->odel_dirty = true;       // ... and so are the delayed blocks of the ODE-error operator
     c->adjw_dirty = true;
     emi::kkt_mesh_changed(c->kkt);
     for (emi::KktWorkspace* w : c->kkt_shard) emi::kkt_mesh_changed(w);
@@ -392,6 +393,7 @@ int emi_set_delays(emi_ctx_t c, int x_horizon, int u_horizon, double dt) {
     c->nch = c->nc - rest / (1 + u_horizon);
     c->delay_dt = dt;
     c->delay_dirty = true;
+    c->odel_dirty = true;
     c->adjw_dirty = true;
     return EMI_OK;
 }

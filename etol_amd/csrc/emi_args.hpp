@@ -102,6 +102,23 @@ template <typename T> struct OdeResidArgs {
     ModelParams<T> P;
 };
 
+// ... of a context with delays (emi_ode_resid_delay_kernel): the model's NC inputs are the ncf free controls, then the delayed slots
+// in the order of emi_set_delays.  Zs rows hold [E x | E' x | D x | Edel(dt) x | .. | Edel((xh-1) dt) x] (2 np + M + (xh-1) np
+// columns), Zc rows (instance, FREE control) hold [E u | Edel(dt) u | .. | Edel(uh dt) u] ((1 + uh) np columns); np = 5 (M-1)
+template <typename T> struct OdeResidDelayArgs {
+    const T* Zs;        // [B*ns][lds]
+    const T* Zc;        // [B*ncf][ldc]
+    const T* tq;
+    const T* scale;
+    const T* ul;        // [ncf] bounds of the free controls (a delayed copy is clipped with its source's); null: no clip
+    const T* uu;
+    T* eta;             // [B][ns][M-1]
+    int M, B, lds, ldc;
+    int ncf, ns, xh, uh;
+    T h;
+    ModelParams<T> P;
+};
+
 struct SymDefectArgs {
     const double* X;
     const double* U;

@@ -144,6 +144,11 @@ struct emi_ctx_s {
     emi::DeviceArray<double> d_ode_tq;      // [5 (M-1)] times of the points, then [M-1] interval scales (tau_k+1 - tau_k) / 2 * h
     emi::DeviceArray<double> d_ode_ub;      // [2][nc]: ul, uu
     emi::DeviceArray<double> d_ode_ws;      // [B ns][2 * 5 (M-1) + M] | [B nc][5 (M-1)] | eta [B][ns][M-1]
+    // ... of a context with delays (emi_ode_error_total_*): the stacked operators of the mesh and the delays in force, rows of the
+    // same even length; the workspace above holds [B ns][(2 + max(xh-1, 0)) 5 (M-1) + M] | [B ncf][(1 + uh) 5 (M-1)] | eta then
+    bool odel_dirty = true;     // the stacks must be rebuilt (set wherever ode_dirty or delay_dirty is)
+    emi::DeviceArray<double> d_odel_ops;    // [E | E' | D | Edel(dt) .. Edel((xh-1) dt)]: the state rows' operator
+    emi::DeviceArray<double> d_odel_opc;    // [E | Edel(dt) .. Edel(uh dt)]: the free controls'
     // node blocks of the Newton step (emi_kkt_blocks_*): the (variable, VALS entry) pairs of the path rows, the per-entry term
     // lists built from them (uploaded once per list) and the workspace of the kernels, grown on demand
     bool blk_rows_set = false;          // emi_kkt_blocks_rows was called (else: the layout's default for table rows)

@@ -122,10 +122,11 @@ int emi_model_dims(int model, int* ns, int* nc, int* nparams) {
 // Gauss-Legendre points of every mesh interval; point p = q (M-1) + k is Gauss point q of [tau_k, tau_k+1] (include/emi355x.h).
 // tq[p] is rounded to double first and the operator is that of the rounded abscissa, formed in extended precision:
 //   lam_j = (-1)^j sqrt(w_j) / (s - tau_j),  E_j = lam_j / sum lam,  E'_j = (E_j sum_i lam_i / (s - tau_i) - lam_j / (s - tau_j)) / sum lam
+static const long double gx[5] = {-0.906179845938663992797626878299392965L, -0.538469310105683091036314420700208805L, 0.0L,
+                                  0.538469310105683091036314420700208805L, 0.906179845938663992797626878299392965L};
+
 int emi_ode_error_operator(int M, const double* tau, const double* w, double* E, double* Ed, double* tq) {
     if (M < 2 || !tau || !w || !E || !Ed || !tq) return EMI_ERR_ARG;
-    static const long double gx[5] = {-0.906179845938663992797626878299392965L, -0.538469310105683091036314420700208805L, 0.0L,
-                                      0.538469310105683091036314420700208805L, 0.906179845938663992797626878299392965L};
     const int nq = M - 1;
     std::vector<long double> sw(M), lam(M);
     for (int j = 0; j < M; ++j) sw[j] = ((j & 1) ? -1.0L : 1.0L) * sqrtl((long double)w[j]);
@@ -145,6 +146,42 @@ int emi_ode_error_operator(int M, const double* tau, const double* w, double* E,
                 E[(size_t)p * M + j] = (double)e;
                 Ed[(size_t)p * M + j] = (double)((e * T - lam[j] / (s - (long double)tau[j])) / S);
             }
+        }
+    return EMI_OK;
+}
+
+// The operator of one delay between the nodes: row p of Edel is the Lagrange basis of the mesh at the node coordinate of
+// max(t_p - delay, t0), t_p = t0 + h (s_p + 1) the time of point p of emi_ode_error_operator (the same rounded s_p).  The shifted
+// abscissa is formed in double exactly as emi_delay_matrix forms it at a node (one clamp for both), the row in extended precision
+// in barycentric form; a time at or before t0 gives e_0, an abscissa that is a node exactly gives that node's unit row.
+int emi_ode_error_delay_operator(int M, const double* tau, const double* w, double t0, double tf, double delay, double* Edel) {
+    if (M < 2 || !tau || !w || !Edel || !(tf > t0) || !(delay >= 0)) return EMI_ERR_ARG;
+    const int nq = M - 1;
+    const double hh = (tf - t0) / 2.0;
+    std::vector<long double> sw(M), lam(M);
+    for (int j = 0; j < M; ++j) sw[j] = ((j & 1) ? -1.0L : 1.0L) * sqrtl((long double)w[j]);
+    for (int q = 0; q < 5; ++q)
+        for (int k = 0; k < nq; ++k) {
+            const double sp = (double)((long double)tau[k] + 0.5L * ((long double)tau[k + 1] - (long double)tau[k]) * (gx[q] + 1.0L));
+            const double tp = t0 + hh * (sp + 1.0);
+            double ts = tp - delay;
+            if (ts < t0) ts = t0;
+            const double x = (ts - t0) / hh - 1.0;
+            double* row = Edel + (size_t)(q * nq + k) * M;
+            int hit = -1;
+            for (int j = 0; j < M; ++j)
+                if (x == tau[j]) hit = j;
+            if (ts <= t0) hit = 0;
+            if (hit >= 0) {
+                for (int j = 0; j < M; ++j) row[j] = j == hit ? 1.0 : 0.0;
+                continue;
+            }
+            long double S = 0.0L;
+            for (int j = 0; j < M; ++j) {
+                lam[j] = sw[j] / ((long double)x - (long double)tau[j]);
+                S += lam[j];
+            }
+            for (int j = 0; j < M; ++j) row[j] = (double)(lam[j] / S);
         }
     return EMI_OK;
 }

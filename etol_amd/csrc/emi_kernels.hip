@@ -393,6 +393,17 @@ hipError_t launch_ode_resid(int model, const OdeResidArgs<double>& a, hipStream_
     return hipGetLastError();
 }
 
+hipError_t launch_ode_resid_delay(int model, const OdeResidDelayArgs<double>& a, hipStream_t s) {
+    dim3 grid((a.M - 1 + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
+    switch (model) {
+        case 0: hipLaunchKernelGGL((emi_ode_resid_delay_kernel<double, PointMass2D<double>>), grid, block, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((emi_ode_resid_delay_kernel<double, Quadrotor2D<double>>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((emi_ode_resid_delay_kernel<double, FixedWing12<double>>), grid, block, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_defect_f64(const DefectArgs& a, hipStream_t s) {
     const int mtiles = (a.R + DEF_TM - 1) / DEF_TM, ntiles = (a.M + DEF_TN - 1) / DEF_TN;
     const size_t lds = (size_t)2 * (DEF_TM + DEF_TN) * (DEF_BK + 2) * sizeof(double);

@@ -119,6 +119,9 @@ hipError_t launch_ode_copy_D(const double* D, double* dst, int M, int ldk, hipSt
 hipError_t launch_ode_resid(int model, const OdeResidArgs<double>& a, hipStream_t s);
 struct RtcModel;
 hipError_t rtc_launch_ode_resid(RtcModel* m, const OdeResidArgs<double>& a, hipStream_t s);
+// ... of a context with delays (emi_ode_resid_delay_kernel)
+hipError_t launch_ode_resid_delay(int model, const OdeResidDelayArgs<double>& a, hipStream_t s);
+hipError_t rtc_launch_ode_resid_delay(RtcModel* m, const OdeResidDelayArgs<double>& a, hipStream_t s);
 struct OdeFinishArgs {
     const double* X;        // [B][ns][M]
     const double* Zs;       // [B*ns][lds]: the D x block starts at column dcol

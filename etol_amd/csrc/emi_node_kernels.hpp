@@ -470,4 +470,80 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_kernel(OdeResi
     for (int i = 0; i < NS; ++i) eo[(size_t)i * nq] = sc * acc[i];
 }
 
+// ---------------------------------------------------------------------------
+// KO for a context with delays (emi_ode_error_total_*): the model's NC inputs are the ncf free controls and then the delayed slots
+// in the order of emi_set_delays, x(t - dt) of every state .. x(t - (xh-1) dt), u(t - dt) of every free control .. u(t - uh dt).
+// Input v at point p is one value of the products: block 0 of the control product (free control), block 2 np + M + (i-1) np of
+// the state product (state delayed i steps), block i of the control product (control delayed i steps, clipped with its source's
+// bounds).  Where input v lives depends on the run-time split (ncf, ns, xh, uh) only, so it is worked out once per thread as a
+// wave-uniform offset from the state product, by a walk over the slots that is unrolled with the loop over v: off[], bnd[] and
+// z[] are indexed by compile-time values alone and stay in registers.  One thread per (instance, interval), loads coalesced along
+// k, sums in ascending q, one writer per output, no LDS -- as the kernel above, whose bits this one gives where the split is
+// (NC, NS, 0, 0).
+// ---------------------------------------------------------------------------
+template <typename T, class Model>
+__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_delay_kernel(OdeResidDelayArgs<T> a) {
+    constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV;
+    const int b = blockIdx.y, M = a.M, nq = M - 1;
+    const int k = blockIdx.x * EMI_NODE_THREADS + threadIdx.x;
+    if (k >= nq) return;
+    const T g[5] = {T(0.2369268850561891), T(0.4786286704993665), T(0.5688888888888889), T(0.4786286704993665), T(0.2369268850561891)};
+    const int np = 5 * nq;
+    const T* __restrict__ zs = a.Zs + (size_t)b * NS * a.lds + k;
+    // where input v lies, in elements from zs (the two products are parts of one workspace), and whose bounds clip it (-1: nobody's)
+    const long long czc = (a.Zc - a.Zs) + ((long long)b * a.ncf * a.ldc - (long long)b * NS * a.lds);
+    const int nxd = (a.xh > 1 ? a.xh - 1 : 0) * a.ns;
+    long long off[NC > 0 ? NC : 1];
+    int bnd[NC > 0 ? NC : 1];
+    {
+        int i = 1, r = 0;       // delay index and source row of the slot at hand
+#pragma unroll
+        for (int v = 0; v < NC; ++v) {
+            if (v < a.ncf) {
+                off[v] = czc + (long long)v * a.ldc;
+                bnd[v] = v;
+            } else if (v < a.ncf + nxd) {
+                off[v] = (long long)r * a.lds + 2 * np + M + (long long)(i - 1) * np;
+                bnd[v] = -1;
+                if (++r == a.ns) { r = 0; ++i; }
+            } else {
+                if (v == a.ncf + nxd) { i = 1; r = 0; }
+                off[v] = czc + (long long)r * a.ldc + (long long)i * np;
+                bnd[v] = r;
+                if (++r == a.ncf) { r = 0; ++i; }
+            }
+        }
+    }
+    T acc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) acc[i] = T(0);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const int p = q * nq;
+        T z[NV], f[NS], xd[NS];
+#pragma unroll
+        for (int v = 0; v < NS; ++v) {
+            z[v] = zs[(size_t)v * a.lds + p];
+            xd[v] = zs[(size_t)v * a.lds + np + p] / a.h;
+        }
+#pragma unroll
+        for (int v = 0; v < NC; ++v) {
+            T u = zs[off[v] + p];
+            if (a.ul && bnd[v] >= 0 && u - u == T(0)) {     // a finite value is clipped; a NaN or an infinity stays
+                const T lo = a.ul[bnd[v]], up = a.uu[bnd[v]];
+                u = u < lo ? lo : u;
+                u = u > up ? up : u;
+            }
+            z[NS + v] = u;
+        }
+        Model::f(a.P, z, a.tq[p + k], f);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) acc[i] += g[q] * fabs(xd[i] - f[i]);
+    }
+    const T sc = a.scale[k];
+    T* __restrict__ eo = a.eta + (size_t)b * NS * nq + k;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) eo[(size_t)i * nq] = sc * acc[i];
+}
+
 }  // namespace emi

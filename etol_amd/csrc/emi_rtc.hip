@@ -27,6 +27,7 @@ struct RtcModel {
     hipFunction_t nodes[2][2][2] = {};   // [vec2][jac][defect rows]
     hipFunction_t hess = nullptr;
     hipFunction_t ode_resid = nullptr;   // ODE-error residual at the Gauss points (f64 programs)
+    hipFunction_t ode_resid_delay = nullptr;     // ... of a context with delays
     hipFunction_t ring = nullptr;        // even/odd MFMA defect kernel (f64, LDS permitting)
     hipFunction_t pass[N_PASS_FORMS_RTC] = {};   // the pass as one launch: the rows of EMI_PASS_FORMS_RTC (emi_pass_plan.hpp)
     hipFunction_t node_nt = nullptr;     // node kernel (vec2, Jacobian, no defect rows) with non-temporal stores
@@ -49,7 +50,7 @@ size_t ring_lds_bytes(int ns) { return (size_t)3 * (2 * ns * FUSED_TI + 2 * 64) 
 bool ring_fits(int ns) { return ns <= 8 && ring_lds_bytes(ns) <= 160 * 1024; }
 
 struct Names {
-    std::string nodes[2][2][2], hess, ode_resid, ring, pass[N_PASS_FORMS_RTC], node_nt;
+    std::string nodes[2][2][2], hess, ode_resid, ode_resid_delay, ring, pass[N_PASS_FORMS_RTC], node_nt;
 };
 
 Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
@@ -63,6 +64,7 @@ Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
                                    (j ? "true" : "false") + ", " + (d ? "true" : "false") + ">";
     n.hess = "emi::emi_hess_kernel<" + T + ", " + model + ">";
     if (!f32) n.ode_resid = "emi::emi_ode_resid_kernel<double, " + model + ">";
+    if (!f32) n.ode_resid_delay = "emi::emi_ode_resid_delay_kernel<double, " + model + ">";
     if (with_ring) {
         n.ring = "emi::emi_symdefect_ring_f64_kernel<" + model + ">";
         for (int i = 0; i < N_PASS_FORMS_RTC; ++i) {       // <Model, SW, 2, stores, ring stages>: the rows hold the plain form only
@@ -76,7 +78,7 @@ Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
 }
 
 // compile; on success *code holds the gfx950 code object and *lowered the mangled kernel names in
-// the order nodes[0][0][0..1], nodes[0][1][..], nodes[1][..][..], hess, ODE residual (f64), ring, pass (small, large), node kernel with nt stores
+// the order nodes[0][0][0..1], nodes[0][1][..], nodes[1][..][..], hess, ODE residual and its delayed form (f64), ring, pass (small, large), node kernel with nt stores
 int compile(bool f32, const char* sn, const char* source, int ns, int nc, int npath, int pw, std::vector<char>* code,
             std::vector<std::string>* lowered, bool* has_ring, std::string* log) {
     if (!valid_identifier(sn) || !source || ns < 1 || nc < 0 || ns + nc > 64) {
@@ -113,6 +115,7 @@ int compile(bool f32, const char* sn, const char* source, int ns, int nc, int np
             for (int d = 0; d < 2; ++d) order.push_back(&nm.nodes[v][j][d]);
     order.push_back(&nm.hess);
     if (!f32) order.push_back(&nm.ode_resid);
+    if (!f32) order.push_back(&nm.ode_resid_delay);
     if (with_ring) {
         order.push_back(&nm.ring);
         for (const std::string& f : nm.pass) order.push_back(&f);
@@ -222,6 +225,7 @@ int rtc_build(bool f32, const char* struct_name, const char* source, int ns, int
             for (int d = 0; d < 2 && e == hipSuccess; ++d) e = hipModuleGetFunction(&m->nodes[v][j][d], m->mod, low[i++].c_str());
     if (e == hipSuccess) e = hipModuleGetFunction(&m->hess, m->mod, low[i++].c_str());
     if (e == hipSuccess && !f32) e = hipModuleGetFunction(&m->ode_resid, m->mod, low[i++].c_str());
+    if (e == hipSuccess && !f32) e = hipModuleGetFunction(&m->ode_resid_delay, m->mod, low[i++].c_str());
     if (e == hipSuccess && ring) {
         e = hipModuleGetFunction(&m->ring, m->mod, low[i++].c_str());
         m->ring_lds = ring_lds_bytes(ns);
@@ -265,6 +269,11 @@ template hipError_t rtc_launch_hess<float>(RtcModel*, const HessArgs<float>&, hi
 hipError_t rtc_launch_ode_resid(RtcModel* m, const OdeResidArgs<double>& a, hipStream_t s) {
     dim3 grid((a.M - 1 + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
     return launch(m->ode_resid, grid, block, 0, s, &a, sizeof a);
+}
+
+hipError_t rtc_launch_ode_resid_delay(RtcModel* m, const OdeResidDelayArgs<double>& a, hipStream_t s) {
+    dim3 grid((a.M - 1 + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
+    return launch(m->ode_resid_delay, grid, block, 0, s, &a, sizeof a);
 }
 
 hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t s) {

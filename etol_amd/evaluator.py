@@ -954,6 +954,36 @@ class Evaluator:
         self._ck(fn(self.ctx, A(X), A(U), pb[0], pb[1], A(Eta), A(err)), fn.__name__)
         return err, Eta
 
+    @staticmethod
+    def ode_error_delay_operator(M, mesh=None, t0=0.0, tf=1.0, delay=0.0):
+        """Edel [5 (M-1)][M]: row p is the Lagrange basis of the mesh at the node coordinate of max(t_p - delay, t0), t_p the time
+        of point p of ode_error_operator on [t0, tf] (host, emi_ode_error_delay_operator)"""
+        lib = L.load()
+        tau, w = (np.ascontiguousarray(a, dtype=np.float64) for a in (mesh if mesh is not None else lgl(M))[:2])
+        Edel = np.empty((5 * (int(M) - 1), int(M)))
+        L.check(lib.emi_ode_error_delay_operator(int(M), _dp(tau), _dp(w), float(t0), float(tf), float(delay), _dp(Edel)),
+                what="emi_ode_error_delay_operator")
+        return Edel
+
+    def ode_error_total(self, X, U, ul=None, uu=None, eta=True, dev=True):
+        """ode_error for a context with or without delays (emi_ode_error_total_*): U [B][ncf][M] holds the FREE controls and ul, uu
+        [ncf] their bounds; the delayed values between the nodes are those of the interpolants at max(t - i dt, t0), a delayed
+        control clipped with its source's bounds.  Without delays this is ode_error, bit for bit."""
+        lay = self.layout
+        bd = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (ul, uu)]
+        pb = [None if a is None else _dp(a) for a in bd]
+        if dev:
+            kw = dict(dtype=torch.float64, device=X.device)
+            err = torch.empty((lay.B,), **kw)
+            Eta = torch.empty((lay.B, lay.ns, lay.M - 1), **kw) if eta else None
+        else:
+            assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in (X, U))
+            err, Eta = np.empty(lay.B), (np.empty((lay.B, lay.ns, lay.M - 1)) if eta else None)
+        A = self._ipm_addr
+        fn = self.lib.emi_ode_error_total_dev if dev else self.lib.emi_ode_error_total_host
+        self._ck(fn(self.ctx, A(X), A(U), pb[0], pb[1], A(Eta), A(err)), fn.__name__)
+        return err, Eta
+
     # ---- measurement -----------------------------------------------------------
     def timer_start(self):
         self._ck(self.lib.emi_timer_start(self.ctx), "emi_timer_start")

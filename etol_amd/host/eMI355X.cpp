@@ -734,9 +734,24 @@ double eMI355X::odeError(const std::vector<double>& z, std::vector<double>* z_fi
     const size_t ns = P.nstates, nc = P.ncontrols, nv = ns + nc, M = P.nodes;
     static const double gx[5] = {-0.9061798459386640, -0.5384693101056831, 0.0, 0.5384693101056831, 0.9061798459386640};
     static const double gw[5] = {0.2369268850561891, 0.4786286704993665, 0.5688888888888889, 0.4786286704993665, 0.2369268850561891};
+    if (P.ndelayed > 0) {
+        // a problem with delays: f reads delayed values between the nodes, which the points-only mesh of the host route does not
+        // define.  Whatever Alg::ode_error says, the estimate is the device's (emi_ode_error_total_host: the interpolants at
+        // max(t - i dt, t0), a delayed control clipped like its source) of the STATED problem, z = [X | U(ncontrols)]
+        if (P.lifted) die("odeError(): the context is lifted (a solve() of a delayed problem is running); take the estimate of the stated problem after it");
+        if (_algorithm.ode_error != "host" && _algorithm.ode_error != "device") die("Alg::ode_error must be \"host\" or \"device\"");
+        if (z.size() != nv * M) die("odeError(): z must hold (nstates + ncontrols) x nodes values");
+        emi_ctx_t c = _dev->ctx;
+        if (_dev->nodes != (int)M) configureDevice(_dev.get());
+        double err = 0;
+        must(emi_ode_error_total_host(c, z.data(), z.data() + ns * M, nc ? P.control_lower.data() : nullptr, nc ? P.control_upper.data() : nullptr,
+                                      nullptr, &err), c, "emi_ode_error_total_host");
+        if (z_fine) z_fine->clear();
+        if (nodes_fine) *nodes_fine = 0;
+        return err;
+    }
     if (_algorithm.ode_error == "device") {
         // the whole estimate on the device, on the collocation mesh the context is on: nothing of the mesh goes up or changes
-        if (P.ndelayed > 0) die("Alg::ode_error = \"device\": problems with delays are not taken (f reads the delayed values); use \"host\"");
         emi_ctx_t c = _dev->ctx;
         if (_dev->nodes != (int)M) configureDevice(_dev.get());
         double err = 0;
@@ -861,7 +876,9 @@ NlpProblem make_nlp(const Prob& P, NlpEvaluator* ev) {
         std::vector<double> W(M * M);
         size_t slot = ns + ncf;
         auto add = [&](size_t src, double delay) {
-            if (emi_delay_matrix((int)M, P.tau.data(), P.w.data(), P.t0, P.tf, delay, W.data()) != EMI_OK) return;
+            // (a slot without its coupling row would shift every later one onto the wrong variable)
+            if (emi_delay_matrix((int)M, P.tau.data(), P.w.data(), P.t0, P.tf, delay, W.data()) != EMI_OK)
+                die("make_nlp: emi_delay_matrix refused the mesh or the delay " + std::to_string(delay) + " of a delayed slot");
             NlpLink L;
             L.dst = (int)slot++;
             L.src = (int)src;
@@ -1110,7 +1127,8 @@ std::vector<double> initial_guess(const Prob& P) {
         std::vector<double> W(M * M);
         size_t slot = ns + nc;
         auto fill = [&](size_t src, double delay) {
-            if (emi_delay_matrix((int)M, P.tau.data(), P.w.data(), P.t0, P.tf, delay, W.data()) != EMI_OK) return;
+            if (emi_delay_matrix((int)M, P.tau.data(), P.w.data(), P.t0, P.tf, delay, W.data()) != EMI_OK)
+                die("initial_guess: emi_delay_matrix refused the mesh or the delay " + std::to_string(delay) + " of a delayed slot");
             for (size_t k = 0; k < M; ++k) {
                 double acc = 0;
                 for (size_t j = 0; j < M; ++j) acc += W[k * M + j] * z0[src * M + j];
@@ -1167,7 +1185,18 @@ struct eMI355X::Host : public mi355x::MeshHost {
         self->_solution.linear_solver = dev_kkt ? "device: structured KKT factorisation (Schur complement + Cholesky), Woodbury-corrected" : "host LDL^T";
         return mi355x::solve_nlp(nlp, opt, z0);
     }
-    double ode_error(const std::vector<double>& z) override { return self->odeError(z); }
+    double ode_error(const std::vector<double>& z) override {
+        mi355x::Prob& P = self->_problem;
+        if (!P.lifted) return self->odeError(z);
+        // a lifted solve (Alg::refine_delayed): the estimate is taken of the stated problem -- the device forms the delayed values
+        // for the call -- from the states and the free controls of z, and the lifted form is put back
+        P.lifted = false;
+        self->configureDevice(self->_dev.get());
+        const double err = self->odeError(std::vector<double>(z.begin(), z.begin() + (P.nstates + P.ncontrols) * P.nodes));
+        P.lifted = true;
+        self->configureDevice(self->_dev.get());
+        return err;
+    }
 };
 
 void eMI355X::solve() {
@@ -1178,8 +1207,8 @@ void eMI355X::solve() {
     // sources by linear coupling rows with the interpolation operators W(i dt) of the mesh: node functions, Jacobian entries and Hessian
     // blocks stay node-local (the device kernels on the extended node variables, unchanged), W appears as constant rows of the KKT matrix.
     // The Newton step of such a problem runs on the dense host backend (the structured device step has no place for a second operator
-    // beside D yet), so the mesh is bounded; mesh sequencing and refinement are off (the ODE-error estimate evaluates between the nodes,
-    // where the delayed values of a points-only mesh are not defined).  Which meshes are solved, from which guesses and with which
+    // beside D yet), so the mesh is bounded; mesh sequencing and refinement are off (the ODE-error estimate of the returned trajectory is
+    // taken below, of the stated problem: Sol::ode_error says how well the one mesh resolves the ODE).  Which meshes are solved, from which guesses and with which
     // options, is the MeshDriver's business (emi_mesh_driver.hpp); what is left here is the problem going in and the answer coming out.
     struct Lift {
         eMI355X* self;
@@ -1245,7 +1274,12 @@ void eMI355X::solve() {
     _solution.adjDelayed.clear();
     _solution.certificate = mi355x::Sol::Certificate();
     // the certificate is taken of the problem the caller stated: the lifted form ends here and the device forms the delayed values itself
+    const bool was_lifted = lift.on;
     lift.end();
+    // ... and so is the ODE-error estimate of a delayed solve (the strategy takes none of a lifted problem): of the trajectory
+    // returned, on the stated problem.  Iterates, counts and cost are as they were
+    if (was_lifted && _algorithm.mesh_refinement == "automatic")
+        _solution.ode_error = odeError(std::vector<double>(r.z.begin(), r.z.begin() + (ns + nc) * M));
     if (_algorithm.certify && _solution.lamF.size() == ns * M && _solution.lamC.size() == P.npath * M)
         _solution.certificate = certify(std::vector<double>(r.z.begin(), r.z.begin() + (ns + nc) * M), _solution.lamF, _solution.lamC,
                                         &_solution.adjDelayed);

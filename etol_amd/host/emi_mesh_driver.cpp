@@ -346,7 +346,12 @@ void MeshDriver::restart_after_failed_target() {
 // PSOPT's mesh refinement ("automatic", ePSOPT.cpp:69-71): solve, estimate the ODE error,
 // add nodes and re-solve from the interpolated solution until the tolerance is met.
 void MeshDriver::refine_loop() {
-    const bool refine = alg_.mesh_refinement == "automatic" && !P_.lifted;
+    // a lifted problem (delays) is refined only where Alg::refine_delayed asks for it: the host takes the estimate of the STATED
+    // problem (the delayed values between the nodes are those of the interpolants), the next mesh starts from the interpolated
+    // states and free controls, and initial_guess forms the delayed values on it as W . guess, as it does for a cold start
+    const bool refine = alg_.mesh_refinement == "automatic" && (!P_.lifted || alg_.refine_delayed);
+    // the dense step of a lifted problem takes up to 4000 KKT rows, (2 ns + nc + 2 ndelayed) per node
+    const size_t dense_cap = P_.lifted ? 4000 / (2 * ns_ + nc_ + 2 * P_.ndelayed) : (size_t)-1;
     for (int mr = 0;; ++mr) {
         if (mr == 0 && sequenced_) {
             target_warm();
@@ -369,7 +374,13 @@ void MeshDriver::refine_loop() {
             printf("mesh iteration %d: %zu nodes, cost %.10e, relative ODE error %.3e\n", mr, P_.nodes, r_.cost,
                    sol_.ode_error);
         if (sol_.ode_error <= alg_.ode_tolerance || mr + 1 >= alg_.mr_max_iterations) break;
-        const size_t Mnew = std::min((size_t)alg_.mr_max_nodes, P_.nodes + std::max<size_t>(4, (P_.nodes - 1) / 2));
+        size_t Mnew = std::min((size_t)alg_.mr_max_nodes, P_.nodes + std::max<size_t>(4, (P_.nodes - 1) / 2));
+        if (Mnew > dense_cap) {
+            Mnew = dense_cap;
+            if (Mnew <= P_.nodes && alg_.print_level >= 1)
+                printf("mesh refinement stops on %zu nodes with a relative ODE error of %.3e: the dense Newton step of a problem with delays takes up to "
+                       "4000 KKT rows, %zu nodes\n", P_.nodes, sol_.ode_error, dense_cap);
+        }
         if (Mnew <= P_.nodes) break;
         // refined meshes start from the interpolated solution but with the cold-start barrier settings: the
         // interpolant may cut through keep-outs between the old nodes, and the elastic rows need room to move

@@ -8,8 +8,8 @@
 // implements it with a script or with the CPU oracle, so every branch of the strategy runs without a GPU.
 //
 // Known and untouched here (the driver moves the strategy, it does not change it): a problem with delays is solved
-// lifted, for which sequencing and refinement are silently off; make_nlp / initial_guess do not advance `slot` after an
-// emi_delay_matrix failure; planned_path_guess ignores keep-in rows.
+// lifted, for which sequencing and refinement are silently off (eMI355X::solve takes the ODE-error estimate of such a
+// solve itself, of the stated problem once the lifted form has ended); planned_path_guess ignores keep-in rows.
 #ifndef ETOL_MI355X_EMI_MESH_DRIVER_HPP_
 #define ETOL_MI355X_EMI_MESH_DRIVER_HPP_
 

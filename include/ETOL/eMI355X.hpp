@@ -76,6 +76,10 @@ struct Alg {
     int mr_max_iterations = 10;                    // ePSOPT.cpp:70
     double ode_tolerance = 1.e-4;                  // ePSOPT.cpp:71
     int mr_max_nodes = 513;                        // refinement stops adding nodes here
+    bool refine_delayed = false;                   // a problem with delays (solved lifted, on the dense host step) is refined like any other: the
+                                                   // estimate is taken of the stated problem, the next mesh by the same growth rule, capped by
+                                                   // mr_max_nodes and by the dense step's (2 nstates + ncontrols + 2 ndelayed) nodes <= 4000.
+                                                   // Off: no delayed solve changes its mesh (Sol::ode_error is reported all the same)
     bool inflate_keepouts = false;                 // on the sequencing ladder, grow the keep-outs by half the node spacing
                                                    // (against stepping over thin obstacles; measured: no gain on the
                                                    // Monte-Carlo sets, off by default)
@@ -118,7 +122,8 @@ struct Alg {
     std::string ode_error = "host";                // relative local ODE error of a mesh (odeError, the refinement criterion): "host" (interpolation
                                                    // on the host, f at the points on a points-only mesh of the context, which is then put back on
                                                    // the collocation mesh), or "device" (emi_ode_error_dev on the context's collocation mesh as it
-                                                   // stands: no mesh change; problems without delays)
+                                                   // stands: no mesh change).  A problem with delays goes through emi_ode_error_total_host
+                                                   // whatever this says: the host route has no delayed values between the nodes
     int nlp_iter_max = 200;                        // per NLP solve (one mesh, one start), as ePSOPT.cpp:66
     bool plan_second_start = true;                 // the route planned through the free space of the static keep-outs (clearance-weighted: planned_path_guess) is the
                                                    // second start of a mesh-ladder climb, before the bent lines (false: the last cold-start attempt only).  256-scenario
@@ -236,7 +241,11 @@ class eMI355X : public TrajectoryOptimizer {
     mi355x::Sol* getSolution();
     mi355x::Prob* getProblem();
     // PSOPT-style relative local ODE error of a trajectory z = [X (nstates x nodes), U (ncontrols x nodes)] on the
-    // current mesh (what the automatic mesh refinement compares with ode_tolerance); needs setup()
+    // current mesh (what the automatic mesh refinement compares with ode_tolerance); needs setup().  A problem with delays: U holds
+    // the ncontrols free controls, the delayed values between the nodes are those of the interpolants at max(t - i dt, t0) and the
+    // estimate is the device's (emi_ode_error_total_host) on both settings of Alg::ode_error -- the host route evaluates f on a
+    // points-only mesh, where delayed values are not defined.  solve() of such a problem fills Sol::ode_error with it (where
+    // Alg::mesh_refinement is "automatic"), of the trajectory it returns; it does not refine the mesh
     double odeError(const std::vector<double>& z, std::vector<double>* z_fine = nullptr, size_t* nodes_fine = nullptr);
     // One evaluation pass of the transcribed problem at z = [X (nstates x nodes), U (ncontrols x nodes)] on the device -- what
     // the NLP solver asks ePSOPT for through PSOPT (dae + integrand_cost at every node, defects, quadrature, Jacobian

@@ -645,6 +645,33 @@ int emi_ode_error_operator(int M, const double* tau, const double* w, double* E,
 int emi_interp_dev(emi_ctx_t ctx, int K, int N, int ldk, const void* dOP, const void* dV, int R, int ldo, void* dOut);
 int emi_ode_error_dev(emi_ctx_t ctx, const void* dX, const void* dU, const double* ul, const double* uu, void* dEta, void* dErr);
 int emi_ode_error_host(emi_ctx_t ctx, const double* X, const double* U, const double* ul, const double* uu, double* Eta, double* Err);
+/* ---- ... of a context WITH delays: the _total_ calls --------------------------------------------------------------------------
+ *
+ * Take a context with emi_set_delays(xh, uh, dt): ncf = nc - n_delayed free controls, then the delayed slots in the order of
+ * emi_set_delays.  Everything of the definition above stays (the points s_p, E, E', the clip of the free controls, eta, W, err);
+ * the model is evaluated on the extended node variables
+ *   z~(s_p) = [ x~(s_p) | u~(s_p) clipped | delayed slots ]
+ *   slot q = (source v, delay index i)  ->  z~_v at the time max(t_p - i dt, t0),  t_p = t0 + h (s_p + 1)
+ * which is the clamp of emi_delay_matrix applied between the nodes.  The delayed copy of a control is the same clipped interpolant
+ * at the earlier time: it is clipped with its source's bounds.  W[b][i] and err[b] are as before, from X and D x.
+ *
+ * emi_ode_error_delay_operator (host, no device needed): the operator of one delay, Edel [5 (M-1)][M] row-major.  Row p is the
+ * Lagrange basis of the mesh at x_p, formed in double exactly as emi_delay_matrix forms it at a node: ts = t_p - delay,
+ * ts = max(ts, t0), x_p = (ts - t0) / h - 1, with t_p from the rounded s_p of emi_ode_error_operator.  The row is formed in
+ * extended precision, in barycentric form with the weights (-1)^j sqrt(w_j); where ts <= t0 it is e_0, where x_p == tau_j exactly
+ * it is e_j.  EMI_ERR_ARG: M < 2, a NULL pointer, tf <= t0, delay < 0.
+ * emi_ode_error_total_dev: dX [B][ns][M], dU [B][ncf][M] (the FREE controls) -> dErr [B] and, where dEta is not NULL, dEta
+ * [B][ns][M-1].  ul, uu: host [ncf] arrays, a NULL pair means no clip.  On a context without delays this is emi_ode_error_dev: the
+ * same launches, the same bits.  With delays the state rows go against the stacked operator [E | E' | D | Edel(dt) ..
+ * Edel((xh-1) dt)] and the ncf control rows against [E | Edel(dt) .. Edel(uh dt)], both on emi_interp_dev's kernel; the stacks
+ * are built once per (mesh, delays): max(xh - 1, uh) * 5 (M-1) * ldk doubles go up then.  Asynchronous on the context's stream;
+ * operators and workspace are device arrays of the context (grown as needed, freed with it); the context's mesh, delays, tables
+ * and every later pass's bits are as before the call.  EMI_ERR_UNSUPPORTED: f32 context; more than 65535 instances.
+ * EMI_ERR_STATE: points-only mesh; mesh, model or batch not set.  EMI_ERR_ARG: a NULL that is not optional, half a pair of
+ * bounds.  The _host form takes host arrays and synchronises.  emi_ode_error_dev / _host keep refusing a context with delays.     */
+int emi_ode_error_delay_operator(int M, const double* tau, const double* w, double t0, double tf, double delay, double* Edel);
+int emi_ode_error_total_dev(emi_ctx_t ctx, const void* dX, const void* dU, const double* ul, const double* uu, void* dEta, void* dErr);
+int emi_ode_error_total_host(emi_ctx_t ctx, const double* X, const double* U, const double* ul, const double* uu, double* Eta, double* Err);
 /* ---- Lock-step MESH REFINEMENT: the ladder, with the instances that meet the ODE tolerance retired rung by rung -----------------
  *
  * PSOPT's automatic mesh refinement (solve, estimate the ODE error, add nodes, solve again until ode_tolerance holds: the loop of
