@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-ode-delay-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-ode-delay-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency check-pass-work
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -35,7 +35,7 @@ $(LIBDIR):
 
 CSRC_HDR  := $(wildcard $(CSRC)/*.hpp) include/emi355x.h
 # headers a model program compiled at run time (hiprtc, emi_rtc.hip) includes: embedded as text
-RTC_HDR   := $(CSRC)/emi_models.hpp $(CSRC)/emi_args.hpp $(CSRC)/emi_node_kernels.hpp $(CSRC)/emi_symdefect_kernels.hpp
+RTC_HDR   := $(CSRC)/emi_models.hpp $(CSRC)/emi_pass_work.hpp $(CSRC)/emi_args.hpp $(CSRC)/emi_node_kernels.hpp $(CSRC)/emi_symdefect_kernels.hpp
 
 $(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC_HDR) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -156,6 +156,14 @@ PASS_RES_CHECK_OUT ?= $(LIBDIR)/pass_residency_check
 check-pass-residency: tests/harness/pass_residency_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_RES_CHECK_OUT) tests/harness/pass_residency_main.cpp
 	$(PASS_RES_CHECK_OUT)
+
+# the work table of the one-launch pass (emi_pass_work.hpp, host-only builder over pass_role_of and ring_tile_of; its key from the plan,
+# emi_pass_plan.hpp) as a stand-alone program under the host sanitizers: every entry against the two maps, every (tile, slice) and every
+# node chunk exactly once, every other block idle, over models, meshes, batches, block orders, tile orders, K slices and K halves
+PASS_WORK_CHECK_OUT ?= $(LIBDIR)/pass_work_check
+check-pass-work: tests/harness/pass_work_main.cpp $(CSRC)/emi_pass_work.hpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_WORK_CHECK_OUT) tests/harness/pass_work_main.cpp
+	$(PASS_WORK_CHECK_OUT)
 
 # the register budget of emi_pass_f64_kernel: every instantiation compiled for $(ARCH) (device code only, nothing is kept) and held to the
 # resident workgroups per CU it states -- 3: occupancy 3, at most 168 registers, no scratch; 2: no scratch and what tools/pass_registers.json

@@ -255,6 +255,38 @@ emi::DefectArgsF32 defect_args_f32(emi_ctx_t c, Launch L, const PassIO& io) {
     return emi::DefectArgsF32{(const float*)io.X, (const float*)c->d_D.p, (float*)io.RES, L.B * c->ns, c->M, c->ns, nres_of(c)};
 }
 
+// The work table of a launch on the device (emi_pass_work.hpp): the context's copy where the key is cached -- a steady-state call does no
+// more than compare keys: no synchronisation, no allocation, no copy -- else built by pass_work_build and uploaded on the context's
+// stream, ahead of the launch that reads it.  The slot keeps the host copy, which so outlives the asynchronous copy; a slot that gives
+// way is reused only once the stream has drained (launches in flight read its table, the copy reads its host array).
+int pass_work_table(emi_ctx_t c, const emi::PassWorkKey& key, const emi::PassWork** out) {
+    emi_api::PassWorkCache& pc = c->pass_work;
+    for (emi_api::PassWorkCache::Slot& sl : pc.slot)
+        if (sl.used && sl.key == key) {
+            sl.stamp = ++pc.clock;
+            *out = sl.dev.p;
+            return EMI_OK;
+        }
+    emi_api::PassWorkCache::Slot* lru = &pc.slot[0];     // the first free slot, else the least recently used one
+    for (emi_api::PassWorkCache::Slot& sl : pc.slot)
+        if (lru->used && (!sl.used || sl.stamp < lru->stamp)) lru = &sl;
+    std::vector<emi::PassWork> table;
+    const char* why = "";
+    if (!emi::pass_work_build(key, table, &why))
+        return fail(c, EMI_ERR_UNSUPPORTED, "emi_eval: the launch does not fit the work table of the one-launch pass (%s)", why);
+    if (lru->used) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    lru->used = false;
+    HIP_TRY(c, lru->dev.reserve(table.size()));
+    lru->host.swap(table);
+    HIP_TRY(c, hipMemcpyAsync(lru->dev.p, lru->host.data(), lru->host.size() * sizeof(emi::PassWork), hipMemcpyHostToDevice, c->stream));
+    lru->key = key;
+    lru->used = true;
+    lru->stamp = ++pc.clock;
+    ++pc.uploads;
+    *out = lru->dev.p;
+    return EMI_OK;
+}
+
 // The fp64 pass as ONE launch, by the plan the chooser made: MFMA-role and node-role workgroups in one grid, K slices combined
 // and COST finished in-kernel by ticket.
 int form_pass_f64(emi_ctx_t c, Launch L, const PassIO& io, const emi::PassPlan& pp, ProfEvents* pe) {
@@ -274,9 +306,12 @@ int form_pass_f64(emi_ctx_t c, Launch L, const PassIO& io, const emi::PassPlan& 
     }
     EMI_TRY(ensure_zeroed(c, c->d_ticket, (size_t)L.B * 4, c->stream));
     na.cost_ticket = (unsigned*)c->d_ticket.p;
+    const emi::PassWorkKey key = emi::pass_work_for(plan, c->ns, L.B, c->M, pp.mfma_first);
+    const emi::PassWork* work = nullptr;
+    EMI_TRY(pass_work_table(c, key, &work));
     EMI_TRY(prof_mark(c, pe, K0, AT_ANY, c->stream));
-    if (c->rtc) HIP_TRY(c, emi::rtc_launch_pass(c->rtc, sa, na, plan.sw, c->stream));
-    else HIP_TRY(c, emi::launch_pass(c->model, sa, na, c->stream, plan));
+    if (c->rtc) HIP_TRY(c, emi::rtc_launch_pass(c->rtc, sa, na, plan.sw, c->stream, key, work));
+    else HIP_TRY(c, emi::launch_pass(c->model, sa, na, c->stream, plan, key, work));
     EMI_TRY(prof_mark(c, pe, K1, AT_ANY, c->stream));
     if (pe) pe->level = -1;                 // one bracket: the pass kernel
     c->last_defect_kernel = name_pass_f64(plan);
@@ -639,6 +674,47 @@ int emi_debug_pass_roles(int nm, int nn, int order, int* out_role, int out_cap) 
         const emi::PassRole r = emi::pass_role_of(j, nm, nn, order);
         out_role[j] = r.mfma ? r.index : -1 - r.index;
     }
+    return EMI_OK;
+}
+
+int emi_debug_pass_work(int ns, int B, int M, int sw, int ctc, int ksplit, int hs, int sym_cpart, int sym_gblk, int sym_cx, int order, int* out,
+                        int out_cap, int* info) {
+    if (ns < 1 || B < 1 || M < 128 || M % 128 != 0 || sw < 1 || ns % sw != 0 || (ctc != 1 && ctc != 2) || ksplit < 1 || (hs != 1 && hs != 2) || !info)
+        return EMI_ERR_ARG;
+    // the tile order as a launch of the pass plans it (plan_tiles): the plan's own K slices, made legal in 8-deep K tiles
+    emi::SymPlan p = emi::plan_symdefect(ns, B, M, emi::symdefect_ct_of(ns, sw), emi::legal_ks((M / 2) / 8, ksplit), sym_cpart, sym_gblk, sym_cx, 8, ctc);
+    if (p.ring1 || p.sw != sw || p.ct != ctc) return EMI_ERR_UNSUPPORTED;
+    p.hs = hs;
+    const emi::PassWorkKey key = emi::pass_work_for(p, ns, B, M, order);
+    std::vector<emi::PassWork> table;
+    if (!emi::pass_work_build(key, table)) return EMI_ERR_UNSUPPORTED;
+    const int vals[12] = {(int)key.blocks(), key.nm, key.nn, key.nm8, key.nn8, key.nbx, key.ntiles, key.ngrp, key.cpart, key.cx, key.ks, key.nsg};
+    for (int i = 0; i < 12; ++i) info[i] = vals[i];
+    for (int g = 0; out && g < (int)key.blocks() && 5 * (g + 1) <= out_cap; ++g) {
+        const emi::PassWork e = table[(size_t)emi::pass_work_index(g, key.per_xcd())];
+        int* o = out + 5 * (size_t)g;
+        o[0] = emi::pass_work_role(e);
+        o[1] = o[2] = o[3] = o[4] = 0;
+        if (o[0] == emi::PASS_WORK_MFMA) {
+            o[1] = emi::pass_work_ntile(e);
+            o[2] = emi::pass_work_grp(e);
+            o[3] = emi::pass_work_kslice(e);
+        } else if (o[0] == emi::PASS_WORK_NODE) {
+            o[1] = emi::pass_work_bx(e, 0);
+            o[2] = emi::pass_work_b(e, 0);
+            o[3] = hs == 2 && emi::pass_work_has_chunk(e, 1) ? emi::pass_work_bx(e, 1) : -1;
+            o[4] = hs == 2 && emi::pass_work_has_chunk(e, 1) ? emi::pass_work_b(e, 1) : -1;
+        }
+    }
+    return EMI_OK;
+}
+
+int emi_debug_pass_work_uploads(emi_ctx_t c, unsigned long long* uploads, int* tables) {
+    if (!c || !uploads) return EMI_ERR_ARG;
+    *uploads = c->pass_work.uploads;
+    int n = 0;
+    for (const emi_api::PassWorkCache::Slot& sl : c->pass_work.slot) n += sl.used ? 1 : 0;
+    if (tables) *tables = n;
     return EMI_OK;
 }
 

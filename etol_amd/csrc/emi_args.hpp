@@ -46,6 +46,7 @@
 #define FUSED_BK 16
 
 #include "emi_models.hpp"
+#include "emi_pass_work.hpp"
 
 namespace emi {
 
@@ -159,75 +160,8 @@ struct DefectArgsF32 {
     float* RES;
     int R, M, ns, nres;
 };
-// Which tile a workgroup of the state-split ring kernel works on.  tl counts tiles in XCD-local runs (an XCD gets a contiguous
-// range of the launch); ntiles column tiles, ngrp (instance group x state group) rows of tiles.  cpart = 0: plain order, the
-// column tiles of a group are neighbours.  cpart > 0: XCD x works on column partition x % cpart (ntiles / cpart columns, cx of
-// them interleaved at a time: cx divides that count) and on group partition x / cpart (ngrp cpart / 8 groups).  cpart < 0: the
-// grouped order described in the function (G = -cpart instance groups per super-block, nsg state groups per instance group;
-// needs (ngrp / nsg) % (8 G) == 0 and ntiles % cx == 0: plan_symdefect checks).  One function for
-// the kernel and for the host-side check that every tile is visited exactly once (emi_debug_tile_order, tests/test_abi.py).
-struct RingTile { int ntile, grp; };
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline RingTile ring_tile_of(int tl, int ntiles, int ngrp, int cpart, int cx, int nsg = 1) {
-    RingTile t;
-    if (cpart > 0) {
-        const int per_xcd = ngrp * ntiles / 8;
-        const int x = tl / per_xcd, m = tl - x * per_xcd;
-        const int pc = x % cpart, pg = x / cpart;
-        const int ncol = ntiles / cpart, ng = ngrp / (8 / cpart);
-        const int cb = m / (ng * cx), r = m - cb * ng * cx;
-        t.grp = pg * ng + r / cx;
-        t.ntile = pc * ncol + cb * cx + r % cx;
-    } else if (cpart < 0) {
-        // Grouped order (cpart = -G): an XCD keeps its own contiguous range of instance groups (the range whose node-role
-        // workgroups it also runs in the one-launch pass) and walks it in super-blocks of G groups; inside a super-block the
-        // column tiles go in blocks of cx, and for one column block all G groups x nsg state groups run before the next
-        // block.  X and U of a super-block are then fetched into this XCD's L2 once, by whichever role gets there first,
-        // and a column block's share of De / Do is walked once per super-block instead of once per (group, state group).
-        const int G = -cpart, per_xcd = ngrp * ntiles / 8;
-        const int x = tl / per_xcd, m = tl - x * per_xcd;
-        const int per_sb = G * nsg * ntiles, sb = m / per_sb, r = m - sb * per_sb;
-        const int per_cb = G * nsg * cx, cb = r / per_cb, r2 = r - cb * per_cb;
-        const int g = r2 / (nsg * cx), r3 = r2 - g * (nsg * cx);
-        const int mt = x * (ngrp / nsg / 8) + sb * G + g;
-        t.grp = mt * nsg + r3 / cx;
-        t.ntile = cb * cx + r3 % cx;
-    } else {
-        t.ntile = tl % ntiles;
-        t.grp = tl / ntiles;
-    }
-    return t;
-}
-// Role of block j of an XCD's share of the one-launch pass grid (nm MFMA-role and nn node-role blocks): {is_mfma, index within
-// the role}.  order 0: evenly interleaved; 1: all MFMA blocks first; >= 100: interleaved with the MFMA blocks at order / 100 times
-// the even density until they are used up, node blocks at the tail (a density beyond one MFMA block per block saturates HERE at
-// order 1, which keeps the map a bijection for every caller: the first form of this map, unclamped, sent node workgroups out of range).  One function for the kernel and for the host-side check (emi_debug_pass_roles).
-struct PassRole { int mfma, index; };
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline PassRole pass_role_of(int j, int nm, int nn, int order) {
-    const long long t = (long long)nm + nn;
-    long long m0, m1;
-    const long long d = order >= 100 ? order : 100;
-    // a density beyond one MFMA block per block (d nm > 100 t) would deal two MFMA indices to one block -- the map would no
-    // longer be a bijection: it saturates HERE, for every caller, at "all MFMA blocks first"
-    if (order == 1 || d * nm > 100 * t) {
-        m0 = j < nm ? j : nm;
-        m1 = j < nm ? j + 1 : nm;
-    } else {
-        m0 = ((long long)j * nm * d) / (100 * t);
-        m1 = ((long long)(j + 1) * nm * d) / (100 * t);
-        if (m0 > nm) m0 = nm;
-        if (m1 > nm) m1 = nm;
-    }
-    PassRole r;
-    r.mfma = m1 > m0;
-    r.index = (int)(r.mfma ? m0 : j - m0);
-    return r;
-}
+// ring_tile_of (which tile a workgroup of the state-split ring kernel works on), pass_role_of (the role of a block of the one-launch
+// pass) and the work table built from the two: emi_pass_work.hpp
 // the whole pass as one launch (emi_pass_f64_kernel): both roles' arguments and how the grid is dealt between them
 struct PassArgs {
     SymDefectArgs s;
@@ -235,6 +169,7 @@ struct PassArgs {
     int nm8, nn8;           // MFMA / node workgroups per XCD (counts rounded up to a multiple of 8 ...
     int nm, nn;             // ... the workgroups past these real counts do nothing)
     int nbx;                // node chunks per instance
+    const PassWork* work;   // [8][nm8 + nn8] what each block of the grid does (pass_work_build, emi_pass_work.hpp): read-only for the launch
 };
 
 }  // namespace emi

@@ -31,6 +31,24 @@ struct ProfEvents {
     int level = 0;          // 1: every bracket; 2: the defect (MFMA) kernel only; 3: the node kernel only; -1: one bracket K0..K1, the pass kernel
 };
 
+// The work tables of the one-launch pass on the device (emi_pass_work.hpp), by key: batch, mesh and plan stay the same from call to
+// call, so a steady-state emi_eval_dev only compares keys.  A few slots, because the pieces of a large batch (and its remainder) and
+// the rungs of a ladder are separate launches with tables of their own; the least recently used one gives way.  A slot owns the
+// device copy AND the host copy the asynchronous upload reads from, which therefore outlives that copy.
+struct PassWorkCache {
+    static constexpr int SLOTS = 8;
+    struct Slot {
+        bool used = false;
+        emi::PassWorkKey key;
+        std::vector<emi::PassWork> host;
+        emi::DeviceArray<emi::PassWork> dev;
+        unsigned long long stamp = 0;
+    };
+    Slot slot[SLOTS];
+    unsigned long long clock = 0;
+    unsigned long long uploads = 0;     // tables built and uploaded so far (emi_debug_pass_work_uploads)
+};
+
 }  // namespace emi_api
 using emi_api::DevBuf, emi_api::ProfEvents;
 
@@ -124,6 +142,7 @@ struct emi_ctx_s {
     int pass_order = -1;        // "pass_order" option: one-launch pass, MFMA workgroups of an XCD first (1), interleaved with the node
                                 // workgroups (0), or by batch size (-1: first for small batches)
     int sym_combine = 1;        // "sym_combine" option: 1 slices combined in-kernel by ticket, 0 by emi_symdefect_combine_kernel
+    emi_api::PassWorkCache pass_work;   // work tables of the one-launch pass on the device, by key (freed with the context, after its streams drained)
     emi::KeepRecord keep;       // which VALS buffer holds this problem's model-invariant rows (EMI_EVAL_KEEP_INVARIANT)
     // host-form staging: named buffers of the evaluation and adjoint host forms, slots of every other one (HostStager)
     DevBuf s_X, s_U, s_RES, s_VALS, s_COST, s_LF, s_LC, s_H;

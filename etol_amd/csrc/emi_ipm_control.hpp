@@ -5,7 +5,7 @@
 // rules on a per-instance state record.  They are the rules of solve_nlp's phases (host/emi_nlp.cpp: test_and_update_barrier,
 // line_search, futile_escalation, escalate_penalty, acceptable, armijo, raise_dc), as functions of plain structs: the control
 // kernels call them with one thread per instance, and the host shim of the CPU test calls the same text (the pattern of
-// pass_role_of in emi_args.hpp).
+// pass_role_of in emi_pass_work.hpp).
 //
 // Where a rule differs from solve_nlp because the round is batched:
 //   * a round that escalated the penalty runs NO barrier update.  solve_nlp resets the elastic multipliers in place and goes on

@@ -59,7 +59,9 @@ inline void operator_fragments(int M, const double* De, const double* Do, double
 // the whole pass as one launch (MFMA-role and node-role workgroups in one grid; COST finished in-kernel), in the form of the plan: a row
 // of EMI_PASS_FORMS (emi_pass_plan.hpp), anything else is an error
 bool pass_model_supported(int model);
-hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& plan);
+// (work: the device copy of the work table of `key`, pass_work_for in emi_pass_plan.hpp -- a table built for other counts is an error)
+hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& plan, const PassWorkKey& key,
+                       const PassWork* work);
 
 // the adjoint pass (emi_adjoint.hip): Lagrangian gradient G[B][ns+nc][M] and the per-instance KKT certificate, fp64
 struct AdjointArgs {
@@ -197,7 +199,7 @@ hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t
 // the one-launch pass of a run-time compiled model: which state split it was compiled with for large batches (small ones take
 // SW = 1), whether (sw, store mode) is available, and the launch
 int rtc_pass_sw_large(const RtcModel* m);
-hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s);
+hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s, const PassWorkKey& key, const PassWork* work);
 hipError_t rtc_launch_nodes_nt(RtcModel* m, const NodeArgs<double>& a, hipStream_t s);   // vec2, Jacobian, no defect rows, non-temporal stores
 
 // Newton step on the device (emi_kkt.hip)

@@ -6,7 +6,8 @@
 //   * resolve_form: the one place where a wanted feature is snapped to a form that exists;
 //   * PassPolicyIn: what the policy reads (emi_api_pass.hip fills it from the context);
 //   * the BAND TABLE (PASS_BANDS): the defaults by launch size, each row with the measurements behind it;
-//   * plan_symdefect, store_mode_for, plan_pass, plan_piece, report_pass as pure functions of PassPolicyIn and the batch.
+//   * plan_symdefect, store_mode_for, plan_pass, plan_piece, report_pass as pure functions of PassPolicyIn and the batch;
+//   * pass_work_for: the key of the work table of a planned launch (the table itself: emi_pass_work.hpp).
 // A new kernel form is one row of EMI_PASS_FORMS (plus its precondition in form_fits, if it has one) and one row of PASS_BANDS.
 #pragma once
 #include <stddef.h>
@@ -15,6 +16,7 @@
 #include <climits>
 
 #include "emi355x.h"
+#include "emi_pass_work.hpp"
 
 namespace emi {
 
@@ -447,6 +449,12 @@ inline SymPlan plan_tiles(const PassPolicyIn& in, int B, const PassWants& w, con
     p.dop = f.dop;
     p.res = r.res;
     return p;
+}
+
+// The key of the work table of a planned launch (emi_pass_work.hpp): what the blocks of its grid do follows from the form's tiles and
+// K slices, its tile order and the block order, and from nothing else.
+inline PassWorkKey pass_work_for(const SymPlan& sym, int ns, int B, int M, int order) {
+    return pass_work_key(ns, B, M, sym.sw, sym.ct, sym.ks, sym.hs, sym.cpart, sym.cx, order);
 }
 
 // Every choice can be forced through emi_set_option (sym_ct, sym_ksplit, sym_cpart, sym_gblk, sym_cx, sym_nst, sym_bk, sym_ctc, sym_hs,

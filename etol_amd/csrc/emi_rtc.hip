@@ -284,7 +284,7 @@ hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t
 int rtc_pass_sw_large(const RtcModel* m) { return m ? pass_class_sw(SWC_LARGE, m->ns) : 0; }
 
 // the row of EMI_PASS_FORMS_RTC for sw states per workgroup and the store flavour of na (plan_pass resolves to one; none is an error)
-hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s) {
+hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<double>& na, int sw, hipStream_t s, const PassWorkKey& key, const PassWork* work) {
     PassShape shape;
     shape.ns = m->ns;
     shape.M = sa.M;
@@ -303,6 +303,11 @@ hipError_t rtc_launch_pass(RtcModel* m, const SymDefectArgs& sa, const NodeArgs<
     a.nn = nn;
     a.nm8 = (nm + 7) / 8;
     a.nn8 = (nn + 7) / 8;
+    // the work table the blocks read was built for exactly this grid and these counts, or the launch is an error
+    if (!work || key.nm != nm || key.nn != nn || key.nm8 != a.nm8 || key.nn8 != a.nn8 || key.nbx != a.nbx || key.hs != 1 || key.nsg != m->ns / sw ||
+        key.ntiles != ntiles || key.ks != (sa.ksplit > 1 ? sa.ksplit : 1) || key.order != sa.mfma_first || key.cpart != sa.cpart || key.cx != sa.cx)
+        return hipErrorInvalidValue;
+    a.work = work;
     const size_t lds = (size_t)f->nst * ((2 * sw * FUSED_TI + 2 * 64 + 63) / 64 * 64) * f->bk * sizeof(double);     // the ring stages
     return launch(m->pass[f - PASS_FORMS_RTC], dim3(8 * (a.nm8 + a.nn8)), dim3(256), lds, s, &a, sizeof a);
 }

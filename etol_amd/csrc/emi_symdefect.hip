@@ -111,7 +111,7 @@ static hipError_t launch_ring2_planned(const SymDefectArgs& a, hipStream_t s, co
 // ---------------------------------------------------------------------------------------------
 // the pass as one launch (emi_pass_f64_kernel): MFMA-role and node-role workgroups interleaved per XCD
 template <class Model, int SW, int NST, int BK = 8, int CT = 1, int HS = 1, bool DOP = false>
-static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, int res) {
+static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, int res, const PassWorkKey& key, const PassWork* work) {
     constexpr int NS = Model::NS;
     PassArgs a;
     a.s = sa;
@@ -124,6 +124,11 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
     a.nn = nn;
     a.nm8 = (nm + 7) / 8;
     a.nn8 = ((nn + HS - 1) / HS + 7) / 8;          // node-role WORKGROUPS per XCD: one takes HS chunks
+    // the work table the blocks read was built for exactly this grid and these counts, or the launch is an error
+    if (!work || key.nm != nm || key.nn != nn || key.nm8 != a.nm8 || key.nn8 != a.nn8 || key.nbx != a.nbx || key.hs != HS || key.nsg != NS / SW ||
+        key.ntiles != ntiles || key.ks != (sa.ksplit > 1 ? sa.ksplit : 1) || key.order != sa.mfma_first || key.cpart != sa.cpart || key.cx != sa.cx)
+        return hipErrorInvalidValue;
+    a.work = work;
     // a ring stage: forward and mirrored x rows, De and Do rows, in whole DMA instructions -- DOP: the x rows only (whole instructions as they are)
     const size_t lds = DOP ? (size_t)NST * (2 * SW * FUSED_TI) * BK * sizeof(double)
                            : (size_t)HS * NST * ((2 * SW * FUSED_TI + 2 * 64 * CT + 63) / 64 * 64) * BK * sizeof(double);
@@ -168,12 +173,13 @@ static hipError_t launch_pass_model(const SymDefectArgs& sa, const NodeArgs<doub
 // The form of the plan, by walking the form table (EMI_PASS_FORMS, emi_pass_plan.hpp): a row is instantiated here and nowhere else, for the
 // models its SW class applies to.  plan_pass resolves every plan to a row; a plan that names none is an error, not another kernel.
 template <class Model>
-static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p) {
+static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p, const PassWorkKey& key,
+                                      const PassWork* work) {
     constexpr int NS = Model::NS;
 #define EMI_PASS_FORM_LAUNCH(CLS, NST, BK, CT, HS, DOP, SLICES, STORES)                                                                   \
     if constexpr (pass_class_applies(CLS, NS)) {                                                                                          \
         if (p.sw == pass_class_sw(CLS, NS) && p.nst == NST && p.bk == BK && p.ct == CT && p.hs == HS && p.dop == DOP && (SLICES || p.ks == 1)) \
-            return launch_pass_model<Model, pass_class_sw(CLS, NS), NST, BK, CT, HS, DOP>(sa, na, s, p.res);                             \
+            return launch_pass_model<Model, pass_class_sw(CLS, NS), NST, BK, CT, HS, DOP>(sa, na, s, p.res, key, work);                  \
     }
     EMI_PASS_FORMS(EMI_PASS_FORM_LAUNCH)
 #undef EMI_PASS_FORM_LAUNCH
@@ -183,9 +189,10 @@ static hipError_t launch_pass_planned(const SymDefectArgs& sa, const NodeArgs<do
 // the built-in models the pass kernels (and the even/odd MFMA defect kernels) are instantiated for
 bool pass_model_supported(int model) { return model == EMI_MODEL_POINTMASS2D || model == EMI_MODEL_QUADROTOR2D; }
 
-hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p) {
-    if (model == EMI_MODEL_POINTMASS2D) return launch_pass_planned<PointMass2D<double>>(sa, na, s, p);
-    if (model == EMI_MODEL_QUADROTOR2D) return launch_pass_planned<Quadrotor2D<double>>(sa, na, s, p);
+hipError_t launch_pass(int model, const SymDefectArgs& sa, const NodeArgs<double>& na, hipStream_t s, const SymPlan& p, const PassWorkKey& key,
+                       const PassWork* work) {
+    if (model == EMI_MODEL_POINTMASS2D) return launch_pass_planned<PointMass2D<double>>(sa, na, s, p, key, work);
+    if (model == EMI_MODEL_QUADROTOR2D) return launch_pass_planned<Quadrotor2D<double>>(sa, na, s, p, key, work);
     return hipErrorInvalidValue;
 }
 

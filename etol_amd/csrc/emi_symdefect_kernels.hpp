@@ -519,6 +519,24 @@ EMI_DEV void ring_epilogue(const SymDefectArgs& a, const d4 (&acc_a)[SW], const 
     ring_epilogue_pre<Model, SW, false>(a, acc_a, acc_b, inst0, i0, s0, wid, r16, kq, none);
 }
 
+// Which tile and K slice workgroup bid (tile-and-slice id, XCD-local runs) of the state-split ring takes, by the formula: the
+// stand-alone ring kernel works it out here; the one-launch pass reads it from its work table, which the host builds by the same
+// ring_tile_of (emi_pass_work.hpp).  bid / KS counts tiles in XCD-local runs (an XCD gets a contiguous range).  Plain order: the ntiles
+// column tiles of an X tile (same instance group, same states) are neighbours, so an XCD's L2 sees each X tile once --
+// but every XCD then walks ALL of De / Do (4 MB at 1024 nodes = the whole L2 of an XCD), and beside the node role's
+// store stream the panels are fetched again and again: 12 % of the pass at 1024 instances (tools/diag/x_traffic_probe.py:
+// 0.2408 ms against 0.2107 with all tiles reading the same 64 rows).  Partitioned order (a.cpart > 0): XCD x works on
+// column partition x % cpart only (its share of De / Do stays in L2) and on group partition x / cpart; X tiles are then
+// read by cpart XCDs instead of one, which costs little (they come from the Infinity Cache).
+struct RingWork { int ntile, grp, kslice; };
+template <class Model, int SW>
+EMI_DEV RingWork emi_ring2_tile_of(const SymDefectArgs& a, const int bid) {
+    constexpr int NSG = Model::NS / SW;
+    const int KS = a.ksplit > 1 ? a.ksplit : 1;
+    const RingTile rt = ring_tile_of(bid / KS, (a.M >> 1) / 64, (a.B + FUSED_TI - 1) / FUSED_TI * NSG, a.cpart, a.cx, NSG);
+    return RingWork{rt.ntile, rt.grp, bid % KS};
+}
+
 // a.ksplit > 1: the K range of a tile is cut into ksplit slices, one workgroup each (a shard of config 4 has 64
 // tiles for 256 CUs); a slice leaves its partial sums in a.slab[tile][slice][2 SW][4][256 threads] and
 // emi_symdefect_combine_kernel adds the slices IN SLICE ORDER (bitwise reproducible) and runs the epilogue.
@@ -543,7 +561,7 @@ EMI_DEV void ring_epilogue(const SymDefectArgs& a, const d4 (&acc_a)[SW], const 
 // offset, dealt into the first gaps of tile kt's MFMAs.  Same operands, same MFMA order: the defect rows are bitwise those of the staged form.
 // Unsplit form only: SW 1 / 2, 16-deep tiles, one sub-tile, three stages.  (tools/diag/mfma_mix_probe.hip, profiles/r06_notes.md.)
 template <class Model, int SW, int NST = 3, int BK = 8, int CT = 1, int HS = 1, bool DOP = false>
-EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-slice id, XCD-local runs */) {
+EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int ntile, const int grp, const int kslice /* which tile and K slice: emi_ring2_tile_of, or the work table of the one-launch pass */) {
     constexpr int NS = Model::NS;
     constexpr int TI = FUSED_TI, TM = SW * TI, TN = 64 * CT, CH = BK / 2, NSG = NS / SW;
     static_assert(CT == 1 || CT == 2, "one or two column sub-tiles per wave");
@@ -566,16 +584,6 @@ EMI_DEV void emi_ring2_body(const SymDefectArgs& a, const int bid /* tile-and-sl
     const int M = a.M, Hh = M >> 1, B = a.B;
     const int ntiles = Hh / TN;
     const int KS = (HS == 1 && !DOP && a.ksplit > 1) ? a.ksplit : 1;    // (slices through the slab: the undivided workgroup only)
-    const int kslice = bid % KS;
-    // Which tile.  bid / KS counts tiles in XCD-local runs (an XCD gets a contiguous range).  Plain order: the ntiles
-    // column tiles of an X tile (same instance group, same states) are neighbours, so an XCD's L2 sees each X tile once --
-    // but every XCD then walks ALL of De / Do (4 MB at 1024 nodes = the whole L2 of an XCD), and beside the node role's
-    // store stream the panels are fetched again and again: 12 % of the pass at 1024 instances (tools/diag/x_traffic_probe.py:
-    // 0.2408 ms against 0.2107 with all tiles reading the same 64 rows).  Partitioned order (a.cpart > 0): XCD x works on
-    // column partition x % cpart only (its share of De / Do stays in L2) and on group partition x / cpart; X tiles are then
-    // read by cpart XCDs instead of one, which costs little (they come from the Infinity Cache).
-    const RingTile rt = ring_tile_of(bid / KS, ntiles, (B + TI - 1) / TI * NSG, a.cpart, a.cx, NSG);
-    const int ntile = rt.ntile, grp = rt.grp;
     const int tile = grp * ntiles + ntile;              // slab / ticket index
     const int sg = grp % NSG, mtile = grp / NSG;
     const int inst0 = mtile * TI, i0 = ntile * TN, s0 = sg * SW;
@@ -951,7 +959,8 @@ __global__ __launch_bounds__(256, 2) void emi_symdefect_ring2_f64_kernel(SymDefe
         const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
         bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
     }
-    emi_ring2_body<Model, SW>(a, bid);
+    const RingWork w = emi_ring2_tile_of<Model, SW>(a, bid);
+    emi_ring2_body<Model, SW>(a, w.ntile, w.grp, w.kslice);
 }
 
 // second half of a split-K launch: one workgroup per tile, thread layout of the ring kernel
@@ -1024,22 +1033,34 @@ __global__ __launch_bounds__(256 * HS) EMI_PASS_OCC void emi_pass_f64_kernel(Pas
 #ifdef EMI_ENTRY_PAD_NOPS      // build-time experiment (tools/ab_build.sh): shift the whole instruction stream by 4-byte steps
     asm volatile(".rept " EMI_STR(EMI_ENTRY_PAD_NOPS) "\n\ts_nop 0\n\t.endr" ::: "memory");
 #endif
-    const int g = blockIdx.x, xcd = g & 7, j = g >> 3;
-    const PassRole role = pass_role_of(j, a.nm8, a.nn8, a.s.mfma_first);
-    if (a.s.ablate & (role.mfma ? 16 : 32)) return;    // diagnostics: one of the two roles does nothing
-    if (role.mfma) {
-        const int tid = xcd * a.nm8 + role.index;
-        if (tid >= a.nm) return;                        // (the role's count rounded up to a multiple of 8: whole workgroup, before any barrier)
+    // What this workgroup does: its entry of the work table, one scalar load (the index is the same for the whole workgroup).  The
+    // host built the table from pass_role_of and ring_tile_of, which every workgroup used to work out for itself ahead of its first
+    // memory request: two 64-bit divisions for the role, up to twelve 32-bit ones for the tile (emi_pass_work.hpp).
+    const int g = blockIdx.x;
+    const PassWork wk = a.work[pass_work_index(g, a.nm8 + a.nn8)];
+    {   // The kernel arguments either role's first memory requests are made from, asked for HERE, beside the entry: left to itself the
+        // compiler requests each where its branch first uses it, behind the entry -- five dependent scalar round trips ahead of the MFMA
+        // role's first DMA instead of two, which at 128 instances cost what the divisions had (profiles/work_table_notes.md section 4).
+        // (Behind the entry's load in the text: ahead of it the compiler no longer takes the table for unwritten and reads the entry
+        // with a vector load.)
+        const double *sx = a.s.X, *nx = a.n.X, *nu = a.n.U;
+        const int sm = a.s.M, sb = a.s.B, sab = a.s.ablate, nm = a.n.M;
+        asm volatile("" ::"s"(sx), "s"(nx), "s"(nu), "s"(sm), "s"(sb), "s"(sab), "s"(nm));
+    }
+    const int role = pass_work_role(wk);
+    if (role == PASS_WORK_IDLE) return;                 // (a role's count rounded up to a multiple of 8: whole workgroup, before any barrier)
+    if (a.s.ablate & (role == PASS_WORK_MFMA ? 16 : 32)) return;    // diagnostics: one of the two roles does nothing
+    if (role == PASS_WORK_MFMA) {
         // the MFMA role is the latency chain of a small pass (64 dependent K tiles); the streaming role beside it on the
         // same SIMDs waits on memory most of the time: instruction arbitration goes to the MFMA waves first
         __builtin_amdgcn_s_setprio(3);
-        emi_ring2_body<Model, SW, NST, BK, CT, HS, DOP>(a.s, tid);
+        emi_ring2_body<Model, SW, NST, BK, CT, HS, DOP>(a.s, pass_work_ntile(wk), pass_work_grp(wk), pass_work_kslice(wk));
     } else {
         // a.nn counts node chunks; a workgroup of HS x 256 threads takes HS neighbouring ones (a half that has none leaves:
         // barriers only count the waves still running)
-        const int nid = (xcd * a.nn8 + role.index) * HS + (HS > 1 ? (int)(threadIdx.x >> 8) : 0);
-        if (nid >= a.nn) return;
-        emi_nodes_body<double, Model, VEC, true, false, ST, false, KEEP>(a.n, nid % a.nbx, nid / a.nbx, a.nbx);
+        const int half = HS > 1 ? (int)(threadIdx.x >> 8) : 0;
+        if (!pass_work_has_chunk(wk, half)) return;
+        emi_nodes_body<double, Model, VEC, true, false, ST, false, KEEP>(a.n, pass_work_bx(wk, half), pass_work_b(wk, half), a.nbx);
     }
 }
 

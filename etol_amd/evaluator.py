@@ -1021,6 +1021,14 @@ class Evaluator:
         return res.value
 
     @property
+    def pass_work_uploads(self):
+        """(work tables of the one-launch pass this context has built and uploaded so far, tables it holds now): a call whose launch
+        was seen before uploads nothing."""
+        n, held = C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.lib.emi_debug_pass_work_uploads(self.ctx, C.byref(n), C.byref(held)), "emi_debug_pass_work_uploads")
+        return n.value, held.value
+
+    @property
     def last_defect_kernel(self):
         return self.lib.emi_last_defect_kernel(self.ctx).decode()
 
@@ -1029,3 +1037,22 @@ class Evaluator:
         f = C.c_int()
         self._ck(self.lib.emi_last_path(self.ctx, C.byref(f)), "emi_last_path")
         return bool(f.value)
+
+
+
+PASS_WORK_INFO = ("blocks", "nm", "nn", "nm8", "nn8", "nbx", "ntiles", "ngrp", "cpart", "cx", "ks", "nsg")
+
+
+def debug_pass_work(ns, B, M, sw, ctc=1, ksplit=1, hs=1, sym_cpart=0, sym_gblk=0, sym_cx=0, order=0):
+    """The work table of a launch of the one-launch pass, without a device (emi_debug_pass_work): (table, info) or None where
+    plan_symdefect admits no such launch.  table[g] = (role, ntile | bx, grp | b, K slice | second bx, second b) of grid block g."""
+    lib = L.load()
+    info = (C.c_int * 12)()
+    args = [int(v) for v in (ns, B, M, sw, ctc, ksplit, hs, sym_cpart, sym_gblk, sym_cx, order)]
+    if lib.emi_debug_pass_work(*args, None, 0, info) != 0:
+        return None
+    table = np.zeros((info[0], 5), dtype=np.intc)
+    st = lib.emi_debug_pass_work(*args, table.ctypes.data_as(C.POINTER(C.c_int)), table.size, info)
+    if st != 0:
+        raise L.EmiError(f"emi_debug_pass_work: status {st}")
+    return table, dict(zip(PASS_WORK_INFO, info))

@@ -1079,7 +1079,7 @@ int emi_profile_read(emi_ctx_t ctx, float* node_ms, int* node_launches,
  * size; -1 = plain (the column tiles of an X tile are neighbours, X tiles dealt over
  * the XCDs); 1 / 2 / 4 / 8 = the column tiles cut into that many partitions, each
  * worked on by 8 / cpart XCDs, so that an XCD's share of De / Do stays in its L2.
- * "sym_gblk" / "sym_cx": the GROUPED tile order (csrc/emi_args.hpp ring_tile_of): an XCD keeps a contiguous range of instance
+ * "sym_gblk" / "sym_cx": the GROUPED tile order (csrc/emi_pass_work.hpp ring_tile_of): an XCD keeps a contiguous range of instance
  * groups -- the range whose node-role workgroups it also runs -- and walks it in super-blocks of sym_gblk 16-instance groups,
  * the column tiles in blocks of sym_cx (0: 2); X and U of a super-block then reach that XCD's L2 once for every consumer.
  * sym_gblk 0: off (unless the policy chooses it: inputs that do not stay in the Infinity Cache between passes).
@@ -1123,6 +1123,19 @@ int emi_debug_operator_fragments(int M, const double* D, double* out);
  * 0 evenly interleaved, 1 MFMA blocks first, >= 100 interleaved at order / 100 times the even MFMA density).  out_role[j] =
  * MFMA block index (>= 0) or -1 - node block index; every index of either role must occur exactly once.                      */
 int emi_debug_pass_roles(int nm, int nn, int order, int* out_role, int out_cap);
+/* Diagnostics, no device needed: the WORK TABLE of a launch of the one-launch pass (csrc/emi_pass_work.hpp): what every block of its
+ * grid does, as the host builds it from the two maps above and as emi_pass_f64_kernel reads it.  The launch: B instances of ns states on
+ * M nodes, sw states and ctc 64-column sub-tiles per MFMA workgroup, ksplit K slices per tile (made legal as a launch does), hs K
+ * halves (1 or 2: a node workgroup then takes two chunks), the tile order by "sym_cpart" / "sym_gblk" / "sym_cx", the block order
+ * "pass_order".  info[12] = {blocks of the grid, nm, nn, nm8, nn8, nbx, ntiles, ngrp, cpart, cx, K slices, state groups}; out (may be
+ * NULL) takes five ints per block g while out_cap has room: role (0 idle, 1 MFMA, 2 node); MFMA: column tile, group, K slice, 0;
+ * node: chunk and instance of the first 256 threads, then of the second 256 (-1, -1: none).  EMI_ERR_UNSUPPORTED where
+ * plan_symdefect admits no such launch or it does not fit the fields of an entry.                                              */
+int emi_debug_pass_work(int ns, int B, int M, int sw, int ctc, int ksplit, int hs, int sym_cpart, int sym_gblk, int sym_cx, int order,
+                        int* out, int out_cap, int* info);
+/* ... and of a context: work tables it has built and uploaded so far (a call whose launch was seen before uploads nothing) and,
+ * where tables is not NULL, how many it holds now.                                                                             */
+int emi_debug_pass_work_uploads(emi_ctx_t ctx, unsigned long long* uploads, int* tables);
 /* name of the kernel that produced the defect rows in this context's last
  * emi_eval_dev (what a rocprofv3 kernel trace will show); "" before the first  */
 const char* emi_last_defect_kernel(emi_ctx_t ctx);
