@@ -147,12 +147,19 @@ __global__ __launch_bounds__(ROUTE_T) void emi_plan_route_kernel(StartArgs a) {
 // the blocked bits
 struct StartGuessWs {
     DevBuf par;
+    // the host side of `par`: page-locked, so that the copy is asynchronous on the context's stream as the header promises, and an
+    // event recorded behind that copy -- the next call fills par_h only once the copy of this one has read it
+    PinnedArray<double> par_h;
+    hipEvent_t par_up = nullptr;
     DeviceArray<double> cost, dist, extra;
     DeviceArray<int> cells;
     DeviceArray<unsigned char> bits;
 };
 
-void start_guess_destroy(StartGuessWs* w) { delete w; }
+void start_guess_destroy(StartGuessWs* w) {
+    if (w && w->par_up) (void)hipEventDestroy(w->par_up);
+    delete w;
+}
 
 int start_guess(emi_ctx_t c, const emi_start_t& st, void* dX, void* dLevel) {
     const char* who = "emi_start_guess_dev";
@@ -162,15 +169,22 @@ int start_guess(emi_ctx_t c, const emi_start_t& st, void* dX, void* dLevel) {
     const bool planned = st.kind == EMI_START_PLANNED;
     // what goes up: a few doubles per set, and the mesh's abscissae with the sines of the bend (the host's sin: one table for both forms)
     const size_t per = (size_t)2 * ns + 4;
-    std::vector<double> h(per * st.nsets + 2 * (size_t)M, 0.0);
+    const size_t nh = per * st.nsets + 2 * (size_t)M;
+    if (!w.par_up) HIP_TRY_AS(c, who, hipEventCreateWithFlags(&w.par_up, hipEventDisableTiming));
+    HIP_TRY_AS(c, who, hipEventSynchronize(w.par_up));          // (an event that was never recorded is complete)
+    HIP_TRY_AS(c, who, w.par_h.reserve(nh));
+    EMI_TRY(emi_api::ensure(c, w.par, nh * 8));
+    double* h = w.par_h.p;
+    std::fill(h, h + nh, 0.0);
     for (int s = 0; s < st.nsets; ++s) {
-        std::copy(st.xa + (size_t)s * ns, st.xa + (size_t)(s + 1) * ns, h.begin() + s * per);
-        std::copy(st.xb + (size_t)s * ns, st.xb + (size_t)(s + 1) * ns, h.begin() + s * per + ns);
-        if (st.box) std::copy(st.box + (size_t)s * 4, st.box + (size_t)(s + 1) * 4, h.begin() + s * per + 2 * ns);
+        std::copy(st.xa + (size_t)s * ns, st.xa + (size_t)(s + 1) * ns, h + s * per);
+        std::copy(st.xb + (size_t)s * ns, st.xb + (size_t)(s + 1) * ns, h + s * per + ns);
+        if (st.box) std::copy(st.box + (size_t)s * 4, st.box + (size_t)(s + 1) * 4, h + s * per + 2 * ns);
     }
-    double* tau = h.data() + per * st.nsets;
+    double* tau = h + per * st.nsets;
     for (int k = 0; k < M; ++k) { tau[k] = c->h_tau[k]; tau[M + k] = std::sin(1.5707963267948966 * (c->h_tau[k] + 1.0)); }
-    EMI_TRY(emi_api::upload_bytes(c, w.par, h.data(), h.size() * 8));
+    HIP_TRY_AS(c, who, hipMemcpyAsync(w.par.p, h, nh * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY_AS(c, who, hipEventRecord(w.par_up, c->stream));
     StartArgs a{};
     a.X = (double*)dX; a.level = (int*)dLevel;
     a.recs = (const double*)c->d_path.p;

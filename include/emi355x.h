@@ -782,7 +782,8 @@ int emi_ipm_solve_refine_host(emi_ctx_t ctx, int nrungs, const emi_ipm_rung_t* r
  * clearance.
  *
  * emi_start_guess_dev writes dX[B][ns][M] on the context's mesh for its model, batch, record table (shared or per instance) and
- * position states px, py (emi_set_path); asynchronous on the context's stream:
+ * position states px, py (emi_set_path); asynchronous on the context's stream (the end states go up from one page-locked buffer of
+ * the context: a call issued while the copy of the previous one is still queued waits on the host for that copy, and no longer):
  *   1. every state i: a_i + (b_i - a_i) 0.5 (tau_k + 1) with a = xa, b = xb of the instance's set;
  *   2. EMI_START_PLANNED: rows px, py replaced by emi_plan_route's xs, ys (ends and box of the instance's set) where it has a route;
  *   3. EMI_START_BEND, and PLANNED instances without a route while bend != 0: rows px, py bent by half a sine wave,
