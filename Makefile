@@ -20,7 +20,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Iinclude -Wall
 XML2_INC  := -I/usr/include/libxml2
 XML2_LIB  := -lxml2
 
-.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-ode-delay-operator check-plan-route check-pass-plan check-pass-registers check-pass-residency check-pass-work
+.PHONY: all lib host oracle clean check-keep-record check-refine-book check-restart-book check-nlp check-mesh-driver check-ode-operator check-ode-delay-operator check-plan-route check-pass-plan check-param-table-plan check-pass-registers check-pass-residency check-pass-work
 ifneq ($(wildcard etol_amd/host/eMI355X.cpp),)
 all: lib host oracle
 else
@@ -50,7 +50,7 @@ $(LIBDIR)/emi_host.o: $(CSRC)/emi_host.cpp $(CSRC)/emi_plan_route.hpp include/em
 $(LIBDIR)/emi_comm.o: $(CSRC)/emi_comm.cpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
-LIB_OBJ := emi_kernels emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_api_ode emi_rtc emi_kkt emi_adjoint \
+LIB_OBJ := emi_kernels emi_kernels_tab emi_symdefect emi_defect_f32 emi_api emi_api_pass emi_api_adjoint emi_api_kkt emi_api_ipm emi_api_ode emi_rtc emi_kkt emi_adjoint \
            emi_kkt_blocks emi_ipm emi_ipm_solve emi_ipm_ladder emi_ode_error emi_start_guess emi_api_start emi_host emi_comm
 $(LIBDIR)/libemi355x.so: $(LIB_OBJ:%=$(LIBDIR)/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lhiprtc -lrocsolver -lrocblas -ldl
@@ -71,7 +71,8 @@ $(LIBDIR)/etol_mi355x_montecarlo: etol_amd/examples/etol_mi355x_montecarlo.cpp $
 	$(CXX) $(CXXFLAGS) -I$(HOST) -pthread -o $@ $< -L$(LIBDIR) -letol_mi355x -lemi355x -Wl,-rpath,'$$ORIGIN'
 
 HARNESS_SRC := tests/harness/etol_harness.cpp tests/harness/etol_harness_certify.cpp tests/harness/etol_harness_delay_certify.cpp tests/harness/etol_harness_blocks.cpp tests/harness/etol_harness_ipm.cpp tests/harness/etol_harness_lockstep.cpp tests/harness/etol_harness_ladder.cpp tests/harness/etol_harness_rescue.cpp \
-               tests/harness/etol_harness_ode_error.cpp tests/harness/etol_harness_track_ladder.cpp tests/harness/etol_harness_delay_ode_error.cpp
+               tests/harness/etol_harness_ode_error.cpp tests/harness/etol_harness_track_ladder.cpp tests/harness/etol_harness_delay_ode_error.cpp \
+               tests/harness/etol_harness_param_table.cpp
 tests/harness/libetol_harness.so: $(HARNESS_SRC) $(LIBDIR)/libetol_mi355x.so $(HOST_HDR) $(CSRC)/emi_ipm_control.hpp
 	$(CXX) $(CXXFLAGS) -I$(HOST) -I$(CSRC) -shared -o $@ $(HARNESS_SRC) -L$(LIBDIR) -letol_mi355x -lemi355x -ldl \
 		-Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
@@ -149,6 +150,13 @@ PASS_PLAN_CHECK_OUT ?= $(LIBDIR)/pass_plan_check
 check-pass-plan: tests/harness/pass_plan_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
 	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PASS_PLAN_CHECK_OUT) tests/harness/pass_plan_main.cpp
 	$(PASS_PLAN_CHECK_OUT)
+
+# ... and what that policy makes of a context with a per-instance parameter table (PassPolicyIn::param_table: never overlapped, never one
+# launch, no pieces, the report of "overlap" 0), the same way
+PARAM_PLAN_CHECK_OUT ?= $(LIBDIR)/param_table_plan_check
+check-param-table-plan: tests/harness/param_table_plan_main.cpp $(CSRC)/emi_pass_plan.hpp include/emi355x.h | $(LIBDIR)
+	$(CXX) $(SANITIZE) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $(PARAM_PLAN_CHECK_OUT) tests/harness/param_table_plan_main.cpp
+	$(PARAM_PLAN_CHECK_OUT)
 
 # the residency rule of that policy ("sym_res": three resident workgroups per CU only with a direct-operator row, the default by band, built-in
 # models only, the order in which resolve_form grants the wants) as a stand-alone program under the host sanitizers

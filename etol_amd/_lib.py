@@ -200,6 +200,8 @@ SYMBOLS = {
     "emi_kkt_solve_shard_dev": (C.c_int, [_P, _P, C.POINTER(C.c_ubyte)]),
     "emi_kkt_solve_refined_shard_dev": (C.c_int, [_P, _P, C.POINTER(C.c_ubyte), _D, C.c_int, _D, _I, _I, _I]),
     "emi_set_batch": (C.c_int, [_P, C.c_int]),
+    "emi_set_model_params_batch": (C.c_int, [_P, _D, C.c_int, C.c_int]),
+    "emi_get_model_params_batch": (C.c_int, [_P, _D, _I, _I]),
     "emi_set_path": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.c_int]),
     "emi_set_tracks": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
     "emi_set_track_waypoints": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _I, _D, _D, _D]),

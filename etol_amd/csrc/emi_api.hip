@@ -306,6 +306,9 @@ static void model_in_force(emi_ctx_t c, int model, int ns, int nc, int npath, co
     c->maximize = maximize ? 1 : 0;
     memset(c->params, 0, sizeof c->params);
     for (int i = 0; i < nparams; ++i) c->params[i] = params[i];
+    c->nparams = nparams;
+    c->ptab_sets = 0;           // a per-instance table was the previous model's
+    c->h_ptab.clear();
     c->np = 0;
     c->path_sets = 0;
     c->path_has_track = false;
@@ -371,13 +374,54 @@ int emi_set_batch(emi_ctx_t c, int B) {
     const size_t rb = c->f32 ? 4 : 8;
     int st = ensure(c, c->d_cost_part, (size_t)B * emi::node_chunks(c->M) * rb);
     if (st) return st;
+    if (B != c->B) {            // a per-instance parameter table is one row per instance of the batch it was set for
+        c->ptab_sets = 0;
+        c->h_ptab.clear();
+    }
     c->B = B;
+    return EMI_OK;
+}
+
+int emi_set_model_params_batch(emi_ctx_t c, const double* params, int nsets, int nparams) {
+    if (!c) return EMI_ERR_ARG;
+    if (c->model < 0) return fail(c, EMI_ERR_STATE, "emi_set_model / emi_set_model_source must precede emi_set_model_params_batch");
+    if (c->B <= 0) return fail(c, EMI_ERR_STATE, "emi_set_batch must precede emi_set_model_params_batch");
+    if (nsets == 0) {           // back to the shared set of emi_set_model*
+        if (c->ptab_sets > 0) c->keep.bump();
+        c->ptab_sets = 0;
+        c->h_ptab.clear();
+        return EMI_OK;
+    }
+    if (nsets != c->B) return fail(c, EMI_ERR_ARG, "emi_set_model_params_batch: %d sets, the batch is %d (0 removes the table)", nsets, c->B);
+    if (nparams != c->nparams || (nparams > 0 && !params))
+        return fail(c, EMI_ERR_ARG, "emi_set_model_params_batch: the model takes %d parameters, got %d", c->nparams, nparams);
+    if (c->nch > 0)
+        return fail(c, EMI_ERR_UNSUPPORTED, "emi_set_model_params_batch: contexts with delays (emi_set_delays) take the shared parameter set only");
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<double> rows((size_t)nsets * EMI_MAX_PARAMS, 0.0);
+    for (int b = 0; b < nsets; ++b)
+        for (int i = 0; i < nparams; ++i) rows[(size_t)b * EMI_MAX_PARAMS + i] = params[(size_t)b * nparams + i];
+    c->keep.bump();             // the model-invariant rows of VALS are functions of the parameters
+    EMI_TRY(upload_real(c, c->d_ptab, rows.data(), rows.size()));      // (rounded once, as fill_node_args rounds the shared set)
+    c->h_ptab.assign(params, params + (size_t)nsets * nparams);
+    c->ptab_sets = nsets;
+    return EMI_OK;
+}
+
+int emi_get_model_params_batch(emi_ctx_t c, double* params, int* nsets, int* nparams) {
+    if (!c) return EMI_ERR_ARG;
+    if (nsets) *nsets = c->ptab_sets;
+    if (nparams) *nparams = c->model < 0 ? 0 : c->nparams;
+    if (params && c->ptab_sets > 0) std::copy(c->h_ptab.begin(), c->h_ptab.end(), params);
     return EMI_OK;
 }
 
 int emi_set_delays(emi_ctx_t c, int x_horizon, int u_horizon, double dt) {
     if (!c || x_horizon < 0 || u_horizon < 0) return fail(c, EMI_ERR_ARG, "emi_set_delays: horizons must be >= 0");
     if (c->model < 0) return fail(c, EMI_ERR_STATE, "emi_set_model / emi_set_model_source must precede emi_set_delays");
+    if (has_param_table(c) && std::max(x_horizon - 1, 0) * c->ns + u_horizon > 0)
+        return fail(c, EMI_ERR_UNSUPPORTED, "emi_set_delays: the context holds a per-instance parameter table (emi_set_model_params_batch), "
+                    "which contexts with delays do not take");
     c->keep.bump();
     const int nxd = std::max(x_horizon - 1, 0) * c->ns;
     // nc_free + nxd + uh * nc_free = nc  (the model's control count includes the delayed values)

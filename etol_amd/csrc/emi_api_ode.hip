@@ -147,7 +147,10 @@ int emi_ode_error_dev(emi_ctx_t c, const void* dX, const void* dU, const double*
     r.ul = clip ? c->d_ode_ub.p : nullptr; r.uu = clip ? c->d_ode_ub.p + nc : nullptr;
     r.eta = eta; r.M = M; r.B = B; r.lds = lds; r.ldc = np; r.h = h;
     for (int i = 0; i < EMI_MAX_PARAMS; ++i) r.P.p[i] = c->params[i];
-    if (c->rtc) HIP_TRY(c, emi::rtc_launch_ode_resid(c->rtc, r, c->stream));
+    const double* tab = param_rows<double>(c, 0);      // per-instance parameter table: the tabled residual kernel
+    if (tab && c->rtc) HIP_TRY(c, emi::rtc_launch_ode_resid_tab(c->rtc, r, tab, c->stream));
+    else if (tab) HIP_TRY(c, emi::launch_ode_resid_tab(c->model, r, tab, c->stream));
+    else if (c->rtc) HIP_TRY(c, emi::rtc_launch_ode_resid(c->rtc, r, c->stream));
     else HIP_TRY(c, emi::launch_ode_resid(c->model, r, c->stream));
     const emi::OdeFinishArgs f{(const double*)dX, Zs, eta, (double*)dErr, B, M, ns, lds, 2 * np, h};
     HIP_TRY(c, emi::launch_ode_finish(f, c->stream));

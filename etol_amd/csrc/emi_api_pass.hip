@@ -38,6 +38,7 @@ emi::PassPolicyIn policy_in(emi_ctx_t c) {
     in.node_store = c->node_store;
     in.slice = c->slice;
     in.small_rows = c->small_rows;
+    in.param_table = has_param_table(c);
     return in;
 }
 
@@ -178,7 +179,7 @@ FormChoice choose_form(emi_ctx_t c, Launch L, unsigned flags) {
     if (nodes && defect && !ch.small && emi::pass_overlapped(in)) {
         ch.plan = emi::plan_pass(in, L.B, jac);
         ch.form = ch.plan.one_launch ? Form::PassF64 : Form::TwoKernelF64;
-    } else if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused) {
+    } else if (c->f32 && nodes && defect && jac && !c->rtc && c->allow_fused && !in.param_table) {
         if ((c->overlap_mode == 3 || (c->overlap_mode == 0 && c->f32_one_launch)) && emi::pass_f32_supported(c->model, L.B * c->ns, c->M, L.B))
             ch.form = Form::PassF32;
         else if (c->overlap_mode == 2 && emi::defect_f32_mfma_supported(c->M))
@@ -453,7 +454,11 @@ template <typename T>
 int launch_nodes_alone(emi_ctx_t c, Launch L, const PassIO& io, bool jac) {
     emi::NodeArgs<T> a;
     fill_node_args(c, L, a, io);
-    if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<T>(c->rtc, a, jac, true, c->stream));
+    // (a per-instance parameter table: the tabled instantiations, on the rows from the launch's first instance on)
+    const T* tab = param_rows<T>(c, L.first);
+    if (tab && c->rtc) HIP_TRY(c, emi::rtc_launch_nodes_tab<T>(c->rtc, a, tab, jac, c->stream));
+    else if (tab) HIP_TRY(c, emi::launch_nodes_tab<T>(c->model, a, tab, jac, c->stream));
+    else if (c->rtc) HIP_TRY(c, emi::rtc_launch_nodes<T>(c->rtc, a, jac, true, c->stream));
     else HIP_TRY(c, emi::launch_nodes<T>(c->model, a, jac, true, c->stream));
     HIP_TRY(c, emi::launch_cost_finish<T>(a.cost_part, a.cost, L.B, emi::node_chunks(c->M), a.sgn * a.h, c->stream));
     return EMI_OK;
@@ -465,7 +470,7 @@ int form_sequential(emi_ctx_t c, Launch L, const PassIO& io, unsigned flags, boo
     if (flags & EMI_EVAL_NODES) EMI_TRY(c->f32 ? launch_nodes_alone<float>(c, L, io, jac) : launch_nodes_alone<double>(c, L, io, jac));
     EMI_TRY(prof_mark(c, pe, E1, AT_ANY, c->stream));
     if ((flags & EMI_EVAL_DEFECT) && c->f32) {
-        const bool mfma = emi::defect_f32_mfma_supported(c->M) && c->allow_fused;
+        const bool mfma = emi::defect_f32_mfma_supported(c->M) && c->allow_fused && !has_param_table(c);      // (a table: the route of "overlap" 0)
         if (mfma) HIP_TRY(c, emi::launch_defect_f32_mfma(defect_args_f32(c, L, io), c->stream, c->f32_ring, c->f32_ring_wgs));
         else HIP_TRY(c, emi::launch_defect_f32(defect_args_f32(c, L, io), c->stream));
         c->last_defect_kernel = name_defect_f32(c, mfma);
@@ -551,8 +556,10 @@ int emi_eval_dev(emi_ctx_t c, const void* dX, const void* dU, void* dRES, void* 
     // large batches go out in pieces only where something forces them (plan_piece); not while per-kernel profiling is on
     int piece = 0;
     const emi::PassPolicyIn in = policy_in(c);
-    if (!c->profile && (flags & EMI_EVAL_ALL) == EMI_EVAL_ALL && emi::pass_overlapped(in) && dX && dU && dRES && dCOST &&
-        (dVALS || (flags & EMI_EVAL_NOJAC)))
+    // (a context with a parameter table: only the pieces the "slice" option asks for -- the sequential route has no operand offsets to
+    // keep below 4 GB; each piece reads the table's rows from its first instance on)
+    if (!c->profile && (flags & EMI_EVAL_ALL) == EMI_EVAL_ALL && (emi::pass_overlapped(in) || (in.param_table && in.slice > 0)) && dX && dU && dRES &&
+        dCOST && (dVALS || (flags & EMI_EVAL_NOJAC)))
         piece = emi::plan_piece(in, c->B);
     const PassIO io{dX, dU, dRES, dVALS, dCOST};
     // EMI_EVAL_KEEP_INVARIANT: honoured where this pass writes the Jacobian into the buffer the record names, under the generation
@@ -617,12 +624,18 @@ int emi_hess_dev(emi_ctx_t c, const void* dX, const void* dU, const void* dLamF,
     if (c->f32) {
         emi::HessArgs<float> a;
         fill(a);
-        if (c->rtc) HIP_TRY(c, emi::rtc_launch_hess<float>(c->rtc, a, c->stream));
+        const float* tab = param_rows<float>(c, 0);
+        if (tab && c->rtc) HIP_TRY(c, emi::rtc_launch_hess_tab<float>(c->rtc, a, tab, c->stream));
+        else if (tab) HIP_TRY(c, emi::launch_hess_tab<float>(c->model, a, tab, c->stream));
+        else if (c->rtc) HIP_TRY(c, emi::rtc_launch_hess<float>(c->rtc, a, c->stream));
         else HIP_TRY(c, emi::launch_hess<float>(c->model, a, c->stream));
     } else {
         emi::HessArgs<double> a;
         fill(a);
-        if (c->rtc) HIP_TRY(c, emi::rtc_launch_hess<double>(c->rtc, a, c->stream));
+        const double* tab = param_rows<double>(c, 0);
+        if (tab && c->rtc) HIP_TRY(c, emi::rtc_launch_hess_tab<double>(c->rtc, a, tab, c->stream));
+        else if (tab) HIP_TRY(c, emi::launch_hess_tab<double>(c->model, a, tab, c->stream));
+        else if (c->rtc) HIP_TRY(c, emi::rtc_launch_hess<double>(c->rtc, a, c->stream));
         else HIP_TRY(c, emi::launch_hess<double>(c->model, a, c->stream));
     }
     return EMI_OK;

@@ -120,6 +120,15 @@ template <typename T> struct OdeResidDelayArgs {
     ModelParams<T> P;
 };
 
+// An argument block with a per-instance parameter table behind it (emi_set_model_params_batch): what the TABLED instantiations of the
+// node, Hessian and ODE-residual kernels take.  tab [B][EMI_MAX_PARAMS], in the context's real type, already at the launch's first
+// instance; the workgroup of instance blockIdx.y reads row blockIdx.y in place of a.P, which it ignores.  The blocks themselves, and
+// so what the untabled instantiations read, are as they were.
+template <class A, typename T> struct Tabled {
+    A a;
+    const T* tab;
+};
+
 struct SymDefectArgs {
     const double* X;
     const double* U;

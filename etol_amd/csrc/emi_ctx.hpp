@@ -86,6 +86,13 @@ struct emi_ctx_s {
     // model
     int model = -1, ns = 0, nc = 0, maximize = 0;
     double params[EMI_MAX_PARAMS] = {0};
+    int nparams = 0;            // ... how many of them the model takes
+    // per-instance parameter table (emi_set_model_params_batch): row b is the parameter set of instance b, in place of `params`.
+    // While it is in force every kernel that evaluates the model runs in its tabled instantiation and the pass takes the sequential
+    // route (has_param_table below).  Survives mesh, path table, tracks and stream; dropped by a new model and by another batch size
+    int ptab_sets = 0;          // 0: none; else B
+    DevBuf d_ptab;              // [B][EMI_MAX_PARAMS] in the context's real type, rows zero padded
+    std::vector<double> h_ptab; // [B][nparams] as given (emi_get_model_params_batch)
     emi::KktWorkspace* kkt = nullptr;   // Newton-step workspace (emi_kkt_factor)
     std::vector<emi::KktWorkspace*> kkt_shard;  // one more per instance of the batch (emi_kkt_*_shard_dev), created on demand; apart from `kkt`
     int kkt_method = 1;                 // 1: Schur complement + Cholesky (falls back to 0 if not quasi-definite); 0: LU of K
@@ -267,6 +274,11 @@ inline int np_total(emi_ctx_t c) { return c->np + c->np_model; }     // rows of 
 inline int nvals_of(emi_ctx_t c) { return c->ns * (c->ns + c->nc) + 2 * c->np + c->np_model * (int)c->pvars.size() + (c->ns + c->nc); }
 inline int nres_of(emi_ctx_t c) { return c->ns + np_total(c); }
 inline int nhess_of(emi_ctx_t c) { const int nv = c->ns + c->nc; return nv * (nv + 1) / 2; }
+inline bool has_param_table(emi_ctx_t c) { return c->ptab_sets > 0; }
+// the rows of the table from instance `first` on, as the tabled kernels take them (null without a table)
+template <typename T> inline const T* param_rows(emi_ctx_t c, int first) {
+    return has_param_table(c) ? (const T*)c->d_ptab.p + (size_t)first * EMI_MAX_PARAMS : nullptr;
+}
 inline int ready(emi_ctx_t c) {
     if (!c) return EMI_ERR_ARG;
     if (c->M <= 0) return fail(c, EMI_ERR_STATE, "emi_set_mesh has not been called");
@@ -276,6 +288,8 @@ inline int ready(emi_ctx_t c) {
         return fail(c, EMI_ERR_STATE, "path table has %d sets, batch is %d", c->path_sets, c->B);
     if (c->ntracks > 0 && c->track_sets != 1 && c->track_sets != c->B)
         return fail(c, EMI_ERR_STATE, "track table has %d sets, batch is %d", c->track_sets, c->B);
+    if (c->ptab_sets > 0 && c->ptab_sets != c->B)
+        return fail(c, EMI_ERR_STATE, "parameter table has %d sets, batch is %d", c->ptab_sets, c->B);
     return EMI_OK;
 }
 

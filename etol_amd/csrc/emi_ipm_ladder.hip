@@ -474,6 +474,9 @@ struct LadderRun {
 int ipm_solve_refine(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, double t0, double tf, const emi_ipm_refine_t& rf, const void* dX0,
                      const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC, emi_ipm_result_t* results, double* err,
                      emi_ipm_refine_result_t* out) {
+    if (emi_api::has_param_table(c))
+        return emi_api::fail(c, EMI_ERR_UNSUPPORTED, "emi_ipm_solve_refine_dev: the context holds a per-instance parameter table (emi_set_model_params_batch); "
+                             "this driver compacts the batch and has no row map for the table");
     LadderRun run{c, "emi_ipm_solve_refine_dev", nrungs, rungs, t0, tf, &rf, dX0, dU0, ldm, dX, dU, dLamF, dLamC};
     run.book.begin(c->B, nrungs, rf.first_check, results, err, out);
     return run.run();
@@ -496,6 +499,9 @@ int ipm_solve_restart(emi_ctx_t c, int nrungs, const emi_ipm_rung_t* rungs, doub
                       const emi_ipm_restart_t& rs, const void* dX0, const void* dU0, int ldm, void* dX, void* dU, void* dLamF, void* dLamC,
                       emi_ipm_result_t* results, double* err, emi_ipm_restart_result_t* out) {
     const char* entry = "emi_ipm_solve_restart_dev";
+    if (emi_api::has_param_table(c))
+        return emi_api::fail(c, EMI_ERR_UNSUPPORTED, "%s: the context holds a per-instance parameter table (emi_set_model_params_batch); "
+                             "this driver compacts the batch and has no row map for the table", entry);
     const int B = c->B, ns = c->ns, A = (dX0 ? 1 : 0) + rs.nstarts;
     RestartBook rb;
     rb.begin(B, A, nrungs, rf ? rf->first_check : RefineBook::NEVER, rs.retry_mask, results, err, out);

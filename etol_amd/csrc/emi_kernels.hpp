@@ -23,6 +23,10 @@ bool invariant_rows(int model, int np, unsigned char* mask);    // [ns nv + 2 np
 template <typename T>
 hipError_t launch_nodes(int model, const NodeArgs<T>& a, bool jac, bool defect_rows, hipStream_t s);
 template <typename T> hipError_t launch_hess(int model, const HessArgs<T>& a, hipStream_t s);
+// ... of a context with a per-instance parameter table (emi_kernels_tab.hip): tab [a.B][EMI_MAX_PARAMS] at the launch's first instance.
+// The node kernel always with the defect rows and plain stores: such a context takes the sequential route
+template <typename T> hipError_t launch_nodes_tab(int model, const NodeArgs<T>& a, const T* tab, bool jac, hipStream_t s);
+template <typename T> hipError_t launch_hess_tab(int model, const HessArgs<T>& a, const T* tab, hipStream_t s);
 hipError_t launch_defect_f64(const DefectArgs& a, hipStream_t s);
 bool defect_small_supported(int R);
 hipError_t launch_defect_small_f64(const DefectArgs& a, hipStream_t s);
@@ -121,6 +125,8 @@ hipError_t launch_ode_copy_D(const double* D, double* dst, int M, int ldk, hipSt
 hipError_t launch_ode_resid(int model, const OdeResidArgs<double>& a, hipStream_t s);
 struct RtcModel;
 hipError_t rtc_launch_ode_resid(RtcModel* m, const OdeResidArgs<double>& a, hipStream_t s);
+hipError_t launch_ode_resid_tab(int model, const OdeResidArgs<double>& a, const double* tab, hipStream_t s);     // per-instance parameter table
+hipError_t rtc_launch_ode_resid_tab(RtcModel* m, const OdeResidArgs<double>& a, const double* tab, hipStream_t s);
 // ... of a context with delays (emi_ode_resid_delay_kernel)
 hipError_t launch_ode_resid_delay(int model, const OdeResidDelayArgs<double>& a, hipStream_t s);
 hipError_t rtc_launch_ode_resid_delay(RtcModel* m, const OdeResidDelayArgs<double>& a, hipStream_t s);
@@ -195,6 +201,9 @@ bool rtc_has_symdefect(const RtcModel* m);
 template <typename T>
 hipError_t rtc_launch_nodes(RtcModel* m, const NodeArgs<T>& a, bool jac, bool defect_rows, hipStream_t s);
 template <typename T> hipError_t rtc_launch_hess(RtcModel* m, const HessArgs<T>& a, hipStream_t s);
+// ... with a per-instance parameter table (the tabled kernels of the model program; the node kernel with the defect rows)
+template <typename T> hipError_t rtc_launch_nodes_tab(RtcModel* m, const NodeArgs<T>& a, const T* tab, bool jac, hipStream_t s);
+template <typename T> hipError_t rtc_launch_hess_tab(RtcModel* m, const HessArgs<T>& a, const T* tab, hipStream_t s);
 hipError_t rtc_launch_symdefect(RtcModel* m, const SymDefectArgs& a, hipStream_t s);
 // the one-launch pass of a run-time compiled model: which state split it was compiled with for large batches (small ones take
 // SW = 1), whether (sw, store mode) is available, and the launch

@@ -114,6 +114,25 @@ template <typename T> EMI_DEV T wave_sum(T v) {
     return v;
 }
 
+// Row b of a per-instance parameter table ([B][EMI_MAX_PARAMS], Tabled<> of emi_args.hpp).  The address depends on a kernel argument
+// and the workgroup's instance alone, and the table is read-only for the launch: constant address space, so the loads are scalar
+// and the row sits in scalar registers, as the by-value set of an untabled launch does.
+template <typename T> EMI_DEV ModelParams<T> load_param_row(const T* tab, int b) {
+    typedef const __attribute__((address_space(4))) T* cptr_t;
+    cptr_t r = (cptr_t)(tab + (size_t)b * EMI_MAX_PARAMS);
+    ModelParams<T> P;
+#pragma unroll
+    for (int i = 0; i < EMI_MAX_PARAMS; ++i) P.p[i] = r[i];
+    return P;
+}
+
+// the argument block of an instantiation: the block itself, or the block with a table behind it (TAB)
+template <bool TAB, class A, typename T> struct MaybeTabled { using type = A; };
+template <class A, typename T> struct MaybeTabled<true, A, T> { using type = Tabled<A, T>; };
+template <typename T> EMI_DEV const HessArgs<T>& args_of(const HessArgs<T>& a) { return a; }
+template <typename T> EMI_DEV const OdeResidArgs<T>& args_of(const OdeResidArgs<T>& a) { return a; }
+template <class A, typename T> EMI_DEV const A& args_of(const Tabled<A, T>& t) { return t.a; }
+
 // ---------------------------------------------------------------------------
 // K1+K2+K3+K5: one thread = VEC consecutive nodes of one instance.
 //   grid.x = node chunks (EMI_NODE_THREADS*VEC nodes each), grid.y = instance
@@ -138,9 +157,13 @@ template <typename T> EMI_DEV T wave_sum(T v) {
 // are functions of the mesh, the parameters and the cost sign alone (0, -h, D_kk, -h / p ...; 50 of the quadrotor's 96 VALS rows)
 // and VALS still holds them from an earlier full pass of the same context (EMI_EVAL_KEEP_INVARIANT; emi_api_pass.hip keeps the record
 // that says so).  Whole rows are skipped; what fed only those stores goes with them.  Path partials, RES and COST always vary.
-template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST, bool DEFATOMIC = false, bool KEEP = false>
-EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, const int nbx) {
+// TAB: the model parameters are row b of `tab` (load_param_row, once, ahead of everything else) instead of a.P.
+template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, int ST, bool DEFATOMIC = false, bool KEEP = false, bool TAB = false>
+EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, const int nbx, const T* tab = nullptr) {
     constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV;
+    ModelParams<T> Prow;
+    if constexpr (TAB) Prow = load_param_row<T>(tab, b);
+    const ModelParams<T>& P = TAB ? Prow : a.P;
     const int M = a.M;
     // a workgroup of 2 x EMI_NODE_THREADS threads (the one-launch pass with its K range in two halves) runs two of these
     // bodies side by side, one per half, each on its own (bx, b): tix is the thread's index within its half
@@ -176,11 +199,11 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
 #pragma unroll
                 for (int v = 0; v < NV; ++v) ze[v] = z[v][e];
                 if (DEFROWS) {
-                    Model::f(a.P, ze, tk[e], fe);
+                    Model::f(P, ze, tk[e], fe);
 #pragma unroll
                     for (int i = 0; i < NS; ++i) fo[i][e] = -h * fe[i];
                 }
-                lsum = fma1(wk[e], Model::cost(a.P, ze, tk[e]), lsum);
+                lsum = fma1(wk[e], Model::cost(P, ze, tk[e]), lsum);
             }
             if constexpr (DEFROWS && DEFATOMIC) {
 #pragma unroll
@@ -201,8 +224,8 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
                 T ze[NV], Je[NS][NV], ge[NV];
 #pragma unroll
                 for (int v = 0; v < NV; ++v) ze[v] = z[v][e];
-                Model::jac(a.P, ze, tk[e], Je);
-                Model::grad(a.P, ze, tk[e], ge);
+                Model::jac(P, ze, tk[e], Je);
+                Model::grad(P, ze, tk[e], ge);
 #pragma unroll
                 for (int i = 0; i < NS; ++i)
 #pragma unroll
@@ -301,7 +324,7 @@ EMI_DEV void emi_nodes_body(const NodeArgs<T>& a, const int bx, const int b, con
                     T ze[NV], ce[NPM], cde[NPM * PW];
 #pragma unroll
                     for (int v = 0; v < NV; ++v) ze[v] = z[v][e];
-                    Model::path(a.P, ze, tk[e], ce, cde);
+                    Model::path(P, ze, tk[e], ce, cde);
 #pragma unroll
                     for (int j = 0; j < NPM; ++j) cm[j][e] = ce[j];
 #pragma unroll
@@ -351,6 +374,12 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_nodes_kernel(NodeArgs<T>
     emi_nodes_body<T, Model, VEC, JAC, DEFROWS, ST, false, KEEP>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
 }
 
+// ... with a per-instance parameter table: the sequential route's forms (plain stores) of a context that holds one
+template <typename T, class Model, int VEC, bool JAC, bool DEFROWS, bool KEEP = false>
+__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_nodes_tab_kernel(Tabled<NodeArgs<T>, T> t) {
+    emi_nodes_body<T, Model, VEC, JAC, DEFROWS, 0, false, KEEP, true>(t.a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, t.tab);
+}
+
 template <typename T>
 __global__ void emi_cost_finish_kernel(const T* __restrict__ part, T* __restrict__ cost, int B,
                                        int nchunks, T scale) {
@@ -365,10 +394,15 @@ __global__ void emi_cost_finish_kernel(const T* __restrict__ part, T* __restrict
 // KH: Lagrangian Hessian node blocks (packed lower triangle, (NV)(NV+1)/2).
 //   H = sigma*sgn*h*w_k L_zz  - h sum_i lamF[i][k] f_i,zz  + sum_j lamC[j][k] c_j,zz
 // ---------------------------------------------------------------------------
-template <typename T, class Model>
-__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(HessArgs<T> a) {
+// TAB: the tabled instantiation (argument block Tabled<HessArgs<T>, T>), the parameters are row b of the table instead of a.P
+template <typename T, class Model, bool TAB = false>
+__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(typename MaybeTabled<TAB, HessArgs<T>, T>::type arg) {
     constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV, NH = NV * (NV + 1) / 2;
+    const HessArgs<T>& a = args_of(arg);
     const int b = blockIdx.y;
+    ModelParams<T> Prow;
+    if constexpr (TAB) Prow = load_param_row<T>(arg.tab, b);
+    const ModelParams<T>& P = TAB ? Prow : a.P;
     const int M = a.M;
     const int k = blockIdx.x * EMI_NODE_THREADS + threadIdx.x;
     if (k >= M) return;
@@ -382,7 +416,7 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(HessArgs<T> 
 #pragma unroll
     for (int q = 0; q < NH; ++q) H[q] = T(0);
     const T cL = a.sigma * a.sgn * a.h * a.w[k];
-    Model::hess(a.P, z, a.node_t[k], cL, cf, H);
+    Model::hess(P, z, a.node_t[k], cL, cf, H);
     const int np = a.np - Model::NPATH;          // rows of the record table; the model's own rows follow them
     if (a.np > 0) {
         const int set = a.path_sets > 1 ? b : 0;
@@ -406,7 +440,7 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(HessArgs<T> 
             T mu[Model::NPATH];
 #pragma unroll
             for (int j = 0; j < Model::NPATH; ++j) mu[j] = a.lamC[((size_t)b * a.np + np + j) * M + k];
-            Model::path_hess(a.P, z, a.node_t[k], mu, H);
+            Model::path_hess(P, z, a.node_t[k], mu, H);
         }
         const int lo = a.px < a.py ? a.px : a.py, hi = a.px < a.py ? a.py : a.px;
         const int qxx = a.px * (a.px + 1) / 2 + a.px, qyy = a.py * (a.py + 1) / 2 + a.py;
@@ -427,10 +461,15 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_hess_kernel(HessArgs<T> 
 // loaded coalesced along k (the point order is q-major), the controls clipped, f evaluated.  Sums in ascending q; a NaN anywhere
 // in the inputs of an interval stays in its eta.  No LDS.
 // ---------------------------------------------------------------------------
-template <typename T, class Model>
-__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_kernel(OdeResidArgs<T> a) {
+// (TAB: as emi_hess_kernel)
+template <typename T, class Model, bool TAB = false>
+__global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_kernel(typename MaybeTabled<TAB, OdeResidArgs<T>, T>::type arg) {
     constexpr int NS = Model::NS, NC = Model::NC, NV = Model::NV;
+    const OdeResidArgs<T>& a = args_of(arg);
     const int b = blockIdx.y, M = a.M, nq = M - 1;
+    ModelParams<T> Prow;
+    if constexpr (TAB) Prow = load_param_row<T>(arg.tab, b);
+    const ModelParams<T>& P = TAB ? Prow : a.P;
     const int k = blockIdx.x * EMI_NODE_THREADS + threadIdx.x;
     if (k >= nq) return;
     // 5-point Gauss-Legendre weights on [-1, 1]
@@ -460,7 +499,7 @@ __global__ __launch_bounds__(EMI_NODE_THREADS) void emi_ode_resid_kernel(OdeResi
             }
             z[NS + v] = u;
         }
-        Model::f(a.P, z, a.tq[p + k], f);
+        Model::f(P, z, a.tq[p + k], f);
 #pragma unroll
         for (int i = 0; i < NS; ++i) acc[i] += g[q] * fabs(xd[i] - f[i]);
     }

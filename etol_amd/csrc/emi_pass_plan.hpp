@@ -250,11 +250,14 @@ struct PassPolicyIn {
     // the options (emi_set_option), as the context holds them
     int allow_fused = 1, overlap_mode = 0, sym_ct = 0, sym_ksplit = 0, sym_cpart = 0, sym_gblk = 0, sym_cx = 0, sym_nst = 3, sym_hs = 0, sym_ctc = 0,
         sym_bk = 0, sym_dop = 0, sym_res = 0, pass_order = -1, node_store = -1, slice = 0, small_rows = 24;
+    // the context holds a per-instance parameter table (emi_set_model_params_batch): the MFMA forms evaluate f in their epilogue for 16
+    // instances per tile, one per lane, and have no tabled instantiation -- such a context takes the sequential route, as under "overlap" 0
+    bool param_table = false;
 };
 
 // the even/odd MFMA defect kernel beside the node kernel (or both roles in one launch): needs an exactly centro-antisymmetric D
 inline bool pass_overlapped(const PassPolicyIn& in) {
-    if (in.f32 || !in.allow_fused || !in.symmetric || in.M <= 0 || in.model_class == PASS_MODEL_NONE) return false;
+    if (in.f32 || !in.allow_fused || in.param_table || !in.symmetric || in.M <= 0 || in.model_class == PASS_MODEL_NONE) return false;
     if (in.model_class == PASS_MODEL_RTC) return in.M % 128 == 0;
     return symdefect_shape_ok(in.M, in.sym_ct);
 }

@@ -26,6 +26,8 @@ struct RtcModel {
     hipModule_t mod = nullptr;
     hipFunction_t nodes[2][2][2] = {};   // [vec2][jac][defect rows]
     hipFunction_t hess = nullptr;
+    hipFunction_t nodes_tab[2][2] = {};  // per-instance parameter table: [vec2][jac], with the defect rows
+    hipFunction_t hess_tab = nullptr, ode_resid_tab = nullptr;
     hipFunction_t ode_resid = nullptr;   // ODE-error residual at the Gauss points (f64 programs)
     hipFunction_t ode_resid_delay = nullptr;     // ... of a context with delays
     hipFunction_t ring = nullptr;        // even/odd MFMA defect kernel (f64, LDS permitting)
@@ -51,6 +53,7 @@ bool ring_fits(int ns) { return ns <= 8 && ring_lds_bytes(ns) <= 160 * 1024; }
 
 struct Names {
     std::string nodes[2][2][2], hess, ode_resid, ode_resid_delay, ring, pass[N_PASS_FORMS_RTC], node_nt;
+    std::string nodes_tab[2][2], hess_tab, ode_resid_tab;
 };
 
 Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
@@ -63,6 +66,11 @@ Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
                 n.nodes[v][j][d] = "emi::emi_nodes_kernel<" + T + ", " + model + ", " + (v ? "2" : "1") + ", " +
                                    (j ? "true" : "false") + ", " + (d ? "true" : "false") + ">";
     n.hess = "emi::emi_hess_kernel<" + T + ", " + model + ">";
+    for (int v = 0; v < 2; ++v)
+        for (int j = 0; j < 2; ++j)
+            n.nodes_tab[v][j] = "emi::emi_nodes_tab_kernel<" + T + ", " + model + ", " + (v ? "2" : "1") + ", " + (j ? "true" : "false") + ", true>";
+    n.hess_tab = "emi::emi_hess_kernel<" + T + ", " + model + ", true>";
+    if (!f32) n.ode_resid_tab = "emi::emi_ode_resid_kernel<double, " + model + ", true>";
     if (!f32) n.ode_resid = "emi::emi_ode_resid_kernel<double, " + model + ">";
     if (!f32) n.ode_resid_delay = "emi::emi_ode_resid_delay_kernel<double, " + model + ">";
     if (with_ring) {
@@ -78,7 +86,8 @@ Names kernel_names(const char* sn, bool f32, bool with_ring, int ns) {
 }
 
 // compile; on success *code holds the gfx950 code object and *lowered the mangled kernel names in
-// the order nodes[0][0][0..1], nodes[0][1][..], nodes[1][..][..], hess, ODE residual and its delayed form (f64), ring, pass (small, large), node kernel with nt stores
+// the order nodes[0][0][0..1], nodes[0][1][..], nodes[1][..][..], hess, ODE residual and its delayed form (f64), ring, pass (small, large), node kernel with nt stores,
+// then the tabled kernels: nodes_tab[0][0..1], nodes_tab[1][..], hess_tab, ODE residual (f64)
 int compile(bool f32, const char* sn, const char* source, int ns, int nc, int npath, int pw, std::vector<char>* code,
             std::vector<std::string>* lowered, bool* has_ring, std::string* log) {
     if (!valid_identifier(sn) || !source || ns < 1 || nc < 0 || ns + nc > 64) {
@@ -121,6 +130,10 @@ int compile(bool f32, const char* sn, const char* source, int ns, int nc, int np
         for (const std::string& f : nm.pass) order.push_back(&f);
         order.push_back(&nm.node_nt);
     }
+    for (int v = 0; v < 2; ++v)
+        for (int j = 0; j < 2; ++j) order.push_back(&nm.nodes_tab[v][j]);
+    order.push_back(&nm.hess_tab);
+    if (!f32) order.push_back(&nm.ode_resid_tab);
     for (const std::string* s : order) hiprtcAddNameExpression(p, s->c_str());
 
     // (-Wno-inline-asm: the DMA instructions of the MFMA kernels name m0 in their clobber list, which clang reports as a reserved register)
@@ -232,6 +245,10 @@ int rtc_build(bool f32, const char* struct_name, const char* source, int ns, int
         for (int k = 0; k < N_PASS_FORMS_RTC && e == hipSuccess; ++k) e = hipModuleGetFunction(&m->pass[k], m->mod, low[i++].c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m->node_nt, m->mod, low[i++].c_str());
     }
+    for (int v = 0; v < 2 && e == hipSuccess; ++v)
+        for (int j = 0; j < 2 && e == hipSuccess; ++j) e = hipModuleGetFunction(&m->nodes_tab[v][j], m->mod, low[i++].c_str());
+    if (e == hipSuccess) e = hipModuleGetFunction(&m->hess_tab, m->mod, low[i++].c_str());
+    if (e == hipSuccess && !f32) e = hipModuleGetFunction(&m->ode_resid_tab, m->mod, low[i++].c_str());
     if (e != hipSuccess) {
         if (log) *log = std::string("loading the model code object failed: ") + hipGetErrorString(e);
         rtc_destroy(m);
@@ -269,6 +286,35 @@ template hipError_t rtc_launch_hess<float>(RtcModel*, const HessArgs<float>&, hi
 hipError_t rtc_launch_ode_resid(RtcModel* m, const OdeResidArgs<double>& a, hipStream_t s) {
     dim3 grid((a.M - 1 + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
     return launch(m->ode_resid, grid, block, 0, s, &a, sizeof a);
+}
+
+// ... with a per-instance parameter table: the argument block and the table pointer behind it, as one packed buffer (Tabled<>)
+template <typename T>
+hipError_t rtc_launch_nodes_tab(RtcModel* m, const NodeArgs<T>& a, const T* tab, bool jac, hipStream_t s) {
+    if (!tab) return hipErrorInvalidValue;
+    const bool vec2 = a.M % 2 == 0;
+    const int per_block = EMI_NODE_THREADS * (vec2 ? 2 : 1);
+    dim3 grid((a.M + per_block - 1) / per_block, a.B), block(EMI_NODE_THREADS);
+    const Tabled<NodeArgs<T>, T> t{a, tab};
+    return launch(m->nodes_tab[vec2][jac], grid, block, 0, s, &t, sizeof t);
+}
+template hipError_t rtc_launch_nodes_tab<double>(RtcModel*, const NodeArgs<double>&, const double*, bool, hipStream_t);
+template hipError_t rtc_launch_nodes_tab<float>(RtcModel*, const NodeArgs<float>&, const float*, bool, hipStream_t);
+
+template <typename T> hipError_t rtc_launch_hess_tab(RtcModel* m, const HessArgs<T>& a, const T* tab, hipStream_t s) {
+    if (!tab) return hipErrorInvalidValue;
+    dim3 grid((a.M + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
+    const Tabled<HessArgs<T>, T> t{a, tab};
+    return launch(m->hess_tab, grid, block, 0, s, &t, sizeof t);
+}
+template hipError_t rtc_launch_hess_tab<double>(RtcModel*, const HessArgs<double>&, const double*, hipStream_t);
+template hipError_t rtc_launch_hess_tab<float>(RtcModel*, const HessArgs<float>&, const float*, hipStream_t);
+
+hipError_t rtc_launch_ode_resid_tab(RtcModel* m, const OdeResidArgs<double>& a, const double* tab, hipStream_t s) {
+    if (!tab) return hipErrorInvalidValue;
+    dim3 grid((a.M - 1 + EMI_NODE_THREADS - 1) / EMI_NODE_THREADS, a.B), block(EMI_NODE_THREADS);
+    const Tabled<OdeResidArgs<double>, double> t{a, tab};
+    return launch(m->ode_resid_tab, grid, block, 0, s, &t, sizeof t);
 }
 
 hipError_t rtc_launch_ode_resid_delay(RtcModel* m, const OdeResidDelayArgs<double>& a, hipStream_t s) {

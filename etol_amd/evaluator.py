@@ -148,6 +148,29 @@ class Evaluator:
         self._ck(self.lib.emi_set_batch(self.ctx, B), "emi_set_batch")
         self._changed()
 
+    def set_model_params(self, table):
+        """Per-instance model parameters (include/emi355x.h, emi_set_model_params_batch): table [B][nparams], row b the parameter
+        set of instance b; None removes the table and the shared set of set_model / set_model_source is in force again."""
+        if table is None:
+            self._ck(self.lib.emi_set_model_params_batch(self.ctx, None, 0, 0), "emi_set_model_params_batch")
+        else:
+            t = np.ascontiguousarray(table, dtype=np.float64)
+            assert t.ndim == 2, "parameter table: [B][nparams]"
+            self._ck(self.lib.emi_set_model_params_batch(self.ctx, _dp(t) if t.size else None, t.shape[0], t.shape[1]),
+                     "emi_set_model_params_batch")
+        self._changed()
+
+    def get_model_params(self):
+        """The per-instance parameter table in force, [B][nparams], or None."""
+        ns, npar = C.c_int(), C.c_int()
+        self._ck(self.lib.emi_get_model_params_batch(self.ctx, None, C.byref(ns), C.byref(npar)), "emi_get_model_params_batch")
+        if ns.value == 0:
+            return None
+        t = np.empty((ns.value, npar.value), dtype=np.float64)
+        self._ck(self.lib.emi_get_model_params_batch(self.ctx, _dp(t) if t.size else None, C.byref(ns), C.byref(npar)),
+                 "emi_get_model_params_batch")
+        return t
+
     def set_delays(self, x_horizon, u_horizon, dt):
         """Delayed states / controls as extra inputs of the node functions (include/emi355x.h, emi_set_delays): the model is
         written on nc + (x_horizon - 1) ns + u_horizon nc controls, evaluations keep taking U[B][nc][M]."""

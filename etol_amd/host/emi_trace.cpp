@@ -383,15 +383,15 @@ std::string Trace::generate_model(const std::string& name, int ns, int nc, const
         o << pv[pw - 1] << "; }\n";
     }
     // f
-    o << "    EMI_DEV static void f(const ModelParams<T>&, const T* z, T tk, T* fo) {\n";
+    o << "    EMI_DEV static void f(const ModelParams<T>& P, const T* z, T tk, T* fo) {\n";
     {
         std::vector<std::string> t;
         for (int i = 0; i < ns; ++i) t.push_back("fo[" + std::to_string(i) + "]");
         o << emit(f, t, false, "        ");
     }
-    o << "        (void)tk;\n    }\n";
+    o << "        (void)P; (void)tk;\n    }\n";
     // jac
-    o << "    EMI_DEV static void jac(const ModelParams<T>&, const T* z, T tk, T (*J)[NV]) {\n";
+    o << "    EMI_DEV static void jac(const ModelParams<T>& P, const T* z, T tk, T (*J)[NV]) {\n";
     o << "        for (int i = 0; i < NS; ++i)\n            for (int v = 0; v < NV; ++v) J[i][v] = T(0);\n";
     {
         std::vector<int> outs;
@@ -405,13 +405,13 @@ std::string Trace::generate_model(const std::string& name, int ns, int nc, const
             }
         o << emit(outs, t, false, "        ");
     }
-    o << "        (void)tk; (void)z;\n    }\n";
+    o << "        (void)P; (void)tk; (void)z;\n    }\n";
     // cost
-    o << "    EMI_DEV static T cost(const ModelParams<T>&, const T* z, T tk) {\n        T Lv;\n";
+    o << "    EMI_DEV static T cost(const ModelParams<T>& P, const T* z, T tk) {\n        T Lv;\n";
     o << emit({L}, {"Lv"}, false, "        ");
-    o << "        (void)tk;\n        return Lv;\n    }\n";
+    o << "        (void)P; (void)tk;\n        return Lv;\n    }\n";
     // grad
-    o << "    EMI_DEV static void grad(const ModelParams<T>&, const T* z, T tk, T* g) {\n";
+    o << "    EMI_DEV static void grad(const ModelParams<T>& P, const T* z, T tk, T* g) {\n";
     o << "        for (int v = 0; v < NV; ++v) g[v] = T(0);\n";
     {
         std::vector<int> outs;
@@ -423,15 +423,15 @@ std::string Trace::generate_model(const std::string& name, int ns, int nc, const
         }
         o << emit(outs, t, false, "        ");
     }
-    o << "        (void)tk; (void)z;\n    }\n";
+    o << "        (void)P; (void)tk; (void)z;\n    }\n";
     // hess: cc[0] = cL, cc[1+i] = cf[i]
-    o << "    EMI_DEV static void hess(const ModelParams<T>&, const T* z, T tk, T cL, const T* cf, T* H) {\n";
+    o << "    EMI_DEV static void hess(const ModelParams<T>& P, const T* z, T tk, T cL, const T* cf, T* H) {\n";
     o << "        T cc[NS + 1];\n        cc[0] = cL;\n        for (int i = 0; i < NS; ++i) cc[1 + i] = cf[i];\n";
     o << emit(H, Ht, true, "        ");
-    o << "        (void)tk; (void)z; (void)cc;\n    }\n";
+    o << "        (void)P; (void)tk; (void)z; (void)cc;\n    }\n";
     if (npath > 0) {
         // path rows: values and partials w.r.t. the PW variables of pvar()
-        o << "    EMI_DEV static void path(const ModelParams<T>&, const T* z, T tk, T* c, T* cd) {\n";
+        o << "    EMI_DEV static void path(const ModelParams<T>& P, const T* z, T tk, T* c, T* cd) {\n";
         o << "        for (int j = 0; j < NPATH * PW; ++j) cd[j] = T(0);\n";
         {
             std::vector<int> outs;
@@ -448,11 +448,11 @@ std::string Trace::generate_model(const std::string& name, int ns, int nc, const
             }
             o << emit(outs, t, false, "        ");
         }
-        o << "        (void)tk; (void)z;\n    }\n";
+        o << "        (void)P; (void)tk; (void)z;\n    }\n";
         // adds sum_j cc[j] c_j,zz into the packed lower triangle H of the node block
-        o << "    EMI_DEV static void path_hess(const ModelParams<T>&, const T* z, T tk, const T* cc, T* H) {\n";
+        o << "    EMI_DEV static void path_hess(const ModelParams<T>& P, const T* z, T tk, const T* cc, T* H) {\n";
         o << emit(PH, PHt, true, "        ");
-        o << "        (void)tk; (void)z; (void)cc; (void)H;\n    }\n";
+        o << "        (void)P; (void)tk; (void)z; (void)cc; (void)H;\n    }\n";
     }
     o << "};\n";
     return o.str();

@@ -205,6 +205,27 @@ int emi_set_model_source(emi_ctx_t ctx, const char* struct_name, const char* sou
 int emi_check_model_source(const char* struct_name, const char* source, int ns,
                            int nc, int npath, int n_path_vars, int f32, char* log, size_t log_len);
 int emi_set_batch(emi_ctx_t ctx, int B);
+/* PER-INSTANCE MODEL PARAMETERS: params host [nsets][nparams], row b the parameter set of instance b (mass, inertia, aero
+ * coefficients, cost weights of a dispersion study) in place of the one set of emi_set_model*.  nsets == B and nparams the
+ * model's count (emi_model_dims; what emi_set_model_source was given), else EMI_ERR_ARG; no model or no batch yet:
+ * EMI_ERR_STATE.  The context keeps the table on the device in its own real type, rounded once as emi_set_model rounds its set.
+ * nsets == 0 (params may be NULL) removes the table: the context has the shared set again, with the launch policy and the bits
+ * of a context that never had a table.
+ * While a table is in force every kernel that evaluates the model (node, Hessian and ODE-residual kernels, built-in and run-time
+ * compiled models, both precisions) runs in an instantiation that reads row b once per workgroup, by scalar loads, and an
+ * evaluation pass takes the sequential route -- node kernel, then defect kernel: what the option "overlap" 0 selects, at every
+ * mesh and batch size (the one-launch pass and the MFMA defect forms evaluate f for 16 instances per tile and have no tabled
+ * form); emi_plan_pass and emi_last_path report that.  Instance b has the bits of a context of the same B, M and tables that
+ * holds row b as its shared set under "overlap" 0.  emi_eval_*, emi_hess_*, emi_ode_error_*, emi_ipm_solve_shard_* and
+ * emi_ipm_solve_ladder_* take such a context; emi_ipm_solve_refine_* and emi_ipm_solve_restart_*, which compact the batch,
+ * return EMI_ERR_UNSUPPORTED.  Contexts with delays: EMI_ERR_UNSUPPORTED here, and from emi_set_delays once a table is set.
+ * The table survives emi_set_mesh, emi_set_path, emi_set_tracks, emi_set_track_waypoints and emi_set_stream; emi_set_model,
+ * emi_set_model_source and an emi_set_batch to another B drop it.  Setting or removing it voids the record of
+ * EMI_EVAL_KEEP_INVARIANT (the model-invariant Jacobian rows depend on the parameters).  Synchronises, as emi_set_path does.
+ * emi_get_model_params_batch: what is in force -- *nsets 0 (none) or B, *nparams the model's count, params (NULL: not wanted)
+ * the rows as they were given, [nsets][nparams].                                                                          */
+int emi_set_model_params_batch(emi_ctx_t ctx, const double* params, int nsets, int nparams);
+int emi_get_model_params_batch(emi_ctx_t ctx, double* params, int* nsets, int* nparams);
 /* Delayed states and controls -- what ePSOPT::dae appends to the callbacks' x and u through PSOPT's get_delayed_state /
  * get_delayed_control (reference src/ePSOPT/ePSOPT.cpp:231-248): x(t - i dt) of every state for i = 1 .. x_horizon - 1 and
  * u(t - i dt) of every control for i = 1 .. u_horizon.  On the device they are extra INPUTS of the node functions: the model
