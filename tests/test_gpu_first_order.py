@@ -10,7 +10,8 @@ the mesh is the oracle's for the nodes-only passes and emi_lgl's for the full on
 centro-antisymmetric to the bit), and the reference is built on the mesh the context holds; every output buffer holds NaN before
 the pass, and every check prints its worst ratio and where it is (pytest -s).
 
-Out of scope here: the fp32 context (test_gpu_f32.py), contexts with delays, the TABLED instantiations (test_gpu_param_table.py
+Out of scope here: the fp32 context (test_gpu_f32.py), contexts with delays (test_gpu_delay_values.py holds the delayed values
+elementwise and ties the passes bit for bit to contexts without delays), the TABLED instantiations (test_gpu_param_table.py
 ties them bit for bit to untabled contexts).
 """
 import numpy as np

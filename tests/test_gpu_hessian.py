@@ -6,7 +6,8 @@ be exactly zero; the worst ratio and its position are printed (pytest -s).  Ever
 into a buffer that held a NaN bit pattern in every word, which must be overwritten everywhere and give hess_host's bits.
 The inputs are fixture points (tests/golden/hessian_terms.npz) laid out as [B][M] by index; the mesh is the oracle's.
 
-Models with delays and the traced path rows of generated models stay with tests/test_gpu_delays.py and tests/test_gpu_traced.py.
+Models with delays stay with tests/test_gpu_delay_values.py (the Hessian of a context with delays: the bits of a context without
+them on the extended controls) and tests/test_gpu_delays.py, the traced path rows of generated models with tests/test_gpu_traced.py.
 """
 import numpy as np
 import pytest
